@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X delta-sketching engine.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step` = wall time of
+one timed step).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64,
+<= 64 MB in all; see dump_outputs).  Everything else the benchmark measures runs only under --full.
 
 Default workload (BASELINE.json configs[1], per GPU): 10 synthetic 50-Mbp FASTAs resident in HBM,
 HyperLogLog log2m=14, k-sweep 4..40 (K=37).  One STEP = one pass of the whole hot path over that
@@ -21,11 +25,15 @@ world-size-2 tests run.
 
 Extra objects on the JSON line (DESIGN.md "Measurement"):
   roofline      dominant kernel (K1): algorithmic bytes / its HIP-event time vs 8 TB/s, plus the VALU-issue bound
+                (from the timed steps themselves: on every run)
+only with --full (each of the first four can be left out with --no-cpu-baseline / --no-accuracy / --no-secondary / --no-ingest):
   cpu_baseline  Dashing itself when a `dashing` binary is on PATH (registers diffed against the oracle), else the
                 CPU oracle run the way DandD drives Dashing (one job per (genome, k), each re-parsing the FASTA)
   accuracy_vs_exact   cardinality and delta errors of ALL leaves and the root against the GPU exact counter
   secondary     the same step at log2m 16 (where delta meets the 1 % target) and at DandD's default log2m 20
   ingest        dd_sketch_files on FASTA files (PCIe and file reads included; never `value`)
+  roofline_k2   the --config's K2 schedule (all pairs / progressive) timed in launches of its own
+  accuracy_subsample   cfg5 / cfg5share: delta of genome 0 against the GPU exact counter
 """
 import argparse
 import json
@@ -515,6 +523,36 @@ def write_detail(full, path):
         return None
 
 
+DUMP_LIMIT = 64_000_000     # bytes of all --dump-outputs files together
+
+
+def dump_outputs(d, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: `arrays` {name: numpy array or torch tensor, CPU or device} -> d/<name>.npy.  Integer and float32 data
+    are written as float32 (the registers: 0..64, exact), float64 as float64.  Smallest first, each array gets an equal share
+    of what is left of `limit`; one that does not fit is replaced by a fixed sample: the elements of the flattened array at
+    np.unique(default_rng(SEED).integers(0, size, n)) -- the same indices for the same shape on every run."""
+    os.makedirs(d, exist_ok=True)
+    items = []
+    for name, a in arrays.items():
+        is_f64 = str(a.dtype) in ("float64", "torch.float64")
+        items.append((int(np.prod(a.shape)) * (8 if is_f64 else 4), name, a, np.float64 if is_f64 else np.float32))
+    items.sort(key=lambda t: t[0])
+    left = limit - 256 * len(items)                      # (.npy headers)
+    for i, (nbytes, name, a, dt) in enumerate(items):
+        share = left // (len(items) - i)
+        if nbytes > share:
+            per = np.dtype(dt).itemsize
+            idx = np.unique(np.random.default_rng(SEED).integers(0, nbytes // per, share // per))
+            if isinstance(a, np.ndarray):
+                a = a.reshape(-1)[idx]
+            else:                                        # a torch tensor: gathered on its own device
+                import torch
+                a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        out = (a if isinstance(a, np.ndarray) else a.cpu().numpy()).astype(dt)
+        np.save(os.path.join(d, f"{name}.npy"), out)
+        left -= out.nbytes
+
+
 class Workload:
     """The genomes of one rank in HBM and the engine-backed callbacks of dandd_amd.dist.sharded_ksweep."""
 
@@ -755,6 +793,11 @@ def main():
     ap.add_argument("--kmax", type=int, default=None)
     ap.add_argument("--log2m", type=int, default=14)
     ap.add_argument("--nrec", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; <= 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: CPU baseline, accuracy against the exact counter, "
+                         "secondary register counts and workloads, ingest probes, the K2 schedule's own roofline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-accuracy", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
@@ -789,7 +832,7 @@ def main():
 
     # CPU baseline first (rank 0, N=1 only), before this process touches the GPU
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(int(args.cpu_sample_mbp * 1e6), cfg["nrec"], cfg["kmin"], cfg["kmax"], args.log2m)
 
     import torch
@@ -879,6 +922,14 @@ def main():
     # which GPU every rank really ran on (rank 0 prints them: one entry per rank, all different on a real node)
     gpus_active = ddist.gather_strings(f"cuda:{local_rank} {torch.cuda.get_device_name(local_rank)} "
                                        f"uuid={getattr(torch.cuda.get_device_properties(local_rank), 'uuid', '?')}")
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the step receives from its last run: this rank's leaf registers + the root over all ranks,
+        # every cardinality, delta and its argmax-k per sketch, and the config's schedule cardinalities
+        outs = {"registers": wl.regs, "cardinality": card, "delta": delta, "argmax_k": bestk.astype(np.float64)}
+        for attr, name in (("pair", "pairwise_cardinality"), ("prog", "progressive_cardinality")):
+            if getattr(wl, attr, None) is not None:
+                outs[name] = np.asarray(getattr(wl, attr), dtype=np.float64)
+        dump_outputs(args.dump_outputs, outs)
 
     extras = {}
     if cfg["extra"] == "progressive" and getattr(wl, "prog", None) is not None and n_sched == total_genomes:
@@ -888,7 +939,7 @@ def main():
                               "last_prefix_equals_root": ok}
         if not ok:
             raise SystemExit("bench.py: progressive schedule's full union differs from the root sketch")
-    if rank == 0 and world == 1 and headline:
+    if rank == 0 and world == 1 and headline and args.full:
         if not args.no_accuracy:
             extras["accuracy_vs_exact"] = accuracy_block(
                 wl, card, f"log2m {p}: all {ng} leaves + their root, k {kmin}-{kmax}; exact = GPU sort+distinct of canonical "
@@ -1005,7 +1056,7 @@ def main():
     # run's workload is a profiled one)
     # the K2 schedule of the config (all pairs / progressive) timed on its own, against its own roofline
     k2 = None
-    if rank == 0 and cfg["extra"] and ng:
+    if rank == 0 and cfg["extra"] and ng and args.full:
         slab, n = wl.sched        # rank 0 alone from here on: no collective may be called
         run = (lambda: eng.pairwise_device(slab.data_ptr(), n, K)) if cfg["extra"] == "pairwise" else \
               (lambda: eng.progressive_device(slab.data_ptr(), n, K, orderings))
@@ -1078,7 +1129,7 @@ def main():
             k2["traffic"], k2["traffic_from"] = k2_traffic(("cfg3" if stream_pairs else ("cfg4share" if n == 8 else "cfg4")))
 
     # BASELINE cfg 5's accuracy clause ("delta within 1 % of exact on a subsample"): genome 0 of the share
-    if rank == 0 and args.config in ("cfg5", "cfg5share") and not args.no_accuracy and ng:
+    if rank == 0 and args.config in ("cfg5", "cfg5share") and args.full and not args.no_accuracy and ng:
         extras["accuracy_subsample"] = subsample_accuracy(eng, wl, card, int(bestk[0]), p)
 
     if rank == 0:

@@ -6,7 +6,7 @@ OUT=gpurun_out/${1:-r03_k2cfg3}; mkdir -p $OUT
 for P in 14 20; do
   for set in FETCH_SIZE WRITE_SIZE; do
     rm -rf $OUT/raw
-    timeout 600 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/raw -o x -- python3 bench.py --config cfg3 --log2m $P --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_p${P}_$set.json 2> $OUT/bench_p${P}_$set.err
+    timeout 600 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/raw -o x -- python3 bench.py --full --config cfg3 --log2m $P --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_p${P}_$set.json 2> $OUT/bench_p${P}_$set.err
     cp "$(find $OUT/raw -name '*counter_collection.csv' | head -1)" $OUT/counters_p${P}_$set.csv
     rm -rf $OUT/raw
   done

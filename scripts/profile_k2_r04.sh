@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-r04_k2}; CFG=${2:-cfg4share}; mkdir -p $OUT
 for P in 14 20; do
   for set in FETCH_SIZE WRITE_SIZE; do
     rm -rf $OUT/raw
-    timeout 900 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/raw -o x -- python3 bench.py --config $CFG --log2m $P --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_${CFG}_p${P}_$set.json 2> $OUT/bench_${CFG}_p${P}_$set.err
+    timeout 900 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/raw -o x -- python3 bench.py --full --config $CFG --log2m $P --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_${CFG}_p${P}_$set.json 2> $OUT/bench_${CFG}_p${P}_$set.err
     cp "$(find $OUT/raw -name '*counter_collection.csv' | head -1)" $OUT/counters_${CFG}_p${P}_$set.csv
     rm -rf $OUT/raw
   done

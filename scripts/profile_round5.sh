@@ -5,7 +5,7 @@
 # usage: profile_round5.sh OUTNAME     (results under gpurun_out/OUTNAME; copy into profiles/ as r05_<v>_*)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/${1:-r05_v2}; mkdir -p $OUT
-timeout 900 python3 bench.py --detail $OUT/bench_default_detail.json > $OUT/bench_default_line.json 2> $OUT/bench_default.err
+timeout 900 python3 bench.py --full --detail $OUT/bench_default_detail.json > $OUT/bench_default_line.json 2> $OUT/bench_default.err
 for P in 14 20; do
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats$P -o st -- python3 bench.py --steps 5 --warmup 1 --log2m $P --no-cpu-baseline --no-accuracy --no-secondary --no-ingest --detail $OUT/bench_prof_p${P}_detail.json > $OUT/bench_prof_p$P.json 2> $OUT/bench_prof_p$P.err
   cp "$(find $OUT/stats$P -name '*kernel_stats.csv' | head -1)" $OUT/kernel_stats_p$P.csv

@@ -1,5 +1,7 @@
 import os
+import shutil
 import sys
+import tempfile
 
 import pytest
 
@@ -18,6 +20,15 @@ def orc():
     from oracle import dd_oracle
     dd_oracle.lib()
     return dd_oracle
+
+
+@pytest.fixture
+def sock_dir():
+    """A short directory for unix sockets: a socket's path holds at most 107 bytes, and pytest's tmp_path under a deep
+    home or TMPDIR can be that long by itself."""
+    d = tempfile.mkdtemp(prefix="dd_sock_", dir="/tmp" if os.access("/tmp", os.W_OK) else None)
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
 
 
 @pytest.fixture(scope="session")

@@ -105,7 +105,7 @@ def test_bench_config_presets_run(torch_cuda, tmp_path, config, extra):
     """The --config presets (BASELINE cfg 3 / 4 / 5 shapes, shrunk) produce a well-formed line: right k range, the
     extra schedule in the step, strong/weak scaling flag, finite throughput."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline", "--detail", str(tmp_path / "detail.json")] + extra, capture_output=True, text=True, timeout=240, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--detail", str(tmp_path / "detail.json")] + extra, capture_output=True, text=True, timeout=240, cwd=ROOT)
     j = _line(r)
     want_k = {"cfg3": (2, 32), "cfg4share": (2, 32), "cfg5share": (4, 64)}[config]
     assert (j["config"]["kmin"], j["config"]["kmax"]) == want_k
@@ -128,7 +128,7 @@ def test_bench_progressive_line_names_the_bit_plane_scan_at_log2m_20(torch_cuda,
     """From log2m 18 on (n <= 32) dd_progressive_device runs the bit-plane AND-scan: the line must say pscan_kernel and
     price it against the LDS read rate -- round 3's line named progressive_kernel on the HBM roof for a kernel that had not run."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg4share", "--steps", "1", "--warmup", "1", "--mbp", "2",
-                        "--log2m", "20", "--no-cpu-baseline", "--detail", str(tmp_path / "detail.json")], capture_output=True, text=True, timeout=300, cwd=ROOT)
+                        "--log2m", "20", "--full", "--no-cpu-baseline", "--detail", str(tmp_path / "detail.json")], capture_output=True, text=True, timeout=300, cwd=ROOT)
     j = _line(r)
     assert j["roofline_k2"]["path"] == "progressive_pscan" and j["roofline_k2"]["bound"] == "lds" and 0 < j["roofline_k2"]["frac"] < 1
     k2 = _detail(j)["roofline_k2"]
@@ -251,14 +251,14 @@ def test_bench_without_enough_gpus_fails_loudly():
 
 @pytest.mark.gpu
 def test_bench_headline_line_has_every_object(torch_cuda, tmp_path):
-    """The driver's command shape on a shrunk workload (3 x 2 Mbp): bench.py prints ONE line of at most 6000 bytes -- round 4's
+    """`bench.py --full` on a shrunk workload (3 x 2 Mbp): bench.py prints ONE line of at most 6000 bytes -- round 4's
     21.9 KB line could not be read by the driver -- that carries the contract's keys, `roofline` (frac, traffic key, the VALU
     bound's three numbers), `cpu_baseline` (value, cores, kind, sample, stages), the accuracy verdict, one {value, ms, frac,
     frac_of_mix} entry per secondary step (log2m 16 / 20, small genomes, realistic genomes, the cfg 5 share) and per ingest
     probe, no prose; the FULL object (every roofline with its per-kernel issue model, every `what` / `why`) is in the sidecar
     the line names."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--genomes", "3", "--mbp", "2",
-                        "--cpu-sample-mbp", "2", "--share-mbp", "3", "--detail", str(tmp_path / "bench_detail.json")],
+                        "--full", "--cpu-sample-mbp", "2", "--share-mbp", "3", "--detail", str(tmp_path / "bench_detail.json")],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     j = _line(r)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
@@ -300,6 +300,60 @@ def test_bench_headline_line_has_every_object(torch_cuda, tmp_path):
     sm = d["secondary"]["log2m20_64x5Mbp"]["roofline"]
     assert "k1_counters_64x5_p20.json" in sm["traffic_from"] and sm["valu_bound"]["issue_model"]["by_kernel"]
     assert "what" in d["ingest"] and "why" in d["secondary"]["log2m16"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(torch_cuda, orc, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries none of the --full blocks; --dump-outputs writes the last
+    step's registers, cardinalities and deltas, which are the oracle's for the same seeded genomes, and are the same on a second run."""
+    def run(d):
+        return _line(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                                     "--genomes", "2", "--mbp", "1", "--kmin", "10", "--kmax", "13", "--dump-outputs", str(d),
+                                     "--detail", str(tmp_path / "detail.json")], capture_output=True, text=True, timeout=300, cwd=ROOT))
+    j = run(tmp_path / "a")
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+    for key in ("cpu_baseline", "accuracy_vs_exact", "secondary", "ingest"):
+        assert key not in j, key
+    assert j["roofline_k2"] is None
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"registers", "cardinality", "delta", "argmax_k"}
+    assert got["registers"].dtype == np.float32 and got["registers"].shape == (3, 4, 1 << 14)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    leaves = [orc.sketch_sweep(orc.synth_fasta(0xD4ADD, g, 1_000_000, 5), 10, 13, 14) for g in range(2)]
+    want = np.stack(leaves + [np.maximum(*leaves)])
+    assert np.array_equal(got["registers"], want.astype(np.float32))
+    card = np.array([[orc.card(want[g, kk], 14) for kk in range(4)] for g in range(3)])
+    assert np.array_equal(got["cardinality"], card)
+    d = card / np.arange(10, 14)
+    assert np.array_equal(got["delta"], d.max(axis=1)) and np.array_equal(got["argmax_k"], d.argmax(axis=1) + 10.0)
+    run(tmp_path / "b")
+    for name, a in got.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f"{name}.npy"), a), name
+
+
+def test_dump_outputs_stays_within_its_limit_with_a_fixed_sample(tmp_path):
+    """bench.dump_outputs: float32 / float64 files only, the small arrays whole, an array over its share of the limit replaced
+    by the same seeded sample on every call (numpy or torch input alike)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import torch
+    regs = np.random.default_rng(1).integers(0, 64, (5, 7, 4096), dtype=np.uint8)
+    card = np.random.default_rng(2).random((5, 7))
+    limit = 50_000
+    for name, big in (("np", regs), ("torch", torch.from_numpy(regs))):
+        for rep in range(2):
+            d = tmp_path / f"{name}{rep}"
+            bench.dump_outputs(str(d), {"registers": big, "cardinality": card, "delta": card.max(axis=1)}, limit=limit)
+            assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= limit
+            r, c = np.load(d / "registers.npy"), np.load(d / "cardinality.npy")
+            assert r.dtype == np.float32 and c.dtype == np.float64 and np.array_equal(c, card)
+            assert 0 < r.size * 4 <= limit and r.ndim == 1 and set(np.unique(r)) <= set(range(64))
+    first = np.load(tmp_path / "np0" / "registers.npy")
+    for other in ("np1", "torch0", "torch1"):
+        assert np.array_equal(np.load(tmp_path / other / "registers.npy"), first), other
+    whole = tmp_path / "whole"
+    bench.dump_outputs(str(whole), {"registers": regs})
+    assert np.array_equal(np.load(whole / "registers.npy"), regs.astype(np.float32))
 
 
 def test_compact_line_is_bounded_and_keeps_the_contract():

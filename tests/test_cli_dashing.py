@@ -133,10 +133,10 @@ def test_parallel_name_takes_only_the_k_batch(parallel, dashing, tmp_path):
     assert r.returncode == 1 and "no CPU path" in r.stderr and "REAL" not in r.stdout
 
 
-def test_resident_form_answers_and_survives_bad_clients(dashing, tmp_path):
+def test_resident_form_answers_and_survives_bad_clients(dashing, tmp_path, sock_dir):
     """`dashing serve`: ping, a command that fails (no GPU here) with its message sent back, a client that hangs up mid-request, shutdown"""
     import socket
-    sock = str(tmp_path / "d.sock")
+    sock = os.path.join(sock_dir, "d.sock")
     env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
     env.pop("DANDD_DASHING_SERVER", None)
     srv = _start_server(dashing, sock, env)
@@ -242,14 +242,14 @@ def _replay(dashing, work, commands, env, orc, check_oracle, batches=(), paralle
 
 
 @pytest.mark.gpu
-def test_reference_command_trace_replayed_through_the_product(dashing, tmp_path, orc, torch_cuda):
+def test_reference_command_trace_replayed_through_the_product(dashing, tmp_path, sock_dir, orc, torch_cuda):
     """Every command line the unmodified reference issued over eleven CLI scenarios (742 of them), through the resident form
     (one process keeps the GPU contexts; the traced argv is what a client process sends), in a directory laid out as the
     reference laid it out.  Then the reference's own cardinality caches, asked for again in one multi-path `card`."""
     t = _trace()
     work = str(tmp_path / "w")
     shutil.copytree(os.path.join(GOLD, "fasta"), os.path.join(work, "data"))
-    sock = str(tmp_path / "d.sock")
+    sock = os.path.join(sock_dir, "d.sock")
     env = dict(os.environ)
     env.pop("DANDD_DASHING_SERVER", None)
     env.pop("DANDD_SKETCH_FORMAT", None)
@@ -365,7 +365,7 @@ def test_cli_at_baseline_genome_size_and_default_registers(dashing, tmp_path, or
 
 
 @pytest.mark.gpu
-def test_reference_k_batches_run_fused(dashing, parallel, tmp_path, orc, torch_cuda):
+def test_reference_k_batches_run_fused(dashing, parallel, tmp_path, sock_dir, orc, torch_cuda):
     """The reference's k-batch call site itself (lib/huffman_dandd.py:214-218,233): each of the 163 `parallel -j 95% '<dashing ...
     {} ...>' ::: k ...` calls the unmodified reference made goes, argv as its shell handed it over, to the product's `parallel`
     (one process, ONE fused sweep over the node's FASTA for all its ks / its unions k by k), the 371 `card` lines to `dashing`.
@@ -374,7 +374,7 @@ def test_reference_k_batches_run_fused(dashing, parallel, tmp_path, orc, torch_c
     t = _trace()
     work = str(tmp_path / "w")
     shutil.copytree(os.path.join(GOLD, "fasta"), os.path.join(work, "data"))
-    sock = str(tmp_path / "d.sock")
+    sock = os.path.join(sock_dir, "d.sock")
     env = dict(os.environ)
     env.pop("DANDD_DASHING_SERVER", None)
     env.pop("DANDD_SKETCH_FORMAT", None)
@@ -411,11 +411,11 @@ def test_reference_k_batches_run_fused(dashing, parallel, tmp_path, orc, torch_c
 
 
 @pytest.mark.gpu
-def test_forty_clients_at_once_like_gnu_parallel(dashing, tmp_path, orc, torch_cuda):
+def test_forty_clients_at_once_like_gnu_parallel(dashing, tmp_path, sock_dir, orc, torch_cuda):
     """What GNU parallel does to a resident `dashing serve` when DandD's k-batch is NOT taken by dandd_amd/bin/fused/parallel: K client
     processes started together, one listening socket.  All forty are answered, every file is the oracle's."""
     from concurrent.futures import ThreadPoolExecutor
-    sock = str(tmp_path / "d.sock")
+    sock = os.path.join(sock_dir, "d.sock")
     env = dict(os.environ)
     env.pop("DANDD_DASHING_SERVER", None)
     env.pop("DANDD_SKETCH_FORMAT", None)

@@ -39,7 +39,7 @@ def _files(d):
     return out
 
 
-def _run_both(tmp_path, backend_env, regs, timeout=600):
+def _run_both(tmp_path, sock_dir, backend_env, regs, timeout=600):
     """the same three commands one-shot (fresh process each) under tmp/one and through a server under tmp/srv, the data at the
     SAME absolute path for both (moved in and out: pickles and CSVs hold absolute paths)"""
     base = str(tmp_path)
@@ -60,7 +60,7 @@ def _run_both(tmp_path, backend_env, regs, timeout=600):
             f.write("\n".join(os.path.join(data, n) for n in names[:4]) + "\n")
         times = []
         if mode == "srv":
-            sock = os.path.join(base, "dandd.sock")
+            sock = os.path.join(sock_dir, "dandd.sock")
             srv = subprocess.Popen([sys.executable, WORKER, "serve", sock], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
             try:
                 line = srv.stdout.readline()
@@ -124,12 +124,12 @@ def _assert_same_outputs(results):
     assert any(n.endswith(".kij.csv") for n in one) and any(n.endswith("_deltas.csv") for n in one) and any(n.endswith("summary.csv") for n in one)
 
 
-def test_server_outputs_equal_one_shot_cli_with_checker_backend(tmp_path):
-    _assert_same_outputs(_run_both(tmp_path, {"SERVER_WORKER_BACKEND": "oracle"}, 12))
+def test_server_outputs_equal_one_shot_cli_with_checker_backend(tmp_path, sock_dir):
+    _assert_same_outputs(_run_both(tmp_path, sock_dir, {"SERVER_WORKER_BACKEND": "oracle"}, 12))
 
 
-def test_client_without_a_server_runs_the_command_itself(tmp_path):
-    env = dict(os.environ, DANDD_SERVER=str(tmp_path / "nobody.sock"))
+def test_client_without_a_server_runs_the_command_itself(tmp_path, sock_dir):
+    env = dict(os.environ, DANDD_SERVER=os.path.join(sock_dir, "nobody.sock"))
     r = subprocess.run([sys.executable, "-m", "dandd_amd.host.client", "tree", "-o", str(tmp_path)], env=env, capture_output=True, text=True, timeout=120, cwd=ROOT)
     assert r.returncode == 1 and "ERROR: You must provide" in r.stdout          # the one-shot CLI's own answer
     r = subprocess.run([sys.executable, "-m", "dandd_amd.host.client", "tree", "-o", str(tmp_path)], env=dict(env, DANDD_SERVER_REQUIRED="1"),
@@ -138,6 +138,6 @@ def test_client_without_a_server_runs_the_command_itself(tmp_path):
 
 
 @pytest.mark.gpu
-def test_server_outputs_equal_one_shot_cli_on_the_gpu(tmp_path, torch_cuda):
-    res = _run_both(tmp_path, {"SERVER_WORKER_BACKEND": "hip"}, 14)
+def test_server_outputs_equal_one_shot_cli_on_the_gpu(tmp_path, sock_dir, torch_cuda):
+    res = _run_both(tmp_path, sock_dir, {"SERVER_WORKER_BACKEND": "hip"}, 14)
     _assert_same_outputs(res)
