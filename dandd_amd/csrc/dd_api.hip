@@ -2002,6 +2002,57 @@ int dd_pairwise(dd_ctx* c, const uint8_t* leaf, int n, int K, double* card) {
     return dd_pairwise_device(c, static_cast<const uint8_t*>(c->regs.p), n, K, card);
 }
 
+// -------------------------------------------------------------------------- leave-out
+int dd_leave_out_device(dd_ctx* c, const uint8_t* leaf_dev, int n, int K, const int32_t* group, int ngroups, double* card) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 1 || K < 1 || !leaf_dev || !group || !card) return fail(DD_EINVAL, "bad argument");
+    if (ngroups < 1) return fail(DD_EINVAL, "ngroups=%d: at least one group is needed", ngroups);
+    if (ngroups > n) return fail(DD_EINVAL, "ngroups=%d is more than the %d leaves", ngroups, n);
+    for (int i = 0; i < n; ++i)
+        if (group[i] < -1 || group[i] >= ngroups) return fail(DD_EINVAL, "group[%d]=%d outside -1..%d", i, group[i], ngroups - 1);
+    // the kernel's slot table: leaves ordered by group (the floor, -1, first), the last slot of each group carrying its id
+    std::vector<int> start(ngroups + 2, 0);          // slots of group g: [start[g + 1], start[g + 2])
+    for (int i = 0; i < n; ++i) ++start[group[i] + 2];
+    for (int g = 0; g < ngroups; ++g)
+        if (start[g + 2] == n) return fail(DD_EINVAL, "group %d holds every leaf: the union of the rest is empty", g);
+    for (int s = 1; s <= ngroups + 1; ++s) start[s] += start[s - 1];
+    std::vector<int32_t> tab((size_t)2 * n);
+    std::vector<int> fill(start.begin(), start.end() - 1);
+    for (int i = 0; i < n; ++i) {
+        const int j = fill[group[i] + 1]++;
+        tab[2 * j] = i;
+        tab[2 * j + 1] = (j + 1 == start[group[i] + 2]) ? group[i] : -2;
+    }
+    DeviceGuard guard(c->device);
+    const int nslots = (int)(tab.size() / 2);
+    const size_t njobs = (size_t)(ngroups + 1) * K;
+    int rc;
+    if ((rc = c->hist.reserve(njobs * 64 * sizeof(uint32_t)))) return rc;
+    if ((rc = c->ord.reserve(sizeof(int32_t) * tab.size()))) return rc;
+    DD_HIP(hipEventSynchronize(c->stage_free));
+    if ((rc = c->stage.reserve(sizeof(int32_t) * tab.size()))) return rc;
+    if ((rc = upload(c, c->stage, c->ord.p, tab.data(), sizeof(int32_t) * tab.size(), 0))) return rc;
+    DD_HIP(hipEventRecord(c->stage_free, c->stream));
+    {
+        Span sp(c, DD_KERNEL_UNION);
+        dd::launch_leaveout(leaf_dev, K, c->p, static_cast<const int32_t*>(c->ord.p), nslots, ngroups,
+                            static_cast<uint32_t*>(c->hist.p), c->stream);
+    }
+    DD_HIP(hipGetLastError());
+    return estimates_from_hist(c, static_cast<const uint32_t*>(c->hist.p), njobs, card);
+}
+
+int dd_leave_out(dd_ctx* c, const uint8_t* leaf, int n, int K, const int32_t* group, int ngroups, double* card) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 1 || K < 1 || !leaf) return fail(DD_EINVAL, "bad argument");
+    DeviceGuard guard(c->device);
+    const size_t bytes = ((size_t)n * K) << c->p;
+    int rc;
+    if ((rc = c->regs.reserve(bytes))) return rc;
+    DD_HIP(hipMemcpyAsync(c->regs.p, leaf, bytes, hipMemcpyHostToDevice, c->stream));
+    return dd_leave_out_device(c, static_cast<const uint8_t*>(c->regs.p), n, K, group, ngroups, card);
+}
+
 // ------------------------------------------------------------------------- measurement
 int dd_timing_enable(dd_ctx* c, int on) {
     if (check_ctx(c)) return DD_EINVAL;

@@ -186,6 +186,11 @@ size_t pscan_scratch_bytes(int n, int K, int log2m, int norder);
 bool launch_progressive_pscan(const uint8_t* leaf_dev, int n, int K, int log2m, const int32_t* ord_dev, int norder, const uint32_t* rng_host,
                               void* scratch, uint32_t* hist_dev, hipStream_t st);
 void launch_mle(const uint32_t* hist_dev, size_t njobs, int log2m, double* est_dev, hipStream_t st);
+// leave-out unions (dd_leaveout.hip): hist[g*K + kk][64] = |union of the leaves outside group g|, g < G; row G*K + kk the
+// full union.  tab_dev[nslots][2]: (leaf row, group if the slot ends its group -- -1 the floor -- else -2), the leaves of a
+// group consecutive, the floor first.  Zeroes hist_dev itself.
+void launch_leaveout(const uint8_t* leaf_dev, int K, int log2m, const int32_t* tab_dev, int nslots, int G, uint32_t* hist_dev,
+                     hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // exact distinct k-mer count (KMC stand-in): extract -> radix sort -> count distinct

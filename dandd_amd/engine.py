@@ -24,7 +24,7 @@ EXPORTS = [
     "dd_abi_version", "dd_last_error", "dd_create", "dd_destroy", "dd_set_stream", "dd_synchronize",
     "dd_sketch_buffer", "dd_sketch_fasta", "dd_sketch_files", "dd_inflate_files", "dd_last_ingest_stats", "dd_sketch_device", "dd_union", "dd_union_device",
     "dd_card", "dd_card_batch", "dd_card_batch_device", "dd_hist_batch_device", "dd_ertl_mle",
-    "dd_progressive", "dd_progressive_device", "dd_pairwise", "dd_pairwise_device",
+    "dd_progressive", "dd_progressive_device", "dd_pairwise", "dd_pairwise_device", "dd_leave_out", "dd_leave_out_device",
     "dd_exact_count", "dd_exact_count_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
@@ -128,6 +128,10 @@ def load_library(path=None):
     lib.dd_pairwise.argtypes = [vp, vp, i32, i32, vp]
     lib.dd_pairwise_device.restype = i32
     lib.dd_pairwise_device.argtypes = [vp, vp, i32, i32, vp]
+    lib.dd_leave_out.restype = i32
+    lib.dd_leave_out.argtypes = [vp, vp, i32, i32, vp, i32, vp]
+    lib.dd_leave_out_device.restype = i32
+    lib.dd_leave_out_device.argtypes = [vp, vp, i32, i32, vp, i32, vp]
     lib.dd_exact_count.restype = i32
     lib.dd_exact_count.argtypes = [vp, C.POINTER(C.c_char_p), i32, i32, C.POINTER(u64)]
     lib.dd_exact_count_device.restype = i32
@@ -437,6 +441,25 @@ class Engine:
     def pairwise_device(self, leaf_ptr, n, K):
         card = np.empty((n, n, K), dtype=np.float64)
         self._check(self._lib.dd_pairwise_device(self._ctx, C.c_void_p(int(leaf_ptr)), n, K, card.ctypes.data))
+        return card
+
+    def leave_out(self, leaf, group, ngroups=None):
+        """leaf [n][K][m] uint8 (host), group [n] int (-1: in every union) -> card [G+1][K] float64: row g the union of the
+        leaves outside group g, row G the union of all.  G = max(group) + 1 unless given."""
+        leaf = _u8(leaf)
+        n, K = leaf.shape[0], leaf.shape[1]
+        grp = np.ascontiguousarray(group, dtype=np.int32).reshape(n)
+        ngroups = int(grp.max()) + 1 if ngroups is None else int(ngroups)
+        card = np.empty((max(ngroups, 0) + 1, K), dtype=np.float64)
+        self._check(self._lib.dd_leave_out(self._ctx, leaf.ctypes.data, n, K, grp.ctypes.data, ngroups, card.ctypes.data))
+        return card
+
+    def leave_out_device(self, leaf_ptr, n, K, group, ngroups=None):
+        grp = np.ascontiguousarray(group, dtype=np.int32).reshape(n)
+        ngroups = int(grp.max()) + 1 if ngroups is None else int(ngroups)
+        card = np.empty((max(ngroups, 0) + 1, K), dtype=np.float64)
+        self._check(self._lib.dd_leave_out_device(self._ctx, C.c_void_p(int(leaf_ptr)), n, K, grp.ctypes.data, ngroups,
+                                                  card.ctypes.data))
         return card
 
     # -- exact distinct k-mer count (KMC stand-in) ----------------------------------------

@@ -493,6 +493,18 @@ class HipBackend:
         ords = perm[np.asarray(orderings, dtype=np.int64).reshape(-1, len(leaf_paths))]
         return self.engine.progressive_device(ptr, len(leaf_paths), len(leaf_paths[0]), ords)
 
+    def leave_out_cards(self, leaf_paths, group):
+        """|union of every leaf whose group != g| for g < G, and the union of all leaves as row G: float64 [G+1][K].
+        group[i] = -1: leaf i is in every union.  The rows are indexed by group, whatever order the slab keeps the leaves in."""
+        group = np.asarray(group, dtype=np.int64).reshape(len(leaf_paths))
+        ngroups = int(group.max()) + 1
+        ptr, perm = self._device_slab(leaf_paths)
+        if ptr is None:
+            return self.engine.leave_out(self._leaf_slab(leaf_paths), group, ngroups)
+        slab_group = np.empty_like(group)
+        slab_group[perm] = group                         # slab row perm[i] holds the caller's leaf i
+        return self.engine.leave_out_device(ptr, len(leaf_paths), len(leaf_paths[0]), slab_group, ngroups)
+
     def close(self):
         if self._dev is not None:
             self.engine.device_free(self._dev[1])

@@ -1,4 +1,4 @@
-"""`dandd tree | progressive | kij` on the MI355X engine: same sub-commands, flags, defaults and
+"""`dandd tree | progressive | kij | deltadelta` on the MI355X engine: same sub-commands, flags, defaults and
 output files as /root/reference/lib/dandd_cmd.py (flags :141-286, handlers :43-132); only the
 sketching backend differs.  Run as  python -m dandd_amd.host.cli <subcommand> ...
 """
@@ -105,6 +105,82 @@ def kij_command(args):
     if args.afproject:
         with open(outfile + "_AFtuples.pickle", "wb") as f:
             pickle.dump(tree.prepare_AFproject(kij_rows, j_rows), f)
+
+
+def _deltadelta_groups(tree, args):
+    """-> (groups as lists of leaf FASTAs, their labels) from -f / -g, or every leaf on its own in tree order"""
+    leaves = tree.leaf_nodes()
+    by_name = {}
+    for leaf in leaves:
+        f = leaf.fastas[0]
+        for key in {f, os.path.abspath(f)}:
+            by_name[key] = f
+    base_count = {}
+    for leaf in leaves:
+        b = os.path.basename(leaf.fastas[0])
+        base_count[b] = base_count.get(b, 0) + 1
+    for leaf in leaves:
+        b = os.path.basename(leaf.fastas[0])
+        if base_count[b] == 1:
+            by_name.setdefault(b, leaf.fastas[0])
+
+    def leaf_of(name):
+        f = by_name.get(name) or by_name.get(os.path.abspath(name))
+        if f is None:
+            sys.exit(f"deltadelta: {name} is not a leaf of the tree {args.delta_tree}")
+        return f
+
+    def lines(path):
+        with open(path) as fh:
+            return [line.rstrip("\n") for line in fh if line.strip()]
+
+    if args.flist_loc and args.groups_loc:
+        sys.exit("deltadelta: -f/--fastas and -g/--groups are mutually exclusive")
+    if args.groups_loc:
+        groups, labels = [], []
+        for n, line in enumerate(lines(args.groups_loc), 1):
+            parts = line.split("\t")
+            if len(parts) != 2 or not parts[0].strip() or not parts[1].strip():
+                sys.exit(f"deltadelta: {args.groups_loc}:{n}: expected 'fasta<TAB>group', found {line!r}")
+            f, label = leaf_of(parts[0].strip()), parts[1].strip()
+            if label not in labels:
+                labels.append(label)
+                groups.append([])
+            groups[labels.index(label)].append(f)
+        return groups, labels
+    if args.flist_loc:
+        seen, groups = set(), []
+        for name in lines(args.flist_loc):
+            f = leaf_of(name.strip())
+            if f not in seen:
+                seen.add(f)
+                groups.append([f])
+    else:
+        groups = [[leaf.fastas[0]] for leaf in leaves]
+    title = {leaf.fastas[0]: leaf.node_title for leaf in leaves}
+    return groups, [title[g[0]] for g in groups]
+
+
+def deltadelta_command(args):
+    """How much each genome (or group of genomes) adds to the collection's delta: delta(all) - delta(all but it), the quantity
+    of the reference's DeltaTree.find_delta_delta (lib/huffman_dandd.py:559-566), for every group in one command."""
+    tree = _load_tree(args.delta_tree)
+    tree.speciesinfo.update(tool=tree.experiment["tool"])
+    if not args.tag:
+        args.tag = tree.speciesinfo.tag
+    outfile = tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
+    groups, labels = _deltadelta_groups(tree, args)
+    os.makedirs(args.outdir, exist_ok=True)
+    window = (int(args.mink), int(args.maxk)) if args.ksweep else (None, None)
+    try:
+        rows, summary = tree.leave_out_deltas(groups, *window, labels=labels)
+    except ValueError as e:
+        sys.exit(f"deltadelta: {e}")
+    write_listdict_to_csv(outfile + ".deltadelta.csv", rows)
+    if summary:
+        write_listdict_to_csv(outfile + "_deltadeltasummary.csv", summary)
+    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
+    tree.speciesinfo.save_references(fast=False)
 
 
 def serve_command(args):
@@ -260,6 +336,18 @@ def build_parser():
     k.add_argument("--afproject", dest="afproject", default=False, action="store_true")
     k.add_argument("--jaccard", dest="jaccard", default=False, action="store_true")
     k.set_defaults(func=kij_command)
+
+    dd = subs.add_parser("deltadelta", parents=[common, sweep],
+                         description="delta(all) - delta(all but a genome or group): each one's contribution")
+    dd.add_argument("-d", "--dtree", dest="delta_tree", required=True)
+    dd.add_argument("-s", "--tag", dest="tag", type=str)
+    dd.add_argument("-f", "--fastas", dest="flist_loc", default=None, type=str,
+                    help="leave each listed FASTA out on its own (default: every leaf); the others stay in every union")
+    dd.add_argument("-g", "--groups", dest="groups_loc", default=None, type=str,
+                    help="'fasta<TAB>group' lines: each group left out as a whole; unlisted leaves stay in every union")
+    dd.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
+    dd.add_argument("-l", "--label", dest="label", default="")
+    dd.set_defaults(func=deltadelta_command)
 
     # (not in the reference: its every command is a fresh process that shells out to fresh `dashing` processes)
     sv = subs.add_parser("serve", description="keep the GPU context alive and run the commands dandd_amd.host.client forwards")

@@ -858,6 +858,117 @@ class DeltaTree:
         for node in self._dt:
             node.node_ksweep(mink=mink, maxk=maxk)
 
+    # ---- relative contributions: delta(all) - delta(all but a group) (lib/huffman_dandd.py:559-566) ---------------------
+    def leave_out_deltas(self, groups, mink=None, maxk=None, labels=None):
+        """One row per group of leaf FASTAs (`groups`, in order): delta_all - delta_rest, where `rest` is every leaf of the tree
+        outside the group (leaves in no group are in every `rest`).
+          * Hill-climb (no window: neither mink/maxk nor the tree's --ksweep): exactly what find_delta_delta(group) would give,
+            called group after group -- the same climb from speciesinfo.kstart, which each climb moves for the next --, with
+            delta_all the tree's own root delta.
+          * A window [mink, maxk] (given, or the tree's --ksweep): the reference has no delta for a union there (SubSpider.delta
+            stays None), so delta here is max over k in the window of card / k, ties going to the larger k (the climb's `<=`),
+            for the rest and, by the same rule, for the union of all leaves.  Per-k rows come back too.
+        With a backend that has leave_out_cards (the GPU) every complement at every k of a window comes from ONE launch over the
+        leaf slab and the climbs walk that table (_FlatUnion), falling back to files where a climb leaves it; otherwise (exact
+        trees, the CPU checkers) each group goes through SubSpider / find_delta_delta on the object path.
+        -> (rows, per-k rows)"""
+        leaves = self.leaf_nodes()
+        by_fasta = {leaf.fastas[0]: leaf for leaf in leaves}
+        groups = [list(g) for g in groups]
+        owner = {}
+        for gi, g in enumerate(groups):
+            if not g:
+                raise ValueError(f"group {gi + 1} is empty")
+            for f in g:
+                if f not in by_fasta:
+                    raise ValueError(f"{f} is not a leaf of this tree")
+                if owner.setdefault(f, gi) != gi:
+                    raise ValueError(f"{f} is in more than one group")
+            if len(set(g)) == len(leaves):
+                raise ValueError(f"group {gi + 1} holds every leaf of the tree: there is nothing left to compare with")
+        labels = list(labels) if labels is not None else [str(i + 1) for i in range(len(groups))]
+        if mink is None or maxk is None:
+            window = self.experiment["ksweep"]
+        else:
+            window = (int(mink), int(maxk))
+        exp = dict(self.experiment, ksweep=tuple(int(v) for v in window) if window is not None else None)
+        be = backend_for(exp)
+        sched = None
+        if hasattr(be, "leave_out_cards") and exp.get("tool") != "kmc" and not exp.get("safety") \
+                and not os.environ.get("DD_NO_PREFETCH"):
+            if window is not None:
+                lo, hi = exp["ksweep"]
+            else:   # the window progressive_union takes: the climbs stay within a few k of the leaves' and the root's argmax
+                lo = max(1, min(leaf.bestk for leaf in leaves) - 2)
+                hi = self.root_k() + 3
+                if exp["tool"] == "dashing":
+                    hi = min(hi, 32)
+            lo = max(1, int(lo))
+            if hi >= lo:
+                group_of = [owner.get(leaf.fastas[0], -1) for leaf in leaves]
+                paths = self._leaf_files(leaves, lo, int(hi))
+                sched = (be.leave_out_cards(paths, group_of), lo, int(hi))
+        rows, summary = [], []
+        full = None
+        for gi, g in enumerate(groups):
+            out = set(g)
+            kids = [leaf for leaf in leaves if leaf.fastas[0] not in out]     # tree order, as nodes_from_fastas gives them
+            row = {"group": labels[gi], "fastas": "|".join(f for f in self.fastas if f in out),
+                   "nout": len(out), "ngen_rest": len(kids)}
+            if window is None:
+                if sched is None:
+                    # find_delta_delta's own steps, keeping the spider it builds (its result is `self - small`)
+                    small = SubSpider(self.nodes_from_fastas([f for f in self.fastas if f not in out]), self.speciesinfo, exp)
+                    print("Full Tree Delta: ", self.delta)
+                    print("Subtree Delta: ", small.delta)
+                    row["deltadelta"] = self - small
+                    row["delta_rest"], row["k_rest"] = small.delta, small.root_k()
+                else:
+                    sub = self._leave_out_union(kids, exp, sched, gi)
+                    sub.find_delta(self.speciesinfo.kstart)       # SubSpider.__init__ ...
+                    sub.fill()                                    # ... and its fill_tree
+                    print("Full Tree Delta: ", self.delta)
+                    print("Subtree Delta: ", sub.delta)
+                    print("Larger Tree Delta: ", self.delta)
+                    print("Subtree Delta: ", sub.delta)
+                    print("Subtraction Result: ", self.delta - sub.delta)
+                    row["deltadelta"] = self.delta - sub.delta
+                    row["delta_rest"], row["k_rest"] = sub.delta, sub.bestk
+                row["delta_all"], row["k_all"] = self.delta, self.root_k()
+            else:
+                lo, hi = exp["ksweep"]
+                ks = list(range(max(1, lo), hi + 1))
+                if sched is None:
+                    if full is None:
+                        full_tree = SubSpider(leaves, self.speciesinfo, exp)
+                        full = [full_tree.root.ksketches[k].card for k in ks]
+                    small = SubSpider(kids, self.speciesinfo, exp)
+                    rest = [small.root.ksketches[k].card for k in ks]
+                else:
+                    if full is None:
+                        full = [float(v) for v in sched[0][len(groups)]]
+                    sub = self._leave_out_union(kids, exp, sched, gi)
+                    sub.node_ksweep(lo, hi)
+                    rest = [sub.card(k) for k in ks]
+                row["delta_all"], row["k_all"] = _window_delta(full, ks)
+                row["delta_rest"], row["k_rest"] = _window_delta(rest, ks)
+                row["deltadelta"] = row["delta_all"] - row["delta_rest"]
+                for k, a, r in zip(ks, full, rest):
+                    summary.append({"group": labels[gi], "kval": k, "card_all": a, "card_rest": r, "delta_pos_rest": r / k})
+            rows.append(row)
+        return rows, summary
+
+    def _leave_out_union(self, kids, experiment, sched, gi):
+        """The union of `kids` (the complement of group gi) as a _FlatUnion over the leave-out table, its cardinalities stored
+        in the cache under the names its union sketches would have (as `kij`'s schedule does).  One kid: its own files."""
+        table, lo, hi = sched
+        sub = _FlatUnion(self, kids, experiment, table[gi] if len(kids) > 1 else None, lo, hi)
+        if sub.row is not None:
+            cards = self.speciesinfo.cardkey
+            for kk, k in enumerate(range(lo, hi + 1)):
+                cards[sub.tmpl.with_k(k)] = float(sub.row[kk])
+        return sub
+
     # ---- batched GPU union schedules ------------------------------------------------------------------
     def _leaf_files(self, leaves, lo, hi):
         """Make sure every leaf has its sketch file for k in [lo, hi] (one fused GPU pass per leaf)
@@ -1152,6 +1263,15 @@ def write_phylip(tuples, path, k=0):
         for i, a in enumerate(names):
             print(" ".join(map(str, [a] + [recs[(a, b)] for b in names[:i]])), file=f)
     return names
+
+
+def _window_delta(cards, ks):
+    """delta over a k window: max of card / k, ties going to the larger k (the hill-climb's `<=`) -> (delta, k)"""
+    best, bestk = 0, 0
+    for c, k in zip(cards, ks):
+        if best <= c / k:
+            best, bestk = c / k, k
+    return best, bestk
 
 
 class SubSpider(DeltaTree):

@@ -128,6 +128,19 @@ int dd_pairwise(dd_ctx *, const uint8_t *leaf /*[n][K][m]*/, int n, int K,
                 double *card /*[n][n][K]*/);
 int dd_pairwise_device(dd_ctx *, const uint8_t *leaf_dev, int n, int K, double *card);
 
+/* ---- leave-out unions ------------------------------------------------------------
+ * Replaces the (n-1)-way unions of DeltaTree.find_delta_delta (lib/huffman_dandd.py:559-566), one per
+ * left-out set and climb step:
+ * card[g][kk] = |union of every leaf whose group != g| at k = kmin+kk, for g < ngroups; card[ngroups][kk] = |union of all|.
+ * group[i] == -1: the leaf is in every union and is never left out.  A group that holds every leaf is an error.
+ * One read of the slab: per register the largest value, a group that holds it and the largest value outside that
+ * group give every complement's histogram as integer corrections of the full union's (dd_leaveout.hip): the same
+ * integers as a byte-max + histogram per complement.  ngroups <= n.  Register bytes must be <= 63. */
+int dd_leave_out(dd_ctx *, const uint8_t *leaf /*[n][K][m]*/, int n, int K,
+                 const int32_t *group /*[n]*/, int ngroups, double *card /*[ngroups+1][K]*/);
+int dd_leave_out_device(dd_ctx *, const uint8_t *leaf_dev, int n, int K,
+                        const int32_t *group, int ngroups, double *card);
+
 /* ---- exact distinct k-mer count (the KMC stand-in) --------------------------------------
  * Replaces   kmc -ci1 -cs2 -k<K> [-b] -fm <fasta> <db> <tmp>   +   kmc_tools complex (set union)
  * +   kmc_tools info <db> | grep 'total k-mers'   (lib/sketch_classes.py:395,444-448,453-465):

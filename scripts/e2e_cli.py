@@ -1,4 +1,4 @@
-"""End-to-end timing of the drop-in CLI (tree -> progressive -> kij) on synthetic genomes written as
+"""End-to-end timing of the drop-in CLI (tree -> progressive -> kij -> deltadelta) on synthetic genomes written as
 FASTA files, i.e. everything a DandD user pays for: Python start-up, file reads, H2D copies, K0..K3,
 the host-side tree / spider logic, pickles and CSVs.  Development aid, not the contract bench.
 
@@ -125,6 +125,7 @@ def measure(args, run, cli, gdir, out, sweep, timings):
     run("tree_again_cached", cli + ["tree", "-d", gdir, "-o", out, "-s", "e2e", "-r", str(args.registers)] + sweep)
     run("progressive", cli + ["progressive", "-d", dtree, "-o", out, "-n", str(args.norderings)] + sweep)
     run("kij", cli + ["kij", "-d", dtree, "-o", out] + (["--jaccard"] + sweep if sweep else []))
+    run("deltadelta", cli + ["deltadelta", "-d", dtree, "-o", out] + sweep)
 
 
 
