@@ -1,0 +1,170 @@
+// dd_ctx.h -- the context behind the C ABI's opaque dd_ctx, and the host-side helpers the ABI's sources share
+// (dd_api.hip: sketch, union, card, K2, comm; dd_ingest.hip: the file-ingestion pipeline).  Callers see dandd_hip.h only.
+#pragma once
+#include "../../include/dandd_hip.h"
+#include <sched.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+#include <string>
+#include <thread>
+#include <vector>
+#include "dd_common.h"
+#include "dd_io.h"
+#include "dd_kernels.h"
+#include "dd_plan.h"
+
+// the calling thread's last error (dd_last_error); ONE object for the whole library (defined in dd_api.hip)
+extern thread_local std::string g_err;
+inline int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt), vsnprintf(buf, sizeof buf, fmt, ap), va_end(ap);
+    g_err = buf;
+    return code;
+}
+#define DD_HIP(expr)                                                                                                     \
+    do {                                                                                                                 \
+        hipError_t e_ = (expr);                                                                                          \
+        if (e_ != hipSuccess) return fail(DD_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+// grow-only allocations: device memory (DevBuf) and pinned host staging (HostBuf)
+template <bool Host>
+struct GrowBuf {
+    void* p = nullptr; size_t cap = 0;
+    int reserve(size_t n) {
+        if (n <= cap) return DD_OK;
+        release();
+        size_t want = n + n / 8 + 256;
+        if ((Host ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want)) != hipSuccess) {
+            p = nullptr;
+            return fail(DD_ENOMEM, Host ? "hipHostMalloc(%zu) failed" : "hipMalloc(%zu) failed", want);
+        }
+        cap = want;
+        return DD_OK;
+    }
+    void release() {
+        if (p) (void)(Host ? hipHostFree(p) : hipFree(p));
+        p = nullptr, cap = 0;
+    }
+};
+using DevBuf = GrowBuf<false>;
+using HostBuf = GrowBuf<true>;
+struct TimedSpan { hipEvent_t a, b; };
+
+// One of the ingestion pipeline's two buffer sets (batch b uses set b & 1): FASTA bytes in, register slabs out, a pinned
+// bounce buffer for the results, the device decoders' inputs and tables, and the set's three events.
+struct PipeSet {
+    DevBuf fasta, regs; HostBuf out;
+    // BGZF files inflated on the device (dd_ginflate.hip): compressed bytes, block table and error count of a batch
+    DevBuf gz, jobs, err; HostBuf jobs_host, err_host;
+    // single-member gzip files inflated on the device: symbols, windows, the piece tables (RawFile[], starts, lens, offs,
+    // chunk0, crcs) and their host copies
+    DevBuf sym, win, raw; HostBuf raw_host, crc_host;
+    // kseq's record rules over device-inflated texts (dd_fastq.hip): the batch's TextJob table, newline counts and positions
+    DevBuf txt; HostBuf txt_host;
+    hipEvent_t h2d = nullptr, done = nullptr, d2h = nullptr;
+    void release() {
+        for (DevBuf* b : {&fasta, &regs, &gz, &jobs, &err, &sym, &win, &raw, &txt}) b->release();
+        for (HostBuf* b : {&out, &jobs_host, &err_host, &raw_host, &crc_host, &txt_host}) b->release();
+        for (hipEvent_t* e : {&h2d, &done, &d2h})
+            if (*e) (void)hipEventDestroy(*e), *e = nullptr;
+    }
+};
+
+// The ingestion pipeline's state on a context (dd_sketch_files, dd_ingest.hip): pinned host buffers for the loader
+// threads, a copy stream, two buffer sets, and what the device decoders' refusals have decided
+struct IngestState {
+    std::vector<dd::FileBuf*> file_pool;
+    hipStream_t copy_stream_b = nullptr;  // device-inflated batches alternate between two: a launch of the inflate kernel is as long as ONE block takes, two in flight hide each other
+    hipStream_t copy_stream = nullptr, out_stream = nullptr;  // H2D and D2H on streams of their own: an in-order stream would park batch b+1's upload behind batch b's results
+    PipeSet pipe[2];
+    bool no_gpu_inflate = false;   // this context inflates on the host (set for the retry of a call, for good after three)
+    int inflate_refusals = 0;      // calls in which the device decoder refused a block
+    bool inflate_retry = false;    // ... and the call that met it is run again
+    bool inflate_retry_counts = false;   // ... and counts towards the three strikes (a size mismatch or a lack of device memory does not:
+                                         //     the decoder did its work, the FILE -- damaged trailer, two members, text beyond 4 GiB -- is not for it)
+    // dd_inflate_files: the text of every file of the running dd_sketch_files pass, as K0 is about to read it, goes here
+    struct TextSink { uint8_t* const* out; const size_t* caps; size_t* lens; bool short_buffer; };
+    TextSink* text_sink = nullptr;
+    int calls = 0;                // dd_sketch_files calls; ms: the last one's wall, waiting for loaders, batches, bytes (as a double)
+    double ms[4] = {0, 0, 0, 0};
+    void release() {
+        for (dd::FileBuf*& fb : file_pool) delete fb, fb = nullptr;
+        for (PipeSet& s : pipe) s.release();
+        for (hipStream_t* s : {&copy_stream, &copy_stream_b, &out_stream})
+            if (*s) (void)hipStreamDestroy(*s), *s = nullptr;
+    }
+};
+
+struct dd_ctx {
+    int device = 0, p = 14, canonical = 1;
+    hipStream_t stream = nullptr;
+    bool timing = false;
+    std::vector<TimedSpan> spans[DD_KERNEL_COUNT];
+    std::vector<hipEvent_t> pool;
+    // workspaces
+    DevBuf tokens, scratch, tables, fasta, regs, ptrs, hist, est, ord, bitmaps, bigmaps, exact, buckets, gram, synth;
+    HostBuf stage, stage_jobs, stage_rows;  // genome/pack tables and K1 job tables are uploaded in two steps
+    // the job tables of the last few sketch calls: a call over genomes of the same sizes and the same k range (a
+    // pipeline sketching batches of a few recurring shapes, a benchmark loop) reuses them, on the host and in HBM
+    struct PlanEntry {
+        bool valid = false;
+        int kmin = 0, kmax = 0;
+        std::vector<size_t> sizes;
+        dd::PlanKnobs knobs;
+        std::vector<dd::SweepClass> classes;
+        std::vector<size_t> job_off;
+        DevBuf jobtab;
+        unsigned long long last_use = 0;
+    };
+    PlanEntry plans[8];
+    unsigned long long plan_clock = 0;
+    hipEvent_t stage_free = nullptr;  // signalled when the last upload from `stage` completed
+    // a second set of staging buffers: dd_sketch_device alternates, so that a call can be issued while the uploads of
+    // the call before it are still queued behind work of other streams (the ingestion pipeline issues batch b + 1
+    // while batch b waits for its files to be copied or inflated)
+    HostBuf stage_alt, stage_jobs_alt, stage_rows_alt;
+    hipEvent_t stage_free_alt = nullptr;
+    IngestState ingest;  // dd_sketch_files
+    hipStream_t side[8] = {};  // k classes of a small call run side by side
+    hipEvent_t side_done[8] = {}, side_go = nullptr;
+    // HBM the record streams of one log2m >= 17 call may take: a sixth of the device (48 GiB of 288), 16 GiB at least
+    size_t bucket_budget = (size_t)16 << 30;
+    // stats of the last sketch call
+    uint64_t st_tokens = 0, st_updates = 0;
+    int st_blocks = 0;
+    int k2_path = 0;  // DD_K2_*: what the last progressive / pairwise call ran
+    // multi-GPU (dd_comm_*): this context's rank in an RCCL communicator, one context = one process = one GPU
+    void* comm = nullptr;
+    int comm_rank = 0, comm_world = 1;
+    unsigned long long comm_calls[2] = {0, 0};   // all-reduces, all-gathers issued
+};
+struct DeviceGuard {  // the context's device for the scope of a call
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        (void)hipGetDevice(&prev);
+        if (prev != dev) (void)hipSetDevice(dev);
+        else prev = -1;
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// CPUs this process may really use: the affinity mask capped by the cgroup quota (a container that shows
+// 256 logical CPUs behind a 16-CPU quota must not get 256 loader threads)
+inline int usable_cpus() {
+    int n = (int)std::max(1u, std::thread::hardware_concurrency());
+    cpu_set_t set;
+    if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::max(1, CPU_COUNT(&set));
+    if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
+        char quota[32];
+        long period = 0;
+        if (fscanf(f, "%31s %ld", quota, &period) == 2 && strcmp(quota, "max") != 0 && period > 0)
+            n = std::min(n, std::max(1, (int)(atol(quota) / period)));
+        fclose(f);
+    }
+    return n;
+}
+inline int check_ctx(dd_ctx* c) { return c ? DD_OK : fail(DD_EINVAL, "null context"); }
