@@ -354,29 +354,14 @@ class HipBackend:
     def _seed_device_slab(self, leaf_paths, regs):
         """A resident server that has just sketched a collection leaves its leaf slab in HBM (_device_slab's layout and key): the
         `progressive` / `kij` that follow find it there."""
-        n, K = len(leaf_paths), len(leaf_paths[0])
-        nbytes = (n * K) << self.log2m
-        limit = int(os.environ.get("DANDD_DEVICE_CACHE_MB", "16384")) << 20
-        if nbytes > limit or not hasattr(self.engine, "device_alloc"):
+        order, key = self._device_slab_key(leaf_paths)
+        if order is None:
             return
-        order = sorted(range(n), key=lambda i: leaf_paths[i][0])
-        key = []
-        for i in order:
-            for p in leaf_paths[i]:
-                st = os.stat(p)
-                key.append((os.path.abspath(p), st.st_size, st.st_mtime_ns))
-        if self._dev is None or self._dev[2] < nbytes:
-            if self._dev is not None:
-                self.engine.device_free(self._dev[1])
-                self._dev = None
-            ptr, cap = self.engine.device_alloc(nbytes), nbytes
-        else:
-            ptr, cap = self._dev[1], self._dev[2]
-        self._dev = None
-        per_leaf = K << self.log2m
+        per_leaf = len(leaf_paths[0]) << self.log2m
+        ptr, cap = self._device_buffer(len(order) * per_leaf)
         for rank, i in enumerate(order):
             self.engine.device_upload(ptr + rank * per_leaf, regs[i])
-        self._dev = (tuple(key), ptr, cap)
+        self._dev = (key, ptr, cap)
 
     def union(self, in_paths, out_path):
         cold = [p for p in in_paths if p not in self._recent]
@@ -445,37 +430,50 @@ class HipBackend:
         0.13 s + 0.06 s of a 0.55 s command).  The copy is trusted only while every file still has the absolute path, size and
         modification time it had when it was loaded; DANDD_DEVICE_CACHE_MB bounds it (default 16384, 0 = off).
         -> (device address, permutation), or (None, None) (too large: the caller goes through host memory)"""
-        n, K = len(leaf_paths), len(leaf_paths[0])
-        nbytes = (n * K) << self.log2m
+        order, key = self._device_slab_key(leaf_paths)
+        if order is None:
+            return None, None
+        perm = np.empty(len(order), dtype=np.int64)
+        perm[order] = np.arange(len(order))              # caller's leaf i is row perm[i] of the slab
+        if self._dev is not None and self._dev[0] == key:
+            return self._dev[1], perm
+        slab = self._leaf_slab([leaf_paths[i] for i in order])
+        ptr, cap = self._device_buffer(slab.nbytes)
+        self.engine.device_upload(ptr, slab)
+        self._dev = (key, ptr, cap)
+        return ptr, perm
+
+    def _device_slab_key(self, leaf_paths):
+        """-> (order, key) of the leaf slab in HBM: its rows are the caller's leaves in `order`, and the copy is trusted while
+        `key` -- (absolute path, size, mtime) of every file, row by row -- stands.  (None, None) when the slab is over
+        DANDD_DEVICE_CACHE_MB or the engine cannot keep device memory."""
+        nbytes = (len(leaf_paths) * len(leaf_paths[0])) << self.log2m
         limit = int(os.environ.get("DANDD_DEVICE_CACHE_MB", "16384")) << 20
         if nbytes > limit or not hasattr(self.engine, "device_alloc"):
             return None, None
         # (the slab is kept in the order of its rows' first paths, whatever order the caller lists the leaves in: `progressive`
         # names them in its first ordering's order, `kij` in the tree's -- the same files, one copy)
-        order = sorted(range(n), key=lambda i: leaf_paths[i][0])
-        perm = np.empty(n, dtype=np.int64)
-        perm[order] = np.arange(n)                       # caller's leaf i is row perm[i] of the slab
-        rows = [leaf_paths[i] for i in order]
+        order = sorted(range(len(leaf_paths)), key=lambda i: leaf_paths[i][0])
         key = []
-        for row in rows:
-            for p in row:
+        for i in order:
+            for p in leaf_paths[i]:
                 st = os.stat(p)
                 key.append((os.path.abspath(p), st.st_size, st.st_mtime_ns))
-        key = tuple(key)
-        if self._dev is not None and self._dev[0] == key:
-            return self._dev[1], perm
-        slab = self._leaf_slab(rows)
-        if self._dev is None or self._dev[2] < nbytes:
+        return order, tuple(key)
+
+    def _device_buffer(self, nbytes):
+        """-> (address, capacity) of device memory for a slab of nbytes: the held buffer when it is large enough, else a new one
+        in its place.  Whatever the held buffer said is forgotten (not trusted while it is being overwritten); the caller sets
+        self._dev once its upload is done."""
+        if self._dev is not None and self._dev[2] >= nbytes:
+            ptr, cap = self._dev[1], self._dev[2]
+        else:
             if self._dev is not None:
                 self.engine.device_free(self._dev[1])
                 self._dev = None
             ptr, cap = self.engine.device_alloc(nbytes), nbytes
-        else:
-            ptr, cap = self._dev[1], self._dev[2]
-        self._dev = None                       # (not trusted while it is being overwritten)
-        self.engine.device_upload(ptr, slab)
-        self._dev = (key, ptr, cap)
-        return ptr, perm
+        self._dev = None
+        return ptr, cap
 
     def pairwise_cards(self, leaf_paths):
         """|leaf_i U leaf_j| for all pairs and every k column: float64 [n][n][K]"""

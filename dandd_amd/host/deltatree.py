@@ -19,6 +19,7 @@ import os
 import weakref
 import pickle
 import sys
+from collections import namedtuple
 from itertools import permutations
 from math import factorial
 from random import sample, shuffle
@@ -354,7 +355,44 @@ def sketch_class(experiment):
 
 
 # ---------------------------------------------------------------------------------------------
-class DeltaTreeNode:
+class _Climber:
+    """The argmax-k local search of a union (lib/huffman_dandd.py:106-146) and its per-k summary rows, shared by DeltaTreeNode
+    (sketch objects) and _FlatUnion (a row of a union table).  A subclass gives _climb_step(k) -- bring k-1..k+1 up to date,
+    -> card / k at k -- and _summary_cells(k) -> (card, delta_pos, command)."""
+
+    def find_delta_helper(self, kval, direction=1):
+        while True:
+            if self.experiment["tool"] == "dashing" and kval > 32 and not self.experiment.get("allow_k64"):
+                raise ValueError("Exploratory k value is too high for dashing. Either something is amiss "
+                                 "with your data or you need to be using --exact mode")
+            if kval < 1:
+                return
+            candidate = self._climb_step(kval)
+            if direction < 0:
+                self.mink = kval
+            else:
+                self.maxk = kval
+            if not self.delta <= candidate:  # ties keep climbing
+                return
+            self.speciesinfo.kstart = kval
+            self.bestk = kval
+            self.delta = candidate
+            kval += direction
+
+    def find_delta(self, kval):
+        self.find_delta_helper(kval, 1)
+        self.find_delta_helper(kval, -1)
+
+    def summarize(self, mink=0, maxk=0, ordering_number=0):
+        rows = []
+        for k in range(mink, maxk + 1):
+            card, delta_pos, command = self._summary_cells(k)
+            rows.append({"ngen": self.ngen, "kval": k, "card": card, "delta_pos": delta_pos,
+                         "title": self.node_title, "command": command, "ordering": ordering_number})
+        return rows
+
+
+class DeltaTreeNode(_Climber):
     def __init__(self, node_title, children, speciesinfo, experiment, progeny=None):
         self.experiment = experiment
         self.speciesinfo = speciesinfo
@@ -464,65 +502,62 @@ class DeltaTreeNode:
                 self.update_node(k)
         self.mink, self.maxk = mink, maxk
 
-    # ---- argmax-k local search (lib/huffman_dandd.py:106-146) --------------------------------------
-    def find_delta_helper(self, kval, direction=1):
-        if self.experiment["tool"] == "dashing" and kval > 32 and not self.experiment.get("allow_k64"):
-            raise ValueError("Exploratory k value is too high for dashing. Either something is amiss "
-                             "with your data or you need to be using --exact mode")
-        if kval < 1:
-            return
+    # ---- argmax-k local search (_Climber) ----------------------------------------------------------
+    def _climb_step(self, kval):
         self._grow(kval + 1)
         self.node_ksweep(mink=kval - 1, maxk=kval + 1)
         self.update_node(kval)
-        if direction < 0:
-            self.mink = kval
-        else:
-            self.maxk = kval
-        candidate = self.ksketches[kval].delta_pos
-        if self.delta <= candidate:  # ties keep climbing
-            self.speciesinfo.kstart = kval
-            self.bestk = kval
-            self.delta = candidate
-            self.find_delta_helper(kval + direction, direction)
+        return self.ksketches[kval].delta_pos
 
     def find_delta(self, kval):
-        self.find_delta_helper(kval, 1)
-        self.find_delta_helper(kval, -1)
+        super().find_delta(kval)
         self.card = self.ksketches[self.bestk].card
 
-    def summarize(self, mink=0, maxk=0, ordering_number=0):
-        rows = []
-        for k in range(mink, maxk + 1):
-            s = self.ksketches[k]
-            rows.append({"ngen": self.ngen, "kval": k, "card": s.card, "delta_pos": s.delta_pos,
-                         "title": self.node_title, "command": s.cmd, "ordering": ordering_number})
-        return rows
+    def _summary_cells(self, k):
+        s = self.ksketches[k]
+        return s.card, s.delta_pos, s.cmd
 
 
 # ---------------------------------------------------------------------------------------------
-class _FlatUnion:
-    """The body node of a SubSpider as NUMBERS.  When a whole union schedule has come back from the GPU as one table of
-    cardinalities (prefetch_union_cards: every pair x k of `kij`, every prefix x k of `progressive`), a SubSpider per pair or
-    prefix -- a DeltaTreeNode, a Sketch object and a SketchPath per (set, k), 76 608 of them for 64 genomes -- computes nothing:
-    it walks dictionaries.  This class goes through the same steps on the table itself -- find_delta / find_delta_helper with
-    their `<=` ties and the kstart they move (lib/huffman_dandd.py:106-146), node_ksweep's k-1..k+1 window (:117), fill_tree's
-    update_node of every bestk (:451-457), summarize (:289-301) -- and leaves the same traces a tree save reads: the base names in
-    the experiment's base set, their sketchinfo entries, the ngen*/k* directories.  A k outside the table goes through the
-    file-based backend (leaf sketches, union, card) as the object path does."""
+# Cardinalities of a whole union schedule from one GPU launch, k in [lo, hi] along the last axis: table[i, j] for the pair of
+# leaves i, j (`kij`), table[o, j] for the first j+1 leaves of ordering o (`progressive`), table[g] for every leaf outside group g
+# (`deltadelta`).  index: id(leaf) -> its number in the table; orders: ordering as a tuple of leaf numbers -> o.
+UnionTable = namedtuple("UnionTable", "table lo hi index orders", defaults=(None, None))
 
-    def __init__(self, tree, kids, experiment, table_row, lo, hi):
+
+def _cache_row(cards, tmpl, row, lo):
+    """A table row stored in the cardinality cache under the names the union's sketch files of each k would have."""
+    for kk, card in enumerate(row):
+        cards[tmpl.with_k(lo + kk)] = float(card)
+
+
+class _FlatUnion(_Climber):
+    """The body node of a SubSpider as NUMBERS.  When a whole union schedule has come back from the GPU as one table of
+    cardinalities (UnionTable: every pair x k of `kij`, every prefix x k of `progressive`, every complement x k of `deltadelta`),
+    a SubSpider per pair or prefix -- a DeltaTreeNode, a Sketch object and a SketchPath per (set, k), 76 608 of them for 64
+    genomes -- computes nothing: it walks dictionaries.  This class goes through the same steps on one row of the table --
+    _Climber's find_delta with its `<=` ties and the kstart it moves, node_ksweep's k-1..k+1 window (lib/huffman_dandd.py:117),
+    fill_tree's update_node of every bestk (:451-457), summarize (:289-301) -- and leaves the same traces a tree save reads: the
+    base names in the experiment's base set, their sketchinfo entries, the row's cardinalities in the cache under the union's
+    sketch names.  A one-leaf union uses the leaf's own files, not the row.  A k outside the table goes through the file-based
+    backend (leaf sketches, union, card) as the object path does."""
+
+    def __init__(self, tree, kids, experiment, table, row):
         sp = tree.speciesinfo
-        self.sp, self.experiment, self.kids = sp, experiment, list(kids)
-        self.row, self.lo, self.hi = table_row, int(lo), int(hi)
+        self.speciesinfo, self.experiment, self.kids = sp, experiment, list(kids)
+        self.lo, self.hi = int(table.lo), int(table.hi)
         self.fastas = [leaf.fastas[0] for c in self.kids for leaf in c.progeny]
         self.ngen = len(self.fastas)
-        self.title = "_".join(os.path.basename(c.node_title) for c in self.kids)
+        self.node_title = "_".join(os.path.basename(c.node_title) for c in self.kids)
         self.tmpl = SketchPath(self.fastas, 0, sp, experiment)   # (the '{}' form: registers its base as the node's placeholder sketch does)
         experiment["baseset"].add(self.tmpl.base)
         self.delta, self.bestk, self.mink, self.maxk = 0, 0, 0, 0
         self._touched = set()
         self._be = backend_for(experiment)
         self._base = self.tmpl.base.split("{}")       # the base name around its k
+        self.row = row if self.ngen > 1 else None
+        if self.row is not None:
+            _cache_row(sp.cardkey, self.tmpl, row, self.lo)
 
     def touch(self, k):
         """what update_node(k) leaves behind besides the Sketch object: the base name in the experiment's base set and its
@@ -534,15 +569,15 @@ class _FlatUnion:
         self._touched.add(k)
         base = str(k).join(self._base)
         self.experiment["baseset"].add(base)
-        if base not in self.sp.sketchinfo:
-            self.sp.sketchinfo[base] = {"sketchbase": base, "files": self.tmpl.files, "ngen": self.ngen, "kval": k,
+        if base not in self.speciesinfo.sketchinfo:
+            self.speciesinfo.sketchinfo[base] = {"sketchbase": base, "files": self.tmpl.files, "ngen": self.ngen, "kval": k,
                                         "registers": self.experiment["registers"]}
 
     def card(self, k):
         if self.row is not None and self.lo <= k <= self.hi:
             return float(self.row[k - self.lo])
         path = self.tmpl.with_k(k)
-        cards = self.sp.cardkey
+        cards = self.speciesinfo.cardkey
         if float(cards.get(path) or 0) > 0:
             return float(cards[path])
         # outside the table: the files, as DeltaTreeNode.ksweep_update_node + Sketch would (a hill-climb that leaves the window)
@@ -553,10 +588,6 @@ class _FlatUnion:
             self._be.union([c.ksketches[0].sfp.with_k(k) for c in self.kids], path)
         cards[path] = float(self._be.card(path))
         return cards[path]
-
-    def command(self, k):
-        op = "sketch" if self.ngen == 1 else "union"
-        return self._be.describe(op, k=k, out=os.path.basename(self.tmpl.with_k(k))) if hasattr(self._be, "describe") else op
 
     def node_ksweep(self, mink, maxk):
         lo = max(1, mink)
@@ -569,7 +600,7 @@ class _FlatUnion:
             bases = [pre + str(k) + post for k in ks]
             self._touched.update(ks)
             self.experiment["baseset"].update(bases)
-            info, files, ngen, regs = self.sp.sketchinfo, self.tmpl.files, self.ngen, self.experiment["registers"]
+            info, files, ngen, regs = self.speciesinfo.sketchinfo, self.tmpl.files, self.ngen, self.experiment["registers"]
             for k, base in zip(ks, bases):
                 if base not in info:
                     info[base] = {"sketchbase": base, "files": files, "ngen": ngen, "kval": k, "registers": regs}
@@ -578,29 +609,9 @@ class _FlatUnion:
                 self.touch(k)
         self.mink, self.maxk = mink, maxk
 
-    def find_delta_helper(self, kval, direction):
-        while True:
-            if self.experiment["tool"] == "dashing" and kval > 32 and not self.experiment.get("allow_k64"):
-                raise ValueError("Exploratory k value is too high for dashing. Either something is amiss "
-                                 "with your data or you need to be using --exact mode")
-            if kval < 1:
-                return
-            self.node_ksweep(kval - 1, kval + 1)
-            if direction < 0:
-                self.mink = kval
-            else:
-                self.maxk = kval
-            candidate = self.card(kval) / kval
-            if not self.delta <= candidate:  # ties keep climbing
-                return
-            self.sp.kstart = kval
-            self.bestk = kval
-            self.delta = candidate
-            kval += direction
-
-    def find_delta(self, kval):
-        self.find_delta_helper(kval, 1)
-        self.find_delta_helper(kval, -1)
+    def _climb_step(self, kval):
+        self.node_ksweep(kval - 1, kval + 1)
+        return self.card(kval) / kval
 
     def fill(self):
         """SubSpider.fill_tree in a hill-climb run: the root brought up to date at every node's argmax-k"""
@@ -608,17 +619,13 @@ class _FlatUnion:
             if k > 0:
                 self.touch(k)
 
-    def summarize(self, mink, maxk, ordering_number):
-        rows = []
-        for k in range(mink, maxk + 1):
-            if k == 0:   # the placeholder sketch (a hill-climb run's summary is made of these: SURVEY.md section 9)
-                rows.append({"ngen": self.ngen, "kval": 0, "card": 0, "delta_pos": 0, "title": self.title, "command": None,
-                             "ordering": ordering_number})
-                continue
-            c = self.card(k)
-            rows.append({"ngen": self.ngen, "kval": k, "card": c, "delta_pos": c / k, "title": self.title,
-                         "command": self.command(k), "ordering": ordering_number})
-        return rows
+    def _summary_cells(self, k):
+        if k == 0:   # the placeholder sketch (a hill-climb run's summary is made of these: SURVEY.md section 9)
+            return 0, 0, None
+        c = self.card(k)
+        op = "sketch" if self.ngen == 1 else "union"
+        command = self._be.describe(op, k=k, out=os.path.basename(self.tmpl.with_k(k))) if hasattr(self._be, "describe") else op
+        return c, c / k, command
 
 
 # ---------------------------------------------------------------------------------------------
@@ -896,18 +903,11 @@ class DeltaTree:
         sched = None
         if hasattr(be, "leave_out_cards") and exp.get("tool") != "kmc" and not exp.get("safety") \
                 and not os.environ.get("DD_NO_PREFETCH"):
-            if window is not None:
-                lo, hi = exp["ksweep"]
-            else:   # the window progressive_union takes: the climbs stay within a few k of the leaves' and the root's argmax
-                lo = max(1, min(leaf.bestk for leaf in leaves) - 2)
-                hi = self.root_k() + 3
-                if exp["tool"] == "dashing":
-                    hi = min(hi, 32)
-            lo = max(1, int(lo))
+            lo, hi = self._table_window(exp)
+            lo = max(1, lo)
             if hi >= lo:
                 group_of = [owner.get(leaf.fastas[0], -1) for leaf in leaves]
-                paths = self._leaf_files(leaves, lo, int(hi))
-                sched = (be.leave_out_cards(paths, group_of), lo, int(hi))
+                sched = UnionTable(be.leave_out_cards(self._leaf_files(leaves, lo, hi), group_of), lo, hi)
         rows, summary = [], []
         full = None
         for gi, g in enumerate(groups):
@@ -915,30 +915,25 @@ class DeltaTree:
             kids = [leaf for leaf in leaves if leaf.fastas[0] not in out]     # tree order, as nodes_from_fastas gives them
             row = {"group": labels[gi], "fastas": "|".join(f for f in self.fastas if f in out),
                    "nout": len(out), "ngen_rest": len(kids)}
+            sub = _FlatUnion(self, kids, exp, sched, sched.table[gi]) if sched is not None else None
             if window is None:
-                if sched is None:
+                if sub is None:
                     # find_delta_delta's own steps, keeping the spider it builds (its result is `self - small`)
                     small = SubSpider(self.nodes_from_fastas([f for f in self.fastas if f not in out]), self.speciesinfo, exp)
-                    print("Full Tree Delta: ", self.delta)
-                    print("Subtree Delta: ", small.delta)
-                    row["deltadelta"] = self - small
-                    row["delta_rest"], row["k_rest"] = small.delta, small.root_k()
+                    k_rest = small.root_k()
                 else:
-                    sub = self._leave_out_union(kids, exp, sched, gi)
                     sub.find_delta(self.speciesinfo.kstart)       # SubSpider.__init__ ...
                     sub.fill()                                    # ... and its fill_tree
-                    print("Full Tree Delta: ", self.delta)
-                    print("Subtree Delta: ", sub.delta)
-                    print("Larger Tree Delta: ", self.delta)
-                    print("Subtree Delta: ", sub.delta)
-                    print("Subtraction Result: ", self.delta - sub.delta)
-                    row["deltadelta"] = self.delta - sub.delta
-                    row["delta_rest"], row["k_rest"] = sub.delta, sub.bestk
+                    small, k_rest = sub, sub.bestk
+                print("Full Tree Delta: ", self.delta)
+                print("Subtree Delta: ", small.delta)
+                row["deltadelta"] = self - small
+                row["delta_rest"], row["k_rest"] = small.delta, k_rest
                 row["delta_all"], row["k_all"] = self.delta, self.root_k()
             else:
                 lo, hi = exp["ksweep"]
                 ks = list(range(max(1, lo), hi + 1))
-                if sched is None:
+                if sub is None:
                     if full is None:
                         full_tree = SubSpider(leaves, self.speciesinfo, exp)
                         full = [full_tree.root.ksketches[k].card for k in ks]
@@ -946,8 +941,7 @@ class DeltaTree:
                     rest = [small.root.ksketches[k].card for k in ks]
                 else:
                     if full is None:
-                        full = [float(v) for v in sched[0][len(groups)]]
-                    sub = self._leave_out_union(kids, exp, sched, gi)
+                        full = [float(v) for v in sched.table[len(groups)]]
                     sub.node_ksweep(lo, hi)
                     rest = [sub.card(k) for k in ks]
                 row["delta_all"], row["k_all"] = _window_delta(full, ks)
@@ -958,18 +952,19 @@ class DeltaTree:
             rows.append(row)
         return rows, summary
 
-    def _leave_out_union(self, kids, experiment, sched, gi):
-        """The union of `kids` (the complement of group gi) as a _FlatUnion over the leave-out table, its cardinalities stored
-        in the cache under the names its union sketches would have (as `kij`'s schedule does).  One kid: its own files."""
-        table, lo, hi = sched
-        sub = _FlatUnion(self, kids, experiment, table[gi] if len(kids) > 1 else None, lo, hi)
-        if sub.row is not None:
-            cards = self.speciesinfo.cardkey
-            for kk, k in enumerate(range(lo, hi + 1)):
-                cards[sub.tmpl.with_k(k)] = float(sub.row[kk])
-        return sub
-
     # ---- batched GPU union schedules ------------------------------------------------------------------
+    def _table_window(self, experiment):
+        """[lo, hi] of a union table for climbs over this tree's leaves: the --ksweep window, or a hill-climb's guess -- the
+        climbs stay within a few k of the leaves' and the root's argmax (capped at 32 for dashing, allow_k64 or not)."""
+        if experiment["ksweep"] is not None:
+            lo, hi = experiment["ksweep"]
+        else:
+            lo = max(1, min(leaf.bestk for leaf in self.leaf_nodes()) - 2)
+            hi = self.root_k() + 3
+            if experiment["tool"] == "dashing":
+                hi = min(hi, 32)
+        return int(lo), int(hi)
+
     def _leaf_files(self, leaves, lo, hi):
         """Make sure every leaf has its sketch file for k in [lo, hi] (one fused GPU pass per leaf)
         and return the paths as [leaf][k]."""
@@ -990,20 +985,17 @@ class DeltaTree:
             rows.append([tmpl.with_k(k) for k in range(lo, hi + 1)])
         return rows
 
-    def prefetch_union_cards(self, groups, lo, hi, experiment, schedule=False):
-        """Cardinalities of the unions `groups` (lists of leaf nodes) for k in [lo, hi], computed by
-        ONE batched GPU launch per schedule instead of one union + one card per (set, k), and stored
-        in the cardinality cache under the names the union sketches would have.  A backend without
-        batch entry points (the CPU checkers used in tests) makes this a no-op.
-        schedule=True: the table itself comes back -- {"table", "index" (id(leaf) -> row), "lo", "hi", "orders" (ordering as a
-        tuple of rows -> its number in the table)} or None -- and the CALLER stores what it uses in the cache (the summaries
-        below work on the table: _FlatUnion)."""
+    def prefetch_union_cards(self, groups, lo, hi, experiment):
+        """Cardinalities of the unions `groups` (lists of leaf nodes) for k in [lo, hi], computed by ONE batched GPU launch
+        instead of one union + one card per (set, k): every pair when all groups are pairs, else every prefix of every group
+        that holds all leaves (an ordering).  -> UnionTable, or None when the backend has no batch entry points (the CPU
+        checkers used in tests).  The caller walks its rows (_FlatUnion), which puts them in the cardinality cache."""
         be = backend_for(experiment)
         if lo < 1 or hi < lo or not groups or os.environ.get("DD_NO_PREFETCH"):
-            return None if schedule else 0
+            return None
         pair_mode = all(len(g) == 2 for g in groups)
         if not hasattr(be, "pairwise_cards" if pair_mode else "progressive_cards"):
-            return None if schedule else 0
+            return None
         leaves = []
         seen = set()
         for g in groups:
@@ -1013,42 +1005,15 @@ class DeltaTree:
                     leaves.append(leaf)
         index = {id(leaf): i for i, leaf in enumerate(leaves)}
         paths = self._leaf_files(leaves, lo, hi)
-        cards = self.speciesinfo.cardkey
-        filled = 0
         if pair_mode:
-            table = be.pairwise_cards(paths)
-            if schedule:
-                experiment["prefetched"] = True
-                return {"table": table, "index": index, "lo": lo, "hi": hi, "orders": {}}
-            for a, b in groups:
-                tmpl = SketchPath([a.fastas[0], b.fastas[0]], 0, self.speciesinfo, experiment)
-                row = table[index[id(a)], index[id(b)]]
-                for kk, k in enumerate(range(lo, hi + 1)):
-                    cards[tmpl.with_k(k)] = float(row[kk])
-                    filled += 1
+            table, orders = be.pairwise_cards(paths), None
         else:
-            # every group is treated as an ordering; prefixes of length >= 2 are unions
-            n = len(leaves)
-            ords, used = [], []
-            for g in groups:
-                if len(g) == n:
-                    ords.append([index[id(leaf)] for leaf in g])
-                    used.append(g)
+            ords = [[index[id(leaf)] for leaf in g] for g in groups if len(g) == len(leaves)]
             if not ords:
-                return None if schedule else 0
-            table = be.progressive_cards(paths, ords)
-            if schedule:
-                experiment["prefetched"] = True
-                return {"table": table, "index": index, "lo": lo, "hi": hi, "orders": {tuple(o): i for i, o in enumerate(ords)}}
-            for o, g in enumerate(used):
-                for j in range(1, n):
-                    fastas = [leaf.fastas[0] for leaf in g[: j + 1]]
-                    tmpl = SketchPath(fastas, 0, self.speciesinfo, experiment)
-                    for kk, k in enumerate(range(lo, hi + 1)):
-                        cards[tmpl.with_k(k)] = float(table[o, j, kk])
-                        filled += 1
+                return None
+            table, orders = be.progressive_cards(paths, ords), {tuple(o): i for i, o in enumerate(ords)}
         experiment["prefetched"] = True
-        return filled
+        return UnionTable(table, lo, hi, index, orders)
 
     # ---- progressive unions (lib/huffman_dandd.py:574-663) -------------------------------------------
     def progressive_fastas(self, flist_loc=None):
@@ -1093,15 +1058,8 @@ class DeltaTree:
         sched = None
         if step == 1 and len(flist) > 1 and not self.experiment.get("safety"):
             by_fasta = {leaf.fastas[0]: leaf for leaf in spider.leaf_nodes()}
-            if self.experiment["ksweep"] is not None:
-                lo, hi = self.experiment["ksweep"]
-            else:  # the hill-climbs stay within a few k of the leaves' and the root's argmax
-                lo = max(1, min(leaf.bestk for leaf in by_fasta.values()) - 2)
-                hi = spider.root.bestk + 3
-                if self.experiment["tool"] == "dashing":
-                    hi = min(hi, 32)
             groups = [[by_fasta[spider.fastas[j]] for j in ordering] for ordering in orderings]
-            sched = spider.prefetch_union_cards(groups, int(lo), int(hi), self.experiment, schedule=True)
+            sched = spider.prefetch_union_cards(groups, *spider._table_window(self.experiment), self.experiment)
         results, summary = [], []
         for i, ordering in enumerate(orderings):
             if self.experiment["verbose"]:
@@ -1124,8 +1082,8 @@ class DeltaTree:
         o = None
         if schedule is not None and step == 1:
             by_fasta = {leaf.fastas[0]: leaf for leaf in leaves}
-            key = tuple(schedule["index"].get(id(by_fasta.get(self.fastas[j]))) for j in ordering)
-            o = schedule["orders"].get(key)
+            key = tuple(schedule.index.get(id(by_fasta.get(self.fastas[j]))) for j in ordering)
+            o = schedule.orders.get(key)
         for i in range(1, len(ordering) + 1):
             if i % step:
                 continue
@@ -1133,13 +1091,7 @@ class DeltaTree:
             if o is not None:
                 inside = set(prefix)
                 kids = [leaf for leaf in leaves if leaf.fastas[0] in inside]      # tree order, as nodes_from_fastas gives them
-                sub = _FlatUnion(self, kids, self.experiment, schedule["table"][o, i - 1], schedule["lo"], schedule["hi"])
-                if i > 1 and sub.row is not None:   # what the union sketches' cardinalities would have been cached as
-                    cards = self.speciesinfo.cardkey
-                    for kk, k in enumerate(range(sub.lo, sub.hi + 1)):
-                        cards[sub.tmpl.with_k(k)] = float(sub.row[kk])
-                if i == 1:
-                    sub.row = None                   # a single leaf: its own sketch files and cached cardinalities
+                sub = _FlatUnion(self, kids, self.experiment, schedule, schedule.table[o, i - 1])
                 if self.experiment["ksweep"] is None:
                     sub.find_delta(self.speciesinfo.kstart)
                     sub.fill()
@@ -1175,15 +1127,19 @@ class DeltaTree:
         # every 2-way union of every pair at every k in one GPU launch
         sched = None
         if mink and maxk and len(leaves) > 1:
-            sched = self.prefetch_union_cards([[a, b] for i, a in enumerate(leaves) for b in leaves[i + 1:]],
-                                              int(mink), min(int(maxk), 64), pair_exp,
-                                              schedule=int(maxk) <= 64 and not pair_exp.get("safety"))
-        if isinstance(sched, dict):
+            pairs = [[a, b] for i, a in enumerate(leaves) for b in leaves[i + 1:]]
+            sched = self.prefetch_union_cards(pairs, int(mink), min(int(maxk), 64), pair_exp)
+            if sched is not None and (int(maxk) > 64 or pair_exp.get("safety")):
+                # (--safe, or ks beyond the table: the object path below, its union cardinalities cached from the table)
+                for a, b in pairs:
+                    tmpl = SketchPath([a.fastas[0], b.fastas[0]], 0, self.speciesinfo, pair_exp)
+                    _cache_row(self.speciesinfo.cardkey, tmpl, sched.table[sched.index[id(a)], sched.index[id(b)]], sched.lo)
+                sched = None
+        if sched is not None:
             # ... and every pair's summary from that table (_FlatUnion): the steps SubSpider + find_delta + kij_summarize +
             # jaccard_summarize take (lib/huffman_dandd.py:685-690, 772-815), in the same order -- the climbs move
             # speciesinfo.kstart, which the next pair starts from --, without a SubSpider, a node and a Sketch per (pair, k)
-            table, index, lo, hi = sched["table"], sched["index"], sched["lo"], sched["hi"]
-            cards = self.speciesinfo.cardkey
+            table, index = sched.table, sched.index
             if jaccard:
                 for leaf in leaves:
                     leaf.node_ksweep(mink=mink, maxk=maxk)     # (once per leaf: what every pair's ksweep asks of its two leaves)
@@ -1193,9 +1149,7 @@ class DeltaTree:
                 leaf_cards = {id(leaf): [leaf.ksketches[k].card for k in ks] for leaf in leaves}
             for i, a in enumerate(leaves):
                 for b in leaves[i + 1:]:
-                    pair = _FlatUnion(self, [a, b], pair_exp, table[index[id(a)], index[id(b)]], lo, hi)
-                    for kk, k in enumerate(range(lo, hi + 1)):   # what the union sketches' cardinalities would have been cached as
-                        cards[pair.tmpl.with_k(k)] = float(pair.row[kk])
+                    pair = _FlatUnion(self, [a, b], pair_exp, sched, table[index[id(a)], index[id(b)]])
                     pair.find_delta(self.speciesinfo.kstart)       # SubSpider.__init__ ...
                     pair.fill()
                     pair.find_delta(self.root_k())                 # ... and the climb from the tree's own argmax-k
