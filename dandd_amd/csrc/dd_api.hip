@@ -942,6 +942,72 @@ int dd_leave_out(dd_ctx* c, const uint8_t* leaf, int n, int K, const int32_t* gr
     return dd_leave_out_device(c, static_cast<const uint8_t*>(c->regs.p), n, K, group, ngroups, card);
 }
 
+// ------------------------------------------------------------------------ all subsets
+// dd_subsets.hip: every subset's histogram from threshold bit planes.  Columns are taken Kc at a time so that the
+// histograms (2^n Kc 64 u32) stay within 256 MiB and the partial counts within 512 MiB.
+int dd_subsets_device(dd_ctx* c, const uint8_t* leaf_dev, int n, int K, double* card) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 1 || n > 16) return fail(DD_EINVAL, "n=%d outside 1..16: the unions of all 2^n subsets are computed", n);
+    if (K < 1 || !leaf_dev || !card) return fail(DD_EINVAL, "bad argument");
+    DeviceGuard guard(c->device);
+    const size_t nsub = (size_t)1 << n;
+    const int Kc = (int)std::min<size_t>((size_t)K, std::max<size_t>(1, ((size_t)256 << 20) / (nsub * 64 * sizeof(uint32_t))));
+    const size_t part_budget = (size_t)512 << 20;
+    int rc;
+    if ((rc = c->gram.reserve((size_t)K * 2 * sizeof(uint32_t)))) return rc;
+    if ((rc = c->hist.reserve(nsub * Kc * 64 * sizeof(uint32_t)))) return rc;
+    std::vector<uint32_t> rng((size_t)K * 2);
+    dd::launch_register_range(leaf_dev, n, K, c->p, static_cast<uint32_t*>(c->gram.p), c->stream);
+    DD_HIP(hipMemcpyAsync(rng.data(), c->gram.p, rng.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    DD_HIP(hipStreamSynchronize(c->stream));
+    // the workgroup tables of every chunk after the ranges, one upload
+    std::vector<dd::SubsetsPlan> plans;
+    std::vector<int32_t> tab(rng.begin(), rng.end());
+    std::vector<size_t> wg_off;
+    size_t part_bytes = 0;
+    for (int k0 = 0; k0 < K; k0 += Kc) {
+        plans.push_back(dd::plan_subsets(n, c->p, rng.data(), k0, std::min(Kc, K - k0), part_budget));
+        wg_off.push_back(tab.size());
+        tab.insert(tab.end(), plans.back().wg.begin(), plans.back().wg.end());
+        part_bytes = std::max(part_bytes, plans.back().part_bytes);
+    }
+    if ((rc = c->gram.reserve(part_bytes))) return rc;
+    if ((rc = c->ord.reserve(sizeof(int32_t) * tab.size()))) return rc;
+    DD_HIP(hipEventSynchronize(c->stage_free));
+    if ((rc = c->stage.reserve(sizeof(int32_t) * tab.size()))) return rc;
+    if ((rc = upload(c, c->stage, c->ord.p, tab.data(), sizeof(int32_t) * tab.size(), 0))) return rc;
+    DD_HIP(hipEventRecord(c->stage_free, c->stream));
+    const uint32_t* rng_dev = static_cast<const uint32_t*>(c->ord.p);
+    uint32_t* part_dev = static_cast<uint32_t*>(c->gram.p);
+    std::vector<double> est;
+    for (size_t i = 0; i < plans.size(); ++i) {
+        const int k0 = (int)i * Kc, kc = std::min(Kc, K - k0);
+        {
+            Span sp(c, DD_KERNEL_UNION);
+            dd::launch_subsets(leaf_dev, n, K, c->p, k0, kc, plans[i], static_cast<const int32_t*>(c->ord.p) + wg_off[i], rng_dev,
+                               part_dev, static_cast<uint32_t*>(c->hist.p), c->stream);
+        }
+        DD_HIP(hipGetLastError());
+        est.resize(nsub * kc);
+        if ((rc = estimates_from_hist(c, static_cast<const uint32_t*>(c->hist.p), nsub * kc, est.data()))) return rc;
+        for (size_t s = 0; s < nsub; ++s) memcpy(card + s * K + k0, est.data() + s * kc, sizeof(double) * kc);
+    }
+    for (int kk = 0; kk < K; ++kk) card[kk] = 0.0;   // the empty set
+    return DD_OK;
+}
+
+int dd_subsets(dd_ctx* c, const uint8_t* leaf, int n, int K, double* card) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 1 || n > 16) return fail(DD_EINVAL, "n=%d outside 1..16: the unions of all 2^n subsets are computed", n);
+    if (K < 1 || !leaf) return fail(DD_EINVAL, "bad argument");
+    DeviceGuard guard(c->device);
+    const size_t bytes = ((size_t)n * K) << c->p;
+    int rc;
+    if ((rc = c->regs.reserve(bytes))) return rc;
+    DD_HIP(hipMemcpyAsync(c->regs.p, leaf, bytes, hipMemcpyHostToDevice, c->stream));
+    return dd_subsets_device(c, static_cast<const uint8_t*>(c->regs.p), n, K, card);
+}
+
 // ------------------------------------------------------------------------- measurement
 int dd_timing_enable(dd_ctx* c, int on) {
     if (check_ctx(c)) return DD_EINVAL;

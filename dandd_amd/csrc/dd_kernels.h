@@ -191,6 +191,17 @@ void launch_mle(const uint32_t* hist_dev, size_t njobs, int log2m, double* est_d
 // group consecutive, the floor first.  Zeroes hist_dev itself.
 void launch_leaveout(const uint8_t* leaf_dev, int K, int log2m, const int32_t* tab_dev, int nslots, int G, uint32_t* hist_dev,
                      hipStream_t st);
+// all-subset unions (dd_subsets.hip) of columns k0 .. k0 + Kc - 1: hist[(s * Kc + kk)][64] = histogram of the byte-max over
+// the leaves in mask s, s < 2^n (n <= 16); s = 0 gets m in bin 0.  rng as launch_register_range leaves it (all K columns).
+// wg: (column, first job, threshold offset) per workgroup, uploaded by the caller; part: part_bytes of scratch.
+struct SubsetsPlan {
+    int HC = 1, nchunks = 1, RR = 1, D = 1, tiles = 1;
+    size_t part_bytes = 0, lds_bytes = 0;
+    std::vector<int32_t> wg;
+};
+SubsetsPlan plan_subsets(int n, int log2m, const uint32_t* rng_host, int k0, int Kc, size_t part_budget);
+void launch_subsets(const uint8_t* leaf_dev, int n, int K, int log2m, int k0, int Kc, const SubsetsPlan& plan, const int32_t* wg_dev,
+                    const uint32_t* rng_dev, uint32_t* part_dev, uint32_t* hist_dev, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // exact distinct k-mer count (KMC stand-in): extract -> radix sort -> count distinct

@@ -25,6 +25,7 @@ EXPORTS = [
     "dd_sketch_buffer", "dd_sketch_fasta", "dd_sketch_files", "dd_inflate_files", "dd_last_ingest_stats", "dd_sketch_device", "dd_union", "dd_union_device",
     "dd_card", "dd_card_batch", "dd_card_batch_device", "dd_hist_batch_device", "dd_ertl_mle",
     "dd_progressive", "dd_progressive_device", "dd_pairwise", "dd_pairwise_device", "dd_leave_out", "dd_leave_out_device",
+    "dd_subsets", "dd_subsets_device",
     "dd_exact_count", "dd_exact_count_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
@@ -132,6 +133,10 @@ def load_library(path=None):
     lib.dd_leave_out.argtypes = [vp, vp, i32, i32, vp, i32, vp]
     lib.dd_leave_out_device.restype = i32
     lib.dd_leave_out_device.argtypes = [vp, vp, i32, i32, vp, i32, vp]
+    lib.dd_subsets.restype = i32
+    lib.dd_subsets.argtypes = [vp, vp, i32, i32, vp]
+    lib.dd_subsets_device.restype = i32
+    lib.dd_subsets_device.argtypes = [vp, vp, i32, i32, vp]
     lib.dd_exact_count.restype = i32
     lib.dd_exact_count.argtypes = [vp, C.POINTER(C.c_char_p), i32, i32, C.POINTER(u64)]
     lib.dd_exact_count_device.restype = i32
@@ -460,6 +465,20 @@ class Engine:
         card = np.empty((max(ngroups, 0) + 1, K), dtype=np.float64)
         self._check(self._lib.dd_leave_out_device(self._ctx, C.c_void_p(int(leaf_ptr)), n, K, grp.ctypes.data, ngroups,
                                                   card.ctypes.data))
+        return card
+
+    def subsets(self, leaf):
+        """leaf [n][K][m] uint8 (host), n <= 16 -> card [2^n][K] float64: row s the union of the leaves i with bit i of s set
+        (row 0, the empty set, 0.0)."""
+        leaf = _u8(leaf)
+        n, K = leaf.shape[0], leaf.shape[1]
+        card = np.empty((1 << min(max(n, 0), 16), K), dtype=np.float64)
+        self._check(self._lib.dd_subsets(self._ctx, leaf.ctypes.data, n, K, card.ctypes.data))
+        return card
+
+    def subsets_device(self, leaf_ptr, n, K):
+        card = np.empty((1 << min(max(int(n), 0), 16), int(K)), dtype=np.float64)
+        self._check(self._lib.dd_subsets_device(self._ctx, C.c_void_p(int(leaf_ptr)), int(n), int(K), card.ctypes.data))
         return card
 
     # -- exact distinct k-mer count (KMC stand-in) ----------------------------------------

@@ -503,6 +503,20 @@ class HipBackend:
         slab_group[perm] = group                         # slab row perm[i] holds the caller's leaf i
         return self.engine.leave_out_device(ptr, len(leaf_paths), len(leaf_paths[0]), slab_group, ngroups)
 
+    def subset_cards(self, leaf_paths):
+        """|union of the leaves i with bit i of s set| for every s < 2^n (n <= 16) and every k column: float64 [2^n][K], row 0
+        (the empty set) 0.0.  The rows are indexed by the caller's leaves, whatever order the slab keeps them in."""
+        n = len(leaf_paths)
+        ptr, perm = self._device_slab(leaf_paths)
+        if ptr is None:
+            return self.engine.subsets(self._leaf_slab(leaf_paths))
+        table = self.engine.subsets_device(ptr, n, len(leaf_paths[0]))
+        masks = np.arange(1 << n, dtype=np.int64)
+        slab_mask = np.zeros_like(masks)
+        for i in range(n):                               # caller's leaf i is slab row perm[i]
+            slab_mask |= ((masks >> i) & 1) << int(perm[i])
+        return table[slab_mask]
+
     def close(self):
         if self._dev is not None:
             self.engine.device_free(self._dev[1])

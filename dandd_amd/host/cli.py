@@ -1,4 +1,4 @@
-"""`dandd tree | progressive | kij | deltadelta` on the MI355X engine: same sub-commands, flags, defaults and
+"""`dandd tree | progressive | kij | deltadelta | abba` on the MI355X engine: same sub-commands, flags, defaults and
 output files as /root/reference/lib/dandd_cmd.py (flags :141-286, handlers :43-132); only the
 sketching backend differs.  Run as  python -m dandd_amd.host.cli <subcommand> ...
 """
@@ -107,8 +107,9 @@ def kij_command(args):
             pickle.dump(tree.prepare_AFproject(kij_rows, j_rows), f)
 
 
-def _deltadelta_groups(tree, args):
-    """-> (groups as lists of leaf FASTAs, their labels) from -f / -g, or every leaf on its own in tree order"""
+def _leaf_lookup(tree, cmd, tree_path):
+    """-> leaf_of(name): the tree's leaf FASTA a name means -- its path, its absolute path or its basename when that is unique
+    -- or an exit with a `<cmd>: ...` message"""
     leaves = tree.leaf_nodes()
     by_name = {}
     for leaf in leaves:
@@ -127,8 +128,15 @@ def _deltadelta_groups(tree, args):
     def leaf_of(name):
         f = by_name.get(name) or by_name.get(os.path.abspath(name))
         if f is None:
-            sys.exit(f"deltadelta: {name} is not a leaf of the tree {args.delta_tree}")
+            sys.exit(f"{cmd}: {name} is not a leaf of the tree {tree_path}")
         return f
+    return leaf_of
+
+
+def _deltadelta_groups(tree, args):
+    """-> (groups as lists of leaf FASTAs, their labels) from -f / -g, or every leaf on its own in tree order"""
+    leaves = tree.leaf_nodes()
+    leaf_of = _leaf_lookup(tree, "deltadelta", args.delta_tree)
 
     def lines(path):
         with open(path) as fh:
@@ -179,6 +187,91 @@ def deltadelta_command(args):
     write_listdict_to_csv(outfile + ".deltadelta.csv", rows)
     if summary:
         write_listdict_to_csv(outfile + "_deltadeltasummary.csv", summary)
+    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
+    tree.speciesinfo.save_references(fast=False)
+
+
+def _write_csv(path, cols, rows):
+    """rows (lists) under the header `cols`, in that order; None is an empty cell"""
+    import csv
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(cols)
+        w.writerows(rows)
+
+
+def abba_command(args):
+    """Exact order effects over ALL n! orderings of n <= 16 genomes, from the unions of all 2^n subsets: the growth curve,
+    each genome's mean / min / max contribution, and "A before B, B before A" -- b's mean increment at each of its
+    positions over the orderings with a before it and over those with a after it.  The reference planned this sub-command
+    (lib/dandd_cmd.py:248-258, commented out) and sampled orderings with `progressive` in its place."""
+    tree = _load_tree(args.delta_tree)
+    tree.speciesinfo.update(tool=tree.experiment["tool"])
+    if not args.tag:
+        args.tag = tree.speciesinfo.tag
+    outfile = tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
+    if args.ksweep:
+        window = (int(args.mink), int(args.maxk))
+    elif tree.experiment.get("ksweep") is not None:
+        window = tuple(int(v) for v in tree.experiment["ksweep"])
+    else:
+        sys.exit("abba: a k window is needed: give --ksweep --mink --maxk, or a tree built with --ksweep "
+                 "(hill-climb deltas per subset would depend on the order of the climbs)")
+    if args.safety:
+        tree.experiment["safety"] = True
+    leaf_of = _leaf_lookup(tree, "abba", args.delta_tree)
+    fastas = tree.progressive_fastas(args.flist_loc)
+    n = len(fastas)
+    if n < 2:
+        sys.exit(f"abba: {n} genome(s) in the universe: at least 2 are needed")
+    if n > 16:
+        sys.exit(f"abba: {n} genomes in the universe: at most 16 (2^n subset unions); choose them with -f/--fastas")
+    if (args.fastaA is None) != (args.fastaB is None):
+        sys.exit("abba: -A/--fastaA and -B/--fastaB go together")
+    pairs = [(a, b) for a in range(n) for b in range(n) if a != b]
+    if args.fastaA is not None:
+        fa, fb = leaf_of(args.fastaA), leaf_of(args.fastaB)
+        if fa == fb:
+            sys.exit(f"abba: -A and -B name the same genome {fa}")
+        for f in (fa, fb):
+            if f not in fastas:
+                sys.exit(f"abba: {f} is not in the universe of this run (-f)")
+        ia, ib = fastas.index(fa), fastas.index(fb)
+        pairs = [(ia, ib), (ib, ia)]
+    if deltatree.dist_ranks()[1] > 1:
+        # every rank sketches its share of the leaves for the window; rank 0 finishes alone
+        tree.presketch_range(*window)
+        if deltatree.dist_ranks()[0] != 0:
+            return
+    os.makedirs(args.outdir, exist_ok=True)
+    ex = tree.ordering_expectations(fastas, *window)
+    delta, kval, growth, contrib = ex["delta"], ex["kval"], ex["growth"], ex["contrib"]
+    from math import factorial
+    half, per = factorial(n) // 2, factorial(n - 2)
+    rows = []
+    for a, b in pairs:
+        for s in range(1, n + 1):
+            nb, na = (s - 1) * per, (n - s) * per
+            mb = float(ex["before"][a, b, s - 1]) if nb else None
+            ma = float(ex["after"][a, b, s - 1]) if na else None
+            rows.append([fastas[a], fastas[b], s, nb, mb, na, ma, mb - ma if nb and na else None])
+        mb, ma = float(ex["before_all"][a, b]), float(ex["after_all"][a, b])
+        rows.append([fastas[a], fastas[b], "all", half, mb, half, ma, mb - ma])
+    _write_csv(outfile + ".abba.csv", ["a", "b", "step", "orderings_a_before", "mean_a_before", "orderings_a_after",
+                                       "mean_a_after", "abba"], rows)
+    full = (1 << n) - 1
+    rows = [[f, float(delta[1 << g]), int(kval[1 << g]), float(contrib[g, 0]), float(contrib[g, 1]), float(contrib[g, 2]),
+             float(delta[full] - delta[full ^ (1 << g)])] for g, f in enumerate(fastas)]
+    _write_csv(outfile + ".abba_contrib.csv", ["fasta", "delta_alone", "k_alone", "mean_contrib", "min_contrib", "max_contrib",
+                                               "delta_last"], rows)
+    rows = [[ng, int(growth[ng - 1, 0]), float(growth[ng - 1, 1]), float(growth[ng - 1, 2]), float(growth[ng - 1, 3]),
+             float(growth[ng - 1, 4])] for ng in range(1, n + 1)]
+    _write_csv(outfile + ".abba_growth.csv", ["ngen", "nsubsets", "mean", "sd", "min", "max"], rows)
+    if args.subsets:
+        size = ex["size"]
+        rows = [[mask, int(size[mask]), float(delta[mask]), int(kval[mask]),
+                 "|".join(fastas[i] for i in range(n) if mask >> i & 1)] for mask in range(1, full + 1)]
+        _write_csv(outfile + ".abba_subsets.csv", ["mask", "ngen", "delta", "kval", "fastas"], rows)
     tree.speciesinfo.save_cardkey(tree.experiment["tool"])
     tree.speciesinfo.save_references(fast=False)
 
@@ -348,6 +441,20 @@ def build_parser():
     dd.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     dd.add_argument("-l", "--label", dest="label", default="")
     dd.set_defaults(func=deltadelta_command)
+
+    ab = subs.add_parser("abba", parents=[common, sweep],
+                         description="exact order effects over all n! orderings of n <= 16 genomes, from all 2^n subset unions")
+    ab.add_argument("-d", "--dtree", dest="delta_tree", required=True)
+    ab.add_argument("-s", "--tag", dest="tag", type=str)
+    ab.add_argument("-f", "--fastas", dest="flist_loc", default=None, type=str,
+                    help="the genomes to order (default: every leaf), in the order `progressive -f` takes them")
+    ab.add_argument("-A", "--fastaA", dest="fastaA", default=None, type=str, help="report only the pairs (A, B) and (B, A)")
+    ab.add_argument("-B", "--fastaB", dest="fastaB", default=None, type=str)
+    ab.add_argument("--subsets", dest="subsets", default=False, action="store_true",
+                    help="also write every subset's delta (<prefix>.abba_subsets.csv)")
+    ab.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
+    ab.add_argument("-l", "--label", dest="label", default="")
+    ab.set_defaults(func=abba_command)
 
     # (not in the reference: its every command is a fresh process that shells out to fresh `dashing` processes)
     sv = subs.add_parser("serve", description="keep the GPU context alive and run the commands dandd_amd.host.client forwards")

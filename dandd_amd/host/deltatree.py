@@ -24,6 +24,8 @@ from itertools import permutations
 from math import factorial
 from random import sample, shuffle
 
+import numpy as np
+
 from .store import Catalog, SketchPath, ensure_dir, forget_sketch, sketch_exists
 
 # ---------------------------------------------------------------------------------------------
@@ -952,6 +954,42 @@ class DeltaTree:
             rows.append(row)
         return rows, summary
 
+    # ---- exact order effects over all n! orderings, from the 2^n subset unions (`dandd abba`) ---------------------------
+    def ordering_expectations(self, fastas, lo, hi):
+        """Window delta of the union of every subset of `fastas` (n <= 16 leaf FASTAs, the universe U) over k in
+        [max(1, lo), hi] -- the largest card / k, ties going to the larger k; 0 for the empty set -- and what they give over
+        all n! orderings of U (abba_expectations).  Bit i of a mask is fastas[i].
+          * Schedule path (a backend with subset_cards): the leaves' window sketches, then every subset at every k of the
+            window from ONE launch over the leaf slab.  Subset unions are neither written nor cached (65 536 at n = 16).
+          * Object path (exact trees, --safe, DD_NO_PREFETCH, the CPU checkers): one SubSpider per non-empty subset.
+        -> dict: ks, cards [2^n][K], delta [2^n], kval [2^n] and the abba_expectations entries"""
+        by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
+        nodes = [by_fasta[f] for f in fastas]
+        n = len(nodes)
+        lo, hi = max(1, int(lo)), int(hi)
+        if hi < lo:
+            raise ValueError(f"empty k window {lo}..{hi}")
+        ks = np.arange(lo, hi + 1)
+        exp = dict(self.experiment, ksweep=(lo, hi))
+        be = backend_for(exp)
+        if hasattr(be, "subset_cards") and exp.get("tool") != "kmc" and not exp.get("safety") \
+                and not os.environ.get("DD_NO_PREFETCH"):
+            cards = np.asarray(be.subset_cards(self._leaf_files(nodes, lo, hi)), dtype=np.float64).reshape(1 << n, len(ks))
+        else:
+            cards = np.zeros((1 << n, len(ks)))
+            for mask in range(1, 1 << n):
+                sub = SubSpider([nodes[i] for i in range(n) if mask >> i & 1], self.speciesinfo, exp)
+                sub.root.node_ksweep(lo, hi)
+                cards[mask] = [sub.root.ksketches[k].card for k in ks]
+        ratio = cards / ks
+        last = len(ks) - 1 - np.argmax(ratio[:, ::-1], axis=1)        # (ties: the larger k, as _window_delta)
+        delta = ratio[np.arange(1 << n), last]
+        kval = ks[last]
+        delta[0], kval[0] = 0.0, 0
+        out = dict(ks=ks, cards=cards, delta=delta, kval=kval)
+        out.update(abba_expectations(delta))
+        return out
+
     # ---- batched GPU union schedules ------------------------------------------------------------------
     def _table_window(self, experiment):
         """[lo, hi] of a union table for climbs over this tree's leaves: the --ksweep window, or a hill-climb's guess -- the
@@ -1226,6 +1264,70 @@ def _window_delta(cards, ks):
         if best <= c / k:
             best, bestk = c / k, k
     return best, bestk
+
+
+def abba_expectations(delta):
+    """Exact expectations over all n! orderings of n items from delta[mask] of every subset (delta[0] = 0; n = log2 of the
+    length).  A prefix of an ordering is a subset P, and the item b that follows it adds delta(P | b) - delta(P); every
+    subset of size s stands for s! (n - s)! orderings of its prefix and suffix.
+      growth      [n][5]: per ngen 1..n the count, mean, population SD, min and max of delta over the subsets of that size
+                  (= the ngen-th prefix over all orderings)
+      contrib     [n][3]: per item g the mean of its increment over all orderings (weights s! (n - s - 1)! / n! for |P| = s),
+                  and its min and max over all P not holding g
+      before, after [a][b][n]: per ordered pair (a, b) and b's position s (1..n), the mean of b's increment over the orderings
+                  with a before b (P holds a), and with a after b; nan where there are none (s = 1 before, s = n after)
+      before_all, after_all [a][b]: the same over all n! / 2 orderings of each side
+    No Python loop over subsets or orderings."""
+    delta = np.asarray(delta, dtype=np.float64)
+    n = int(delta.size).bit_length() - 1
+    if delta.size != 1 << n or n < 1:
+        raise ValueError(f"{delta.size} deltas: not 2^n of n >= 1 items")
+    masks = np.arange(1 << n, dtype=np.int64)
+    size = np.zeros(1 << n, dtype=np.int64)
+    for i in range(n):
+        size += (masks >> i) & 1
+    growth = np.zeros((n, 5))
+    order = np.argsort(size, kind="stable")
+    bounds = np.searchsorted(size[order], np.arange(n + 2))
+    for ng in range(1, n + 1):
+        v = delta[order[bounds[ng]:bounds[ng + 1]]]
+        growth[ng - 1] = (v.size, v.mean(), v.std(), v.min(), v.max())
+    comb = np.array([[float(_comb(a, b)) for b in range(n + 1)] for a in range(n + 1)])
+    contrib = np.zeros((n, 3))
+    before = np.full((n, n, n), np.nan)
+    after = np.full((n, n, n), np.nan)
+    before_all = np.full((n, n), np.nan)
+    after_all = np.full((n, n), np.nan)
+    steps = np.arange(1, n + 1)
+    for b in range(n):
+        P = masks[((masks >> b) & 1) == 0]                    # every subset without b: b's prefix at step |P| + 1
+        inc = delta[P | (1 << b)] - delta[P]
+        onehot = np.zeros((P.size, n))
+        onehot[np.arange(P.size), size[P]] = inc              # row P: its increment in the column of its size
+        total = onehot.sum(axis=0)                            # [s - 1]: sum over |P| = s - 1
+        contrib[b] = ((total / (n * comb[n - 1, :n])).sum(), inc.min(), inc.max())
+        member = ((P[None, :] >> np.arange(n)[:, None]) & 1).astype(np.float64)   # [a][P]: a in P
+        sb = member @ onehot                                  # [a][s - 1]: sums with a before b
+        sa = total[None, :] - sb
+        nb = comb[n - 2, np.maximum(steps - 2, 0)] * (steps >= 2)          # subsets per step with a in P, b not
+        na = comb[n - 2, np.minimum(steps - 1, n - 2)] * (steps <= n - 1)  # ... with neither
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mb = np.where(nb > 0, sb / np.where(nb > 0, nb, 1), np.nan)
+            ma = np.where(na > 0, sa / np.where(na > 0, na, 1), np.nan)
+        for a in range(n):
+            if a == b:
+                continue
+            before[a, b], after[a, b] = mb[a], ma[a]
+            # orderings at step s: (s - 1) (n - 2)! with a before, (n - s) (n - 2)! with a after; n! / 2 each in all
+            before_all[a, b] = np.nansum(mb[a] * (steps - 1)) * 2 / (n * (n - 1))
+            after_all[a, b] = np.nansum(ma[a] * (n - steps)) * 2 / (n * (n - 1))
+    return dict(n=n, size=size, growth=growth, contrib=contrib, before=before, after=after, before_all=before_all,
+                after_all=after_all)
+
+
+def _comb(a, b):
+    from math import comb
+    return comb(a, b) if 0 <= b <= a else 0
 
 
 class SubSpider(DeltaTree):

@@ -141,6 +141,17 @@ int dd_leave_out(dd_ctx *, const uint8_t *leaf /*[n][K][m]*/, int n, int K,
 int dd_leave_out_device(dd_ctx *, const uint8_t *leaf_dev, int n, int K,
                         const int32_t *group, int ngroups, double *card);
 
+/* ---- all-subset unions ---------------------------------------------------------------
+ * For `dandd abba`: every prefix of every ordering of the n leaves is a subset, so the unions of all 2^n subsets give
+ * exact expectations over all n! orderings.
+ * card[s][kk] = |union of the leaves i with bit i of s set| at k = kmin+kk, for s < 2^n; card[0][kk] = 0.0.
+ * One pass over the slab per column chunk: threshold bit planes AND-ed over a lattice of (high, low) leaf subsets
+ * (dd_subsets.hip), the same integers as a byte-max + histogram per subset.  1 <= n <= 16 (else DD_EINVAL).
+ * Register bytes must be <= 63. */
+int dd_subsets(dd_ctx *, const uint8_t *leaf /*[n][K][m]*/, int n, int K,
+               double *card /*[2^n][K]*/);
+int dd_subsets_device(dd_ctx *, const uint8_t *leaf_dev, int n, int K, double *card);
+
 /* ---- exact distinct k-mer count (the KMC stand-in) --------------------------------------
  * Replaces   kmc -ci1 -cs2 -k<K> [-b] -fm <fasta> <db> <tmp>   +   kmc_tools complex (set union)
  * +   kmc_tools info <db> | grep 'total k-mers'   (lib/sketch_classes.py:395,444-448,453-465):
