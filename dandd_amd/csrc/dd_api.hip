@@ -507,22 +507,26 @@ int dd_sketch_buffer(dd_ctx* c, const uint8_t* fasta, size_t nbytes, int kmin, i
 }
 
 // ------------------------------------------------------------------------- exact count
-int dd_exact_count_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int k,
-                          uint64_t* distinct) {
-    if (check_ctx(c)) return DD_EINVAL;
-    if (n < 0 || !distinct || (n && (!fasta_dev || !nbytes))) return fail(DD_EINVAL, "null argument");
-    if (k < 1 || k > 64) return fail(DD_EINVAL, "k=%d outside 1..64", k);
+namespace {
+
+// K0 over the n inputs of an exact call (once per call, whatever the number of ks) and where each genome's k-mers go
+struct ExactInputs {
+    const dd::ExactGenome* etab_dev = nullptr;
+    size_t slots = 0, max_segments = 0;   // slots = 0: no input has a token
+};
+
+int exact_check_inputs(const uint8_t* const* fasta_dev, const size_t* nbytes, int n) {
     for (int g = 0; g < n; ++g) {
         if (nbytes[g] && !fasta_dev[g]) return fail(DD_EINVAL, "input %d: null buffer", g);
         if (reinterpret_cast<uintptr_t>(fasta_dev[g]) & 15)
             return fail(DD_EINVAL, "input %d: device buffer must be 16-byte aligned", g);
     }
-    *distinct = 0;
-    if (!n) return DD_OK;
-    DeviceGuard guard(c->device);
+    return DD_OK;
+}
+
+int exact_prepare(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, ExactInputs& in) {
     hipStream_t st = c->stream;
     int rc;
-
     // token streams (K0), laid out like dd_sketch_device does
     std::vector<size_t> off_codes(n), off_bad(n), off_ntok(n), off_scratch(n);
     size_t tot = 0, scratch_tot = 0, slots = 0, max_segments = 0, max_chunks = 0;
@@ -542,16 +546,8 @@ int dd_exact_count_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size
         max_segments = std::max(max_segments, segs);
         max_chunks = std::max(max_chunks, dd::pack_chunks(nbytes[g]));
     }
+    in.slots = slots, in.max_segments = max_segments;
     if (!slots) return DD_OK;
-    const bool wide = k > 32;
-    const size_t arrays = wide ? 4 : 2;
-    // HBM for the k-mer arrays (keys + the sort's other half): everything at once when that fits the budget,
-    // else in passes over disjoint parts of the k-mer space (below).  KMC unions arbitrarily many databases
-    // (/root/reference/lib/sketch_classes.py:453-465); so must this.
-    size_t budget = (size_t)24 << 30;
-    if (const char* e = getenv("DD_EXACT_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
-    const bool single = arrays * slots * sizeof(uint64_t) <= budget;
-    const size_t cap = single ? slots : std::max<size_t>(budget / (arrays * sizeof(uint64_t)), 4096);  // k-mers per pass
     if ((rc = c->tokens.reserve(tot))) return rc;
     if ((rc = c->scratch.reserve(scratch_tot))) return rc;
     char* tb = static_cast<char*>(c->tokens.p);
@@ -578,7 +574,67 @@ int dd_exact_count_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size
         Span sp(c, DD_KERNEL_PACK);
         dd::launch_pack_batch(reinterpret_cast<const dd::PackGenome*>(tdev), n, max_chunks, st);
     }
-    const dd::ExactGenome* etab_dev = reinterpret_cast<const dd::ExactGenome*>(tdev + pbytes);
+    in.etab_dev = reinterpret_cast<const dd::ExactGenome*>(tdev + pbytes);
+    return DD_OK;
+}
+
+size_t exact_budget() {
+    size_t budget = (size_t)24 << 30;
+    if (const char* e = getenv("DD_EXACT_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
+    return budget;
+}
+
+// the files of a path form, read and uploaded into the context's FASTA buffer
+int exact_upload_files(dd_ctx* c, const char* const* paths, int n, std::vector<const uint8_t*>& ptrs, std::vector<size_t>& sizes) {
+    std::vector<size_t> offs(n);
+    std::vector<FileBuf> bufs(n);
+    sizes.assign(n, 0);
+    ptrs.assign(n, nullptr);
+    size_t tot = 0;
+    for (int i = 0; i < n; ++i) {
+        std::string err;
+        if (!paths[i] || !read_fasta_file(paths[i], bufs[i], err, usable_cpus())) return fail(DD_EIO, "%s", err.c_str());
+        sizes[i] = bufs[i].size();
+        offs[i] = tot;
+        tot += align_up(sizes[i] + 16, 256);
+    }
+    int rc;
+    if ((rc = c->fasta.reserve(tot + 16))) return rc;
+    for (int i = 0; i < n; ++i) {
+        ptrs[i] = static_cast<const uint8_t*>(c->fasta.p) + offs[i];
+        if (sizes[i])
+            DD_HIP(hipMemcpyAsync(const_cast<uint8_t*>(ptrs[i]), bufs[i].data(), sizes[i], hipMemcpyHostToDevice, c->stream));
+    }
+    DD_HIP(hipStreamSynchronize(c->stream));  // host buffers are pageable; release them before the sort
+    return DD_OK;
+}
+
+}  // namespace
+
+int dd_exact_count_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int k,
+                          uint64_t* distinct) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 0 || !distinct || (n && (!fasta_dev || !nbytes))) return fail(DD_EINVAL, "null argument");
+    if (k < 1 || k > 64) return fail(DD_EINVAL, "k=%d outside 1..64", k);
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    *distinct = 0;
+    if (!n) return DD_OK;
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n, in))) return rc;
+    const size_t slots = in.slots, max_segments = in.max_segments;
+    if (!slots) return DD_OK;
+    const dd::ExactGenome* etab_dev = in.etab_dev;
+    const bool wide = k > 32;
+    const size_t arrays = wide ? 4 : 2;
+    // HBM for the k-mer arrays (keys + the sort's other half): everything at once when that fits the budget,
+    // else in passes over disjoint parts of the k-mer space (below).  KMC unions arbitrarily many databases
+    // (/root/reference/lib/sketch_classes.py:453-465); so must this.
+    const size_t budget = exact_budget();
+    const bool single = arrays * slots * sizeof(uint64_t) <= budget;
+    const size_t cap = single ? slots : std::max<size_t>(budget / (arrays * sizeof(uint64_t)), 4096);  // k-mers per pass
 
     // layout of the k-mer workspace for `cap` keys: counters (256 B) | histogram (32 KiB) | lo | lo_alt [| hi | hi_alt] | temp
     const size_t hist_bytes = (size_t)dd::kExactBins * sizeof(unsigned long long);
@@ -607,11 +663,14 @@ int dd_exact_count_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size
         const size_t temp_bytes = dd::exact_sort_temp_bytes(slots, k);
         if ((rc = carve(slots, temp_bytes, counters, hist, lo, lo_alt, hi, hi_alt, temp))) return rc;
         DD_HIP(hipMemsetAsync(counters, 0, 256, st));
-        DD_HIP(hipMemsetAsync(lo, 0xFF, key_bytes, st));  // unwritten slots read as the all-ones sentinel
-        if (wide) DD_HIP(hipMemsetAsync(hi, 0xFF, key_bytes, st));
-        dd::launch_kmer_extract(etab_dev, n, max_segments, k, c->canonical, lo, hi, counters, st);
-        DD_HIP(hipGetLastError());
-        DD_HIP(dd::launch_exact_sort_count(lo, hi, lo_alt, hi_alt, slots, k, temp, temp_bytes, counters, st));
+        {
+            Span sp(c, DD_KERNEL_EXACT);
+            DD_HIP(hipMemsetAsync(lo, 0xFF, key_bytes, st));  // unwritten slots read as the all-ones sentinel
+            if (wide) DD_HIP(hipMemsetAsync(hi, 0xFF, key_bytes, st));
+            dd::launch_kmer_extract(etab_dev, n, max_segments, k, c->canonical, lo, hi, counters, st);
+            DD_HIP(hipGetLastError());
+            DD_HIP(dd::launch_exact_sort_count(lo, hi, lo_alt, hi_alt, slots, k, temp, temp_bytes, counters, st));
+        }
         unsigned long long h[3] = {0, 0, 0};
         DD_HIP(hipMemcpyAsync(h, counters, sizeof h, hipMemcpyDeviceToHost, st));
         DD_HIP(hipStreamSynchronize(st));
@@ -628,7 +687,10 @@ int dd_exact_count_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size
     size_t temp_bytes = dd::exact_sort_temp_bytes(cap, k);
     if ((rc = carve(cap, temp_bytes, counters, hist, lo, lo_alt, hi, hi_alt, temp))) return rc;
     DD_HIP(hipMemsetAsync(counters, 0, 256 + hist_bytes, st));
-    dd::launch_kmer_extract(etab_dev, n, max_segments, k, c->canonical, lo, hi, counters, st, 1, hist, 0, 0);
+    {
+        Span sp(c, DD_KERNEL_EXACT);
+        dd::launch_kmer_extract(etab_dev, n, max_segments, k, c->canonical, lo, hi, counters, st, 1, hist, 0, 0);
+    }
     DD_HIP(hipGetLastError());
     std::vector<unsigned long long> bins(dd::kExactBins);
     DD_HIP(hipMemcpyAsync(bins.data(), hist, hist_bytes, hipMemcpyDeviceToHost, st));
@@ -651,10 +713,13 @@ int dd_exact_count_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size
         while (b1 < (uint32_t)dd::kExactBins && in_pass + bins[b1] <= pass_cap) in_pass += bins[b1++];
         if (in_pass) {
             DD_HIP(hipMemsetAsync(counters, 0, 256, st));
-            dd::launch_kmer_extract(etab_dev, n, max_segments, k, c->canonical, lo, hi, counters, st, 2, hist, b0, b1);
-            DD_HIP(hipGetLastError());
-            // (every slot below in_pass is written: no sentinel, T^k is an ordinary value here)
-            DD_HIP(dd::launch_exact_sort_count(lo, hi, lo_alt, hi_alt, (size_t)in_pass, k, temp, temp_bytes, counters, st));
+            {
+                Span sp(c, DD_KERNEL_EXACT);
+                dd::launch_kmer_extract(etab_dev, n, max_segments, k, c->canonical, lo, hi, counters, st, 2, hist, b0, b1);
+                DD_HIP(hipGetLastError());
+                // (every slot below in_pass is written: no sentinel, T^k is an ordinary value here)
+                DD_HIP(dd::launch_exact_sort_count(lo, hi, lo_alt, hi_alt, (size_t)in_pass, k, temp, temp_bytes, counters, st));
+            }
             unsigned long long h[4] = {0, 0, 0, 0};
             DD_HIP(hipMemcpyAsync(h, counters, sizeof h, hipMemcpyDeviceToHost, st));
             DD_HIP(hipStreamSynchronize(st));
@@ -673,27 +738,323 @@ int dd_exact_count(dd_ctx* c, const char* const* paths, int n, int k, uint64_t* 
     if (check_ctx(c)) return DD_EINVAL;
     if (n < 0 || !distinct || (n && !paths)) return fail(DD_EINVAL, "null argument");
     DeviceGuard guard(c->device);
-    std::vector<size_t> sizes(n), offs(n);
-    std::vector<FileBuf> bufs(n);
-    size_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        std::string err;
-        if (!paths[i] || !read_fasta_file(paths[i], bufs[i], err, usable_cpus())) return fail(DD_EIO, "%s", err.c_str());
-        sizes[i] = bufs[i].size();
-        offs[i] = tot;
-        tot += align_up(sizes[i] + 16, 256);
-    }
+    std::vector<const uint8_t*> ptrs;
+    std::vector<size_t> sizes;
     int rc;
-    if ((rc = c->fasta.reserve(tot + 16))) return rc;
-    std::vector<const uint8_t*> ptrs(n);
-    for (int i = 0; i < n; ++i) {
-        ptrs[i] = static_cast<const uint8_t*>(c->fasta.p) + offs[i];
-        if (sizes[i])
-            DD_HIP(hipMemcpyAsync(const_cast<uint8_t*>(ptrs[i]), bufs[i].data(), sizes[i], hipMemcpyHostToDevice, c->stream));
-    }
-    DD_HIP(hipStreamSynchronize(c->stream));  // host buffers are pageable; release them before the sort
-    std::vector<FileBuf>().swap(bufs);
+    if ((rc = exact_upload_files(c, paths, n, ptrs, sizes))) return rc;
     return dd_exact_count_device(c, ptrs.data(), sizes.data(), n, k, distinct);
+}
+
+// ------------------------------------------------------------------- exact union schedules
+// dd_exact_sched.hip: one sort of the universe per k, a membership mask per distinct k-mer, one accumulator per schedule.
+namespace {
+
+// The driver behind the four schedules: K0 once, then for every k extract (with the genome's index) -> sort -> reduce +
+// accumulate, everything at once or in passes over bins of the k-mer space exactly as dd_exact_count_device does.
+// out[kk] receives the accumulator's exact_sched_acc_words() counts of k = kmin + kk.
+int exact_schedule(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, dd::ExactSched s,
+                   const std::vector<uint64_t>& table, std::vector<std::vector<unsigned long long>>& out) {
+    hipStream_t st = c->stream;
+    int rc;
+    const size_t words = dd::exact_sched_acc_words(s);
+    out.assign((size_t)(kmax - kmin + 1), std::vector<unsigned long long>(words, 0ull));
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n, in))) return rc;
+    c->st_blocks = 0;
+    if (!in.slots) return DD_OK;
+    if ((rc = c->hist.reserve(words * sizeof(unsigned long long)))) return rc;
+    s.acc = static_cast<unsigned long long*>(c->hist.p);
+    if (!table.empty()) {
+        const size_t tbytes = table.size() * sizeof(uint64_t);
+        if ((rc = c->ord.reserve(tbytes))) return rc;
+        DD_HIP(hipEventSynchronize(c->stage_free));
+        if ((rc = c->stage.reserve(tbytes))) return rc;
+        if ((rc = upload(c, c->stage, c->ord.p, table.data(), tbytes, 0))) return rc;
+        DD_HIP(hipEventRecord(c->stage_free, st));
+        s.table = static_cast<const uint64_t*>(c->ord.p);
+    }
+    const size_t slots = in.slots, budget = exact_budget();
+    const size_t hist_bytes = (size_t)dd::kExactBins * sizeof(unsigned long long);
+    int most_passes = 0;
+    for (int k = kmin; k <= kmax; ++k) {
+        const bool wide = k > 32, sep = dd::exact_tag_mode(k) == 2;
+        const size_t arrays = wide ? 4 : 2, per_slot = arrays * sizeof(uint64_t) + (sep ? 2 : 0);
+        const bool single = per_slot * slots <= budget;
+        size_t cap = single ? slots : std::max<size_t>(budget / per_slot, 4096);   // k-mers per pass
+        // workspace for `keys` k-mers: counters (256 B) | bin histogram (32 KiB) | lo | lo_alt [| hi | hi_alt] [| g | g_alt] | sort temp | chunk summaries
+        unsigned long long *counters = nullptr, *hist = nullptr;
+        uint64_t *lo = nullptr, *lo_alt = nullptr, *hi = nullptr, *hi_alt = nullptr;
+        uint8_t *g = nullptr, *g_alt = nullptr;
+        void *temp = nullptr, *summaries = nullptr;
+        size_t temp_bytes = 0;
+        auto carve = [&](size_t keys) -> int {
+            const size_t stride = align_up(keys * sizeof(uint64_t), 256), gstride = sep ? align_up(keys, 256) : 0;
+            temp_bytes = dd::exact_sched_temp_bytes(keys, k);
+            int r = c->exact.reserve(256 + hist_bytes + arrays * stride + 2 * gstride + align_up(temp_bytes, 256) +
+                                     dd::exact_sched_scratch_bytes(keys) + 256);
+            if (r) return r;
+            char* eb = static_cast<char*>(c->exact.p);
+            counters = reinterpret_cast<unsigned long long*>(eb);
+            hist = reinterpret_cast<unsigned long long*>(eb + 256);
+            char* kb = eb + 256 + hist_bytes;
+            lo = reinterpret_cast<uint64_t*>(kb);
+            lo_alt = reinterpret_cast<uint64_t*>(kb + stride);
+            hi = wide ? reinterpret_cast<uint64_t*>(kb + 2 * stride) : nullptr;
+            hi_alt = wide ? reinterpret_cast<uint64_t*>(kb + 3 * stride) : nullptr;
+            kb += arrays * stride;
+            g = sep ? reinterpret_cast<uint8_t*>(kb) : nullptr;
+            g_alt = sep ? reinterpret_cast<uint8_t*>(kb + gstride) : nullptr;
+            kb += 2 * gstride;
+            temp = kb;
+            summaries = kb + align_up(temp_bytes, 256);
+            return DD_OK;
+        };
+        const int tag = sep ? 2 : 1;
+        DD_HIP(hipMemsetAsync(s.acc, 0, words * sizeof(unsigned long long), st));
+        int npass = 0;
+        if (single) {
+            if ((rc = carve(slots))) return rc;
+            Span sp(c, DD_KERNEL_EXACT);
+            DD_HIP(hipMemsetAsync(counters, 0, 256, st));
+            // unwritten slots: the all-ones key (T^k's run) with genome 0xFF, which sets no bit
+            DD_HIP(hipMemsetAsync(lo, 0xFF, slots * sizeof(uint64_t), st));
+            if (wide) DD_HIP(hipMemsetAsync(hi, 0xFF, slots * sizeof(uint64_t), st));
+            if (sep) DD_HIP(hipMemsetAsync(g, 0xFF, slots, st));
+            dd::launch_kmer_extract(in.etab_dev, n, in.max_segments, k, c->canonical, lo, hi, counters, st, 0, nullptr, 0, 0, tag, g);
+            DD_HIP(hipGetLastError());
+            dd::ExactSorted sorted{};
+            DD_HIP(dd::launch_exact_sort_tagged(lo, hi, lo_alt, hi_alt, g, g_alt, slots, k, temp, temp_bytes, st, &sorted));
+            DD_HIP(dd::launch_exact_sched(sorted, slots, k, s, summaries, st));
+            npass = 1;
+        } else {
+            if ((rc = carve(cap))) return rc;
+            DD_HIP(hipMemsetAsync(counters, 0, 256 + hist_bytes, st));
+            {
+                Span sp(c, DD_KERNEL_EXACT);
+                dd::launch_kmer_extract(in.etab_dev, n, in.max_segments, k, c->canonical, lo, hi, counters, st, 1, hist, 0, 0);
+            }
+            DD_HIP(hipGetLastError());
+            std::vector<unsigned long long> bins(dd::kExactBins);
+            DD_HIP(hipMemcpyAsync(bins.data(), hist, hist_bytes, hipMemcpyDeviceToHost, st));
+            DD_HIP(hipStreamSynchronize(st));
+            const unsigned long long biggest = *std::max_element(bins.begin(), bins.end());
+            if (biggest > cap) {   // (one bin over the budget: the arrays grow to hold it, as in dd_exact_count_device)
+                cap = (size_t)biggest;
+                if ((rc = carve(cap)))
+                    return fail(DD_ENOMEM, "exact schedule: one part of the k-mer space holds %llu k-mers, more than fits in HBM", biggest);
+            }
+            for (uint32_t b0 = 0; b0 < (uint32_t)dd::kExactBins;) {
+                unsigned long long in_pass = 0;
+                uint32_t b1 = b0;
+                while (b1 < (uint32_t)dd::kExactBins && in_pass + bins[b1] <= cap) in_pass += bins[b1++];
+                if (in_pass) {
+                    DD_HIP(hipMemsetAsync(counters, 0, 256, st));
+                    {
+                        Span sp(c, DD_KERNEL_EXACT);
+                        dd::launch_kmer_extract(in.etab_dev, n, in.max_segments, k, c->canonical, lo, hi, counters, st, 2, hist, b0, b1, tag, g);
+                        DD_HIP(hipGetLastError());
+                        dd::ExactSorted sorted{};
+                        DD_HIP(dd::launch_exact_sort_tagged(lo, hi, lo_alt, hi_alt, g, g_alt, (size_t)in_pass, k, temp, temp_bytes, st, &sorted));
+                        DD_HIP(dd::launch_exact_sched(sorted, (size_t)in_pass, k, s, summaries, st));
+                    }
+                    unsigned long long h[4] = {0, 0, 0, 0};
+                    DD_HIP(hipMemcpyAsync(h, counters, sizeof h, hipMemcpyDeviceToHost, st));
+                    DD_HIP(hipStreamSynchronize(st));
+                    if (h[3] != in_pass) return fail(DD_EHIP, "exact schedule: pass over bins %u..%u appended %llu k-mers, %llu expected", b0, b1, h[3], in_pass);
+                    ++npass;
+                }
+                b0 = b1;
+            }
+        }
+        DD_HIP(hipMemcpyAsync(out[(size_t)(k - kmin)].data(), s.acc, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+        most_passes = std::max(most_passes, npass);
+    }
+    c->st_blocks = most_passes;   // (dd_last_sketch_stats: the passes of the k that took the most)
+    return DD_OK;
+}
+
+int exact_sched_args(dd_ctx* c, const void* inputs, int n, int nmax, int kmin, int kmax, const void* card) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 1 || n > nmax)
+        return nmax == 16 ? fail(DD_EINVAL, "n=%d outside 1..16: the unions of all 2^n subsets are computed", n)
+                          : fail(DD_EINVAL, "n=%d outside 1..64: a membership mask has one bit per input", n);
+    if (!inputs || !card) return fail(DD_EINVAL, "null argument");
+    if (kmin < 1 || kmax > 64 || kmin > kmax) return fail(DD_EINVAL, "k range %d..%d outside 1..64", kmin, kmax);
+    return DD_OK;
+}
+
+// the schedules' argument rules (those of the HLL forms) and what they hand the accumulators
+int progressive_table(const int32_t* orderings, int norder, int n, std::vector<uint64_t>& table) {
+    if (norder < 1 || !orderings) return fail(DD_EINVAL, "bad argument");
+    table.assign((size_t)norder * n, 0ull);
+    for (int o = 0; o < norder; ++o) {
+        uint64_t seen = 0;
+        for (int j = 0; j < n; ++j) {
+            const int32_t v = orderings[(size_t)o * n + j];
+            if (v < 0 || v >= n) return fail(DD_EINVAL, "ordering entry %d outside 0..%d", v, n - 1);
+            if ((seen >> v) & 1ull) return fail(DD_EINVAL, "ordering %d is not a permutation of 0..%d: %d appears twice", o, n - 1, v);
+            seen |= 1ull << v;
+            table[(size_t)o * n + j] = seen;
+        }
+    }
+    return DD_OK;
+}
+
+int leave_out_table(const int32_t* group, int ngroups, int n, std::vector<uint64_t>& table) {
+    if (!group) return fail(DD_EINVAL, "bad argument");
+    if (ngroups < 1) return fail(DD_EINVAL, "ngroups=%d: at least one group is needed", ngroups);
+    if (ngroups > n) return fail(DD_EINVAL, "ngroups=%d is more than the %d leaves", ngroups, n);
+    table.assign((size_t)64 + ngroups, 0ull);
+    for (int i = 0; i < 64; ++i) table[i] = ~0ull;
+    const uint64_t all = n == 64 ? ~0ull : ((1ull << n) - 1ull);
+    for (int i = 0; i < n; ++i) {
+        if (group[i] < -1 || group[i] >= ngroups) return fail(DD_EINVAL, "group[%d]=%d outside -1..%d", i, group[i], ngroups - 1);
+        if (group[i] < 0) continue;
+        table[i] = (uint64_t)group[i];
+        table[64 + group[i]] |= 1ull << i;
+    }
+    for (int g = 0; g < ngroups; ++g)
+        if (table[64 + g] == all) return fail(DD_EINVAL, "group %d holds every leaf: the union of the rest is empty", g);
+    return DD_OK;
+}
+
+// accumulator counts -> the cards of the ABI
+void pairwise_cards(const std::vector<std::vector<unsigned long long>>& acc, int n, uint64_t* card) {
+    const size_t K = acc.size();
+    auto at = [n](int i, int j) { return (size_t)1 + (size_t)i * n - (size_t)i * (i - 1) / 2 + (size_t)(j - i); };
+    for (size_t kk = 0; kk < K; ++kk)
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) {
+                const int a = std::min(i, j), b = std::max(i, j);
+                const unsigned long long ci = acc[kk][at(a, a)], cj = acc[kk][at(b, b)];
+                card[((size_t)i * n + j) * K + kk] = a == b ? ci : ci + cj - acc[kk][at(a, b)];
+            }
+}
+
+int subsets_from_hist(const unsigned long long* hist, int n, uint64_t* card, size_t stride) {
+    const size_t nsub = (size_t)1 << n;
+    std::vector<uint64_t> sub(hist, hist + nsub);
+    uint64_t total = 0;
+    for (size_t s = 0; s < nsub; ++s) total += sub[s];
+    for (int b = 0; b < n; ++b)   // subset-sum (zeta) transform: sub[T] = sum of hist[mask] over mask inside T
+        for (size_t s = 0; s < nsub; ++s)
+            if (s & ((size_t)1 << b)) sub[s] += sub[s ^ ((size_t)1 << b)];
+    for (size_t s = 0; s < nsub; ++s) card[s * stride] = total - sub[(nsub - 1) ^ s];
+    return DD_OK;
+}
+
+// a path form: the files read and uploaded, then the device form (which checks the schedule's own arguments)
+extern "C++" template <class DeviceForm>
+int exact_path_form(dd_ctx* c, const char* const* paths, int n, DeviceForm device_form) {
+    DeviceGuard guard(c->device);
+    for (int i = 0; i < n; ++i)
+        if (!paths[i]) return fail(DD_EINVAL, "null argument");
+    std::vector<const uint8_t*> ptrs;
+    std::vector<size_t> sizes;
+    int rc;
+    if ((rc = exact_upload_files(c, paths, n, ptrs, sizes))) return rc;
+    return device_form(ptrs.data(), sizes.data());
+}
+
+}  // namespace
+
+int dd_exact_pairwise_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, uint64_t* card) {
+    if (exact_sched_args(c, fasta_dev, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedPairwise, n, 0, 0, nullptr, nullptr}, {}, acc))) return rc;
+    pairwise_cards(acc, n, card);
+    return DD_OK;
+}
+
+int dd_exact_progressive_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax,
+                                const int32_t* orderings, int norder, uint64_t* card) {
+    if (exact_sched_args(c, fasta_dev, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    std::vector<uint64_t> table;
+    if (progressive_table(orderings, norder, n, table)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedProgressive, n, norder, 0, nullptr, nullptr}, table, acc))) return rc;
+    const size_t K = acc.size();
+    for (size_t kk = 0; kk < K; ++kk)
+        for (int o = 0; o < norder; ++o) {
+            uint64_t run = 0;   // |union of the first j+1| = k-mers whose first genome stands at a position <= j
+            for (int j = 0; j < n; ++j) {
+                run += acc[kk][1 + (size_t)o * n + j];
+                card[((size_t)o * n + j) * K + kk] = run;
+            }
+        }
+    return DD_OK;
+}
+
+int dd_exact_leave_out_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax,
+                              const int32_t* group, int ngroups, uint64_t* card) {
+    if (exact_sched_args(c, fasta_dev, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    std::vector<uint64_t> table;
+    if (leave_out_table(group, ngroups, n, table)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedLeaveOut, n, 0, ngroups, nullptr, nullptr}, table, acc))) return rc;
+    const size_t K = acc.size();
+    for (size_t kk = 0; kk < K; ++kk) {
+        for (int g = 0; g < ngroups; ++g) card[(size_t)g * K + kk] = acc[kk][0] - acc[kk][1 + g];
+        card[(size_t)ngroups * K + kk] = acc[kk][0];
+    }
+    return DD_OK;
+}
+
+int dd_exact_subsets_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, uint64_t* card) {
+    if (exact_sched_args(c, fasta_dev, n, 16, kmin, kmax, card)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedSubsets, n, 0, 0, nullptr, nullptr}, {}, acc))) return rc;
+    const size_t K = acc.size();
+    for (size_t kk = 0; kk < K; ++kk) subsets_from_hist(acc[kk].data() + 1, n, card + kk, K);
+    return DD_OK;
+}
+
+int dd_exact_subsets_from_hist(const uint64_t* hist, int n, uint64_t* card) {
+    if (n < 1 || n > 16) return fail(DD_EINVAL, "n=%d outside 1..16: the unions of all 2^n subsets are computed", n);
+    if (!hist || !card) return fail(DD_EINVAL, "null argument");
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "u64");
+    return subsets_from_hist(reinterpret_cast<const unsigned long long*>(hist), n, card, 1);
+}
+
+int dd_exact_pairwise(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, uint64_t* card) {
+    if (exact_sched_args(c, paths, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) { return dd_exact_pairwise_device(c, p, s, n, kmin, kmax, card); });
+}
+
+int dd_exact_progressive(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, const int32_t* orderings, int norder, uint64_t* card) {
+    if (exact_sched_args(c, paths, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) {
+        return dd_exact_progressive_device(c, p, s, n, kmin, kmax, orderings, norder, card);
+    });
+}
+
+int dd_exact_leave_out(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, const int32_t* group, int ngroups, uint64_t* card) {
+    if (exact_sched_args(c, paths, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) {
+        return dd_exact_leave_out_device(c, p, s, n, kmin, kmax, group, ngroups, card);
+    });
+}
+
+int dd_exact_subsets(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, uint64_t* card) {
+    if (exact_sched_args(c, paths, n, 16, kmin, kmax, card)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) { return dd_exact_subsets_device(c, p, s, n, kmin, kmax, card); });
 }
 
 // ------------------------------------------------------------------------------- union

@@ -28,13 +28,16 @@ DD_D uint32_t exact_bin(uint64_t lo, uint64_t hi) { return (uint32_t)(splitmix64
 //   MODE 0: the k-mer ending at token t goes to out[base + t] (everything at once; unwritten slots keep a sentinel)
 //   MODE 1: only counts k-mers per bin into hist[4096] (LDS histogram per workgroup, one flush)
 //   MODE 2: k-mers whose bin is in [bin_lo, bin_hi) are appended densely (wave-aggregated atomic on counters[3])
-template <bool CANON, bool WIDE, int MODE>
+//   TAG (modes 0 and 2; the union schedules of dd_exact_sched.hip): every k-mer carries the index of its genome
+//   (blockIdx.y), 1: in the top byte of its most significant word (free while 2k, or 2k - 64, is at most 56),
+//   2: as a byte of out_g next to the key.  Unwritten slots keep 0xFF there: a genome that sets no bit.
+template <bool CANON, bool WIDE, int MODE, int TAG>
 __global__ __launch_bounds__(256) void kmer_extract_kernel(const ExactGenome* __restrict__ tab, int k,
                                                           uint64_t* __restrict__ out_lo,
                                                           uint64_t* __restrict__ out_hi,
                                                           unsigned long long* __restrict__ counters,
                                                           unsigned long long* __restrict__ hist, uint32_t bin_lo,
-                                                          uint32_t bin_hi) {
+                                                          uint32_t bin_hi, uint8_t* __restrict__ out_g) {
     __shared__ uint32_t lhist[MODE == 1 ? (1 << kExactBinBits) : 1];
     if (MODE == 1) {
         for (int i = threadIdx.x; i < (1 << kExactBinBits); i += blockDim.x) lhist[i] = 0;
@@ -94,8 +97,10 @@ __global__ __launch_bounds__(256) void kmer_extract_kernel(const ExactGenome* __
                 }
                 if (MODE == 0) {
                     const unsigned long long pos = g.base + sidx * kSegTokens + (unsigned)t;
-                    out_lo[pos] = al;
-                    if (WIDE) out_hi[pos] = ah;
+                    const uint64_t tag = (TAG == 1) ? (uint64_t)blockIdx.y << 56 : 0ull;
+                    out_lo[pos] = WIDE ? al : (al | tag);
+                    if (WIDE) out_hi[pos] = ah | tag;
+                    if (TAG == 2) out_g[pos] = (uint8_t)blockIdx.y;
                     ++valid;
                     if (al == mlo && ah == mhi) allt = 1;
                 } else if (MODE == 1) {
@@ -111,8 +116,10 @@ __global__ __launch_bounds__(256) void kmer_extract_kernel(const ExactGenome* __
                         basepos = __shfl(basepos, __builtin_ctzll(mask));
                         if (take) {
                             const unsigned long long pos = basepos + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-                            out_lo[pos] = al;
-                            if (WIDE) out_hi[pos] = ah;
+                            const uint64_t tag = (TAG == 1) ? (uint64_t)blockIdx.y << 56 : 0ull;
+                            out_lo[pos] = WIDE ? al : (al | tag);
+                            if (WIDE) out_hi[pos] = ah | tag;
+                            if (TAG == 2) out_g[pos] = (uint8_t)blockIdx.y;
                         }
                     }
                 }
@@ -159,17 +166,23 @@ __global__ __launch_bounds__(256) void count_unique_kernel(const uint64_t* __res
 
 void launch_kmer_extract(const ExactGenome* tab_dev, int ng, size_t max_segments, int k, int canonical,
                          uint64_t* lo, uint64_t* hi, unsigned long long* counters, hipStream_t st, int mode,
-                         unsigned long long* hist, uint32_t bin_lo, uint32_t bin_hi) {
+                         unsigned long long* hist, uint32_t bin_lo, uint32_t bin_hi, int tag, uint8_t* g) {
     if (ng <= 0 || !max_segments) return;
     const dim3 grid((unsigned)((max_segments + 255) / 256), (unsigned)ng), block(256);
     const bool wide = k > 32;
-#define DD_EX(CN, WD, MD) \
-    hipLaunchKernelGGL((kmer_extract_kernel<CN, WD, MD>), grid, block, 0, st, tab_dev, k, lo, hi, counters, hist, bin_lo, bin_hi)
+#define DD_EX(CN, WD, MD, TG) \
+    hipLaunchKernelGGL((kmer_extract_kernel<CN, WD, MD, TG>), grid, block, 0, st, tab_dev, k, lo, hi, counters, hist, bin_lo, bin_hi, g)
+#define DD_EX_TAG(CN, WD, MD)            \
+    do {                                 \
+        if (tag == 0) DD_EX(CN, WD, MD, 0); \
+        else if (tag == 1) DD_EX(CN, WD, MD, 1); \
+        else DD_EX(CN, WD, MD, 2);       \
+    } while (0)
 #define DD_EX_MODE(CN, WD)             \
     do {                               \
-        if (mode == 0) DD_EX(CN, WD, 0); \
-        else if (mode == 1) DD_EX(CN, WD, 1); \
-        else DD_EX(CN, WD, 2);         \
+        if (mode == 0) DD_EX_TAG(CN, WD, 0); \
+        else if (mode == 1) DD_EX(CN, WD, 1, 0); \
+        else DD_EX_TAG(CN, WD, 2);     \
     } while (0)
     if (canonical) {
         if (wide) DD_EX_MODE(true, true); else DD_EX_MODE(true, false);
@@ -177,6 +190,7 @@ void launch_kmer_extract(const ExactGenome* tab_dev, int ng, size_t max_segments
         if (wide) DD_EX_MODE(false, true); else DD_EX_MODE(false, false);
     }
 #undef DD_EX_MODE
+#undef DD_EX_TAG
 #undef DD_EX
 }
 

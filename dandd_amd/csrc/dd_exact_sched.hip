@@ -1,0 +1,473 @@
+// dd_exact_sched.hip -- exact union schedules from ONE sort of the universe per k.
+//
+// The exact counterparts of dd_pairwise / dd_progressive / dd_leave_out / dd_subsets.  Every k-mer occurrence of all n
+// genomes is extracted with the index of its genome (dd_exact.hip, TAG), radix-sorted by the k-mer, and the sorted
+// run of each distinct k-mer is OR-ed into a 64-bit MEMBERSHIP MASK (bit i: genome i holds it).  Every schedule is an
+// additive statistic of those masks, so the masks never reach HBM: a workgroup reduces a chunk of the sorted array
+// into an LDS tile of masks and hands the tile to the schedule's accumulator, whose u64 counts add up over chunks,
+// passes and bins of the k-mer space.
+//
+//   sort          launch_exact_sort_tagged: the sort of dd_exact.hip with the genome carried along
+//   sched_summary one (head seen, OR of the open run) pair per chunk of 2048 sorted slots
+//   sched_carry   segmented OR-scan of those pairs: what the run that crosses into a chunk has collected before it.
+//                 A run may be billions of slots long (poly-A); nothing here ever walks one.
+//   sched_kernel  per chunk: segmented OR-scan of the slots (registers + wave shuffles), a mask leaves at the LAST
+//                 slot of its run and only if it is non-zero -- the slots the single-pass layout never wrote carry
+//                 genome 0xFF, set no bit, and share their run with a genuine T^k whose bits then decide alone --
+//                 into the LDS tile; then the accumulator:
+//                   pairwise     64 masks x 64 bits transposed per wave with one __ballot per genome, plane words in LDS,
+//                                every thread owns (i, j) pairs and adds popcount(plane_i & plane_j) in registers
+//                   progressive  nested prefix masks in LDS, binary search for the first prefix that meets the mask
+//                   leave-out    lowest set bit -> its group -> is the mask inside the group? one counter per group
+//                   subsets      histogram of the masks over 2^n bins in LDS (u32; n = 16: two halves by the top bit, on
+//                                alternate workgroups)
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
+
+#include "dd_common.h"
+#include "dd_kernels.h"
+
+namespace dd {
+namespace {
+
+constexpr int kThreads = 256, kItems = 8, kChunk = kThreads * kItems;  // slots per chunk = masks an LDS tile can hold
+constexpr int kCarryThreads = 1024;
+constexpr size_t kStaticLds = (size_t)kChunk * 8 + 128;   // sched_kernel's own LDS: the tile of masks, the scan's wave totals
+constexpr int kPairSlots = 9;   // ceil(64 * 65 / 2 / 256): (i, j) pairs a thread of the pairwise accumulator owns
+
+struct SortedView {
+    const uint64_t* lo;
+    const uint64_t* hi;
+    const uint8_t* g;   // null: the genome is the top byte of the most significant word
+    uint64_t mlo, mhi;
+    size_t count;
+    int n;              // genomes: a tag outside 0..n-1 sets no bit
+};
+
+// (flag, value) pairs under  (f1, v1) o (f2, v2) = (f1 | f2, f2 ? v2 : v1 | v2): the segmented OR.  Inclusive scan over
+// the workgroup; returns the exclusive prefix of the calling thread in (ef, ev) and the workgroup's total in (tf, tv).
+template <int NWAVES>
+DD_D void block_seg_scan(uint32_t f, uint64_t v, uint32_t* sf, uint64_t* sv, uint32_t& ef, uint64_t& ev, uint32_t& tf,
+                         uint64_t& tv) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t of = __shfl_up(f, d);
+        const uint64_t ov = __shfl_up((unsigned long long)v, d);
+        if (lane >= d) {
+            if (!f) v |= ov;
+            f |= of;
+        }
+    }
+    if (lane == 63) sf[wave] = f, sv[wave] = v;
+    uint32_t xf = __shfl_up(f, 1);
+    uint64_t xv = __shfl_up((unsigned long long)v, 1);
+    if (lane == 0) xf = 0, xv = 0;
+    __syncthreads();
+    uint32_t pf = 0;
+    uint64_t pv = 0;
+    tf = 0, tv = 0;
+    for (int q = 0; q < NWAVES; ++q) {
+        const uint32_t wf = sf[q];
+        const uint64_t wv = sv[q];
+        if (q == wave) pf = tf, pv = tv;
+        tv = wf ? wv : (tv | wv);
+        tf |= wf;
+    }
+    ef = pf | xf;
+    ev = xf ? xv : (pv | xv);
+}
+
+// the calling thread's kItems consecutive slots of a chunk: which start a run, which end one, and their genome bits
+template <bool WIDE>
+DD_D void load_items(const SortedView& s, size_t first, uint32_t& head, uint32_t& tail, uint64_t (&bit)[kItems]) {
+    head = tail = 0;
+    uint64_t pl = 0, ph = 0;
+    bool pvalid = first > 0 && first - 1 < s.count;
+    if (pvalid) {
+        pl = s.lo[first - 1] & s.mlo;
+        if (WIDE) ph = s.hi[first - 1] & s.mhi;
+    }
+#pragma unroll
+    for (int j = 0; j <= kItems; ++j) {
+        const size_t i = first + j;
+        const bool valid = i < s.count;
+        uint64_t rl = 0, rh = 0;
+        if (valid) {
+            rl = s.lo[i];
+            if (WIDE) rh = s.hi[i];
+        }
+        const uint64_t cl = rl & s.mlo, ch = rh & s.mhi;
+        const bool differs = cl != pl || (WIDE && ch != ph);
+        if (j > 0 && pvalid && (!valid || differs)) tail |= 1u << (j - 1);
+        if (j < kItems) {
+            if (valid && (!pvalid || differs)) head |= 1u << j;
+            uint32_t gi = 0xFF;
+            if (valid) gi = s.g ? (uint32_t)s.g[i] : (uint32_t)((WIDE ? rh : rl) >> 56);
+            bit[j] = (gi < (uint32_t)s.n) ? (1ull << gi) : 0ull;
+        }
+        pl = cl, ph = ch, pvalid = valid;
+    }
+}
+
+DD_D void thread_summary(uint32_t head, const uint64_t (&bit)[kItems], uint32_t& f, uint64_t& v) {
+    f = head != 0;
+    v = 0;
+#pragma unroll
+    for (int j = 0; j < kItems; ++j) {
+        if ((head >> j) & 1u) v = 0;
+        v |= bit[j];
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(kThreads) void sched_summary_kernel(SortedView s, uint32_t* __restrict__ sum_f,
+                                                               uint64_t* __restrict__ sum_v) {
+    __shared__ uint32_t sf[kThreads / 64];
+    __shared__ uint64_t sv[kThreads / 64];
+    uint32_t head, tail, f, ef, tf;
+    uint64_t bit[kItems], v, ev, tv;
+    load_items<WIDE>(s, (size_t)blockIdx.x * kChunk + (size_t)threadIdx.x * kItems, head, tail, bit);
+    thread_summary(head, bit, f, v);
+    block_seg_scan<kThreads / 64>(f, v, sf, sv, ef, ev, tf, tv);
+    if (threadIdx.x == 0) sum_f[blockIdx.x] = tf, sum_v[blockIdx.x] = tv;
+}
+
+// one workgroup: carry[c] = the OR the run open at the end of chunk c-1 has collected (chunk c uses it for the slots in
+// front of its first head)
+__global__ __launch_bounds__(kCarryThreads) void sched_carry_kernel(const uint32_t* __restrict__ sum_f,
+                                                                  const uint64_t* __restrict__ sum_v, size_t nchunks,
+                                                                  uint64_t* __restrict__ carry) {
+    __shared__ uint32_t sf[kCarryThreads / 64];
+    __shared__ uint64_t sv[kCarryThreads / 64];
+    uint64_t run = 0;   // (value of everything before this tile; its flag is never needed)
+    for (size_t base = 0; base < nchunks; base += kCarryThreads) {
+        const size_t c = base + threadIdx.x;
+        const uint32_t f = c < nchunks ? sum_f[c] : 0u;
+        const uint64_t v = c < nchunks ? sum_v[c] : 0ull;
+        uint32_t ef, tf;
+        uint64_t ev, tv;
+        block_seg_scan<kCarryThreads / 64>(f, v, sf, sv, ef, ev, tf, tv);
+        if (c < nchunks) carry[c] = ef ? ev : (run | ev);
+        run = tf ? tv : (run | tv);
+        __syncthreads();
+    }
+}
+
+// One round of wave aggregation for a histogram with a dominant bin (progressive: most k-mers meet an ordering at its first
+// genomes): the first valid lane's index is added once for every lane that holds it, the other lanes add for themselves.
+// Called by whole waves.  Worth 3 x to progressive at k = 21 (profiles/exact_schedules.txt).  NOT to be turned into a loop of
+// rounds until every lane is served: that form miscounts in one instantiation for a reason still open;
+// leave-out and subsets use plain LDS atomics.
+DD_D void agg_add(uint32_t* base, uint32_t idx, bool valid) {
+    const unsigned long long act = __ballot(valid);
+    if (!act) return;
+    const int leader = __builtin_ctzll(act);
+    const uint32_t v = __shfl(idx, leader);
+    const unsigned long long same = __ballot(valid && idx == v);
+    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&base[v], (uint32_t)__builtin_popcountll(same));
+    else if (valid && idx != v) atomicAdd(&base[idx], 1u);
+}
+
+struct SchedArgs {
+    int n;
+    int norder;                       // progressive: orderings of this launch
+    int ngroups;                      // leave-out
+    const uint64_t* table;            // progressive: prefix masks [norder][n]; leave-out: group of bit [64], group masks [ngroups]
+    unsigned long long* acc;          // [0] = M (masks seen), then the schedule's counts
+    int add_m;
+    int slices;                       // subsets, n = 16: workgroup w counts the masks whose top bit is w % 2 (every chunk is reduced twice)
+};
+
+// ---- accumulators: init (LDS state), consume (one tile of masks; whole workgroup), flush (once per workgroup) ----
+struct AccSubsets {
+    uint32_t* hist;     // [2^min(n, 15)]: the bins of this workgroup's slice
+    int bits;
+    DD_D void init(const SchedArgs& a, uint64_t* dyn) {
+        bits = a.n < kExactSubsetsLdsN ? a.n : kExactSubsetsLdsN;
+        hist = reinterpret_cast<uint32_t*>(dyn);
+        for (uint32_t b = threadIdx.x; b < (1u << bits); b += kThreads) hist[b] = 0;
+    }
+    DD_D void consume(const SchedArgs&, const uint64_t* tile, uint32_t cnt, uint32_t slice) {
+        for (uint32_t base = 0; base < cnt; base += kThreads) {
+            const uint32_t i = base + threadIdx.x;
+            const uint32_t m = i < cnt ? (uint32_t)tile[i] : 0u;
+            if (i < cnt && (m >> bits) == slice) atomicAdd(&hist[m & ((1u << bits) - 1u)], 1u);
+        }
+    }
+    DD_D void flush(const SchedArgs& a, uint32_t slice) {
+        for (uint32_t b = threadIdx.x; b < (1u << bits); b += kThreads)
+            if (hist[b]) atomicAdd(&a.acc[1 + ((size_t)slice << bits) + b], (unsigned long long)hist[b]);
+    }
+};
+
+struct AccLeaveOut {
+    uint64_t* gmask;    // [64]
+    int32_t* gob;       // [64] group of bit, -1: never left out
+    uint32_t* excl;     // [64] k-mers only group g holds
+    DD_D void init(const SchedArgs& a, uint64_t* dyn) {
+        gmask = dyn;
+        gob = reinterpret_cast<int32_t*>(dyn + 64);
+        excl = reinterpret_cast<uint32_t*>(dyn + 96);
+        if (threadIdx.x < 64) {
+            gob[threadIdx.x] = (int32_t)a.table[threadIdx.x];
+            gmask[threadIdx.x] = (int)threadIdx.x < a.ngroups ? a.table[64 + threadIdx.x] : 0ull;
+            excl[threadIdx.x] = 0;
+        }
+    }
+    DD_D void consume(const SchedArgs&, const uint64_t* tile, uint32_t cnt, uint32_t) {
+        for (uint32_t base = 0; base < cnt; base += kThreads) {
+            const uint32_t i = base + threadIdx.x;
+            const uint64_t m = i < cnt ? tile[i] : 0ull;
+            int32_t g = -1;
+            if (m) g = gob[__builtin_ctzll(m)];
+            const bool only = g >= 0 && (m & ~gmask[g]) == 0;
+            if (only) atomicAdd(&excl[g], 1u);
+        }
+    }
+    DD_D void flush(const SchedArgs& a, uint32_t) {
+        if ((int)threadIdx.x < a.ngroups && excl[threadIdx.x]) atomicAdd(&a.acc[1 + threadIdx.x], (unsigned long long)excl[threadIdx.x]);
+    }
+};
+
+struct AccProgressive {
+    uint64_t* prefix;   // [norder][n]
+    uint32_t* hist;     // [norder][n]: k-mers whose first genome in ordering o stands at position j
+    DD_D void init(const SchedArgs& a, uint64_t* dyn) {
+        prefix = dyn;
+        hist = reinterpret_cast<uint32_t*>(dyn + (size_t)a.norder * a.n);
+        for (int i = threadIdx.x; i < a.norder * a.n; i += kThreads) prefix[i] = a.table[i], hist[i] = 0;
+    }
+    DD_D void consume(const SchedArgs& a, const uint64_t* tile, uint32_t cnt, uint32_t) {
+        for (uint32_t base = 0; base < cnt; base += kThreads) {
+            const uint32_t i = base + threadIdx.x;
+            const bool valid = i < cnt;
+            const uint64_t m = valid ? tile[i] : 0ull;
+            for (int o = 0; o < a.norder; ++o) {
+                const uint64_t* p = prefix + (size_t)o * a.n;
+                int lo = 0, hi = a.n - 1;   // (the last prefix holds every genome: it meets any mask)
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (m & p[mid]) hi = mid;
+                    else lo = mid + 1;
+                }
+                agg_add(hist + (size_t)o * a.n, (uint32_t)lo, valid);
+            }
+        }
+    }
+    DD_D void flush(const SchedArgs& a, uint32_t) {
+        for (int i = threadIdx.x; i < a.norder * a.n; i += kThreads)
+            if (hist[i]) atomicAdd(&a.acc[1 + i], (unsigned long long)hist[i]);
+    }
+};
+
+struct AccPairwise {
+    uint64_t* planes;   // [kChunk / 64][n]: word w of genome i = bit i of masks 64w .. 64w+63 of the tile
+    uint8_t *pi, *pj;   // pair p = (pi[p], pj[p]), i <= j
+    int npairs;
+    unsigned long long sum[kPairSlots];
+    DD_D void init(const SchedArgs& a, uint64_t* dyn) {
+        planes = dyn;
+        pi = reinterpret_cast<uint8_t*>(dyn + (size_t)(kChunk / 64) * a.n);
+        npairs = a.n * (a.n + 1) / 2;
+        pj = pi + npairs;
+        for (int i = threadIdx.x; i < a.n; i += kThreads)
+            for (int j = i; j < a.n; ++j) {
+                const int p = i * a.n - i * (i - 1) / 2 + (j - i);
+                pi[p] = (uint8_t)i, pj[p] = (uint8_t)j;
+            }
+#pragma unroll
+        for (int q = 0; q < kPairSlots; ++q) sum[q] = 0;
+    }
+    DD_D void consume(const SchedArgs& a, const uint64_t* tile, uint32_t cnt, uint32_t) {
+        const uint32_t lane = threadIdx.x & 63, nwords = (cnt + 63) / 64;
+        for (uint32_t w = threadIdx.x >> 6; w < nwords; w += kThreads / 64) {
+            const uint32_t i = w * 64 + lane;
+            const uint64_t m = i < cnt ? tile[i] : 0ull;
+            uint64_t mine = 0;
+            for (int b = 0; b < a.n; ++b) {
+                const uint64_t word = __ballot((m >> b) & 1ull);
+                if ((int)lane == b) mine = word;
+            }
+            if ((int)lane < a.n) planes[(size_t)w * a.n + lane] = mine;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < kPairSlots; ++q) {
+            const int p = q * kThreads + threadIdx.x;
+            if (p < npairs) {
+                const uint64_t *a0 = planes + pi[p], *a1 = planes + pj[p];
+                uint32_t c = 0;
+                for (uint32_t w = 0; w < nwords; ++w) c += __builtin_popcountll(a0[(size_t)w * a.n] & a1[(size_t)w * a.n]);
+                sum[q] += c;
+            }
+        }
+    }
+    DD_D void flush(const SchedArgs& a, uint32_t) {
+#pragma unroll
+        for (int q = 0; q < kPairSlots; ++q) {
+            const int p = q * kThreads + threadIdx.x;
+            if (p < npairs && sum[q]) atomicAdd(&a.acc[1 + p], sum[q]);
+        }
+    }
+};
+
+template <bool WIDE, class Acc>
+__global__ __launch_bounds__(kThreads) void sched_kernel(SortedView s, const uint64_t* __restrict__ carry, size_t nchunks,
+                                                       SchedArgs a) {
+    extern __shared__ uint64_t dyn[];
+    __shared__ uint64_t tile[kChunk];
+    __shared__ uint32_t sf[kThreads / 64];
+    __shared__ uint64_t sv[kThreads / 64];
+    __shared__ uint32_t cnt;
+    Acc acc;
+    acc.init(a, dyn);
+    unsigned long long seen = 0;   // (thread 0: masks of this workgroup)
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t slice = blockIdx.x % (uint32_t)a.slices;   // (the grid is a multiple of the slices)
+    for (size_t chunk = blockIdx.x / (uint32_t)a.slices; chunk < nchunks; chunk += gridDim.x / (uint32_t)a.slices) {
+        if (threadIdx.x == 0) cnt = 0;
+        uint32_t head, tail, f, ef, tf;
+        uint64_t bit[kItems], v, ev, tv;
+        load_items<WIDE>(s, chunk * kChunk + (size_t)threadIdx.x * kItems, head, tail, bit);
+        thread_summary(head, bit, f, v);
+        block_seg_scan<kThreads / 64>(f, v, sf, sv, ef, ev, tf, tv);   // (its barrier also publishes cnt = 0 and the init)
+        uint64_t run = ef ? ev : (ev | carry[chunk]);
+#pragma unroll
+        for (int j = 0; j < kItems; ++j) {
+            if ((head >> j) & 1u) run = 0;
+            run |= bit[j];
+            const bool emit = ((tail >> j) & 1u) && run != 0;
+            const unsigned long long em = __ballot(emit);
+            if (em) {
+                const int leader = __builtin_ctzll(em);
+                uint32_t at = 0;
+                if ((int)lane == leader) at = atomicAdd(&cnt, (uint32_t)__builtin_popcountll(em));
+                at = __shfl(at, leader);
+                if (emit) tile[at + __builtin_popcountll(em & ((1ull << lane) - 1ull))] = run;
+            }
+        }
+        __syncthreads();
+        const uint32_t have = cnt;
+        if (threadIdx.x == 0 && slice == 0) seen += have;
+        acc.consume(a, tile, have, slice);
+        __syncthreads();
+    }
+    __syncthreads();
+    acc.flush(a, slice);
+    if (threadIdx.x == 0 && a.add_m && seen) atomicAdd(&a.acc[0], seen);
+}
+
+// orderings one progressive launch takes: prefix masks + histogram within 40 KiB of LDS
+int max_orderings(int n) { return std::max(1, (40 << 10) / (12 * n)); }
+
+// once per process: every sched_kernel may take the dynamic LDS a CU has left beside the kernel's own (subsets asks for 128 KiB)
+template <class Acc>
+void allow_lds() {
+    for (const void* fn : {reinterpret_cast<const void*>(sched_kernel<true, Acc>), reinterpret_cast<const void*>(sched_kernel<false, Acc>)})
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)160 << 10) - kStaticLds)) != hipSuccess)
+            (void)hipGetLastError();   // (not sticky: a launch that needs the room reports it)
+}
+
+size_t sched_dyn_lds(int kind, int n, int norder) {
+    switch (kind) {
+        case kSchedPairwise: return (size_t)(kChunk / 64) * n * 8 + (size_t)n * (n + 1) + 16;
+        case kSchedProgressive: return (size_t)norder * n * 12 + 16;
+        case kSchedLeaveOut: return 64 * 8 + 64 * 4 + 64 * 4;
+        default: return (size_t)4 << std::min(n, kExactSubsetsLdsN);
+    }
+}
+
+}  // namespace
+
+size_t exact_sched_acc_words(const ExactSched& s) {
+    switch (s.kind) {
+        case kSchedPairwise: return 1 + (size_t)s.n * (s.n + 1) / 2;
+        case kSchedProgressive: return 1 + (size_t)s.norder * s.n;
+        case kSchedLeaveOut: return 1 + (size_t)s.ngroups;
+        default: return 1 + ((size_t)1 << s.n);
+    }
+}
+
+size_t exact_sched_chunks(size_t count) { return (count + kChunk - 1) / kChunk; }
+// per chunk: flag (u32), open-run OR (u64), carry (u64)
+size_t exact_sched_scratch_bytes(size_t count) { return exact_sched_chunks(count) * 24 + 512; }
+
+size_t exact_sched_temp_bytes(size_t n, int k) {
+    size_t a = 0, b = 0, c = 0;
+    uint64_t* nul = nullptr;
+    uint8_t* nul8 = nullptr;
+    (void)rocprim::radix_sort_keys(nullptr, a, nul, nul, n, 0, 64);
+    (void)rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul8, nul8, n, 0, 64);
+    if (k > 32) (void)rocprim::radix_sort_pairs(nullptr, c, nul, nul, nul, nul, n, 0, 64);
+    return std::max(a, std::max(b, c)) + 256;
+}
+
+hipError_t launch_exact_sort_tagged(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, uint8_t* g, uint8_t* g_alt,
+                                    size_t n, int k, void* temp, size_t temp_bytes, hipStream_t st, ExactSorted* out) {
+    const bool sep = exact_tag_mode(k) == 2;
+    hipError_t e;
+    if (k <= 32) {
+        const unsigned bits = (unsigned)(2 * k);
+        if (sep) e = rocprim::radix_sort_pairs(temp, temp_bytes, lo, lo_alt, g, g_alt, n, 0, bits, st);
+        else e = rocprim::radix_sort_keys(temp, temp_bytes, lo, lo_alt, n, 0, bits, st);
+        *out = ExactSorted{lo_alt, nullptr, sep ? g_alt : nullptr};
+        return e;
+    }
+    // stable LSD over the 128-bit key, as in launch_exact_sort_count.  A tag of its own follows through a second sort by
+    // the same keys (the sort is stable and deterministic: the same permutation); only k = 61..64 pay for that.
+    const unsigned bits = (unsigned)(2 * k - 64);
+    if (sep && (e = rocprim::radix_sort_pairs(temp, temp_bytes, lo, lo_alt, g, g_alt, n, 0, 64, st)) != hipSuccess) return e;
+    if ((e = rocprim::radix_sort_pairs(temp, temp_bytes, lo, lo_alt, hi, hi_alt, n, 0, 64, st)) != hipSuccess) return e;
+    if (sep && (e = rocprim::radix_sort_pairs(temp, temp_bytes, hi_alt, hi, g_alt, g, n, 0, bits, st)) != hipSuccess) return e;
+    if ((e = rocprim::radix_sort_pairs(temp, temp_bytes, hi_alt, hi, lo_alt, lo, n, 0, bits, st)) != hipSuccess) return e;
+    *out = ExactSorted{lo, hi, sep ? g : nullptr};
+    return hipSuccess;
+}
+
+hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, const ExactSched& s, void* scratch, hipStream_t st) {
+    if (!count) return hipSuccess;
+    const size_t nchunks = exact_sched_chunks(count);
+    char* sb = static_cast<char*>(scratch);
+    uint64_t* sum_v = reinterpret_cast<uint64_t*>(sb);
+    uint64_t* carry = sum_v + nchunks;
+    uint32_t* sum_f = reinterpret_cast<uint32_t*>(carry + nchunks);
+    const bool wide = k > 32;
+    SortedView v{sorted.lo, sorted.hi, sorted.g, (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1ull),
+                 (k <= 32) ? 0ull : ((k == 64) ? ~0ull : ((1ull << (2 * k - 64)) - 1ull)), count, s.n};
+    if (wide) hipLaunchKernelGGL(sched_summary_kernel<true>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
+    else hipLaunchKernelGGL(sched_summary_kernel<false>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
+    hipLaunchKernelGGL(sched_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, sum_f, sum_v, nchunks, carry);
+    static const bool lds_allowed = (allow_lds<AccPairwise>(), allow_lds<AccProgressive>(), allow_lds<AccLeaveOut>(), allow_lds<AccSubsets>(), true);
+    (void)lds_allowed;
+    const int per = s.kind == kSchedProgressive ? max_orderings(s.n) : 1;
+    for (int o0 = 0; o0 < (s.kind == kSchedProgressive ? s.norder : 1); o0 += per) {
+        SchedArgs a{s.n, 0, s.ngroups, s.table, s.acc, o0 == 0, 1};
+        if (s.kind == kSchedSubsets && s.n > kExactSubsetsLdsN) a.slices = 1 << (s.n - kExactSubsetsLdsN);
+        if (s.kind == kSchedProgressive) {
+            a.norder = std::min(per, s.norder - o0);
+            a.table = s.table + (size_t)o0 * s.n;
+            a.acc = s.acc + (size_t)o0 * s.n;   // (acc[0] of a later launch is never written: add_m = 0)
+        }
+        const size_t dyn = sched_dyn_lds(s.kind, s.n, a.norder);
+        // persistent workgroups (the accumulators flush once each): as many as the CUs hold at this much LDS, 4 per CU at most
+        const size_t per_cu = std::min<size_t>(4, std::max<size_t>(1, ((size_t)160 << 10) / (dyn + kStaticLds)));
+        const unsigned grid = (unsigned)(std::min<size_t>(nchunks, 256 * per_cu) * a.slices);
+#define DD_SCHED(ACC)                                                                                                        \
+    do {                                                                                                                     \
+        if (wide) hipLaunchKernelGGL((sched_kernel<true, ACC>), dim3(grid), dim3(kThreads), dyn, st, v, carry, nchunks, a);  \
+        else hipLaunchKernelGGL((sched_kernel<false, ACC>), dim3(grid), dim3(kThreads), dyn, st, v, carry, nchunks, a);      \
+    } while (0)
+        switch (s.kind) {
+            case kSchedPairwise: DD_SCHED(AccPairwise); break;
+            case kSchedProgressive: DD_SCHED(AccProgressive); break;
+            case kSchedLeaveOut: DD_SCHED(AccLeaveOut); break;
+            default: DD_SCHED(AccSubsets); break;
+        }
+#undef DD_SCHED
+    }
+    return hipGetLastError();
+}
+
+}  // namespace dd

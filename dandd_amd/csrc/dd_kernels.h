@@ -216,15 +216,50 @@ struct ExactGenome {
 //         k-mer is all-ones (T^k, non-canonical)
 // mode 1: hist[4096] += k-mers per bin of the k-mer space (kExactBins bins by a mix of the k-mer)
 // mode 2: k-mers of bins [bin_lo, bin_hi) appended densely from slot counters[3] on (counters[3] += their number)
+// tag (modes 0, 2): 1 = the genome's index in the key's top byte, 2 = in g[slot] (exact_tag_mode below); 0 = keys only
 constexpr int kExactBins = 4096;
 void launch_kmer_extract(const ExactGenome* tab_dev, int ng, size_t max_segments, int k, int canonical,
                          uint64_t* lo, uint64_t* hi, unsigned long long* counters, hipStream_t st, int mode = 0,
-                         unsigned long long* hist = nullptr, uint32_t bin_lo = 0, uint32_t bin_hi = 0);
+                         unsigned long long* hist = nullptr, uint32_t bin_lo = 0, uint32_t bin_hi = 0, int tag = 0,
+                         uint8_t* g = nullptr);
 size_t exact_sort_temp_bytes(size_t n, int k);
 // counters[2] += number of distinct values among the n slots (unwritten slots hold all-ones)
 hipError_t launch_exact_sort_count(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, size_t n,
                                    int k, void* temp, size_t temp_bytes, unsigned long long* counters,
                                    hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
+// exact union schedules (dd_exact_sched.hip): extract with the genome's index -> radix sort -> per distinct k-mer a
+// 64-bit membership mask -> the schedule's accumulator.  Counts are u64 and add up over passes and bins.
+// ---------------------------------------------------------------------------------------
+// how a k-mer carries its genome: 1 = top byte of its most significant word (2k, or 2k - 64, bits leave 8 free), 2 = a
+// byte array next to the keys (k = 29..32, 61..64)
+inline constexpr int exact_tag_mode(int k) { return (k <= 32 ? 2 * k : 2 * k - 64) <= 56 ? 1 : 2; }
+constexpr int kExactSubsetsLdsN = 15;   // subsets: 2^n histogram bins in LDS (u32, 128 KiB at 15); n = 16 as two halves by the top bit
+enum { kSchedPairwise = 0, kSchedProgressive = 1, kSchedLeaveOut = 2, kSchedSubsets = 3 };
+struct ExactSorted {            // where launch_exact_sort_tagged left the sorted k-mers
+    const uint64_t* lo;
+    const uint64_t* hi;         // k > 32
+    const uint8_t* g;           // tag mode 2
+};
+struct ExactSched {
+    int kind, n;
+    int norder;                 // progressive
+    int ngroups;                // leave-out
+    const uint64_t* table;      // device; progressive: prefix masks [norder][n]; leave-out: group of bit i [64] (~0: never left out),
+                                //         then the groups' masks [ngroups]
+    unsigned long long* acc;    // device, exact_sched_acc_words() of them, zeroed by the caller: [0] = M, the number of distinct k-mers,
+                                //   pairwise: then |A_i n A_j| for i <= j, row by row (the diagonal: |A_i|)
+                                //   progressive: then [norder][n] k-mers whose first genome of ordering o stands at position j
+                                //   leave-out: then [ngroups] k-mers no genome outside group g holds
+                                //   subsets: then [2^n] k-mers per membership mask
+};
+size_t exact_sched_acc_words(const ExactSched& s);
+size_t exact_sched_temp_bytes(size_t n, int k);
+size_t exact_sched_scratch_bytes(size_t count);
+hipError_t launch_exact_sort_tagged(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, uint8_t* g, uint8_t* g_alt,
+                                    size_t n, int k, void* temp, size_t temp_bytes, hipStream_t st, ExactSorted* out);
+hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, const ExactSched& s, void* scratch, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // BGZF blocks inflated on the device (dd_ginflate.hip): one wave per block, text straight into the FASTA buffer

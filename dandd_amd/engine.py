@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libdandd_hip.so")
 
-KERNEL_PACK, KERNEL_SWEEP, KERNEL_UNION = 0, 1, 2
+KERNEL_PACK, KERNEL_SWEEP, KERNEL_UNION, KERNEL_EXACT = 0, 1, 2, 3
 ABI_VERSION = 4   # include/dandd_hip.h: DD_ABI_VERSION
 
 EXPORTS = [
@@ -27,6 +27,9 @@ EXPORTS = [
     "dd_progressive", "dd_progressive_device", "dd_pairwise", "dd_pairwise_device", "dd_leave_out", "dd_leave_out_device",
     "dd_subsets", "dd_subsets_device",
     "dd_exact_count", "dd_exact_count_device",
+    "dd_exact_pairwise", "dd_exact_progressive", "dd_exact_leave_out", "dd_exact_subsets",
+    "dd_exact_pairwise_device", "dd_exact_progressive_device", "dd_exact_leave_out_device", "dd_exact_subsets_device",
+    "dd_exact_subsets_from_hist",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
     "dd_comm_unique_id", "dd_comm_init", "dd_comm_destroy", "dd_comm_info", "dd_allreduce_max_u8", "dd_allgather_u8",
@@ -141,6 +144,16 @@ def load_library(path=None):
     lib.dd_exact_count.argtypes = [vp, C.POINTER(C.c_char_p), i32, i32, C.POINTER(u64)]
     lib.dd_exact_count_device.restype = i32
     lib.dd_exact_count_device.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i32, i32, C.POINTER(u64)]
+    paths_t, ptrs_t, sizes_t = C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(sz)
+    for name, src, extra in (("dd_exact_pairwise", [paths_t], []), ("dd_exact_progressive", [paths_t], [vp, i32]),
+                             ("dd_exact_leave_out", [paths_t], [vp, i32]), ("dd_exact_subsets", [paths_t], []),
+                             ("dd_exact_pairwise_device", [ptrs_t, sizes_t], []), ("dd_exact_progressive_device", [ptrs_t, sizes_t], [vp, i32]),
+                             ("dd_exact_leave_out_device", [ptrs_t, sizes_t], [vp, i32]), ("dd_exact_subsets_device", [ptrs_t, sizes_t], [])):
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = [vp] + src + [i32, i32, i32] + extra + [vp]
+    lib.dd_exact_subsets_from_hist.restype = i32
+    lib.dd_exact_subsets_from_hist.argtypes = [vp, i32, vp]
     lib.dd_timing_enable.restype = i32
     lib.dd_timing_enable.argtypes = [vp, i32]
     lib.dd_timing_read.restype = i32
@@ -172,6 +185,20 @@ def ertl_mle(hist, log2m):
     if h.size != 64:
         raise ValueError("histogram must have 64 bins")
     return float(load_library().dd_ertl_mle(h.ctypes.data, int(log2m)))
+
+
+def exact_subsets_from_hist(hist, n):
+    """Host-side (no device needed): hist[mask] = k-mers with that membership mask over n <= 16 genomes -> uint64 [2^n],
+    entry s the number of k-mers of the union of the genomes in s (dd_exact_subsets_from_hist)."""
+    lib = load_library()
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    if not 1 <= int(n) <= 16 or h.size != 1 << int(n):
+        raise ValueError("histogram must have 2^n bins, 1 <= n <= 16")
+    card = np.empty(h.size, dtype=np.uint64)
+    rc = lib.dd_exact_subsets_from_hist(h.ctypes.data, int(n), card.ctypes.data)
+    if rc != 0:
+        raise EngineError(f"libdandd_hip error {rc}: {lib.dd_last_error().decode()}")
+    return card
 
 
 def synth_realistic_size(seed, nbases):
@@ -496,6 +523,64 @@ class Engine:
         d = C.c_uint64()
         self._check(self._lib.dd_exact_count_device(self._ctx, ptrs, ns, n, int(k), C.byref(d)))
         return d.value
+
+    # -- exact union schedules: one sort of all n inputs per k (dd_exact_sched.hip) -----------
+    def _exact_src(self, paths=None, fasta_ptrs=None, nbytes=None):
+        if paths is not None:
+            return [(C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])], len(paths), ""
+        n = len(fasta_ptrs)
+        return [(C.c_void_p * n)(*[int(x) for x in fasta_ptrs]), (C.c_size_t * n)(*[int(x) for x in nbytes])], n, "_device"
+
+    def _exact_sched(self, what, src, shape, kmin, kmax, *extra):
+        args, n, suffix = src
+        K = max(int(kmax) - int(kmin) + 1, 1)
+        card = np.zeros(shape(n) + (K,), dtype=np.uint64)
+        self._check(getattr(self._lib, f"dd_exact_{what}{suffix}")(self._ctx, *args, n, int(kmin), int(kmax), *extra, card.ctypes.data))
+        return card
+
+    def _exact_pairwise(self, src, kmin, kmax):
+        return self._exact_sched("pairwise", src, lambda n: (n, n), kmin, kmax)
+
+    def _exact_progressive(self, src, kmin, kmax, orderings):
+        n = src[1]
+        ords = np.ascontiguousarray(orderings, dtype=np.int32).reshape(-1, max(n, 1))
+        return self._exact_sched("progressive", src, lambda n: (ords.shape[0], n), kmin, kmax, ords.ctypes.data, ords.shape[0])
+
+    def _exact_leave_out(self, src, kmin, kmax, group, ngroups):
+        grp = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        ngroups = int(grp.max()) + 1 if ngroups is None else int(ngroups)
+        return self._exact_sched("leave_out", src, lambda n: (max(ngroups, 0) + 1,), kmin, kmax, grp.ctypes.data, ngroups)
+
+    def _exact_subsets(self, src, kmin, kmax):
+        return self._exact_sched("subsets", src, lambda n: (1 << min(max(n, 0), 16),), kmin, kmax)
+
+    def exact_pairwise(self, paths, kmin, kmax):
+        """FASTA files (n <= 64) -> uint64 [n][n][K]: distinct k-mers of every 2-way union (diagonal: of the file itself)."""
+        return self._exact_pairwise(self._exact_src(paths=paths), kmin, kmax)
+
+    def exact_pairwise_device(self, fasta_ptrs, nbytes, kmin, kmax):
+        return self._exact_pairwise(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax)
+
+    def exact_progressive(self, paths, kmin, kmax, orderings):
+        """-> uint64 [o][n][K]: distinct k-mers of the union of the first j+1 files of every ordering (a permutation of 0..n-1)."""
+        return self._exact_progressive(self._exact_src(paths=paths), kmin, kmax, orderings)
+
+    def exact_progressive_device(self, fasta_ptrs, nbytes, kmin, kmax, orderings):
+        return self._exact_progressive(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, orderings)
+
+    def exact_leave_out(self, paths, kmin, kmax, group, ngroups=None):
+        """-> uint64 [G+1][K]: row g the union of the files outside group g (group[i] == -1: never left out), row G the union of all."""
+        return self._exact_leave_out(self._exact_src(paths=paths), kmin, kmax, group, ngroups)
+
+    def exact_leave_out_device(self, fasta_ptrs, nbytes, kmin, kmax, group, ngroups=None):
+        return self._exact_leave_out(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, group, ngroups)
+
+    def exact_subsets(self, paths, kmin, kmax):
+        """n <= 16 files -> uint64 [2^n][K]: row s the union of the files i with bit i of s set (row 0: 0)."""
+        return self._exact_subsets(self._exact_src(paths=paths), kmin, kmax)
+
+    def exact_subsets_device(self, fasta_ptrs, nbytes, kmin, kmax):
+        return self._exact_subsets(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax)
 
     # -- measurement ----------------------------------------------------------------------
     def timing_enable(self, on=True):

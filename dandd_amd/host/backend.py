@@ -125,7 +125,8 @@ class HipExactBackend:
     """`--exact`: the KMC branch of the reference (lib/sketch_classes.py:377-465), which counts
     distinct canonical k-mers exactly.  A "database" here is a small JSON file listing the FASTAs it
     covers -- base name, the directory it was seen in and its size in bytes -- and, once it has been asked
-    for, their exact distinct k-mer count, computed on the GPU (sort + distinct, dd_exact_count).  Like a KMC
+    for, their exact distinct k-mer count, computed on the GPU (sort + distinct, dd_exact_count; the unions of a whole
+    kij / progressive / deltadelta / abba window from one sort per k, *_cards below).  Like a KMC
     database it answers `info` on its own afterwards, and it survives a moved genome directory as long as
     DANDD_GENOMEDIR (or the recorded directory) still holds files of those names AND sizes.  A genome is
     identified the way DandD's catalog identifies it, by base name (lib/species_specifics.py keys `fastahex` by
@@ -227,6 +228,80 @@ class HipExactBackend:
         db["distinct"] = int(self.engine.exact_count(files, db["k"]))
         self._write(path, db)
         return float(db["distinct"])
+
+    # ---- union schedules: every union of a kij / progressive / deltadelta / abba window from ONE sort of the leaves' k-mers
+    # per k (dd_exact_sched.hip), where card() would read and sort every member again for every union.  Same signatures and
+    # result shapes as HipBackend's; None = no schedule here (more leaves than a membership mask has bits), the caller
+    # takes the object path.
+    MAX_LEAVES, MAX_SUBSET_LEAVES = 64, 16
+
+    def _leaf_window(self, leaf_paths, limit):
+        """-> (dbs [n][K], files [n], kmin, kmax) of leaf databases leaf_paths[i][kk] (one member each, consecutive k per row,
+        the same ks in every row), or None when there are more than `limit` leaves."""
+        if not 1 <= len(leaf_paths) <= limit:
+            return None
+        dbs = [[self._read(p) for p in row] for row in leaf_paths]
+        ks = [int(db["k"]) for db in dbs[0]]
+        if not ks or ks != list(range(ks[0], ks[0] + len(ks))):
+            raise ValueError(f"leaf databases of a schedule must cover consecutive k, found {ks}")
+        files = []
+        for row, paths in zip(dbs, leaf_paths):
+            if [int(db["k"]) for db in row] != ks:
+                raise ValueError(f"{paths[0]}: the leaves of a schedule must cover the same k, found {[db['k'] for db in row]} and {ks}")
+            for db, p in zip(row, paths):
+                if len(db["members"]) != 1 or db["members"][0]["name"] != row[0]["members"][0]["name"]:
+                    raise ValueError(f"{p} is not a database of the one genome {row[0]['members'][0]['name']}")
+            files.append(self._find(row[0]["members"][0]))
+        return dbs, files, ks[0], ks[-1]
+
+    def _seed_leaves(self, leaf_paths, dbs, files, counts):
+        """The leaves' own counts came with the table (counts [n][K]): a leaf database that has none yet keeps its own."""
+        for paths, row, f, cnt in zip(leaf_paths, dbs, files, counts):
+            for p, db, v in zip(paths, row, cnt):
+                if db.get("distinct") is None:
+                    if db["members"][0].get("size") is None:
+                        db["members"][0]["size"] = os.path.getsize(f)
+                    db["distinct"] = int(v)
+                    self._write(p, db)
+
+    def pairwise_cards(self, leaf_paths):
+        """|leaf_i U leaf_j| for all pairs and every k column: float64 [n][n][K]"""
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        dbs, files, kmin, kmax = win
+        table = self.engine.exact_pairwise(files, kmin, kmax)
+        self._seed_leaves(leaf_paths, dbs, files, table[np.arange(len(files)), np.arange(len(files))])
+        return table.astype(np.float64)
+
+    def progressive_cards(self, leaf_paths, orderings):
+        """|union of the first j+1 leaves of ordering o| : float64 [o][n][K]"""
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, kmin, kmax = win
+        return self.engine.exact_progressive(files, kmin, kmax, orderings).astype(np.float64)
+
+    def leave_out_cards(self, leaf_paths, group):
+        """|union of every leaf whose group != g| for g < G, and the union of all leaves as row G: float64 [G+1][K].
+        group[i] = -1: leaf i is in every union."""
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, kmin, kmax = win
+        group = np.asarray(group, dtype=np.int64).reshape(len(leaf_paths))
+        return self.engine.exact_leave_out(files, kmin, kmax, group, int(group.max()) + 1).astype(np.float64)
+
+    def subset_cards(self, leaf_paths):
+        """|union of the leaves i with bit i of s set| for every s < 2^n (n <= 16) and every k column: float64 [2^n][K], row 0
+        (the empty set) 0.0."""
+        win = self._leaf_window(leaf_paths, self.MAX_SUBSET_LEAVES)
+        if win is None:
+            return None
+        dbs, files, kmin, kmax = win
+        table = self.engine.exact_subsets(files, kmin, kmax)
+        self._seed_leaves(leaf_paths, dbs, files, table[[1 << i for i in range(len(files))]])
+        return table.astype(np.float64)
 
     def close(self):
         self.engine.close()

@@ -878,8 +878,9 @@ class DeltaTree:
             stays None), so delta here is max over k in the window of card / k, ties going to the larger k (the climb's `<=`),
             for the rest and, by the same rule, for the union of all leaves.  Per-k rows come back too.
         With a backend that has leave_out_cards (the GPU) every complement at every k of a window comes from ONE launch over the
-        leaf slab and the climbs walk that table (_FlatUnion), falling back to files where a climb leaves it; otherwise (exact
-        trees, the CPU checkers) each group goes through SubSpider / find_delta_delta on the object path.
+        leaf slab (exact trees: one sort of the leaves' k-mers per k) and the climbs walk that table (_FlatUnion), falling back to
+        files where a climb leaves it; otherwise (--safe, DD_NO_PREFETCH, a backend without a table for these leaves, the CPU
+        checkers) each group goes through SubSpider / find_delta_delta on the object path.
         -> (rows, per-k rows)"""
         leaves = self.leaf_nodes()
         by_fasta = {leaf.fastas[0]: leaf for leaf in leaves}
@@ -903,13 +904,14 @@ class DeltaTree:
         exp = dict(self.experiment, ksweep=tuple(int(v) for v in window) if window is not None else None)
         be = backend_for(exp)
         sched = None
-        if hasattr(be, "leave_out_cards") and exp.get("tool") != "kmc" and not exp.get("safety") \
-                and not os.environ.get("DD_NO_PREFETCH"):
+        if hasattr(be, "leave_out_cards") and not exp.get("safety") and not os.environ.get("DD_NO_PREFETCH"):
             lo, hi = self._table_window(exp)
             lo = max(1, lo)
             if hi >= lo:
                 group_of = [owner.get(leaf.fastas[0], -1) for leaf in leaves]
-                sched = UnionTable(be.leave_out_cards(self._leaf_files(leaves, lo, hi), group_of), lo, hi)
+                table = be.leave_out_cards(self._leaf_files(leaves, lo, hi), group_of)
+                if table is not None:       # (None: the backend has no schedule for this many leaves)
+                    sched = UnionTable(table, lo, hi)
         rows, summary = [], []
         full = None
         for gi, g in enumerate(groups):
@@ -961,7 +963,8 @@ class DeltaTree:
         all n! orderings of U (abba_expectations).  Bit i of a mask is fastas[i].
           * Schedule path (a backend with subset_cards): the leaves' window sketches, then every subset at every k of the
             window from ONE launch over the leaf slab.  Subset unions are neither written nor cached (65 536 at n = 16).
-          * Object path (exact trees, --safe, DD_NO_PREFETCH, the CPU checkers): one SubSpider per non-empty subset.
+          * Object path (--safe, DD_NO_PREFETCH, a backend without a table for these leaves, the CPU checkers): one SubSpider
+            per non-empty subset.
         -> dict: ks, cards [2^n][K], delta [2^n], kval [2^n] and the abba_expectations entries"""
         by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
         nodes = [by_fasta[f] for f in fastas]
@@ -972,9 +975,11 @@ class DeltaTree:
         ks = np.arange(lo, hi + 1)
         exp = dict(self.experiment, ksweep=(lo, hi))
         be = backend_for(exp)
-        if hasattr(be, "subset_cards") and exp.get("tool") != "kmc" and not exp.get("safety") \
-                and not os.environ.get("DD_NO_PREFETCH"):
-            cards = np.asarray(be.subset_cards(self._leaf_files(nodes, lo, hi)), dtype=np.float64).reshape(1 << n, len(ks))
+        cards = None
+        if hasattr(be, "subset_cards") and not exp.get("safety") and not os.environ.get("DD_NO_PREFETCH"):
+            cards = be.subset_cards(self._leaf_files(nodes, lo, hi))
+        if cards is not None:
+            cards = np.asarray(cards, dtype=np.float64).reshape(1 << n, len(ks))
         else:
             cards = np.zeros((1 << n, len(ks)))
             for mask in range(1, 1 << n):
@@ -993,7 +998,8 @@ class DeltaTree:
     # ---- batched GPU union schedules ------------------------------------------------------------------
     def _table_window(self, experiment):
         """[lo, hi] of a union table for climbs over this tree's leaves: the --ksweep window, or a hill-climb's guess -- the
-        climbs stay within a few k of the leaves' and the root's argmax (capped at 32 for dashing, allow_k64 or not)."""
+        climbs stay within a few k of the leaves' and the root's argmax (capped at 32 for dashing, allow_k64 or not; at the
+        engine's 64 for exact trees)."""
         if experiment["ksweep"] is not None:
             lo, hi = experiment["ksweep"]
         else:
@@ -1001,6 +1007,8 @@ class DeltaTree:
             hi = self.root_k() + 3
             if experiment["tool"] == "dashing":
                 hi = min(hi, 32)
+            else:
+                hi = min(hi, 64)      # (exact trees: the engine's k <= 64)
         return int(lo), int(hi)
 
     def _leaf_files(self, leaves, lo, hi):
@@ -1050,6 +1058,8 @@ class DeltaTree:
             if not ords:
                 return None
             table, orders = be.progressive_cards(paths, ords), {tuple(o): i for i, o in enumerate(ords)}
+        if table is None:             # (the backend has no schedule for this many leaves: the object path)
+            return None
         experiment["prefetched"] = True
         return UnionTable(table, lo, hi, index, orders)
 

@@ -163,6 +163,39 @@ int dd_exact_count_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_
                           int k, uint64_t *distinct);
 int dd_exact_count(dd_ctx *, const char *const *paths, int n, int k, uint64_t *distinct);
 
+/* ---- exact union schedules -------------------------------------------------------------
+ * The exact counterparts of dd_pairwise / dd_progressive / dd_leave_out / dd_subsets, for trees built with
+ * `--exact` (lib/sketch_classes.py:444-465: one kmc_tools union + info per union there): numbers of distinct
+ * (canonical, per the context) k-mers of unions of the n inputs, for every k in kmin..kmax (K columns, k in 1..64).
+ * Inputs are read, uploaded and packed once per call, and the k-mers of all n inputs are sorted ONCE per k: every
+ * distinct k-mer gets a 64-bit membership mask (bit i: input i holds it) and every union's count is a sum over those
+ * masks (dd_exact_sched.hip).  So 1 <= n <= 64 (subsets: <= 16), else DD_EINVAL.  Empty inputs and inputs without a
+ * k-mer of length k contribute nothing.  The HBM budget and the passes are those of dd_exact_count (DD_EXACT_MB);
+ * dd_last_sketch_stats' third value is the number of passes of the k that took the most.
+ *   pairwise     card[i][j][kk] = |input_i U input_j|, card[i][i][kk] = |input_i|, lower triangle mirrored
+ *   progressive  card[o][j][kk] = |union of inputs ord[o][0..j]|; every ordering a permutation of 0..n-1
+ *   leave_out    card[g][kk] = |union of the inputs whose group != g|, card[ngroups][kk] = |union of all|;
+ *                group[i] == -1: never left out; a group that holds every input is an error
+ *   subsets      card[s][kk] = |union of the inputs i with bit i of s set|, card[0][kk] = 0
+ * The *_device forms take FASTA bytes already on the device, as dd_exact_count_device does (16-byte aligned). */
+int dd_exact_pairwise(dd_ctx *, const char *const *paths, int n, int kmin, int kmax, uint64_t *card /*[n][n][K]*/);
+int dd_exact_progressive(dd_ctx *, const char *const *paths, int n, int kmin, int kmax,
+                         const int32_t *orderings /*[norder][n]*/, int norder, uint64_t *card /*[norder][n][K]*/);
+int dd_exact_leave_out(dd_ctx *, const char *const *paths, int n, int kmin, int kmax,
+                       const int32_t *group /*[n]*/, int ngroups, uint64_t *card /*[ngroups+1][K]*/);
+int dd_exact_subsets(dd_ctx *, const char *const *paths, int n, int kmin, int kmax, uint64_t *card /*[2^n][K]*/);
+int dd_exact_pairwise_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
+                             uint64_t *card);
+int dd_exact_progressive_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
+                                const int32_t *orderings, int norder, uint64_t *card);
+int dd_exact_leave_out_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
+                              const int32_t *group, int ngroups, uint64_t *card);
+int dd_exact_subsets_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
+                            uint64_t *card);
+/* Host arithmetic, no device needed: hist[mask] = number of k-mers with that membership mask (2^n bins, 1 <= n <= 16) ->
+ * card[s] = total - (k-mers whose mask avoids s), by a subset-sum transform of the histogram. */
+int dd_exact_subsets_from_hist(const uint64_t *hist /*[2^n]*/, int n, uint64_t *card /*[2^n]*/);
+
 /* ---- measurement hooks (bench.py) -------------------------------------------------
  * When enabled, every launch of kernel `which` is bracketed by HIP events on the
  * context's stream.  dd_timing_read synchronises the stream and returns the summed
@@ -170,7 +203,8 @@ int dd_exact_count(dd_ctx *, const char *const *paths, int n, int k, uint64_t *d
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_COUNT 3
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules */
+#define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);
 int dd_timing_reset(dd_ctx *);
