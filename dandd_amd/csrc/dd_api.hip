@@ -1369,6 +1369,144 @@ int dd_subsets(dd_ctx* c, const uint8_t* leaf, int n, int K, double* card) {
     return dd_subsets_device(c, static_cast<const uint8_t*>(c->regs.p), n, K, card);
 }
 
+// ---------------------------------------------------------------------- extend / greedy
+namespace {
+
+// one dd_extend step: cards of base U leaf[rows[r]] (base_dev null: of the rows themselves) -> card[nrows][K] on the host
+int extend_step(dd_ctx* c, const uint8_t* base_dev, const uint8_t* leaf_dev, int K, const int32_t* rows, int nrows, double* card) {
+    const size_t njobs = (size_t)nrows * K;
+    int rc;
+    if ((rc = c->hist.reserve((njobs + K) * 64 * sizeof(uint32_t)))) return rc;
+    if ((rc = c->ord.reserve(sizeof(int32_t) * nrows))) return rc;
+    DD_HIP(hipEventSynchronize(c->stage_free));
+    if ((rc = c->stage.reserve(sizeof(int32_t) * nrows))) return rc;
+    if ((rc = upload(c, c->stage, c->ord.p, rows, sizeof(int32_t) * nrows, 0))) return rc;
+    DD_HIP(hipEventRecord(c->stage_free, c->stream));
+    {
+        Span sp(c, DD_KERNEL_UNION);
+        dd::launch_extend(base_dev, leaf_dev, K, c->p, static_cast<const int32_t*>(c->ord.p), nrows, static_cast<uint32_t*>(c->hist.p),
+                          c->stream);
+    }
+    DD_HIP(hipGetLastError());
+    return estimates_from_hist(c, static_cast<const uint32_t*>(c->hist.p), njobs, card);
+}
+
+int extend_args(dd_ctx* c, const uint8_t* leaf, int n, int K, const int32_t* rows, int nrows, const double* card) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 1 || K < 1 || !leaf || !card) return fail(DD_EINVAL, "bad argument");
+    if (nrows < 1) return fail(DD_EINVAL, "nrows=%d: at least one row is needed", nrows);
+    if (rows)
+        for (int r = 0; r < nrows; ++r)
+            if (rows[r] < 0 || rows[r] >= n) return fail(DD_EINVAL, "rows[%d]=%d outside 0..%d", r, rows[r], n - 1);
+    return DD_OK;
+}
+
+int greedy_args(dd_ctx* c, const uint8_t* leaf, int n, int K, int kmin, int mode, const int32_t* cand, int ncand, int nfixed, int nsteps,
+                const int32_t* order, const double* card) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 1 || K < 1 || !leaf || !cand || !order || !card) return fail(DD_EINVAL, "bad argument");
+    if (kmin < 1 || kmin + K - 1 > 64) return fail(DD_EINVAL, "k window %d..%d outside 1..64", kmin, kmin + K - 1);
+    if (mode != DD_GREEDY_MAX && mode != DD_GREEDY_MIN) return fail(DD_EINVAL, "mode=%d: DD_GREEDY_MAX (0) or DD_GREEDY_MIN (1)", mode);
+    if (ncand < 1 || ncand > n) return fail(DD_EINVAL, "ncand=%d outside 1..%d", ncand, n);
+    std::vector<char> seen(n, 0);
+    for (int i = 0; i < ncand; ++i) {
+        if (cand[i] < 0 || cand[i] >= n) return fail(DD_EINVAL, "cand[%d]=%d outside 0..%d", i, cand[i], n - 1);
+        if (seen[cand[i]]) return fail(DD_EINVAL, "cand[%d]=%d is a repeat: candidates are distinct", i, cand[i]);
+        seen[cand[i]] = 1;
+    }
+    if (nfixed < 0 || nfixed > nsteps) return fail(DD_EINVAL, "nfixed=%d outside 0..nsteps=%d", nfixed, nsteps);
+    if (nsteps < 1 || nsteps > ncand) return fail(DD_EINVAL, "nsteps=%d outside 1..ncand=%d", nsteps, ncand);
+    return DD_OK;
+}
+
+// the selection rule of include/dandd_hip.h: the largest card / k of the window, a later k winning a tie
+double window_delta(const double* card, int K, int kmin) {
+    double best = 0.0;
+    for (int kk = 0; kk < K; ++kk) {
+        const double v = card[kk] / (double)(kmin + kk);
+        if (best <= v) best = v;
+    }
+    return best;
+}
+
+}  // namespace
+
+int dd_extend_device(dd_ctx* c, const uint8_t* base_dev, const uint8_t* leaf_dev, int n, int K, const int32_t* rows, int nrows,
+                     double* card) {
+    int rc;
+    if (!rows) nrows = n;
+    if ((rc = extend_args(c, leaf_dev, n, K, rows, nrows, card))) return rc;
+    if ((uintptr_t)base_dev % 16) return fail(DD_EINVAL, "base must be 16-byte aligned");
+    std::vector<int32_t> all;
+    if (!rows) {
+        all.resize(n);
+        for (int i = 0; i < n; ++i) all[i] = i;
+        rows = all.data();
+    }
+    DeviceGuard guard(c->device);
+    return extend_step(c, base_dev, leaf_dev, K, rows, nrows, card);
+}
+
+int dd_extend(dd_ctx* c, const uint8_t* base, const uint8_t* leaf, int n, int K, const int32_t* rows, int nrows, double* card) {
+    int rc;
+    if (!rows) nrows = n;
+    if ((rc = extend_args(c, leaf, n, K, rows, nrows, card))) return rc;
+    DeviceGuard guard(c->device);
+    const size_t bytes = ((size_t)n * K) << c->p, one = (size_t)K << c->p;
+    if ((rc = c->regs.reserve(bytes + (base ? one : 0)))) return rc;
+    uint8_t* dev = static_cast<uint8_t*>(c->regs.p);
+    DD_HIP(hipMemcpyAsync(dev, leaf, bytes, hipMemcpyHostToDevice, c->stream));
+    if (base) DD_HIP(hipMemcpyAsync(dev + bytes, base, one, hipMemcpyHostToDevice, c->stream));
+    return dd_extend_device(c, base ? dev + bytes : nullptr, dev, n, K, rows, nrows, card);
+}
+
+int dd_greedy_device(dd_ctx* c, const uint8_t* leaf_dev, int n, int K, int kmin, int mode, const int32_t* cand, int ncand, int nfixed,
+                     int nsteps, int32_t* order, double* card) {
+    int rc;
+    if ((rc = greedy_args(c, leaf_dev, n, K, kmin, mode, cand, ncand, nfixed, nsteps, order, card))) return rc;
+    DeviceGuard guard(c->device);
+    const size_t one = (size_t)K << c->p;
+    if ((rc = c->gram.reserve(one))) return rc;          // the running union: it never leaves the device
+    uint8_t* base = static_cast<uint8_t*>(c->gram.p);
+    std::vector<int32_t> left(cand + nfixed, cand + ncand);   // in tie-break order throughout
+    std::vector<double> cards((size_t)ncand * K);
+    for (int j = 0; j < nsteps; ++j) {
+        const bool given = j < nfixed;
+        const int32_t* rows = given ? cand + j : left.data();
+        const int nrows = given ? 1 : (int)left.size();
+        if ((rc = extend_step(c, j ? base : nullptr, leaf_dev, K, rows, nrows, cards.data()))) return rc;
+        int pick = 0;
+        double best = window_delta(cards.data(), K, kmin);
+        for (int r = 1; r < nrows; ++r) {
+            const double d = window_delta(cards.data() + (size_t)r * K, K, kmin);
+            if (mode == DD_GREEDY_MAX ? d > best : d < best) best = d, pick = r;
+        }
+        order[j] = rows[pick];
+        memcpy(card + (size_t)j * K, cards.data() + (size_t)pick * K, sizeof(double) * K);
+        if (!given) left.erase(left.begin() + pick);
+        if (j + 1 == nsteps) break;
+        const uint8_t* row = leaf_dev + (size_t)order[j] * one;
+        Span sp(c, DD_KERNEL_UNION);
+        if (j == 0)
+            DD_HIP(hipMemcpyAsync(base, row, one, hipMemcpyDeviceToDevice, c->stream));
+        else
+            dd::launch_extend_fold(base, row, one, c->stream);
+        DD_HIP(hipGetLastError());
+    }
+    return DD_OK;
+}
+
+int dd_greedy(dd_ctx* c, const uint8_t* leaf, int n, int K, int kmin, int mode, const int32_t* cand, int ncand, int nfixed, int nsteps,
+              int32_t* order, double* card) {
+    int rc;
+    if ((rc = greedy_args(c, leaf, n, K, kmin, mode, cand, ncand, nfixed, nsteps, order, card))) return rc;
+    DeviceGuard guard(c->device);
+    const size_t bytes = ((size_t)n * K) << c->p;
+    if ((rc = c->regs.reserve(bytes))) return rc;
+    DD_HIP(hipMemcpyAsync(c->regs.p, leaf, bytes, hipMemcpyHostToDevice, c->stream));
+    return dd_greedy_device(c, static_cast<const uint8_t*>(c->regs.p), n, K, kmin, mode, cand, ncand, nfixed, nsteps, order, card);
+}
+
 // ------------------------------------------------------------------------- measurement
 int dd_timing_enable(dd_ctx* c, int on) {
     if (check_ctx(c)) return DD_EINVAL;

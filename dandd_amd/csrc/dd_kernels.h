@@ -191,6 +191,13 @@ void launch_mle(const uint32_t* hist_dev, size_t njobs, int log2m, double* est_d
 // group consecutive, the floor first.  Zeroes hist_dev itself.
 void launch_leaveout(const uint8_t* leaf_dev, int K, int log2m, const int32_t* tab_dev, int nslots, int G, uint32_t* hist_dev,
                      hipStream_t st);
+// extend unions (dd_extend.hip): hist[(r*K + kk)][64] = histogram of the byte-max of base[kk] and leaf[rows[r]][kk], r < nrows; row
+// nrows*K + kk: base's own.  base_dev null: the empty sketch (the rows' own histograms; row nrows stays zero).  base_dev 16-byte
+// aligned.  Zeroes hist_dev ((nrows + 1) K 64 u32) itself.
+void launch_extend(const uint8_t* base_dev, const uint8_t* leaf_dev, int K, int log2m, const int32_t* rows_dev, int nrows,
+                   uint32_t* hist_dev, hipStream_t st);
+// base = byte-max(base, row) over len bytes (a multiple of 16)
+void launch_extend_fold(uint8_t* base_dev, const uint8_t* row_dev, size_t len, hipStream_t st);
 // all-subset unions (dd_subsets.hip) of columns k0 .. k0 + Kc - 1: hist[(s * Kc + kk)][64] = histogram of the byte-max over
 // the leaves in mask s, s < 2^n (n <= 16); s = 0 gets m in bin 0.  rng as launch_register_range leaves it (all K columns).
 // wg: (column, first job, threshold offset) per workgroup, uploaded by the caller; part: part_bytes of scratch.

@@ -19,13 +19,14 @@ LIB_PATH = os.path.join(_HERE, "lib", "libdandd_hip.so")
 
 KERNEL_PACK, KERNEL_SWEEP, KERNEL_UNION, KERNEL_EXACT = 0, 1, 2, 3
 ABI_VERSION = 4   # include/dandd_hip.h: DD_ABI_VERSION
+GREEDY_MAX, GREEDY_MIN = 0, 1   # include/dandd_hip.h: DD_GREEDY_*
 
 EXPORTS = [
     "dd_abi_version", "dd_last_error", "dd_create", "dd_destroy", "dd_set_stream", "dd_synchronize",
     "dd_sketch_buffer", "dd_sketch_fasta", "dd_sketch_files", "dd_inflate_files", "dd_last_ingest_stats", "dd_sketch_device", "dd_union", "dd_union_device",
     "dd_card", "dd_card_batch", "dd_card_batch_device", "dd_hist_batch_device", "dd_ertl_mle",
     "dd_progressive", "dd_progressive_device", "dd_pairwise", "dd_pairwise_device", "dd_leave_out", "dd_leave_out_device",
-    "dd_subsets", "dd_subsets_device",
+    "dd_subsets", "dd_subsets_device", "dd_extend", "dd_extend_device", "dd_greedy", "dd_greedy_device",
     "dd_exact_count", "dd_exact_count_device",
     "dd_exact_pairwise", "dd_exact_progressive", "dd_exact_leave_out", "dd_exact_subsets",
     "dd_exact_pairwise_device", "dd_exact_progressive_device", "dd_exact_leave_out_device", "dd_exact_subsets_device",
@@ -140,6 +141,12 @@ def load_library(path=None):
     lib.dd_subsets.argtypes = [vp, vp, i32, i32, vp]
     lib.dd_subsets_device.restype = i32
     lib.dd_subsets_device.argtypes = [vp, vp, i32, i32, vp]
+    for fn in (lib.dd_extend, lib.dd_extend_device):
+        fn.restype = i32
+        fn.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp]
+    for fn in (lib.dd_greedy, lib.dd_greedy_device):
+        fn.restype = i32
+        fn.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp]
     lib.dd_exact_count.restype = i32
     lib.dd_exact_count.argtypes = [vp, C.POINTER(C.c_char_p), i32, i32, C.POINTER(u64)]
     lib.dd_exact_count_device.restype = i32
@@ -507,6 +514,52 @@ class Engine:
         card = np.empty((1 << min(max(int(n), 0), 16), int(K)), dtype=np.float64)
         self._check(self._lib.dd_subsets_device(self._ctx, C.c_void_p(int(leaf_ptr)), int(n), int(K), card.ctypes.data))
         return card
+
+    # -- extend / greedy ------------------------------------------------------------------
+    def _extend(self, fn, base, leaf, n, K, rows):
+        if rows is None:
+            rows_ptr, nrows = None, int(n)
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+            rows_ptr, nrows = rows.ctypes.data, rows.size
+        card = np.empty((max(nrows, 0), int(K)), dtype=np.float64)
+        self._check(fn(self._ctx, base, leaf, int(n), int(K), rows_ptr, nrows, card.ctypes.data))
+        return card
+
+    def extend(self, base, leaf, rows=None):
+        """base [K][m] uint8 (host) or None (the empty sketch), leaf [n][K][m] uint8 (host), rows: leaf rows (None: all, in
+        order; repeats allowed) -> card [nrows][K] float64: |base U leaf[rows[r]]|."""
+        leaf = _u8(leaf)
+        n, K = leaf.shape[0], leaf.shape[1]
+        if base is not None:
+            base = _u8(base)
+            if base.size != leaf[0].size:
+                raise ValueError("base is not one [K][m] sketch row of the slab")
+        return self._extend(self._lib.dd_extend, None if base is None else base.ctypes.data, leaf.ctypes.data, n, K, rows)
+
+    def extend_device(self, base_ptr, leaf_ptr, n, K, rows=None):
+        """The same with base (0 / None: the empty sketch) and the slab in device memory."""
+        return self._extend(self._lib.dd_extend_device, C.c_void_p(int(base_ptr)) if base_ptr else None, C.c_void_p(int(leaf_ptr)),
+                            n, K, rows)
+
+    def _greedy(self, fn, leaf, n, K, kmin, mode, cand, nfixed, nsteps):
+        cand = np.ascontiguousarray(np.arange(n) if cand is None else cand, dtype=np.int32).reshape(-1)
+        nsteps = cand.size if nsteps is None else int(nsteps)
+        order = np.empty(max(nsteps, 0), dtype=np.int32)
+        card = np.empty((max(nsteps, 0), int(K)), dtype=np.float64)
+        self._check(fn(self._ctx, leaf, int(n), int(K), int(kmin), int(mode), cand.ctypes.data, cand.size, int(nfixed), nsteps,
+                       order.ctypes.data, card.ctypes.data))
+        return order, card
+
+    def greedy(self, leaf, kmin, mode, cand=None, nfixed=0, nsteps=None):
+        """leaf [n][K][m] uint8 (host), columns k = kmin .. kmin + K - 1; mode GREEDY_MAX / GREEDY_MIN; cand: distinct leaf rows
+        in tie-break order (None: all), the first nfixed of them a given start -> (order int32 [nsteps], card float64
+        [nsteps][K]): the steepest (flattest) ordering by the selection rule of include/dandd_hip.h and its prefix unions."""
+        leaf = _u8(leaf)
+        return self._greedy(self._lib.dd_greedy, leaf.ctypes.data, leaf.shape[0], leaf.shape[1], kmin, mode, cand, nfixed, nsteps)
+
+    def greedy_device(self, leaf_ptr, n, K, kmin, mode, cand=None, nfixed=0, nsteps=None):
+        return self._greedy(self._lib.dd_greedy_device, C.c_void_p(int(leaf_ptr)), n, K, kmin, mode, cand, nfixed, nsteps)
 
     # -- exact distinct k-mer count (KMC stand-in) ----------------------------------------
     def exact_count(self, paths, k):

@@ -592,6 +592,23 @@ class HipBackend:
             slab_mask |= ((masks >> i) & 1) << int(perm[i])
         return table[slab_mask]
 
+    def greedy_cards(self, leaf_paths, mode, nfixed, nsteps, kmin):
+        """The steepest (mode "max") or flattest ("min") ordering of the leaves by the selection rule of include/dandd_hip.h
+        (dd_greedy): leaves 0..nfixed-1 start it in the caller's order, every later step adds the leaf whose union with the
+        chosen ones has the largest (smallest) window delta over k = kmin .. kmin + K - 1, ties going to the leaf the CALLER
+        lists first, whatever order the slab keeps them in.  -> (order [nsteps] as indices into leaf_paths, cards [nsteps][K]:
+        the prefix unions' cardinalities).  One call; the running union never leaves the device."""
+        from ..engine import GREEDY_MAX, GREEDY_MIN
+        code = {"max": GREEDY_MAX, "min": GREEDY_MIN}[mode]
+        n, K = len(leaf_paths), len(leaf_paths[0])
+        ptr, perm = self._device_slab(leaf_paths)
+        if ptr is None:
+            return self.engine.greedy(self._leaf_slab(leaf_paths), kmin, code, None, nfixed, nsteps)
+        order, cards = self.engine.greedy_device(ptr, n, K, kmin, code, perm, nfixed, nsteps)   # cand = the caller's order in slab rows
+        back = np.empty(n, dtype=np.int64)
+        back[perm] = np.arange(n)                        # slab row perm[i] is the caller's leaf i
+        return back[order], cards
+
     def close(self):
         if self._dev is not None:
             self.engine.device_free(self._dev[1])

@@ -1,4 +1,4 @@
-"""`dandd tree | progressive | kij | deltadelta | abba` on the MI355X engine: same sub-commands, flags, defaults and
+"""`dandd tree | progressive | kij | deltadelta | abba | greedy` on the MI355X engine: same sub-commands, flags, defaults and
 output files as /root/reference/lib/dandd_cmd.py (flags :141-286, handlers :43-132); only the
 sketching backend differs.  Run as  python -m dandd_amd.host.cli <subcommand> ...
 """
@@ -276,6 +276,71 @@ def abba_command(args):
     tree.speciesinfo.save_references(fast=False)
 
 
+def greedy_command(args):
+    """The steepest and the flattest growth ordering: add at each step the genome that raises delta the most (--mode max) or
+    the least (min) -- the envelope `progressive`'s sampled orderings are read against, and the answer to "which genome
+    next".  Each step depends on the union so far, so the orderings cannot be listed in advance."""
+    tree = _load_tree(args.delta_tree)
+    tree.speciesinfo.update(tool=tree.experiment["tool"])
+    if not args.tag:
+        args.tag = tree.speciesinfo.tag
+    outfile = tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
+    if args.ksweep:
+        window = (int(args.mink), int(args.maxk))
+    elif tree.experiment.get("ksweep") is not None:
+        window = tuple(int(v) for v in tree.experiment["ksweep"])
+    else:
+        sys.exit("greedy: a k window is needed: give --ksweep --mink --maxk, or a tree built with --ksweep "
+                 "(hill-climb deltas per candidate would depend on the order of the climbs)")
+    if args.safety:
+        tree.experiment["safety"] = True
+    leaf_of = _leaf_lookup(tree, "greedy", args.delta_tree)
+    fastas = tree.progressive_fastas(args.flist_loc)
+    n = len(fastas)
+    if n < 2:
+        sys.exit(f"greedy: {n} genome(s) in the universe: at least 2 are needed")
+    base = []
+    if args.base_loc:
+        with open(args.base_loc) as fh:
+            names = [line.strip() for line in fh if line.strip()]
+        for name in names:
+            f = leaf_of(name)
+            if f not in fastas:
+                sys.exit(f"greedy: {f} (-b) is not in the universe of this run (-f)")
+            if f in base:
+                sys.exit(f"greedy: {f} is listed twice in {args.base_loc}")
+            base.append(f)
+    steps = n if args.steps is None else int(args.steps)
+    if steps < 1 or steps > n:
+        sys.exit(f"greedy: --steps {steps} outside 1..{n}, the genomes in the universe")
+    if steps < len(base):
+        sys.exit(f"greedy: --steps {steps} is fewer than the {len(base)} genomes of -b/--base, which start every ordering")
+    modes = ["max", "min"] if args.mode == "both" else [args.mode]
+    if deltatree.dist_ranks()[1] > 1:
+        # every rank sketches its share of the leaves for the window; rank 0 finishes alone
+        tree.presketch_range(*window)
+        if deltatree.dist_ranks()[0] != 0:
+            return
+    os.makedirs(args.outdir, exist_ok=True)
+    res = tree.greedy_orderings(fastas, *window, modes, base=base, steps=steps)
+    rows, summary = [], []
+    for mode in modes:
+        r = res[mode]
+        prev = 0.0
+        for j, f in enumerate(r["order"]):
+            delta = float(r["delta"][j])
+            rows.append([mode, j + 1, f, delta, int(r["kval"][j]), delta - prev, "|".join(r["order"][:j + 1])])
+            prev = delta
+            for k, c in zip(res["ks"], r["cards"][j]):
+                summary.append([mode, j + 1, int(k), float(c), float(c) / k])
+        with open(f"{outfile}.greedy_{mode}.txt", "w") as fh:
+            fh.write("".join(f + "\n" for f in r["order"]))
+    _write_csv(outfile + ".greedy.csv", ["mode", "ngen", "fasta", "delta", "kval", "gain", "fastas"], rows)
+    _write_csv(outfile + ".greedysummary.csv", ["mode", "ngen", "kval", "card", "delta_pos"], summary)
+    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
+    tree.speciesinfo.save_references(fast=False)
+
+
 def serve_command(args):
     """A resident `dandd`: commands arrive over a unix socket (dandd_amd.host.client), run one at a time in THIS process --
     whose backends (deltatree._backends: GPU context, kernel modules, pinned buffers, job-table cache) outlive them -- with the
@@ -455,6 +520,21 @@ def build_parser():
     ab.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     ab.add_argument("-l", "--label", dest="label", default="")
     ab.set_defaults(func=abba_command)
+
+    gr = subs.add_parser("greedy", parents=[common, sweep],
+                         description="the steepest and the flattest growth ordering: at each step the genome that raises delta the most / the least")
+    gr.add_argument("-d", "--dtree", dest="delta_tree", required=True)
+    gr.add_argument("-s", "--tag", dest="tag", type=str)
+    gr.add_argument("-f", "--fastas", dest="flist_loc", default=None, type=str,
+                    help="the genomes to order (default: every leaf), in the order `progressive -f` takes them; ties go to the earlier one")
+    gr.add_argument("--mode", dest="mode", choices=["max", "min", "both"], default="both")
+    gr.add_argument("-b", "--base", dest="base_loc", default=None, type=str,
+                    help="FASTAs that start every ordering, in the file's order, each in the universe")
+    gr.add_argument("--steps", dest="steps", default=None, type=int,
+                    help="stop after this many genomes in all, the --base ones included (default: all)")
+    gr.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
+    gr.add_argument("-l", "--label", dest="label", default="")
+    gr.set_defaults(func=greedy_command)
 
     # (not in the reference: its every command is a fresh process that shells out to fresh `dashing` processes)
     sv = subs.add_parser("serve", description="keep the GPU context alive and run the commands dandd_amd.host.client forwards")

@@ -995,6 +995,61 @@ class DeltaTree:
         out.update(abba_expectations(delta))
         return out
 
+    # ---- steepest and flattest growth orderings (`dandd greedy`) --------------------------------------------------------
+    def greedy_orderings(self, fastas, lo, hi, modes, base=(), steps=None):
+        """For each mode ("max", "min") the ordering of `fastas` (leaf FASTAs, the universe) that starts with `base` (in its
+        order) and then adds at each step the genome whose union with the chosen ones has the largest (smallest) window delta
+        over k in [max(1, lo), hi], until `steps` genomes stand (default: all).  The rule is _greedy_pick's -- the largest
+        card / k, ties between k to the larger k, ties between genomes to the earlier one of `fastas` -- on every path:
+          * Schedule path (a backend with greedy_cards, the GPU): one call per mode over the leaf slab.
+          * n <= 16 and a backend with subset_cards (exact trees on the GPU): a walk over that one table.
+          * Object path (--safe, DD_NO_PREFETCH, a backend with neither, the CPU checkers, exact trees of n > 16): one
+            SubSpider per (step, candidate), through the cardinality cache.
+        -> dict: ks, and per mode dict(order: FASTAs [steps], cards [steps][K], delta [steps], kval [steps])"""
+        by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
+        base = list(base)
+        given = set(base)
+        seq = base + [f for f in fastas if f not in given]          # candidates in tie-break order behind the given start
+        nodes = [by_fasta[f] for f in seq]
+        n, nfixed = len(nodes), len(base)
+        steps = n if steps is None else int(steps)
+        if not 1 <= steps <= n or steps < nfixed:
+            raise ValueError(f"{steps} steps: between {max(1, nfixed)} and {n}")
+        lo, hi = max(1, int(lo)), int(hi)
+        if hi < lo:
+            raise ValueError(f"empty k window {lo}..{hi}")
+        ks = list(range(lo, hi + 1))
+        exp = dict(self.experiment, ksweep=(lo, hi))
+        be = backend_for(exp)
+        batched = not exp.get("safety") and not os.environ.get("DD_NO_PREFETCH")
+        out = {"ks": ks}
+        table = None
+        for mode in modes:
+            order = cards = None
+            if batched and hasattr(be, "greedy_cards"):
+                got = be.greedy_cards(self._leaf_files(nodes, lo, hi), mode, nfixed, steps, lo)
+                if got is not None:
+                    order = [int(i) for i in got[0]]
+                    cards = np.asarray(got[1], dtype=np.float64).reshape(steps, len(ks))
+            if order is None:
+                if table is None and batched and n <= 16 and hasattr(be, "subset_cards"):
+                    table = be.subset_cards(self._leaf_files(nodes, lo, hi))
+                    if table is not None:
+                        table = np.asarray(table, dtype=np.float64).reshape(1 << n, len(ks))
+                if table is not None:
+                    def card_of(chosen, c, table=table):
+                        return table[sum(1 << i for i in chosen) | 1 << c]
+                else:
+                    def card_of(chosen, c):
+                        sub = SubSpider([nodes[i] for i in chosen] + [nodes[c]], self.speciesinfo, exp)
+                        sub.root.node_ksweep(lo, hi)
+                        return [sub.root.ksketches[k].card for k in ks]
+                order, cards = _greedy_walk(card_of, n, nfixed, steps, mode, ks)
+            picked = [_window_delta([float(c) for c in row], ks) for row in cards]
+            out[mode] = dict(order=[seq[i] for i in order], cards=np.asarray(cards, dtype=np.float64),
+                             delta=[d for d, _ in picked], kval=[k for _, k in picked])
+        return out
+
     # ---- batched GPU union schedules ------------------------------------------------------------------
     def _table_window(self, experiment):
         """[lo, hi] of a union table for climbs over this tree's leaves: the --ksweep window, or a hill-climb's guess -- the
@@ -1274,6 +1329,34 @@ def _window_delta(cards, ks):
         if best <= c / k:
             best, bestk = c / k, k
     return best, bestk
+
+
+def _greedy_pick(cards, ks, mode):
+    """The greedy selection rule (include/dandd_hip.h: dd_greedy): among the candidates' card rows, in tie-break order, the
+    index of the one with the largest (mode "max") or smallest ("min") window delta; equal deltas go to the earlier one."""
+    pick, best = 0, _window_delta(cards[0], ks)[0]
+    for r in range(1, len(cards)):
+        d = _window_delta(cards[r], ks)[0]
+        if d > best if mode == "max" else d < best:
+            pick, best = r, d
+    return pick
+
+
+def _greedy_walk(card_of, n, nfixed, steps, mode, ks):
+    """The walk of dd_greedy over card_of(chosen, c) -> the cards of the union of items `chosen` and c at every k of ks:
+    items 0..nfixed-1 are given, then _greedy_pick among the items not yet chosen, in index order.
+    -> (order [steps], cards [steps][K])"""
+    left = list(range(nfixed, n))
+    order, cards = [], []
+    for j in range(steps):
+        rows = [j] if j < nfixed else left
+        got = [[float(c) for c in card_of(order, c)] for c in rows]
+        pick = 0 if j < nfixed else _greedy_pick(got, ks, mode)
+        order.append(rows[pick])
+        cards.append(got[pick])
+        if j >= nfixed:
+            del left[pick]
+    return order, cards
 
 
 def abba_expectations(delta):

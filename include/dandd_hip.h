@@ -152,6 +152,38 @@ int dd_subsets(dd_ctx *, const uint8_t *leaf /*[n][K][m]*/, int n, int K,
                double *card /*[2^n][K]*/);
 int dd_subsets_device(dd_ctx *, const uint8_t *leaf_dev, int n, int K, double *card);
 
+/* ---- extend unions ------------------------------------------------------------------
+ * The one union schedule whose first operand is NOT a leaf: a base sketch against every listed leaf.
+ * card[r][kk] = |base U leaf[rows[r]]| at k column kk.  base == NULL: the empty sketch (card = |leaf[rows[r]]|).
+ * rows == NULL: all n leaves in order (nrows = n).  Entries of rows in 0..n-1, repeats allowed.
+ * One read of the listed rows: where a leaf's register exceeds base's, its histogram differs from base's by one
+ * register moved between two bins (dd_extend.hip): the same integers as a byte-max + histogram per row.
+ * Register bytes must be <= 63. */
+int dd_extend(dd_ctx *, const uint8_t *base /*[K][m]*/, const uint8_t *leaf /*[n][K][m]*/, int n, int K,
+              const int32_t *rows /*[nrows]*/, int nrows, double *card /*[nrows][K]*/);
+int dd_extend_device(dd_ctx *, const uint8_t *base_dev, const uint8_t *leaf_dev, int n, int K,
+                     const int32_t *rows, int nrows, double *card /*host*/);
+
+/* ---- greedy orderings ---------------------------------------------------------------
+ * For `dandd greedy`: the ordering that adds at each step the candidate that raises (DD_GREEDY_MAX) or lowers
+ * (DD_GREEDY_MIN) delta the most -- the steepest and the flattest growth curve.
+ * cand[ncand]: distinct leaf rows, in tie-break order.  order[j] = cand[j] for j < nfixed (a given start, may be 0);
+ * then order[j] = the candidate c not yet chosen that maximises (minimises) delta(order[0..j-1] + c), for j < nsteps,
+ * nfixed <= nsteps <= ncand, nsteps >= 1.  card[j][kk] = |union of leaf[order[0..j]]| at k = kmin + kk.
+ * THE SELECTION RULE (the host layer's object path implements the same one):
+ *   delta of a set over the window = the largest card[kk] / (kmin + kk) in IEEE double, ties between k going to the
+ *   LARGER k (best <= c / k, walking k upwards from best = 0);
+ *   ties between candidates (equal delta as doubles) go to the candidate that comes FIRST in cand.
+ * One dd_extend step per position inside the call; the running union stays on the device.
+ * 1 <= kmin, kmin + K - 1 <= 64.  Register bytes must be <= 63. */
+#define DD_GREEDY_MAX 0
+#define DD_GREEDY_MIN 1
+int dd_greedy(dd_ctx *, const uint8_t *leaf /*[n][K][m]*/, int n, int K, int kmin, int mode,
+              const int32_t *cand /*[ncand]*/, int ncand, int nfixed, int nsteps,
+              int32_t *order /*[nsteps]*/, double *card /*[nsteps][K]*/);
+int dd_greedy_device(dd_ctx *, const uint8_t *leaf_dev, int n, int K, int kmin, int mode,
+                     const int32_t *cand, int ncand, int nfixed, int nsteps, int32_t *order, double *card);
+
 /* ---- exact distinct k-mer count (the KMC stand-in) --------------------------------------
  * Replaces   kmc -ci1 -cs2 -k<K> [-b] -fm <fasta> <db> <tmp>   +   kmc_tools complex (set union)
  * +   kmc_tools info <db> | grep 'total k-mers'   (lib/sketch_classes.py:395,444-448,453-465):

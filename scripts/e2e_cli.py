@@ -1,4 +1,4 @@
-"""End-to-end timing of the drop-in CLI (tree -> progressive -> kij -> deltadelta) on synthetic genomes written as
+"""End-to-end timing of the drop-in CLI (tree -> progressive -> kij -> deltadelta -> greedy) on synthetic genomes written as
 FASTA files, i.e. everything a DandD user pays for: Python start-up, file reads, H2D copies, K0..K3,
 the host-side tree / spider logic, pickles and CSVs.  Development aid, not the contract bench.
 
@@ -126,6 +126,8 @@ def measure(args, run, cli, gdir, out, sweep, timings):
     run("progressive", cli + ["progressive", "-d", dtree, "-o", out, "-n", str(args.norderings)] + sweep)
     run("kij", cli + ["kij", "-d", dtree, "-o", out] + (["--jaccard"] + sweep if sweep else []))
     run("deltadelta", cli + ["deltadelta", "-d", dtree, "-o", out] + sweep)
+    if sweep:       # (greedy needs a k window, as abba does)
+        run("greedy", cli + ["greedy", "-d", dtree, "-o", out] + sweep)
 
 
 
