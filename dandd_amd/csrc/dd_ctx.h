@@ -1,5 +1,6 @@
 // dd_ctx.h -- the context behind the C ABI's opaque dd_ctx, and the host-side helpers the ABI's sources share
-// (dd_api.hip: sketch, union, card, K2, comm; dd_ingest.hip: the file-ingestion pipeline).  Callers see dandd_hip.h only.
+// (dd_api.hip: context, sketch, timing, synth, comm; dd_k2_api.hip: union, card and the HLL schedules; dd_exact_api.hip:
+// exact count and schedules; dd_ingest.hip: the file-ingestion pipeline).  Callers see dandd_hip.h only.
 #pragma once
 #include "../../include/dandd_hip.h"
 #include <sched.h>
@@ -168,3 +169,110 @@ inline int usable_cpus() {
     return n;
 }
 inline int check_ctx(dd_ctx* c) { return c ? DD_OK : fail(DD_EINVAL, "null context"); }
+
+inline hipEvent_t get_event(dd_ctx* c) {
+    if (!c->pool.empty()) {
+        hipEvent_t e = c->pool.back();
+        c->pool.pop_back();
+        return e;
+    }
+    hipEvent_t e = nullptr;
+    (void)hipEventCreate(&e);
+    return e;
+}
+
+struct Span {  // brackets a launch (or a whole phase) on the context's stream with events when timing is on
+    dd_ctx* c;
+    int which;
+    bool on;
+    TimedSpan s{};
+    Span(dd_ctx* c_, int which_, bool on_ = true) : c(c_), which(which_), on(on_ && c_->timing) {
+        if (on) {
+            s.a = get_event(c);
+            s.b = get_event(c);
+            (void)hipEventRecord(s.a, c->stream);
+        }
+    }
+    ~Span() {
+        if (on) {
+            (void)hipEventRecord(s.b, c->stream);
+            c->spans[which].push_back(s);
+        }
+    }
+};
+
+// upload a host table through the pinned staging buffer (async on the stream)
+inline int upload(dd_ctx* c, HostBuf& stage, void* dst_dev, const void* src, size_t bytes, size_t stage_off) {
+    if (!bytes) return DD_OK;
+    memcpy(static_cast<char*>(stage.p) + stage_off, src, bytes);
+    DD_HIP(hipMemcpyAsync(dst_dev, static_cast<char*>(stage.p) + stage_off, bytes,
+                          hipMemcpyHostToDevice, c->stream));
+    return DD_OK;
+}
+
+// A host table into `dst` (grown to hold it) through c->stage.  The staging buffer may not be rewritten while the upload
+// before this one is in flight: stage_free is waited for first and recorded behind the copy.  (dd_sketch_device alternates
+// two staging sets around its launches and keeps its own sequence.)
+inline int stage_table(dd_ctx* c, DevBuf& dst, const void* src, size_t bytes) {
+    int rc;
+    if ((rc = dst.reserve(bytes))) return rc;
+    DD_HIP(hipEventSynchronize(c->stage_free));
+    if ((rc = c->stage.reserve(bytes))) return rc;
+    if ((rc = upload(c, c->stage, dst.p, src, bytes, 0))) return rc;
+    DD_HIP(hipEventRecord(c->stage_free, c->stream));
+    return DD_OK;
+}
+
+// histograms already on the device -> estimates on the host (device MLE, bit-identical to the
+// host MLE: same IEEE operations, no contraction; asserted by tests/test_gpu_parity.py)
+inline int estimates_from_hist(dd_ctx* c, const uint32_t* hist_dev, size_t njobs, double* est_host) {
+    int rc = c->est.reserve(njobs * sizeof(double));
+    if (rc) return rc;
+    dd::launch_mle(hist_dev, njobs, c->p, static_cast<double*>(c->est.p), c->stream);
+    DD_HIP(hipGetLastError());
+    DD_HIP(hipMemcpyAsync(est_host, c->est.p, njobs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    DD_HIP(hipStreamSynchronize(c->stream));
+    return DD_OK;
+}
+
+// K0's workspace for the n inputs of a call: every input's token stream (codes | bad | ntok, each 256-byte aligned) in
+// c->tokens and its pack scratch in c->scratch.  ptab[g] is what K0 reads; ptab[g].out is where its tokens will be.
+inline int layout_tokens(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, std::vector<dd::PackGenome>& ptab,
+                         size_t& max_chunks) {
+    std::vector<size_t> off_codes(n), off_bad(n), off_ntok(n), off_scratch(n);
+    size_t tot = 0, scratch_tot = 0;
+    for (int g = 0; g < n; ++g) {
+        off_codes[g] = tot;
+        tot += align_up(dd::codes_words(nbytes[g]) * 4, 256);
+        off_bad[g] = tot;
+        tot += align_up(dd::bad_words(nbytes[g]) * 4, 256);
+        off_ntok[g] = tot;
+        tot += 256;
+        off_scratch[g] = scratch_tot;
+        scratch_tot += align_up(dd::pack_scratch_bytes(nbytes[g]), 256);
+    }
+    int rc;
+    if ((rc = c->tokens.reserve(tot))) return rc;
+    if ((rc = c->scratch.reserve(scratch_tot))) return rc;
+    char* tb = static_cast<char*>(c->tokens.p);
+    char* sb = static_cast<char*>(c->scratch.p);
+    ptab.resize(n);
+    max_chunks = 0;
+    for (int g = 0; g < n; ++g) {
+        dd::TokenStream ts{reinterpret_cast<uint32_t*>(tb + off_codes[g]), reinterpret_cast<uint32_t*>(tb + off_bad[g]),
+                           reinterpret_cast<unsigned long long*>(tb + off_ntok[g])};
+        ptab[g] = dd::PackGenome{fasta_dev[g], nbytes[g], dd::pack_chunks(nbytes[g]),
+                                 reinterpret_cast<long long*>(sb + off_scratch[g]), ts};
+        max_chunks = std::max(max_chunks, ptab[g].nchunks);
+    }
+    return DD_OK;
+}
+
+// the group[] / ngroups rules that the HLL and the exact leave-out share
+inline int check_groups(const int32_t* group, int ngroups, int n) {
+    if (ngroups < 1) return fail(DD_EINVAL, "ngroups=%d: at least one group is needed", ngroups);
+    if (ngroups > n) return fail(DD_EINVAL, "ngroups=%d is more than the %d leaves", ngroups, n);
+    for (int i = 0; i < n; ++i)
+        if (group[i] < -1 || group[i] >= ngroups) return fail(DD_EINVAL, "group[%d]=%d outside -1..%d", i, group[i], ngroups - 1);
+    return DD_OK;
+}

@@ -1,0 +1,489 @@
+// dd_exact_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h): dd_exact_count* and the exact union
+// schedules (dd_exact_pairwise / _progressive / _leave_out / _subsets).  Host-side orchestration only; the kernels are in
+// dd_exact.hip and dd_exact_sched.hip.
+#include <functional>
+#include "dd_ctx.h"
+
+using dd::FileBuf;
+using dd::read_fasta_file;
+
+namespace {
+
+// K0 over the n inputs of an exact call (once per call, whatever the number of ks) and where each genome's k-mers go
+struct ExactInputs {
+    const dd::ExactGenome* etab_dev = nullptr;
+    size_t slots = 0, max_segments = 0;   // slots = 0: no input has a token
+};
+
+int exact_check_inputs(const uint8_t* const* fasta_dev, const size_t* nbytes, int n) {
+    for (int g = 0; g < n; ++g) {
+        if (nbytes[g] && !fasta_dev[g]) return fail(DD_EINVAL, "input %d: null buffer", g);
+        if (reinterpret_cast<uintptr_t>(fasta_dev[g]) & 15)
+            return fail(DD_EINVAL, "input %d: device buffer must be 16-byte aligned", g);
+    }
+    return DD_OK;
+}
+
+int exact_prepare(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, ExactInputs& in) {
+    int rc;
+    std::vector<unsigned long long> base(n);
+    for (int g = 0; g < n; ++g) {
+        base[g] = in.slots;
+        const size_t segs = (nbytes[g] + dd::kSegTokens - 1) / dd::kSegTokens;
+        in.slots += segs * dd::kSegTokens;
+        in.max_segments = std::max(in.max_segments, segs);
+    }
+    if (!in.slots) return DD_OK;
+    std::vector<dd::PackGenome> ptab;
+    size_t max_chunks = 0;
+    if ((rc = layout_tokens(c, fasta_dev, nbytes, n, ptab, max_chunks))) return rc;
+    // K0's table and the extract's, one image: PackGenome[n] | ExactGenome[n], each 256-byte aligned
+    const size_t pbytes = align_up(sizeof(dd::PackGenome) * n, 256), ebytes = align_up(sizeof(dd::ExactGenome) * n, 256);
+    std::vector<char> image(pbytes + ebytes, 0);
+    memcpy(image.data(), ptab.data(), sizeof(dd::PackGenome) * n);
+    dd::ExactGenome* etab = reinterpret_cast<dd::ExactGenome*>(image.data() + pbytes);
+    for (int g = 0; g < n; ++g) etab[g] = dd::ExactGenome{ptab[g].out.codes, ptab[g].out.bad, ptab[g].out.ntok, base[g]};
+    if ((rc = stage_table(c, c->tables, image.data(), image.size()))) return rc;
+    char* tdev = static_cast<char*>(c->tables.p);
+    {
+        Span sp(c, DD_KERNEL_PACK);
+        dd::launch_pack_batch(reinterpret_cast<const dd::PackGenome*>(tdev), n, max_chunks, c->stream);
+    }
+    in.etab_dev = reinterpret_cast<const dd::ExactGenome*>(tdev + pbytes);
+    return DD_OK;
+}
+
+size_t exact_budget() {
+    size_t budget = (size_t)24 << 30;
+    if (const char* e = getenv("DD_EXACT_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
+    return budget;
+}
+
+// the files of a path form, read and uploaded into the context's FASTA buffer
+int exact_upload_files(dd_ctx* c, const char* const* paths, int n, std::vector<const uint8_t*>& ptrs, std::vector<size_t>& sizes) {
+    std::vector<size_t> offs(n);
+    std::vector<FileBuf> bufs(n);
+    sizes.assign(n, 0);
+    ptrs.assign(n, nullptr);
+    size_t tot = 0;
+    for (int i = 0; i < n; ++i) {
+        std::string err;
+        if (!paths[i] || !read_fasta_file(paths[i], bufs[i], err, usable_cpus())) return fail(DD_EIO, "%s", err.c_str());
+        sizes[i] = bufs[i].size();
+        offs[i] = tot;
+        tot += align_up(sizes[i] + 16, 256);
+    }
+    int rc;
+    if ((rc = c->fasta.reserve(tot + 16))) return rc;
+    for (int i = 0; i < n; ++i) {
+        ptrs[i] = static_cast<const uint8_t*>(c->fasta.p) + offs[i];
+        if (sizes[i])
+            DD_HIP(hipMemcpyAsync(const_cast<uint8_t*>(ptrs[i]), bufs[i].data(), sizes[i], hipMemcpyHostToDevice, c->stream));
+    }
+    DD_HIP(hipStreamSynchronize(c->stream));  // host buffers are pageable; release them before the sort
+    return DD_OK;
+}
+
+// ------------------------------------------------------------------------ the pass driver
+// What a caller of exact_passes says about its part of the k-mer workspace.
+struct ExactLayout {
+    const char* what;                           // "exact count" / "exact schedule", for the messages
+    int tag;                                    // launch_kmer_extract's tag mode; 2 adds the g | g_alt arrays (a byte per slot each)
+    size_t (*temp_bytes)(size_t keys, int k);   // of the caller's sort
+    size_t (*scratch_bytes)(size_t keys);       // what the caller wants behind the sort's temp (null: nothing)
+};
+
+// c->exact carved for `keys` k-mers:
+// counters (256 B) | bin histogram (32 KiB) | lo | lo_alt [| hi | hi_alt] [| g | g_alt] | sort temp | scratch
+struct ExactArrays {
+    unsigned long long *counters, *hist;
+    uint64_t *lo, *lo_alt, *hi, *hi_alt;   // hi: k > 32
+    uint8_t *g, *g_alt;                    // tag mode 2
+    void *temp, *scratch;
+    size_t temp_bytes;
+};
+
+constexpr size_t kExactHistBytes = (size_t)dd::kExactBins * sizeof(unsigned long long);
+
+int exact_carve(dd_ctx* c, const ExactLayout& L, int k, size_t keys, ExactArrays& a) {
+    const bool wide = k > 32, sep = L.tag == 2;
+    const size_t arrays = wide ? 4 : 2, stride = align_up(keys * sizeof(uint64_t), 256), gstride = sep ? align_up(keys, 256) : 0;
+    a.temp_bytes = L.temp_bytes(keys, k);
+    int rc = c->exact.reserve(256 + kExactHistBytes + arrays * stride + 2 * gstride + align_up(a.temp_bytes, 256) +
+                              (L.scratch_bytes ? L.scratch_bytes(keys) : 0) + 256);
+    if (rc) return rc;
+    char* eb = static_cast<char*>(c->exact.p);
+    a.counters = reinterpret_cast<unsigned long long*>(eb);
+    a.hist = reinterpret_cast<unsigned long long*>(eb + 256);
+    char* kb = eb + 256 + kExactHistBytes;
+    a.lo = reinterpret_cast<uint64_t*>(kb);
+    a.lo_alt = reinterpret_cast<uint64_t*>(kb + stride);
+    a.hi = wide ? reinterpret_cast<uint64_t*>(kb + 2 * stride) : nullptr;
+    a.hi_alt = wide ? reinterpret_cast<uint64_t*>(kb + 3 * stride) : nullptr;
+    kb += arrays * stride;
+    a.g = sep ? reinterpret_cast<uint8_t*>(kb) : nullptr;
+    a.g_alt = sep ? reinterpret_cast<uint8_t*>(kb + gstride) : nullptr;
+    kb += 2 * gstride;
+    a.temp = kb;
+    a.scratch = kb + align_up(a.temp_bytes, 256);
+    return DD_OK;
+}
+
+// the counters of a pass, read back (dd_kernels.h, launch_kmer_extract); single: the pass held every slot of the inputs
+using ExactCounted = std::function<void(const unsigned long long* h, bool single)>;
+
+// The k-mers of the prepared inputs for one k, extracted into c->exact and handed to consume(arrays, count) -- which
+// launches its sort and what follows -- everything at once when that fits exact_budget(), else in passes over disjoint
+// parts of the k-mer space.  KMC unions arbitrarily many databases (lib/sketch_classes.py:453-465 of the reference); so
+// must this.  The counters are zeroed before each pass, outside its timing span.  `counted` receives them after the
+// pass; without it a single pass is not waited for.  c->st_blocks = the number of passes (dd_last_sketch_stats).
+template <class Consume>
+int exact_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const ExactLayout& L, Consume consume, const ExactCounted& counted = nullptr) {
+    hipStream_t st = c->stream;
+    int rc;
+    const bool wide = k > 32;
+    const size_t slots = in.slots, per_slot = (wide ? 4 : 2) * sizeof(uint64_t) + (L.tag == 2 ? 2 : 0), budget = exact_budget();
+    const bool single = per_slot * slots <= budget;
+    size_t cap = single ? slots : std::max<size_t>(budget / per_slot, 4096);   // k-mers per pass
+    ExactArrays a{};
+    if ((rc = exact_carve(c, L, k, cap, a))) return rc;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    if (single) {
+        DD_HIP(hipMemsetAsync(a.counters, 0, 256, st));
+        {
+            Span sp(c, DD_KERNEL_EXACT);
+            // unwritten slots read as the all-ones sentinel (T^k's run), with genome 0xFF, which sets no bit
+            DD_HIP(hipMemsetAsync(a.lo, 0xFF, slots * sizeof(uint64_t), st));
+            if (wide) DD_HIP(hipMemsetAsync(a.hi, 0xFF, slots * sizeof(uint64_t), st));
+            if (a.g) DD_HIP(hipMemsetAsync(a.g, 0xFF, slots, st));
+            dd::launch_kmer_extract(in.etab_dev, n, in.max_segments, k, c->canonical, a.lo, a.hi, a.counters, st, 0, nullptr, 0, 0, L.tag, a.g);
+            DD_HIP(hipGetLastError());
+            if ((rc = consume(a, slots))) return rc;
+        }
+        if (counted) {
+            DD_HIP(hipMemcpyAsync(h, a.counters, sizeof h, hipMemcpyDeviceToHost, st));
+            DD_HIP(hipStreamSynchronize(st));
+            counted(h, true);
+        }
+        c->st_blocks = 1;
+        return DD_OK;
+    }
+
+    // ---- more k-mers than the budget holds: passes over disjoint parts of the k-mer space ------------
+    // The k-mer space is cut into 4096 bins by a mix of the k-mer itself (equal k-mers share a bin), a
+    // counting pass sizes the bins, consecutive bins are grouped into passes of at most `cap` k-mers, and every
+    // pass extracts (densely), sorts and consumes only its own bins.
+    DD_HIP(hipMemsetAsync(a.counters, 0, 256 + kExactHistBytes, st));
+    {
+        Span sp(c, DD_KERNEL_EXACT);
+        dd::launch_kmer_extract(in.etab_dev, n, in.max_segments, k, c->canonical, a.lo, a.hi, a.counters, st, 1, a.hist, 0, 0);
+    }
+    DD_HIP(hipGetLastError());
+    std::vector<unsigned long long> bins(dd::kExactBins);
+    DD_HIP(hipMemcpyAsync(bins.data(), a.hist, kExactHistBytes, hipMemcpyDeviceToHost, st));
+    DD_HIP(hipStreamSynchronize(st));
+    const unsigned long long biggest = *std::max_element(bins.begin(), bins.end());
+    if (biggest > cap) {
+        // one bin alone is over the budget (one k-mer repeated billions of times lands in one bin): the arrays
+        // grow to hold it if the device has the room, otherwise this input cannot be counted here
+        cap = (size_t)biggest;
+        if (exact_carve(c, L, k, cap, a))
+            return fail(DD_ENOMEM, "%s: one part of the k-mer space holds %llu k-mers, more than fits in HBM", L.what, biggest);
+    }
+    int npass = 0;
+    for (uint32_t b0 = 0; b0 < (uint32_t)dd::kExactBins;) {
+        unsigned long long in_pass = 0;
+        uint32_t b1 = b0;
+        while (b1 < (uint32_t)dd::kExactBins && in_pass + bins[b1] <= cap) in_pass += bins[b1++];
+        if (in_pass) {
+            DD_HIP(hipMemsetAsync(a.counters, 0, 256, st));
+            {
+                Span sp(c, DD_KERNEL_EXACT);
+                dd::launch_kmer_extract(in.etab_dev, n, in.max_segments, k, c->canonical, a.lo, a.hi, a.counters, st, 2, a.hist, b0, b1, L.tag, a.g);
+                DD_HIP(hipGetLastError());
+                // (every slot below in_pass is written: no sentinel, T^k is an ordinary value here)
+                if ((rc = consume(a, (size_t)in_pass))) return rc;
+            }
+            DD_HIP(hipMemcpyAsync(h, a.counters, sizeof h, hipMemcpyDeviceToHost, st));
+            DD_HIP(hipStreamSynchronize(st));
+            if (h[3] != in_pass) return fail(DD_EHIP, "%s: pass over bins %u..%u appended %llu k-mers, %llu expected", L.what, b0, b1, h[3], in_pass);
+            if (counted) counted(h, false);
+            ++npass;
+        }
+        b0 = b1;
+    }
+    c->st_blocks = npass;
+    return DD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ------------------------------------------------------------------------- exact count
+int dd_exact_count_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int k,
+                          uint64_t* distinct) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 0 || !distinct || (n && (!fasta_dev || !nbytes))) return fail(DD_EINVAL, "null argument");
+    if (k < 1 || k > 64) return fail(DD_EINVAL, "k=%d outside 1..64", k);
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    *distinct = 0;
+    if (!n) return DD_OK;
+    DeviceGuard guard(c->device);
+    int rc;
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n, in))) return rc;
+    if (!in.slots) return DD_OK;
+    unsigned long long total = 0;
+    rc = exact_passes(
+        c, in, n, k, ExactLayout{"exact count", 0, dd::exact_sort_temp_bytes, nullptr},
+        [&](const ExactArrays& a, size_t count) -> int {
+            DD_HIP(dd::launch_exact_sort_count(a.lo, a.hi, a.lo_alt, a.hi_alt, count, k, a.temp, a.temp_bytes, a.counters, c->stream));
+            return DD_OK;
+        },
+        [&](const unsigned long long* h, bool single) {
+            total += h[2];   // distinct = sum over passes
+            if (!single) return;
+            // the all-ones group holds the sentinels of unwritten slots and/or genuine T^k k-mers
+            const bool sentinel_present = h[0] < (unsigned long long)in.slots, all_t = h[1] != 0;
+            total = total - ((sentinel_present || all_t) ? 1 : 0) + (all_t ? 1 : 0);
+        });
+    if (rc) return rc;
+    *distinct = total;
+    return DD_OK;
+}
+
+int dd_exact_count(dd_ctx* c, const char* const* paths, int n, int k, uint64_t* distinct) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 0 || !distinct || (n && !paths)) return fail(DD_EINVAL, "null argument");
+    DeviceGuard guard(c->device);
+    std::vector<const uint8_t*> ptrs;
+    std::vector<size_t> sizes;
+    int rc;
+    if ((rc = exact_upload_files(c, paths, n, ptrs, sizes))) return rc;
+    return dd_exact_count_device(c, ptrs.data(), sizes.data(), n, k, distinct);
+}
+
+// ------------------------------------------------------------------- exact union schedules
+// dd_exact_sched.hip: one sort of the universe per k, a membership mask per distinct k-mer, one accumulator per schedule.
+namespace {
+
+// The driver behind the four schedules: K0 once, then for every k extract (with the genome's index) -> sort -> reduce +
+// accumulate through exact_passes.  out[kk] receives the accumulator's exact_sched_acc_words() counts of k = kmin + kk.
+int exact_schedule(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, dd::ExactSched s,
+                   const std::vector<uint64_t>& table, std::vector<std::vector<unsigned long long>>& out) {
+    hipStream_t st = c->stream;
+    int rc;
+    const size_t words = dd::exact_sched_acc_words(s);
+    out.assign((size_t)(kmax - kmin + 1), std::vector<unsigned long long>(words, 0ull));
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n, in))) return rc;
+    c->st_blocks = 0;
+    if (!in.slots) return DD_OK;
+    if ((rc = c->hist.reserve(words * sizeof(unsigned long long)))) return rc;
+    s.acc = static_cast<unsigned long long*>(c->hist.p);
+    if (!table.empty()) {
+        if ((rc = stage_table(c, c->ord, table.data(), table.size() * sizeof(uint64_t)))) return rc;
+        s.table = static_cast<const uint64_t*>(c->ord.p);
+    }
+    int most_passes = 0;
+    for (int k = kmin; k <= kmax; ++k) {
+        DD_HIP(hipMemsetAsync(s.acc, 0, words * sizeof(unsigned long long), st));
+        rc = exact_passes(c, in, n, k, ExactLayout{"exact schedule", dd::exact_tag_mode(k), dd::exact_sched_temp_bytes, dd::exact_sched_scratch_bytes},
+                          [&](const ExactArrays& a, size_t count) -> int {
+                              dd::ExactSorted sorted{};
+                              DD_HIP(dd::launch_exact_sort_tagged(a.lo, a.hi, a.lo_alt, a.hi_alt, a.g, a.g_alt, count, k, a.temp, a.temp_bytes, st, &sorted));
+                              DD_HIP(dd::launch_exact_sched(sorted, count, k, s, a.scratch, st));
+                              return DD_OK;
+                          });
+        if (rc) return rc;
+        DD_HIP(hipMemcpyAsync(out[(size_t)(k - kmin)].data(), s.acc, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+        most_passes = std::max(most_passes, c->st_blocks);
+    }
+    c->st_blocks = most_passes;   // (dd_last_sketch_stats: the passes of the k that took the most)
+    return DD_OK;
+}
+
+int exact_sched_args(dd_ctx* c, const void* inputs, int n, int nmax, int kmin, int kmax, const void* card) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (n < 1 || n > nmax)
+        return nmax == 16 ? fail(DD_EINVAL, "n=%d outside 1..16: the unions of all 2^n subsets are computed", n)
+                          : fail(DD_EINVAL, "n=%d outside 1..64: a membership mask has one bit per input", n);
+    if (!inputs || !card) return fail(DD_EINVAL, "null argument");
+    if (kmin < 1 || kmax > 64 || kmin > kmax) return fail(DD_EINVAL, "k range %d..%d outside 1..64", kmin, kmax);
+    return DD_OK;
+}
+
+// the schedules' argument rules (those of the HLL forms) and what they hand the accumulators
+int progressive_table(const int32_t* orderings, int norder, int n, std::vector<uint64_t>& table) {
+    if (norder < 1 || !orderings) return fail(DD_EINVAL, "bad argument");
+    table.assign((size_t)norder * n, 0ull);
+    for (int o = 0; o < norder; ++o) {
+        uint64_t seen = 0;
+        for (int j = 0; j < n; ++j) {
+            const int32_t v = orderings[(size_t)o * n + j];
+            if (v < 0 || v >= n) return fail(DD_EINVAL, "ordering entry %d outside 0..%d", v, n - 1);
+            if ((seen >> v) & 1ull) return fail(DD_EINVAL, "ordering %d is not a permutation of 0..%d: %d appears twice", o, n - 1, v);
+            seen |= 1ull << v;
+            table[(size_t)o * n + j] = seen;
+        }
+    }
+    return DD_OK;
+}
+
+int leave_out_table(const int32_t* group, int ngroups, int n, std::vector<uint64_t>& table) {
+    if (!group) return fail(DD_EINVAL, "bad argument");
+    if (check_groups(group, ngroups, n)) return DD_EINVAL;
+    table.assign((size_t)64 + ngroups, 0ull);
+    for (int i = 0; i < 64; ++i) table[i] = ~0ull;
+    const uint64_t all = n == 64 ? ~0ull : ((1ull << n) - 1ull);
+    for (int i = 0; i < n; ++i) {
+        if (group[i] < 0) continue;
+        table[i] = (uint64_t)group[i];
+        table[64 + group[i]] |= 1ull << i;
+    }
+    for (int g = 0; g < ngroups; ++g)
+        if (table[64 + g] == all) return fail(DD_EINVAL, "group %d holds every leaf: the union of the rest is empty", g);
+    return DD_OK;
+}
+
+// accumulator counts -> the cards of the ABI
+void pairwise_cards(const std::vector<std::vector<unsigned long long>>& acc, int n, uint64_t* card) {
+    const size_t K = acc.size();
+    auto at = [n](int i, int j) { return (size_t)1 + (size_t)i * n - (size_t)i * (i - 1) / 2 + (size_t)(j - i); };
+    for (size_t kk = 0; kk < K; ++kk)
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) {
+                const int a = std::min(i, j), b = std::max(i, j);
+                const unsigned long long ci = acc[kk][at(a, a)], cj = acc[kk][at(b, b)];
+                card[((size_t)i * n + j) * K + kk] = a == b ? ci : ci + cj - acc[kk][at(a, b)];
+            }
+}
+
+int subsets_from_hist(const unsigned long long* hist, int n, uint64_t* card, size_t stride) {
+    const size_t nsub = (size_t)1 << n;
+    std::vector<uint64_t> sub(hist, hist + nsub);
+    uint64_t total = 0;
+    for (size_t s = 0; s < nsub; ++s) total += sub[s];
+    for (int b = 0; b < n; ++b)   // subset-sum (zeta) transform: sub[T] = sum of hist[mask] over mask inside T
+        for (size_t s = 0; s < nsub; ++s)
+            if (s & ((size_t)1 << b)) sub[s] += sub[s ^ ((size_t)1 << b)];
+    for (size_t s = 0; s < nsub; ++s) card[s * stride] = total - sub[(nsub - 1) ^ s];
+    return DD_OK;
+}
+
+// a path form: the files read and uploaded, then the device form (which checks the schedule's own arguments)
+extern "C++" template <class DeviceForm>
+int exact_path_form(dd_ctx* c, const char* const* paths, int n, DeviceForm device_form) {
+    DeviceGuard guard(c->device);
+    for (int i = 0; i < n; ++i)
+        if (!paths[i]) return fail(DD_EINVAL, "null argument");
+    std::vector<const uint8_t*> ptrs;
+    std::vector<size_t> sizes;
+    int rc;
+    if ((rc = exact_upload_files(c, paths, n, ptrs, sizes))) return rc;
+    return device_form(ptrs.data(), sizes.data());
+}
+
+}  // namespace
+
+int dd_exact_pairwise_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, uint64_t* card) {
+    if (exact_sched_args(c, fasta_dev, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedPairwise, n, 0, 0, nullptr, nullptr}, {}, acc))) return rc;
+    pairwise_cards(acc, n, card);
+    return DD_OK;
+}
+
+int dd_exact_progressive_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax,
+                                const int32_t* orderings, int norder, uint64_t* card) {
+    if (exact_sched_args(c, fasta_dev, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    std::vector<uint64_t> table;
+    if (progressive_table(orderings, norder, n, table)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedProgressive, n, norder, 0, nullptr, nullptr}, table, acc))) return rc;
+    const size_t K = acc.size();
+    for (size_t kk = 0; kk < K; ++kk)
+        for (int o = 0; o < norder; ++o) {
+            uint64_t run = 0;   // |union of the first j+1| = k-mers whose first genome stands at a position <= j
+            for (int j = 0; j < n; ++j) {
+                run += acc[kk][1 + (size_t)o * n + j];
+                card[((size_t)o * n + j) * K + kk] = run;
+            }
+        }
+    return DD_OK;
+}
+
+int dd_exact_leave_out_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax,
+                              const int32_t* group, int ngroups, uint64_t* card) {
+    if (exact_sched_args(c, fasta_dev, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    std::vector<uint64_t> table;
+    if (leave_out_table(group, ngroups, n, table)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedLeaveOut, n, 0, ngroups, nullptr, nullptr}, table, acc))) return rc;
+    const size_t K = acc.size();
+    for (size_t kk = 0; kk < K; ++kk) {
+        for (int g = 0; g < ngroups; ++g) card[(size_t)g * K + kk] = acc[kk][0] - acc[kk][1 + g];
+        card[(size_t)ngroups * K + kk] = acc[kk][0];
+    }
+    return DD_OK;
+}
+
+int dd_exact_subsets_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, uint64_t* card) {
+    if (exact_sched_args(c, fasta_dev, n, 16, kmin, kmax, card)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedSubsets, n, 0, 0, nullptr, nullptr}, {}, acc))) return rc;
+    const size_t K = acc.size();
+    for (size_t kk = 0; kk < K; ++kk) subsets_from_hist(acc[kk].data() + 1, n, card + kk, K);
+    return DD_OK;
+}
+
+int dd_exact_subsets_from_hist(const uint64_t* hist, int n, uint64_t* card) {
+    if (n < 1 || n > 16) return fail(DD_EINVAL, "n=%d outside 1..16: the unions of all 2^n subsets are computed", n);
+    if (!hist || !card) return fail(DD_EINVAL, "null argument");
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "u64");
+    return subsets_from_hist(reinterpret_cast<const unsigned long long*>(hist), n, card, 1);
+}
+
+int dd_exact_pairwise(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, uint64_t* card) {
+    if (exact_sched_args(c, paths, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) { return dd_exact_pairwise_device(c, p, s, n, kmin, kmax, card); });
+}
+
+int dd_exact_progressive(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, const int32_t* orderings, int norder, uint64_t* card) {
+    if (exact_sched_args(c, paths, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) {
+        return dd_exact_progressive_device(c, p, s, n, kmin, kmax, orderings, norder, card);
+    });
+}
+
+int dd_exact_leave_out(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, const int32_t* group, int ngroups, uint64_t* card) {
+    if (exact_sched_args(c, paths, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) {
+        return dd_exact_leave_out_device(c, p, s, n, kmin, kmax, group, ngroups, card);
+    });
+}
+
+int dd_exact_subsets(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, uint64_t* card) {
+    if (exact_sched_args(c, paths, n, 16, kmin, kmax, card)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) { return dd_exact_subsets_device(c, p, s, n, kmin, kmax, card); });
+}
+
+}  // extern "C"

@@ -190,7 +190,8 @@ int dd_greedy_device(dd_ctx *, const uint8_t *leaf_dev, int n, int K, int kmin, 
  * number of distinct (canonical, per the context) k-mers over ALL n inputs together, k in 1..64.
  * Uses 16 (k<=32) or 32 (k>32) bytes of HBM per input byte up to a budget of 24 GiB (DD_EXACT_MB overrides);
  * larger inputs are counted in passes over disjoint parts of the k-mer space, so a union of any number of
- * genomes that fits HBM as FASTA bytes can be counted. */
+ * genomes that fits HBM as FASTA bytes can be counted.  After a count of inputs that hold a token,
+ * dd_last_sketch_stats' third value is the number of passes it took (1: everything at once). */
 int dd_exact_count_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n,
                           int k, uint64_t *distinct);
 int dd_exact_count(dd_ctx *, const char *const *paths, int n, int k, uint64_t *distinct);

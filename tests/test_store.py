@@ -28,10 +28,9 @@ def test_at_k_equals_constructor(tmp_path, tool, canon):
     exp = {"tool": tool, "registers": 14, "canonicalize": canon, "safety": False}
     for nfiles in (1, 2, 3):
         cat_a, files = _catalog(tmp_path / f"a{nfiles}", tool)
-        cat_b, _ = _catalog(tmp_path / f"b{nfiles}", tool)
+        cat_b, files_b = _catalog(tmp_path / f"b{nfiles}", tool)
         cat_b.sketchdir = cat_a.sketchdir  # same root, so full paths are comparable
-        subset = files[:nfiles]
-        other = [f.replace(f"a{nfiles}", f"b{nfiles}") for f in subset]
+        subset, other = files[:nfiles], files_b[:nfiles]  # (the same files under b: not by editing the path text, whose parents may hold "a2" too)
         for fa, fb in zip(subset, other):  # leaves first, as in every tree: a union's name needs their digests
             store.SketchPath([fa], 0, cat_a, exp)
             store.SketchPath([fb], 0, cat_b, exp)
