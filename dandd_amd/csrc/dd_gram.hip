@@ -39,7 +39,7 @@
 //     ids are compact now (gram_kernel): n = 128 at log2m 20 8.9 -> 7.7 ms, n = 256 (K 8) 9.0 -> 7.3 ms;
 //   * 128-row diagonal units in workgroups of eight waves (kDiag2): n = 128 7.7 -> 7.4 ms, 0.52-0.56 of the int8 dense peak
 //     at the nominal 2.4 GHz for the whole call (range pass, finish and estimator included).
-#include "dd_common.h"
+#include "dd_k2.h"
 #include "dd_kernels.h"
 
 #include <algorithm>
@@ -51,12 +51,6 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int kGramRange = 1 << 16;  // registers per wave: 2^14 per hit x 2^16 hits stays below 2^31
-
-DD_D uint32_t bmin4(uint32_t a, uint32_t b) {
-    const uint32_t t = (a | 0x80808080u) - b;
-    const uint32_t m = ((t >> 7) & 0x01010101u) * 0xFFu;  // 0xFF where a >= b
-    return (b & m) | (a & ~m);
-}
 
 // smallest and largest register of every k column over all n sketches: rng[2k] = min, rng[2k+1] = max
 // (rng starts as {63, 0} pairs).  One workgroup per (row, 64 KiB piece); HBM-bound, the slab is read once.

@@ -196,6 +196,11 @@ void launch_leaveout(const uint8_t* leaf_dev, int K, int log2m, const int32_t* t
 // aligned.  Zeroes hist_dev ((nrows + 1) K 64 u32) itself.
 void launch_extend(const uint8_t* base_dev, const uint8_t* leaf_dev, int K, int log2m, const int32_t* rows_dev, int nrows,
                    uint32_t* hist_dev, hipStream_t st);
+// the empty base of launch_extend (dd_union.hip: hist_kernel over a row list): hist[(r * K + kk)][64] of leaf[rows[r]][kk] itself;
+// hist_dev zeroed by the caller
+void launch_rows_hist(const uint8_t* leaf_dev, int K, int log2m, const int32_t* rows_dev, int nrows, uint32_t* hist_dev, hipStream_t st);
+// the end of both correction forms (dd_leaveout.hip): rows 0..nrows-1 of hist[.][K][64] hold corrections, add row nrows to them
+void launch_corr_finish(uint32_t* hist_dev, int nrows, int K, hipStream_t st);
 // base = byte-max(base, row) over len bytes (a multiple of 16)
 void launch_extend_fold(uint8_t* base_dev, const uint8_t* row_dev, size_t len, hipStream_t st);
 // all-subset unions (dd_subsets.hip) of columns k0 .. k0 + Kc - 1: hist[(s * Kc + kk)][64] = histogram of the byte-max over

@@ -18,44 +18,39 @@
 // Four registers per dword (SWAR byte max, bytes <= 63), sixteen per thread per 16-byte load; the group ids of the
 // sixteen registers stay in VGPRs.
 //
-// Histograms: the full union in LDS privatised 32 ways (dd_union.hip's image: h[bin][copy]); the corrections of up to
-// kTileG = 256 groups as [group][64] u32 in LDS (64 KiB + 8 KiB: two workgroups per CU).  More groups (n up to 4096) are
+// Histograms: the full union in LDS privatised 32 ways (dd_k2.h's image: h[bin][copy]); the corrections of up to
+// kCorrTile = 256 groups as [group][64] u32 in LDS (64 KiB + 8 KiB: two workgroups per CU).  More groups (n up to 4096) are
 // cut into group tiles of 256, one grid slice each, every slice reading the slab again and only tile 0 counting the full
-// union.  A workgroup flushes once, one global atomic per non-zero bin, 64 contiguous bins per row; leaveout_finish_kernel
+// union.  A workgroup flushes once, one global atomic per non-zero bin, 64 contiguous bins per row; corr_finish_kernel
 // adds the full union to every group row.  HBM-bound: the slab (n K m bytes) is read once per group tile.
-#include "dd_common.h"
+#include "dd_k2.h"
 #include "dd_kernels.h"
 
 namespace dd {
 namespace {
 
-constexpr int kTileG = 256;      // groups whose corrections one workgroup keeps in LDS
-constexpr int kLCopies = 32;     // privatised copies of the full-union histogram
-constexpr int kLThreads = 512;
 constexpr int kNotLast = -2;     // tab[2 j + 1] of a leaf that does not end its group
 constexpr int kUnroll = 8;       // leaf rows in flight per thread
 
 // grid: blockIdx.x = (gtile * K + kk) * tiles + tile; a workgroup takes every tiles-th 16-byte piece of k column kk
 // tab[2 j] = leaf row of slot j, tab[2 j + 1] = its group when slot j is the last of its group (-1: the floor), else kNotLast
-__global__ __launch_bounds__(kLThreads) void leaveout_kernel(const uint8_t* __restrict__ leaf, int K, int p,
-                                                             const int32_t* __restrict__ tab, int nslots, int G, int tiles,
-                                                             uint32_t* __restrict__ hist) {
-    extern __shared__ uint32_t lds[];            // full[64][kLCopies], then corr[gcount][64]
-    uint32_t* full = lds;
-    uint32_t* corr = lds + 64 * kLCopies;
+__global__ __launch_bounds__(kCorrThreads) void leaveout_kernel(const uint8_t* __restrict__ leaf, int K, int p,
+                                                                const int32_t* __restrict__ tab, int nslots, int G, int tiles,
+                                                                uint32_t* __restrict__ hist) {
+    extern __shared__ uint32_t lds[];            // the image of the full union, then corr[gcount][64]
+    uint32_t* corr = corr_of(lds);
     const int tile = blockIdx.x % tiles;
     const int kk = (blockIdx.x / tiles) % K;
     const int gtile = blockIdx.x / tiles / K;
-    const int g0 = gtile * kTileG;
-    const int gcount = G - g0 < kTileG ? G - g0 : kTileG;
+    const int g0 = gtile * kCorrTile;
+    const int gcount = G - g0 < kCorrTile ? G - g0 : kCorrTile;
     const bool count_full = gtile == 0;
-    for (int i = threadIdx.x; i < 64 * kLCopies + gcount * 64; i += blockDim.x) lds[i] = 0;
+    corr_zero(lds, gcount);
     __syncthreads();
 
     const size_t m16 = ((size_t)1 << p) >> 4;
     const size_t row_stride = (size_t)K << p;    // bytes from one leaf's row kk to the next leaf's
     const uint8_t* col = leaf + ((size_t)kk << p);
-    const int copy = threadIdx.x & (kLCopies - 1);
     for (size_t piece = (size_t)tile * blockDim.x + threadIdx.x; piece < m16; piece += (size_t)tiles * blockDim.x) {
         const uint8_t* src = col + (piece << 4);
         uint32_t b1[4] = {0, 0, 0, 0}, b2[4] = {0, 0, 0, 0}, fl[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0};
@@ -63,7 +58,8 @@ __global__ __launch_bounds__(kLThreads) void leaveout_kernel(const uint8_t* __re
 #pragma unroll
         for (int r = 0; r < 16; ++r) g1[r] = -1;
         auto take = [&](const uint4& v, int code) {
-            const uint32_t w[4] = {v.x & 0x3f3f3f3fu, v.y & 0x3f3f3f3fu, v.z & 0x3f3f3f3fu, v.w & 0x3f3f3f3fu};
+            uint32_t w[4];
+            unpack16(v, w);
 #pragma unroll
             for (int q = 0; q < 4; ++q) mx[q] = bmax4(mx[q], w[q]);
             if (code == kNotLast) return;
@@ -73,8 +69,7 @@ __global__ __launch_bounds__(kLThreads) void leaveout_kernel(const uint8_t* __re
             } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    // bit 7 of each byte: M > b1 (128 + M - b1 - 1 stays within 64..190: no borrow between bytes)
-                    const uint32_t gt = ((mx[q] | 0x80808080u) - b1[q] - 0x01010101u) & 0x80808080u;
+                    const uint32_t gt = bgt4(mx[q], b1[q]);   // bit 7 of each byte: M > b1
                     const uint32_t mk = (gt >> 7) * 0xFFu;
                     b2[q] = (b1[q] & mk) | (bmax4(b2[q], mx[q]) & ~mk);
                     b1[q] = bmax4(b1[q], mx[q]);
@@ -101,7 +96,7 @@ __global__ __launch_bounds__(kLThreads) void leaveout_kernel(const uint8_t* __re
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const uint32_t x1 = (u1 >> (8 * b)) & 63u, x2 = (u2 >> (8 * b)) & 63u;
-                if (count_full) atomicAdd(&full[x1 * kLCopies + copy], 1u);
+                if (count_full) hist_add(lds, x1);
                 const int gl = g1[4 * q + b] - g0;
                 if (x2 < x1 && (unsigned)gl < (unsigned)gcount) {
                     atomicAdd(&corr[gl * 64 + x1], 0xFFFFFFFFu);
@@ -111,58 +106,36 @@ __global__ __launch_bounds__(kLThreads) void leaveout_kernel(const uint8_t* __re
         }
     }
     __syncthreads();
-    if (count_full && threadIdx.x < 64) {
-        uint32_t s = 0;
-#pragma unroll
-        for (int c = 0; c < kLCopies; ++c) s += full[threadIdx.x * kLCopies + ((c + threadIdx.x) & (kLCopies - 1))];
-        if (s) atomicAdd(&hist[((size_t)G * K + kk) * 64 + threadIdx.x], s);
-    }
-    for (int i = threadIdx.x; i < gcount * 64; i += blockDim.x) {
-        const uint32_t v = corr[i];
-        if (v) atomicAdd(&hist[((size_t)(g0 + i / 64) * K + kk) * 64 + (i & 63)], v);
-    }
+    corr_flush(lds, count_full, g0, gcount, 1, G, K, kk, hist);
 }
 
-// rows 0..G-1 hold corrections: add the full union (row G)
-__global__ __launch_bounds__(256) void leaveout_finish_kernel(uint32_t* __restrict__ hist, int G, int K) {
-    const size_t per = (size_t)K * 64, total = (size_t)G * per;
+// rows 0..nrows-1 hold corrections: add row nrows (leave-out: the full union; extend: base's own histogram)
+__global__ __launch_bounds__(256) void corr_finish_kernel(uint32_t* __restrict__ hist, int nrows, int K) {
+    const size_t per = (size_t)K * 64, total = (size_t)nrows * per;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
         hist[i] += hist[total + i % per];
 }
 
 }  // namespace
 
-static size_t leaveout_lds_bytes(int G) {
-    const int gcount = G < kTileG ? G : kTileG;
-    return sizeof(uint32_t) * (64 * kLCopies + (size_t)gcount * 64);
+void launch_corr_finish(uint32_t* hist_dev, int nrows, int K, hipStream_t st) {
+    const size_t total = (size_t)nrows * K * 64;
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(corr_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, st, hist_dev, nrows, K);
 }
 
 void launch_leaveout(const uint8_t* leaf_dev, int K, int p, const int32_t* tab_dev, int nslots, int G, uint32_t* hist_dev,
                      hipStream_t st) {
     if (K <= 0 || G <= 0 || nslots <= 0) return;
-    const size_t m16 = ((size_t)1 << p) >> 4;
-    const int threads = (int)(m16 < (size_t)kLThreads ? (m16 < 64 ? 64 : m16) : kLThreads);
-    const int gtiles = (G + kTileG - 1) / kTileG;
-    // about four workgroups per CU over the whole grid (two resident at a time), never more than one piece per thread
-    const size_t most = (m16 + threads - 1) / threads;
-    size_t tiles = (1024 + (size_t)K * gtiles - 1) / ((size_t)K * gtiles);
-    if (tiles > most) tiles = most;
-    if (tiles < 1) tiles = 1;
-    const size_t lds = leaveout_lds_bytes(G);
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(leaveout_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)leaveout_lds_bytes(kTileG)) != hipSuccess)
-            (void)hipGetLastError();
-        attr = true;
-    }
+    const int gtiles = (G + kCorrTile - 1) / kCorrTile;
+    const CorrShape sh = corr_shape(p, K, gtiles);
+    raise_dynamic_lds(leaveout_kernel, corr_lds_bytes(kCorrTile));
     (void)hipMemsetAsync(hist_dev, 0, (size_t)(G + 1) * K * 64 * sizeof(uint32_t), st);
-    hipLaunchKernelGGL(leaveout_kernel, dim3((unsigned)((size_t)gtiles * K * tiles)), dim3(threads), lds, st, leaf_dev, K, p,
-                       tab_dev, nslots, G, (int)tiles, hist_dev);
-    const size_t total = (size_t)G * K * 64;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(leaveout_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, st, hist_dev, G, K);
+    hipLaunchKernelGGL(leaveout_kernel, dim3((unsigned)((size_t)gtiles * K * sh.tiles)), dim3(sh.threads),
+                       corr_lds_bytes(G < kCorrTile ? G : kCorrTile), st, leaf_dev, K, p,
+                       tab_dev, nslots, G, sh.tiles, hist_dev);
+    launch_corr_finish(hist_dev, G, K, st);
 }
 
 }  // namespace dd

@@ -25,7 +25,7 @@
 //             tiles of the range, so nothing is reduced until the very end.
 // The conversion is shared by every ordering and threshold of the workgroup, which is what makes it affordable.
 // Exact integers throughout; tests/test_gpu_parity.py checks every cardinality against the streaming kernel's.
-#include "dd_common.h"
+#include "dd_k2.h"
 #include "dd_kernels.h"
 
 #include <stdlib.h>
@@ -36,6 +36,8 @@ namespace dd {
 namespace {
 
 constexpr int PS_THREADS = 512;
+constexpr int PS_NMAX = 32;    // prefixes a lane holds in registers (n <= PS_NMAX)
+constexpr int PS_UPT = 1;      // (leaf, 32 registers) units a thread converts per tile
 
 // 16 bytes at an absolute LDS byte address (ds_read_b128 with `words` as its immediate offset)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -44,21 +46,6 @@ DD_D uint4 lds_read16(uint32_t byte_addr, int words) {
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-// the six bit planes of 32 registers (8 dwords of 4 bytes): bit i + 8 q of plane b = bit b of byte q of dword i
-DD_D void bit_slice(const uint32_t (&w)[8], uint32_t (&pl)[6]) {
-#pragma unroll
-    for (int b = 0; b < 6; ++b) {
-        uint32_t acc = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint32_t s = i >= b ? w[i] << (i - b) : w[i] >> (b - i);
-            acc |= s & (0x01010101u << i);
-        }
-        pl[b] = acc;
-    }
-}
-
-// NMAX: prefixes held in registers (n <= NMAX); UPT: (leaf, 32 registers) units a thread converts per tile
 // At most 128 registers (the next prefix's reads in flight, the ordering's leaves as bytes, the running store pointer):
 // two workgroups share a CU and hide each other's barriers and LDS latencies, and the host picks tiles small enough
 // for two workgroups' planes.  (One workgroup of 237 registers per CU with the next eight reads in flight during the
@@ -67,10 +54,10 @@ DD_D void bit_slice(const uint32_t (&w)[8], uint32_t (&pl)[6]) {
 // reads).
 // (Converter waves running a tile ahead of the scan on a second set of planes were built and measured no better --
 // profiles/r04_k2_pscan_lds.txt; the kernel converts, then scans, a tile at a time.)
-template <int NMAX, int UPT, int DG>
+template <int DG>
 __global__ __launch_bounds__(PS_THREADS, 4) void pscan_kernel(const uint8_t* __restrict__ leaf, int n, int K, int p,
                                                            const int32_t* __restrict__ ord, int no, const uint32_t* __restrict__ rng,
-                                                           int RR, int tiles_per_range, int D, int chain_pitch,
+                                                           int RR, int tiles, int D, int chain_pitch,
                                                            uint32_t* __restrict__ part) {
     extern __shared__ uint32_t lds[];            // planes [g][t][DP], then the orderings [no][n] as bytes
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)lds != 0u) __builtin_trap();  // (the scan reads at absolute LDS addresses)
@@ -88,26 +75,25 @@ __global__ __launch_bounds__(PS_THREADS, 4) void pscan_kernel(const uint8_t* __r
     const int c = threadIdx.x;
     const bool chain = c < no * T;
     const int o = chain ? c / T : 0, t = chain ? c % T : 0;
-    uint32_t cnt[NMAX], gp[NMAX / 4];            // the ordering's leaves as bytes, four to a register
+    uint32_t cnt[PS_NMAX], gp[PS_NMAX / 4];      // the ordering's leaves as bytes, four to a register
     const uint32_t tDP = (uint32_t)(t * DP), rowDP = (uint32_t)(T * DP);
 #pragma unroll
-    for (int j = 0; j < NMAX / 4; ++j) {
+    for (int j = 0; j < PS_NMAX / 4; ++j) {
         gp[j] = 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) gp[j] |= (uint32_t)ord_s[o * n + (4 * j + i < n ? 4 * j + i : n - 1)] << (8 * i);
     }
 #pragma unroll
-    for (int j = 0; j < NMAX; ++j) cnt[j] = 0;
+    for (int j = 0; j < PS_NMAX; ++j) cnt[j] = 0;
     const int units = n * D;                     // (leaf, 32 registers) pairs of a tile
     const size_t tile_regs = (size_t)32 * D;
-    // ranges of tiles_total / RR tiles, the remainder spread over the first ranges
-    const int tiles_total = tiles_per_range;     // (argument reused: all tiles of a row)
-    const int tile0 = (int)(((long long)tiles_total * rr) / RR), ntiles = (int)(((long long)tiles_total * (rr + 1)) / RR) - tile0;
+    // the row's tiles cut into RR ranges of tiles / RR, the remainder spread over the ranges
+    const int tile0 = (int)(((long long)tiles * rr) / RR), ntiles = (int)(((long long)tiles * (rr + 1)) / RR) - tile0;
     const size_t reg0 = (size_t)tile0 * tile_regs;
     // every thread converts: thread x takes units x, x + PS_THREADS, ..
     constexpr int nconv = PS_THREADS;
     const int cx = (int)threadIdx.x;
-    uint4 cur[UPT][2];
+    uint4 cur[PS_UPT][2];
     auto load1 = [&](int q, int tile) {   // unit q of this thread, of `tile`
         // (threads past the last unit load the last unit again: with every load unconditional the compiler can count
         // them, and waits for the current tile's bytes with the next tile's loads still in flight)
@@ -121,7 +107,7 @@ __global__ __launch_bounds__(PS_THREADS, 4) void pscan_kernel(const uint8_t* __r
     // ---- convert: bytes -> threshold planes of `tile`
     auto convert = [&](int tile) {
 #pragma unroll
-        for (int q = 0; q < UPT; ++q) {
+        for (int q = 0; q < PS_UPT; ++q) {
             const int u = cx + q * nconv;
             if (u < units) {
                 const uint32_t w[8] = {cur[q][0].x, cur[q][0].y, cur[q][0].z, cur[q][0].w, cur[q][1].x, cur[q][1].y, cur[q][1].z, cur[q][1].w};
@@ -147,7 +133,7 @@ __global__ __launch_bounds__(PS_THREADS, 4) void pscan_kernel(const uint8_t* __r
         }
     };
 #pragma unroll
-    for (int q = 0; q < UPT; ++q) load1(q, 0);
+    for (int q = 0; q < PS_UPT; ++q) load1(q, 0);
     for (int tile = 0; tile < ntiles; ++tile) {
         convert(tile);
         __syncthreads();
@@ -170,28 +156,19 @@ __global__ __launch_bounds__(PS_THREADS, 4) void pscan_kernel(const uint8_t* __r
                     asm volatile("" : "+v"(g));   // (keeps the 32 row offsets from being hoisted into 32 registers again)
                     return __umul24(g, row_bytes) + at0;
                 };
-                constexpr bool PF = true;
                 uint4 nxt[DG];
-                if (PF) {
-                    const uint32_t r0 = row(0);
+                const uint32_t r0 = row(0);
 #pragma unroll
-                    for (int q = 0; q < DG; ++q) nxt[q] = lds_read16(r0, 4 * q);
-                }
+                for (int q = 0; q < DG; ++q) nxt[q] = lds_read16(r0, 4 * q);
 #pragma unroll
-                for (int j = 0; j < NMAX; ++j) {
+                for (int j = 0; j < PS_NMAX; ++j) {
                     uint4 xs[DG];
-                    if (PF) {
 #pragma unroll
-                        for (int q = 0; q < DG; ++q) xs[q] = nxt[q];
-                        if (j + 1 < NMAX) {
-                            const uint32_t r1 = row(j + 1);
+                    for (int q = 0; q < DG; ++q) xs[q] = nxt[q];
+                    if (j + 1 < PS_NMAX) {
+                        const uint32_t r1 = row(j + 1);
 #pragma unroll
-                            for (int q = 0; q < DG; ++q) nxt[q] = lds_read16(r1, 4 * q);
-                        }
-                    } else {
-                        const uint32_t r0 = row(j);
-#pragma unroll
-                        for (int q = 0; q < DG; ++q) xs[q] = lds_read16(r0, 4 * q);
+                        for (int q = 0; q < DG; ++q) nxt[q] = lds_read16(r1, 4 * q);
                     }
                     uint32_t cj = cnt[j];
 #pragma unroll
@@ -212,7 +189,7 @@ __global__ __launch_bounds__(PS_THREADS, 4) void pscan_kernel(const uint8_t* __r
     if (chain) {
         uint32_t* out = part + ((size_t)k * RR + rr) * (size_t)n * chain_pitch + c;
 #pragma unroll
-        for (int j = 0; j < NMAX; ++j)
+        for (int j = 0; j < PS_NMAX; ++j)
             if (j < n) gstore4(out + (size_t)j * chain_pitch, cnt[j]);
     }
 }
@@ -283,24 +260,18 @@ bool launch_progressive_pscan(const uint8_t* leaf_dev, int n, int K, int p, cons
     // register ranges: four rounds of two workgroups per CU over all k (just under, never just over), at least 4 tiles each
     int RR = std::max(1, std::min(64, (8 * 256) / K));
     while (RR > 1 && tiles / RR < 4) --RR;
-    const int tiles_per_range = tiles;    // (the kernel cuts [0, tiles) into RR ranges itself)
     uint8_t* base = static_cast<uint8_t*>(scratch);
     const uint32_t* rng = reinterpret_cast<const uint32_t*>(base);
     uint32_t* part = reinterpret_cast<uint32_t*>(base + (((size_t)K * 2 * sizeof(uint32_t) + 255) & ~(size_t)255));
     const int pitch = PS_THREADS;
     for (int o0 = 0; o0 < norder; o0 += group) {
         const int no = std::min(group, norder - o0);
-#define DD_PSCAN_LAUNCH(NMAX, UPT, DG)                                                                                                         \
-    do {                                                                                                                                      \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pscan_kernel<NMAX, UPT, DG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-        hipLaunchKernelGGL((pscan_kernel<NMAX, UPT, DG>), dim3((unsigned)(K * RR)), dim3(PS_THREADS), lds_bytes, st, leaf_dev, n, K, p,        \
-                           ord_dev + (size_t)o0 * n, no, rng, RR, tiles_per_range, D, pitch, part);                                           \
-    } while (0)
         // (D = 4, 8, 16 or 32 plane words per row: one or two 16-byte groups per chunk of the scan; four groups -- 16
         // running ANDs beside the 32 counts -- spill)
-        if (D >= 8) DD_PSCAN_LAUNCH(32, 1, 2);
-        else DD_PSCAN_LAUNCH(32, 1, 1);
-#undef DD_PSCAN_LAUNCH
+        const auto kernel = D >= 8 ? pscan_kernel<2> : pscan_kernel<1>;
+        raise_dynamic_lds(kernel, lds_bytes);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(K * RR)), dim3(PS_THREADS), lds_bytes, st, leaf_dev, n, K, p, ord_dev + (size_t)o0 * n, no,
+                           rng, RR, tiles, D, pitch, part);
         const size_t jobs = (size_t)no * n * K;
         hipLaunchKernelGGL(pscan_finish_kernel, dim3((unsigned)((jobs + 3) / 4)), dim3(256), 0, st, part, n, K, p, no, rng, RR, pitch,
                            hist_dev + (size_t)o0 * n * K * 64);

@@ -13,11 +13,11 @@
 // leaves' words -- every lane reads the same LDS words (broadcast reads).  Then for every h of the chunk Hi_h moves to a
 // scalar register (v_readlane) and each (h, l) costs one v_and and one v_bcnt_u32_b32 into a counter held in a VGPR:
 // three VALU instructions per 64 subsets, plane word and threshold.  A wave is one job (threshold t, chunk of HC h's);
-// a workgroup's eight waves share the planes one convert stage (dd_pscan.hip's bit_slice) makes per tile of D plane
+// a workgroup's eight waves share the planes one convert stage (dd_k2.h's bit_slice) makes per tile of D plane
 // words.  The counts stay in the lanes across every tile of the workgroup's register range and are written once to a
 // scratch slice of their own (no atomics); subsets_finish_kernel sums the ranges and differences F into histograms.
 // Exact integers throughout.
-#include "dd_common.h"
+#include "dd_k2.h"
 #include "dd_kernels.h"
 
 #include <algorithm>
@@ -30,21 +30,6 @@ constexpr int SS_THREADS = 64 * SS_WAVES;
 constexpr int SS_NMAX = 16;       // leaves
 constexpr int SS_LOW = 6;         // leaves whose subsets are spread over the lanes
 constexpr int SS_DMAX = 64;       // plane words per tile
-
-// the six bit planes of 32 registers (8 dwords of 4 bytes): bit i + 8 q of plane b = bit b of byte q of dword i
-// (dd_pscan.hip's bit_slice)
-DD_D void slice6(const uint32_t (&w)[8], uint32_t (&pl)[6]) {
-#pragma unroll
-    for (int b = 0; b < 6; ++b) {
-        uint32_t acc = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint32_t s = i >= b ? w[i] << (i - b) : w[i] >> (b - i);
-            acc |= s & (0x01010101u << i);
-        }
-        pl[b] = acc;
-    }
-}
 
 // wg[3 b .. 3 b + 2] = (k column, first job, offset of the column's first threshold in part) of workgroup b;
 // blockIdx.y = register range.  Job j of column k: threshold j / nchunks, h chunk j % nchunks.
@@ -94,7 +79,7 @@ __global__ __launch_bounds__(SS_THREADS) void subsets_kernel(const uint8_t* __re
             const uint4 b = p >= 5 ? gload16(src + 16) : make_uint4(0x3f3f3f3fu, 0x3f3f3f3fu, 0x3f3f3f3fu, 0x3f3f3f3fu);
             const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
             uint32_t x[6];
-            slice6(w, x);
+            bit_slice(w, x);
             uint32_t* dst = lds + (size_t)g * Tw * DP + d;
             // le(v) = OR of eq(u) for u <= v, eq(u) = AND_q (x[q] ^ (bit q of u clear ? ~0 : 0)).  A rolled loop over the
             // (block-uniform) thresholds: the unrolled 64-way form kept a branch condition per threshold in scalar registers
@@ -239,8 +224,7 @@ void launch_subsets(const uint8_t* leaf_dev, int n, int K, int p, int k0, int Kc
         const dim3 grid(nwg, (unsigned)pl.RR);
 #define DD_SUBSETS_LAUNCH(HC)                                                                                                   \
     do {                                                                                                                        \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(subsets_kernel<HC>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)pl.lds_bytes);                                                                           \
+        raise_dynamic_lds(subsets_kernel<HC>, pl.lds_bytes);                                                                    \
         hipLaunchKernelGGL((subsets_kernel<HC>), grid, dim3(SS_THREADS), pl.lds_bytes, st, leaf_dev, n, K, p, rng_dev, wg_dev,  \
                            pl.nchunks, pl.D, pl.tiles, part_dev);                                                               \
     } while (0)

@@ -1,8 +1,10 @@
-// dd_synth.hip -- "realistic" synthetic genomes on the device (bench / tests only; BASELINE.md section 4 defines the
-// uniform generator, this is its hard-case sibling): GC 35 %, 20 % interspersed repeats (copies of 64 elements of
-// 300..6000 bases), 10 % tandem repeats (units of 2..60 bases), repeats soft-masked, 2 % N in 100-base runs, contigs
-// of 2..200 kbp, 1 % divergence between the genomes of one seed.  Byte-identical to
-// oracle/dd_oracle.c:orc_synth_realistic_fasta (tests/test_gpu_parity.py); counter-based, one thread per output byte.
+// dd_synth.hip -- synthetic genomes on the device (bench / tests only), counter-based, one thread per output byte.
+//
+// The uniform generator of BASELINE.md section 4 (synth_kernel; byte-identical to oracle/dd_oracle.c:orc_synth_fasta), and
+// its hard-case "realistic" sibling: GC 35 %, 20 % interspersed repeats (copies of 64 elements of 300..6000 bases), 10 %
+// tandem repeats (units of 2..60 bases), repeats soft-masked, 2 % N in 100-base runs, contigs of 2..200 kbp, 1 % divergence
+// between the genomes of one seed.  Byte-identical to oracle/dd_oracle.c:orc_synth_realistic_fasta
+// (tests/test_gpu_parity.py).
 #include "dd_common.h"
 #include "dd_kernels.h"
 
@@ -11,6 +13,55 @@
 namespace dd {
 namespace {
 
+// ---- the uniform generator ----------------------------------------------------------------------------------------
+constexpr uint64_t SYN_HDR = 16, SYN_LINE = 80;
+
+DD_HD uint64_t syn_rec_bytes(uint64_t L) { return SYN_HDR + L + (L + SYN_LINE - 1) / SYN_LINE; }
+
+DD_D uint8_t syn_base(uint64_t seed, uint64_t seed_g, uint64_t pos) {
+    uint32_t b = (uint32_t)(splitmix64(seed ^ pos) & 3);
+    const uint64_t r = splitmix64(seed_g ^ pos);
+    if (r % 100 == 0) b = (b + 1 + (uint32_t)((r >> 32) % 3)) & 3;
+    uint8_t ch = (uint8_t)("ACGT"[b]);
+    if (splitmix64(seed_g ^ 0x4E4E4E4E00000000ull ^ (pos / 100)) % 1000 == 0) ch = 'N';
+    if (splitmix64(seed_g ^ 0x6C6C6C6C00000000ull ^ (pos / 500)) % 10 == 0) ch |= 0x20;
+    return ch;
+}
+
+__global__ __launch_bounds__(256) void synth_kernel(uint64_t seed, uint64_t seed_g, int gi,
+                                                    uint64_t nbases, int nrec, uint64_t total,
+                                                    uint8_t* __restrict__ out) {
+    const uint64_t per = nbases / (uint64_t)nrec;
+    const uint64_t recsz = syn_rec_bytes(per);
+    for (uint64_t off = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; off < total;
+         off += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t r = recsz ? off / recsz : 0;
+        if (r > (uint64_t)(nrec - 1)) r = nrec - 1;
+        const uint64_t o = off - r * recsz;
+        const uint64_t L = (r == (uint64_t)(nrec - 1)) ? nbases - per * (uint64_t)(nrec - 1) : per;
+        uint8_t ch;
+        if (o < SYN_HDR) {
+            const char hexd[] = "0123456789abcdef";
+            if (o == 0) ch = '>';
+            else if (o == 1) ch = 'g';
+            else if (o < 6) ch = hexd[(gi >> (12 - 4 * (int)(o - 2))) & 15];
+            else if (o == 6) ch = '.';
+            else if (o == 7) ch = 'r';
+            else if (o < 12) ch = hexd[((int)r >> (12 - 4 * (int)(o - 8))) & 15];
+            else if (o < 15) ch = ' ';
+            else ch = '\n';
+        } else {
+            const uint64_t q = o - SYN_HDR;
+            const uint64_t line = q / (SYN_LINE + 1), col = q % (SYN_LINE + 1);
+            const uint64_t j = line * SYN_LINE + col;
+            if (col == SYN_LINE || j >= L) ch = '\n';
+            else ch = syn_base(seed, seed_g, r * per + j);
+        }
+        out[off] = ch;
+    }
+}
+
+// ---- the realistic generator --------------------------------------------------------------------------------------
 constexpr uint64_t RS_HDR = 16, RS_LINE = 80;
 
 DD_HD uint64_t real_contig_len(uint64_t seed, uint64_t idx) {
@@ -106,6 +157,22 @@ void launch_synth_realistic(uint64_t seed, int gi, const uint64_t* tab_dev, uint
     uint64_t blocks = (total + 255) / 256;
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(synth_realistic_kernel, dim3((unsigned)blocks), dim3(256), 0, st, seed, seed_g, gi, tab_dev, ncontigs, total, out_dev);
+}
+
+size_t synth_size(uint64_t nbases, int nrec) {
+    const uint64_t per = nbases / (uint64_t)nrec;
+    const uint64_t last = nbases - per * (uint64_t)(nrec - 1);
+    return (size_t)(syn_rec_bytes(per) * (uint64_t)(nrec - 1) + syn_rec_bytes(last));
+}
+
+void launch_synth(uint64_t seed, int gi, uint64_t nbases, int nrec, uint8_t* out_dev, hipStream_t st) {
+    const uint64_t total = synth_size(nbases, nrec);
+    if (!total) return;
+    const uint64_t seed_g = splitmix64(seed + (uint64_t)gi + 1);
+    uint64_t blocks = (total + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(synth_kernel, dim3((unsigned)blocks), dim3(256), 0, st, seed, seed_g, gi, nbases,
+                       nrec, total, out_dev);
 }
 
 }  // namespace dd

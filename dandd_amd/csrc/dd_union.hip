@@ -8,29 +8,11 @@
 //                                        equals the flat prefix unions because max is associative)
 //   * all pairs                         (DeltaTree.pairwise_spiders, lib/huffman_dandd.py:666-695)
 // HBM/L2-bound: 16-byte loads, SWAR byte max, LDS histograms privatised 32 ways, bin-major (one bank per copy).
-#include "dd_common.h"
+#include "dd_k2.h"
 #include "dd_kernels.h"
 
 namespace dd {
 namespace {
-
-constexpr int HCOPIES = 32;  // privatised LDS histograms per workgroup
-
-// Histogram image: h[bin][copy], copy = lane % 32.  ds_add_u32 is serviced in two groups of 32 lanes, each over 32
-// banks of 4 bytes: with the copy as the fastest index every lane of a group adds into ITS OWN bank whatever bins the
-// bytes name -- no bank conflict is possible (lanes l and l + 32 share a copy but not a group).  The copy-major
-// image this replaces (h[copy][65]) put (copy + bin) % 32 on the bank: ~3.5 lanes of a group collided on average.
-#ifdef DD_HIST_COPY_MAJOR   // (A/B builds only)
-typedef uint32_t HistImage[HCOPIES][65];
-#define DD_HIST_AT(h, bin, copy) (h)[copy][bin]
-#else
-typedef uint32_t HistImage[64][HCOPIES];
-#define DD_HIST_AT(h, bin, copy) (h)[bin][copy]
-#endif
-
-DD_D uint4 bmax16(uint4 a, uint4 b) {
-    return make_uint4(bmax4(a.x, b.x), bmax4(a.y, b.y), bmax4(a.z, b.z), bmax4(a.w, b.w));
-}
 
 __global__ __launch_bounds__(256) void union_kernel(const uint8_t* const* __restrict__ in, int n,
                                                     size_t len16, uint8_t* __restrict__ out) {
@@ -42,43 +24,18 @@ __global__ __launch_bounds__(256) void union_kernel(const uint8_t* const* __rest
     }
 }
 
-// add the 16 register bytes of v to the workgroup's privatised histograms
-DD_D void hist_add16(HistImage h, uint4 v) {
-    const int copy = threadIdx.x & (HCOPIES - 1);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) atomicAdd(&DD_HIST_AT(h, (w[q] >> (8 * b)) & 63u, copy), 1u);
-    }
-}
-
-DD_D void hist_zero(HistImage h) {
-    for (int i = threadIdx.x; i < (int)(sizeof(HistImage) / 4); i += blockDim.x) (&h[0][0])[i] = 0;
-}
-
-// fold the privatised copies and add them to a global 64-bin histogram
-DD_D void hist_flush(HistImage h, uint32_t* __restrict__ gh, bool exclusive) {
-    if (threadIdx.x < 64) {
-        uint32_t s = 0;
-#pragma unroll
-        for (int c = 0; c < HCOPIES; ++c) s += DD_HIST_AT(h, threadIdx.x, (c + threadIdx.x) & (HCOPIES - 1));  // (rotated: thread t starts at bank t)
-        if (exclusive)
-            gh[threadIdx.x] = s;
-        else if (s)
-            atomicAdd(&gh[threadIdx.x], s);
-    }
-}
-
 // PC = 16-byte pieces per thread: a workgroup's tile is PC x 16 KiB of a row.  Rows of 64 KiB and more use PC = 4:
 // four times fewer barriers, histogram folds and (rows of several tiles add their partial histograms with global
 // atomics) global atomics per byte -- 264 M of those for the pairs of 64 sketches of 1 MiB before.
-// one workgroup per (sketch, tile of its registers)
+// one workgroup per (job, tile of its registers): job's row is row `job` of regs, or with a row list (job = r * K + kk)
+// column kk of leaf rows[r]
 template <int PC>
-__global__ __launch_bounds__(1024) void hist_kernel(const uint8_t* __restrict__ regs, int p,
-                                                    int tiles, uint32_t* __restrict__ hist) {
-    __shared__ HistImage h;
+__global__ __launch_bounds__(1024) void hist_kernel(const uint8_t* __restrict__ regs, int p, int tiles,
+                                                    const int32_t* __restrict__ rows, int K,
+                                                    uint32_t* __restrict__ hist) {
+    __shared__ uint32_t h[kHistWords];
     const int job = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    const size_t row = rows ? (size_t)rows[job / K] * K + job % K : (size_t)job;
     const size_t m16 = ((size_t)1 << p) >> 4;
     const size_t piece = (size_t)tile * blockDim.x * PC + threadIdx.x;
     hist_zero(h);
@@ -86,7 +43,7 @@ __global__ __launch_bounds__(1024) void hist_kernel(const uint8_t* __restrict__ 
 #pragma unroll
     for (int q = 0; q < PC; ++q)
         if (piece + (size_t)q * blockDim.x < m16)
-            hist_add16(h, reinterpret_cast<const uint4*>(regs + ((size_t)job << p))[piece + (size_t)q * blockDim.x]);
+            hist_add16(h, reinterpret_cast<const uint4*>(regs + (row << p))[piece + (size_t)q * blockDim.x]);
     __syncthreads();
     hist_flush(h, hist + (size_t)job * 64, tiles == 1);
 }
@@ -97,7 +54,7 @@ __global__ __launch_bounds__(1024) void progressive_kernel(const uint8_t* __rest
                                                            int K, int p, int tiles,
                                                            const int32_t* __restrict__ ord,
                                                            uint32_t* __restrict__ hist) {
-    __shared__ HistImage h;
+    __shared__ uint32_t h[kHistWords];
     const int tile = blockIdx.x % tiles;
     const int kk = (blockIdx.x / tiles) % K;
     const int o = blockIdx.x / tiles / K;
@@ -128,7 +85,7 @@ template <int PC>
 __global__ __launch_bounds__(1024) void pairwise_kernel(const uint8_t* __restrict__ leaf, int n,
                                                         int K, int p, int tiles,
                                                         uint32_t* __restrict__ hist) {
-    __shared__ HistImage h;
+    __shared__ uint32_t h[kHistWords];
     const int tile = blockIdx.x % tiles;
     const int kk = (blockIdx.x / tiles) % K;
     const int i = blockIdx.x / tiles / K;
@@ -171,54 +128,6 @@ __global__ __launch_bounds__(256) void mle_kernel(const uint32_t* __restrict__ h
     est[j] = (tot == (1ull << p)) ? ertl_mle(c, p, relerr) : 0.0;
 }
 
-// ---- synthetic FASTA (byte-identical to oracle/dd_oracle.c:orc_synth_fasta) ------------
-constexpr uint64_t SYN_HDR = 16, SYN_LINE = 80;
-
-DD_HD uint64_t syn_rec_bytes(uint64_t L) { return SYN_HDR + L + (L + SYN_LINE - 1) / SYN_LINE; }
-
-DD_D uint8_t syn_base(uint64_t seed, uint64_t seed_g, uint64_t pos) {
-    uint32_t b = (uint32_t)(splitmix64(seed ^ pos) & 3);
-    const uint64_t r = splitmix64(seed_g ^ pos);
-    if (r % 100 == 0) b = (b + 1 + (uint32_t)((r >> 32) % 3)) & 3;
-    uint8_t ch = (uint8_t)("ACGT"[b]);
-    if (splitmix64(seed_g ^ 0x4E4E4E4E00000000ull ^ (pos / 100)) % 1000 == 0) ch = 'N';
-    if (splitmix64(seed_g ^ 0x6C6C6C6C00000000ull ^ (pos / 500)) % 10 == 0) ch |= 0x20;
-    return ch;
-}
-
-__global__ __launch_bounds__(256) void synth_kernel(uint64_t seed, uint64_t seed_g, int gi,
-                                                    uint64_t nbases, int nrec, uint64_t total,
-                                                    uint8_t* __restrict__ out) {
-    const uint64_t per = nbases / (uint64_t)nrec;
-    const uint64_t recsz = syn_rec_bytes(per);
-    for (uint64_t off = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; off < total;
-         off += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t r = recsz ? off / recsz : 0;
-        if (r > (uint64_t)(nrec - 1)) r = nrec - 1;
-        const uint64_t o = off - r * recsz;
-        const uint64_t L = (r == (uint64_t)(nrec - 1)) ? nbases - per * (uint64_t)(nrec - 1) : per;
-        uint8_t ch;
-        if (o < SYN_HDR) {
-            const char hexd[] = "0123456789abcdef";
-            if (o == 0) ch = '>';
-            else if (o == 1) ch = 'g';
-            else if (o < 6) ch = hexd[(gi >> (12 - 4 * (int)(o - 2))) & 15];
-            else if (o == 6) ch = '.';
-            else if (o == 7) ch = 'r';
-            else if (o < 12) ch = hexd[((int)r >> (12 - 4 * (int)(o - 8))) & 15];
-            else if (o < 15) ch = ' ';
-            else ch = '\n';
-        } else {
-            const uint64_t q = o - SYN_HDR;
-            const uint64_t line = q / (SYN_LINE + 1), col = q % (SYN_LINE + 1);
-            const uint64_t j = line * SYN_LINE + col;
-            if (col == SYN_LINE || j >= L) ch = '\n';
-            else ch = syn_base(seed, seed_g, r * per + j);
-        }
-        out[off] = ch;
-    }
-}
-
 inline int pieces_for(int p) { return p >= 16 ? 4 : 1; }  // 16-byte pieces per thread (the kernels' PC)
 inline int tiles_for(int p) {
     const size_t m16 = ((size_t)1 << p) >> 4, per_tile = (size_t)1024 * pieces_for(p);
@@ -229,6 +138,11 @@ inline int threads_for(int p) {
     size_t t = m16 < 1024 ? m16 : 1024;
     if (t < 64) t = 64;
     return (int)t;
+}
+// one of a kernel's two PC forms, by the row size: a workgroup per (job, tile)
+template <typename Kernel, typename... Args>
+void launch_pc(Kernel pc4, Kernel pc1, int p, size_t jobs, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL(pieces_for(p) == 4 ? pc4 : pc1, dim3((unsigned)(jobs * tiles_for(p))), dim3(threads_for(p)), 0, st, args...);
 }
 
 }  // namespace
@@ -243,55 +157,32 @@ void launch_union(const uint8_t* const* in_dev, int n, size_t len, uint8_t* out_
 
 void launch_hist(const uint8_t* regs_dev, int njobs, int p, uint32_t* hist_dev, hipStream_t st) {
     if (njobs <= 0) return;
-    const int tiles = tiles_for(p);
-    if (tiles > 1) (void)hipMemsetAsync(hist_dev, 0, (size_t)njobs * 64 * sizeof(uint32_t), st);
-    if (pieces_for(p) == 4)
-        hipLaunchKernelGGL(hist_kernel<4>, dim3((unsigned)(njobs * tiles)), dim3(threads_for(p)), 0, st, regs_dev, p, tiles, hist_dev);
-    else
-        hipLaunchKernelGGL(hist_kernel<1>, dim3((unsigned)(njobs * tiles)), dim3(threads_for(p)), 0, st, regs_dev, p, tiles, hist_dev);
+    if (tiles_for(p) > 1) (void)hipMemsetAsync(hist_dev, 0, (size_t)njobs * 64 * sizeof(uint32_t), st);
+    launch_pc(hist_kernel<4>, hist_kernel<1>, p, njobs, st, regs_dev, p, tiles_for(p), (const int32_t*)nullptr, 1, hist_dev);
+}
+
+void launch_rows_hist(const uint8_t* leaf_dev, int K, int p, const int32_t* rows_dev, int nrows, uint32_t* hist_dev, hipStream_t st) {
+    if (K <= 0 || nrows <= 0) return;
+    launch_pc(hist_kernel<4>, hist_kernel<1>, p, (size_t)nrows * K, st, leaf_dev, p, tiles_for(p), rows_dev, K, hist_dev);
 }
 
 void launch_progressive(const uint8_t* leaf_dev, int n, int K, int p, const int32_t* ord_dev,
                         int norder, uint32_t* hist_dev, hipStream_t st) {
     if (n <= 0 || K <= 0 || norder <= 0) return;
-    const int tiles = tiles_for(p);
-    if (tiles > 1) (void)hipMemsetAsync(hist_dev, 0, (size_t)norder * n * K * 64 * sizeof(uint32_t), st);
-    if (pieces_for(p) == 4)
-        hipLaunchKernelGGL(progressive_kernel<4>, dim3((unsigned)(norder * K * tiles)), dim3(threads_for(p)), 0, st, leaf_dev, n, K, p, tiles, ord_dev, hist_dev);
-    else
-        hipLaunchKernelGGL(progressive_kernel<1>, dim3((unsigned)(norder * K * tiles)), dim3(threads_for(p)), 0, st, leaf_dev, n, K, p, tiles, ord_dev, hist_dev);
+    if (tiles_for(p) > 1) (void)hipMemsetAsync(hist_dev, 0, (size_t)norder * n * K * 64 * sizeof(uint32_t), st);
+    launch_pc(progressive_kernel<4>, progressive_kernel<1>, p, (size_t)norder * K, st, leaf_dev, n, K, p, tiles_for(p), ord_dev, hist_dev);
 }
 
 void launch_pairwise(const uint8_t* leaf_dev, int n, int K, int p, uint32_t* hist_dev, hipStream_t st) {
     if (n <= 0 || K <= 0) return;
-    const int tiles = tiles_for(p);
     (void)hipMemsetAsync(hist_dev, 0, (size_t)n * n * K * 64 * sizeof(uint32_t), st);
-    if (pieces_for(p) == 4)
-        hipLaunchKernelGGL(pairwise_kernel<4>, dim3((unsigned)(n * K * tiles)), dim3(threads_for(p)), 0, st, leaf_dev, n, K, p, tiles, hist_dev);
-    else
-        hipLaunchKernelGGL(pairwise_kernel<1>, dim3((unsigned)(n * K * tiles)), dim3(threads_for(p)), 0, st, leaf_dev, n, K, p, tiles, hist_dev);
+    launch_pc(pairwise_kernel<4>, pairwise_kernel<1>, p, (size_t)n * K, st, leaf_dev, n, K, p, tiles_for(p), hist_dev);
 }
 
 void launch_mle(const uint32_t* hist_dev, size_t njobs, int p, double* est_dev, hipStream_t st) {
     if (!njobs) return;
     hipLaunchKernelGGL(mle_kernel, dim3((unsigned)((njobs + 255) / 256)), dim3(256), 0, st, hist_dev,
                        njobs, p, mle_relerr(p), est_dev);
-}
-
-size_t synth_size(uint64_t nbases, int nrec) {
-    const uint64_t per = nbases / (uint64_t)nrec;
-    const uint64_t last = nbases - per * (uint64_t)(nrec - 1);
-    return (size_t)(syn_rec_bytes(per) * (uint64_t)(nrec - 1) + syn_rec_bytes(last));
-}
-
-void launch_synth(uint64_t seed, int gi, uint64_t nbases, int nrec, uint8_t* out_dev, hipStream_t st) {
-    const uint64_t total = synth_size(nbases, nrec);
-    if (!total) return;
-    const uint64_t seed_g = splitmix64(seed + (uint64_t)gi + 1);
-    uint64_t blocks = (total + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(synth_kernel, dim3((unsigned)blocks), dim3(256), 0, st, seed, seed_g, gi, nbases,
-                       nrec, total, out_dev);
 }
 
 }  // namespace dd

@@ -1,5 +1,6 @@
 """K2 timing probe (not the contract bench): the union schedules of BASELINE cfg 3 (kij: all pairs of
-64 genomes) and cfg 4 (progressive: 10 orderings of 30 genomes) over HBM-resident register slabs.
+64 genomes) and cfg 4 (progressive: 10 orderings of 30 genomes), the root union and cards, the leave-out
+unions of 64 singleton groups and all subsets of 16 leaves, over HBM-resident register slabs.
 Reports device time by HIP events and the algorithmic GB/s (register bytes read per union job)."""
 import os
 import sys
@@ -69,3 +70,13 @@ wall, dev = timed(lambda: eng.union_device(ptrs, K * m, out.data_ptr()))
 print(f"union     n={n} K={K} p={p}: wall {wall:.3f} ms, kernel {dev:.3f} ms, {(n + 1) * K * m / dev / 1e6:.1f} GB/s")
 wall, dev = timed(lambda: eng.card_batch_device(leaf.data_ptr(), n * K))
 print(f"card      jobs={n * K} p={p}: wall {wall:.3f} ms, hist kernel {dev:.3f} ms, {n * K * m / dev / 1e6:.1f} GB/s")
+
+# deltadelta: every leave-one-out union of 64 genomes (the first 64 of the slab above), one read of their rows
+n = 64
+wall, dev = timed(lambda: eng.leave_out_device(leaf.data_ptr(), n, K, np.arange(n)))
+print(f"leave-out n={n} K={K} p={p}: wall {wall:.3f} ms, kernels {dev:.3f} ms, {n * K * m / dev / 1e6:.1f} GB/s (the slab read once)")
+
+# abba: the unions of all 2^16 subsets of 16 genomes
+n = 16
+wall, dev = timed(lambda: eng.subsets_device(leaf.data_ptr(), n, K))
+print(f"subsets   n={n} K={K} p={p}: wall {wall:.2f} ms, kernels {dev:.3f} ms, {(1 << n) * K} subset unions")
