@@ -273,7 +273,7 @@ int dd_sketch_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* n
         const size_t cur_stride = 256;
         const size_t cur_bytes = align_up((size_t)nrows * cur_stride, 256);
         const size_t flt_tot = align_up(nhashed * flt_bytes, 256);
-        // the first epoch's updates of rho = 1: one bit per register instead of a record each (dd_sweep.hip,
+        // the first epoch's updates of rho = 1: one bit per register instead of a record each (dd_scatter.hip,
         // scatter_first_bin_kernel); the bits start at zero with the cursors and filters
         const size_t ones_bytes = m / 8, ones_tot = align_up(nhashed * ones_bytes, 256);
         if ((rc = c->buckets.reserve(tab_bytes + cur_bytes + flt_tot + ones_tot + nhashed * (fill_bytes + area_bytes)))) return rc;

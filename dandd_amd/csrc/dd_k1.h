@@ -1,0 +1,566 @@
+// dd_k1.h -- what the sketching (K1) kernels of dd_sweep.hip and dd_scatter.hip share: the gfx950 forms of the hash, the
+// register stores and the update, the rolling windows of every k class, a tile's input (one copy of the halo and segment
+// loads), the walk over a segment's 64 tokens, the small-k classes' segment, the finish kernels' tile, and the host helpers
+// that pick a <KC, CANON> instantiation and launch it.  Device code is DD_D or constexpr: no kernel calls across files.
+#pragma once
+#include "dd_common.h"
+#include "dd_kernels.h"
+
+#include <algorithm>
+#include <atomic>
+#include <type_traits>
+
+namespace dd {
+
+extern __shared__ __attribute__((aligned(16))) uint8_t g_lds[];
+
+DD_D uint32_t ffbh(uint32_t x) {  // leading zeros; 0xFFFFFFFF for x == 0
+    uint32_t r;
+    asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+DD_D uint32_t mul_lo(uint32_t a, uint32_t c) {  // opaque to the optimiser: stays one v_mul_lo_u32
+    uint32_t r;
+    asm("v_mul_lo_u32 %0, %1, %2" : "=v"(r) : "v"(a), "s"(c));
+    return r;
+}
+template <int SH>
+DD_D uint64_t lshl_add64(uint64_t a, uint64_t b) {  // (a << SH) + b, SH in 0..4, one instruction
+    uint64_t r;
+    asm("v_lshl_add_u64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "n"(SH), "v"(b));
+    return r;
+}
+// x * C + addend (mod 2^64), C a 32-bit constant: v_mad_u64_u32 + v_mul_lo_u32 + v_add_u32
+template <bool HI_ZERO>
+DD_D uint64_t mul64_c32(uint64_t x, uint32_t C, uint64_t addend) {
+    const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+    const uint64_t pr = (uint64_t)lo * C + addend;
+    if (HI_ZERO) return pr;
+    const uint32_t ph = (uint32_t)(pr >> 32) + mul_lo(hi, C);
+    return ((uint64_t)ph << 32) | (uint32_t)pr;
+}
+
+// Thomas Wang 64-bit mix, identical to dd::wang64 (asserted on every lane by the GPU parity tests),
+// arranged for the gfx950 issue costs (dd_sweep.hip, head): 18 instructions.
+template <bool HI_ZERO>
+DD_D uint64_t wang64_fast(uint64_t x) {
+    x = mul64_c32<HI_ZERO>(x, 0x1FFFFFu, ~0ull);  // ~x + (x << 21) = x * (2^21 - 1) - 1
+    x ^= x >> 24;
+    x = mul64_c32<false>(x, 265u, 0ull);          // x + (x << 3) + (x << 8)
+    x ^= x >> 14;
+    x = lshl_add64<2>(lshl_add64<2>(x, x), x);    // x + (x << 2) + (x << 4) = ((5x) << 2) + x
+    x ^= x >> 28;
+    return lshl_add64<0>(x << 31, x);             // x + (x << 31)
+}
+
+// ---- register stores -------------------------------------------------------------------------
+// kernels that address LDS absolutely (RegsLds, scatter_update's filter read) call this first
+DD_D void lds_starts_at_zero() {
+    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)g_lds != 0u) __builtin_trap();
+}
+
+// LDS: byte registers, 32-bit compare-and-swap on the containing word when a register must rise.
+struct RegsLds {
+    uint32_t slot;  // the slot's registers start at byte slot << p of g_lds
+    using Addr = uint32_t;
+    // address of register  hi >> (32-p)  (the top p bits of the hash): one v_alignbit of slot:hi
+    DD_D Addr at(uint32_t hi, int p) const { return __builtin_amdgcn_alignbit(slot, hi, 32 - p); }
+    DD_D static uint32_t shift(Addr a) { return (a & 3u) * 8u; }
+    // Registers are read at their ABSOLUTE LDS address: every kernel that uses this struct has no static LDS, so the
+    // dynamic array g_lds starts at 0 (lds_starts_at_zero() at the top of each checks it), and indexing through the
+    // g_lds symbol would cost a `v_add_u32 v, 0, v` of its link-time address on every read -- 1.5 of the 31.5 VALU
+    // instructions of a k 17..32 update at log2m <= 16.
+    DD_D uint32_t bound(Addr a) const { return *(const __attribute__((address_space(3))) uint8_t*)(uintptr_t)a; }  // the register itself
+    DD_D static uint32_t load32(Addr a) { return *(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)(a & ~3u); }
+    DD_D static uint32_t cas32(Addr a, uint32_t expect, uint32_t desired) {
+        return atomicCAS(reinterpret_cast<uint32_t*>(g_lds + (a & ~3u)), expect, desired);
+    }
+};
+// HBM/L2: same protocol on the genome's slab (p >= 18: one array no longer fits LDS).
+struct RegsGlobal {
+    uint8_t* base;  // 16-byte aligned
+    using Addr = uint8_t*;
+    DD_D Addr at(uint32_t hi, int p) const { return base + (hi >> (32 - p)); }
+    DD_D static uint32_t shift(Addr a) { return ((uint32_t)(uintptr_t)a & 3u) * 8u; }
+    DD_D static uint8_t* word(Addr a) {
+        return static_cast<uint8_t*>(__builtin_assume_aligned(a - ((uintptr_t)a & 3u), 4));
+    }
+    DD_D uint32_t bound(Addr a) const { return gload1_fresh(a); }
+    DD_D static uint32_t load32(Addr a) { return gload4_fresh(word(a)); }
+    DD_D static uint32_t cas32(Addr a, uint32_t expect, uint32_t desired) { return gcas32(word(a), expect, desired); }
+};
+
+// 16 bytes of global memory as other agents' atomics left them (two relaxed agent-scope 8-byte
+// loads: they bypass this XCD's non-coherent L2).
+DD_D uint4 load16_fresh(const uint8_t* p) {
+    const uint8_t* q = static_cast<const uint8_t*>(__builtin_assume_aligned(p, 16));
+    const unsigned long long a = gload8_fresh(q), b = gload8_fresh(q + 8);
+    return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+}
+DD_D uint32_t load4_fresh(const uint32_t* p) { return gload4_fresh(p); }
+
+// hi = top word of h (its top p bits index the register) and lz = rho(h) - 1 (0xFFFFFFFF when the
+// top 32 bits of h << p are all zero)
+struct Probe {
+    uint32_t hi, lz, hiw, lo;
+};
+DD_D Probe probe(uint64_t h, int p) {
+    const uint32_t hi = (uint32_t)(h >> 32), lo = (uint32_t)h;
+    Probe r;
+    r.hi = hi;
+    r.hiw = __builtin_amdgcn_alignbit(hi, lo, 32 - p);  // bits 63..32 of (h << p)
+    r.lz = ffbh(r.hiw);
+    r.lo = lo;
+    return r;
+}
+// rho(h) from a probe: lz + 1, in its long form only when the 32 bits after the index are all zero
+// (p = 2^-32: behind a wave-level branch)
+DD_D uint32_t rho_of(const Probe& q, int p) {
+    uint32_t rho = q.lz + 1;  // 0 where hiw == 0
+    if (__builtin_expect(__any(q.hiw == 0), 0)) {
+        if (q.hiw == 0) rho = 33u + (uint32_t)__builtin_clz((q.lo << p) | (1u << (p - 1)));
+    }
+    return rho;
+}
+// Exact byte-max of rho into the register at `a` through a 32-bit CAS on the containing word,
+// starting from the word value `old`; returns the register's value afterwards.  The byte is raised by
+// ADDING (rho - cur) << shift: no carry can leave the byte.
+template <typename R>
+DD_D uint32_t cas_raise(typename R::Addr a, uint32_t old, uint32_t rho) {
+    const uint32_t sh = R::shift(a);
+    while (true) {
+        const uint32_t cur = (old >> sh) & 0xFFu;
+        if (rho <= cur) return cur;
+        const uint32_t prev = R::cas32(a, old, old + ((rho - cur) << sh));
+        if (prev == old) return rho;
+        old = prev;
+    }
+}
+// The rare path: the register at `a` was seen below rho.  Every instruction here is paid by the
+// whole wave for (typically) one lane, so it is kept short.
+template <typename R>
+DD_D void raise(const R&, typename R::Addr a, const Probe& q, int p) {
+    (void)cas_raise<R>(a, R::load32(a), rho_of(q, p));
+}
+
+DD_D uint32_t min4(uint32_t w) {  // smallest byte
+    const uint32_t a = w & 0xFFu, b = (w >> 8) & 0xFFu, c = (w >> 16) & 0xFFu, d = w >> 24;
+    const uint32_t ab = a < b ? a : b, cd = c < d ? c : d;
+    return ab < cd ? ab : cd;
+}
+// reg[h >> (64-p)] = max(., rho(h)); the common case (no change) is one byte read + compare.
+template <typename R>
+DD_D void hll_update(const R& regs, uint64_t h, int p) {
+    const Probe q = probe(h, p);
+    const typename R::Addr a = regs.at(q.hi, p);
+    if (q.lz >= regs.bound(a)) raise(regs, a, q, p);  // rho > bound, or hiw == 0 (resolved there)
+}
+// two independent updates interleaved: both hash chains and both LDS reads are in flight
+// together, one wave-level branch covers the common no-change case of both
+template <typename R>
+DD_D void hll_update2(const R& r0, uint64_t h0, const R& r1, uint64_t h1, int p) {
+    const Probe qa = probe(h0, p), qb = probe(h1, p);
+    const typename R::Addr a = r0.at(qa.hi, p), b = r1.at(qb.hi, p);
+    const uint32_t c0 = r0.bound(a), c1 = r1.bound(b);
+    if ((qa.lz >= c0) | (qb.lz >= c1)) {
+        if (qa.lz >= c0) raise(r0, a, qa, p);
+        if (qb.lz >= c1) raise(r1, b, qb, p);
+    }
+}
+
+// Reverse the order of the 16 2-bit fields of a code word: the token stream stores token j at bits
+// [2j, 2j+1] (oldest lowest), the forward window wants the newest token lowest.
+DD_D uint32_t pairrev32(uint32_t x) {
+    x = __builtin_bitreverse32(x);  // v_bfrev_b32: fields reversed, but so are the two bits inside each
+    return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
+}
+DD_D uint64_t pack64(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | lo; }
+
+// ---- rolling windows, one set per thread, shared by every k of the group ------------------------
+// prime(hc): the state after pushing the 64 tokens of the previous segment (hc = its four code
+// words), computed with a handful of bit operations instead of 64 pushes.  The reverse-complement
+// window holds tokens in stream order, newest on top, so it is simply the complement of the words.
+//   KC 0: k <= 16 (32-bit windows)   KC 1: 16 <= k <= 32 (64-bit)   KC 3: 33 <= k <= 48 (96-bit: 64 + 32)
+//   KC 2: 49 <= k <= 64 (128-bit: Windows<7>, four 32-bit words)
+template <int KC>
+struct Windows;
+
+template <>
+struct Windows<0> {
+    uint32_t fw = 0, rc = 0;
+    DD_D void prime(const uint4& hc) {
+        fw = pairrev32(hc.w);
+        rc = ~hc.w;
+    }
+    DD_D void push(uint32_t c) {
+        fw = (fw << 2) | c;
+        rc = (rc >> 2) | ((3u - c) << 30);
+    }
+    template <bool CANON>
+    DD_D uint64_t hash(int k) const {
+        const uint32_t f = (k == 16) ? fw : (fw & ((1u << (2 * k)) - 1u));
+        if (!CANON) return wang64_fast<true>(f);
+        const uint32_t r = rc >> (32 - 2 * k);
+        return wang64_fast<true>(f < r ? f : r);
+    }
+};
+
+template <>
+struct Windows<1> {
+    uint64_t fw = 0, rc = 0;
+    DD_D void prime(const uint4& hc) {
+        fw = pack64(pairrev32(hc.z), pairrev32(hc.w));
+        rc = ~pack64(hc.w, hc.z);
+    }
+    DD_D void push(uint32_t c) {
+        fw = (fw << 2) | c;
+        rc = (rc >> 2) | ((uint64_t)(3u - c) << 62);
+    }
+    template <bool CANON>
+    DD_D uint64_t hash(int k) const {
+        // 16 <= k <= 32: the low word of the window belongs to the k-mer whole, only the high word is masked
+        const uint32_t mhi = (k == 32) ? ~0u : ((1u << (2 * k - 32)) - 1u);
+        const uint64_t f = pack64((uint32_t)(fw >> 32) & mhi, (uint32_t)fw);
+        if (!CANON) return wang64_fast<false>(f);
+        const uint64_t r = rc >> (64 - 2 * k);
+        return wang64_fast<false>(f < r ? f : r);
+    }
+};
+
+// The 64-bit class again, as 32-bit halves: a push is two funnel shifts and two shift-or instructions, and the
+// compiler has no 64-bit value to keep a copy of (with u64 members it spent three more instructions per push).
+// Used by the scatter kernels, where the push is paid per (token, k); sweep_kernel shares one push between the
+// ks of a group and keeps Windows<1> (measured equal there).
+template <>
+struct Windows<5> {
+    uint32_t fl = 0, fh = 0, rl = 0, rh = 0;
+    DD_D void prime(const uint4& hc) {
+        fh = pairrev32(hc.z);
+        fl = pairrev32(hc.w);
+        rh = ~hc.w;
+        rl = ~hc.z;
+    }
+    DD_D void push(uint32_t c) {
+        fh = __builtin_amdgcn_alignbit(fh, fl, 30);  // (fw << 2) high word
+        fl = (fl << 2) | c;
+        rl = __builtin_amdgcn_alignbit(rh, rl, 2);   // (rc >> 2) low word
+        rh = (rh >> 2) | ((3u - c) << 30);
+    }
+    template <bool CANON>
+    DD_D uint64_t hash(int k) const {
+        const uint32_t mhi = (k == 32) ? ~0u : ((1u << (2 * k - 32)) - 1u);
+        const uint64_t f = pack64(fh & mhi, fl);
+        if (!CANON) return wang64_fast<false>(f);
+        const uint64_t r = pack64(rh, rl) >> (64 - 2 * k);
+        return wang64_fast<false>(f < r ? f : r);
+    }
+};
+
+// The tail the two 96-bit forms share: the hash of a k-mer of 66..96 bits, (hi, lo) with hi < 2^32 --
+// fold128(hi, lo) as hi * G = hi * G_lo + ((hi * G_hi) << 32) (mod 2^64) -- and the canonical choice between the forward
+// (ah, fl) and the reverse-complement (bh, bl) value in front of it.
+DD_D uint64_t hash96(uint32_t hi, uint64_t lo) {
+    const uint64_t hg = (uint64_t)hi * 0x7F4A7C15u + ((uint64_t)(hi * 0x9E3779B9u) << 32);
+    return wang64_fast<false>(lo ^ hg);
+}
+DD_D uint64_t hash96_canonical(uint32_t ah, uint64_t fl, uint32_t bh, uint64_t bl) {
+    const bool f_lt = (ah < bh) | ((ah == bh) & (fl < bl));  // bitwise: no exec-mask short circuit
+    return hash96(f_lt ? ah : bh, f_lt ? fl : bl);
+}
+
+// 33 <= k <= 48: the k-mer is 66..96 bits, so the high part fits one 32-bit register and every
+// step on it (mask, funnel shift of the reverse complement, compare, select, fold multiply) is a
+// 32-bit instruction instead of a 64-bit pair.
+template <>
+struct Windows<3> {
+    uint64_t fl = 0, rt = 0;  // forward: low 64 bits;  reverse complement, top-aligned: bits 95..32
+    uint32_t fh = 0, rb = 0;  // forward: bits 95..64;  reverse complement: bits 31..0
+    DD_D void prime(const uint4& hc) {
+        fl = pack64(pairrev32(hc.z), pairrev32(hc.w));
+        fh = pairrev32(hc.y);
+        rt = ~pack64(hc.w, hc.z);
+        rb = ~hc.y;
+    }
+    DD_D void push(uint32_t c) {
+        fh = __builtin_amdgcn_alignbit(fh, (uint32_t)(fl >> 32), 30);  // (fh << 2) | (fl >> 62)
+        fl = (fl << 2) | c;
+        rb = __builtin_amdgcn_alignbit((uint32_t)rt, rb, 2);           // (rb >> 2) | (rt << 30)
+        rt = (rt >> 2) | ((uint64_t)(3u - c) << 62);
+    }
+    template <bool CANON>
+    DD_D uint64_t hash(int k) const {
+        const int hb = 2 * k - 64;  // 2..32 bits of the k-mer above bit 63
+        const uint32_t ah = (hb == 32) ? fh : (fh & ((1u << hb) - 1u));
+        if (!CANON) return hash96(ah, fl);
+        const uint32_t s = 96u - 2u * (uint32_t)k;  // 0..30
+        const uint32_t r3 = (uint32_t)(rt >> 32), r2 = (uint32_t)rt;
+        return hash96_canonical(ah, fl, r3 >> s, pack64(__builtin_amdgcn_alignbit(r3, r2, s), __builtin_amdgcn_alignbit(r2, rb, s)));
+    }
+};
+
+// The 96-bit class as three 32-bit words per window (see Windows<5>): used by the scatter kernels.
+template <>
+struct Windows<6> {
+    uint32_t f0 = 0, f1 = 0, f2 = 0;  // forward window, low .. high word
+    uint32_t r0 = 0, r1 = 0, r2 = 0;  // reverse complement, top-aligned in 96 bits: r2 holds bits 95..64
+    DD_D void prime(const uint4& hc) {
+        f0 = pairrev32(hc.w);
+        f1 = pairrev32(hc.z);
+        f2 = pairrev32(hc.y);
+        r2 = ~hc.w;
+        r1 = ~hc.z;
+        r0 = ~hc.y;
+    }
+    DD_D void push(uint32_t c) {
+        f2 = __builtin_amdgcn_alignbit(f2, f1, 30);
+        f1 = __builtin_amdgcn_alignbit(f1, f0, 30);
+        f0 = (f0 << 2) | c;
+        r0 = __builtin_amdgcn_alignbit(r1, r0, 2);
+        r1 = __builtin_amdgcn_alignbit(r2, r1, 2);
+        r2 = (r2 >> 2) | ((3u - c) << 30);
+    }
+    template <bool CANON>
+    DD_D uint64_t hash(int k) const {
+        const int hb = 2 * k - 64;  // 2..32 bits of the k-mer above bit 63
+        const uint32_t ah = (hb == 32) ? f2 : (f2 & ((1u << hb) - 1u));
+        const uint64_t fl = pack64(f1, f0);
+        if (!CANON) return hash96(ah, fl);
+        const uint32_t s = 96u - 2u * (uint32_t)k;  // 0..30
+        return hash96_canonical(ah, fl, r2 >> s, pack64(__builtin_amdgcn_alignbit(r2, r1, s), __builtin_amdgcn_alignbit(r1, r0, s)));
+    }
+};
+
+// The 128-bit class as four 32-bit words per window (see Windows<5>): used by the scatter kernels, whose push is paid per
+// (token, k) -- with u64 members the compiler spent 16 instructions on a push (two 64-bit copies, shift / or pairs,
+// and the funnel shifts that take the words apart again at the hash), this form 12.
+template <>
+struct Windows<7> {
+    uint32_t f0 = 0, f1 = 0, f2 = 0, f3 = 0;  // forward window, low .. high word
+    uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;  // reverse complement, top-aligned in 128 bits
+    DD_D void prime(const uint4& hc) {
+        f0 = pairrev32(hc.w);
+        f1 = pairrev32(hc.z);
+        f2 = pairrev32(hc.y);
+        f3 = pairrev32(hc.x);
+        r3 = ~hc.w;
+        r2 = ~hc.z;
+        r1 = ~hc.y;
+        r0 = ~hc.x;
+    }
+    DD_D void push(uint32_t c) {
+        f3 = __builtin_amdgcn_alignbit(f3, f2, 30);
+        f2 = __builtin_amdgcn_alignbit(f2, f1, 30);
+        f1 = __builtin_amdgcn_alignbit(f1, f0, 30);
+        f0 = (f0 << 2) | c;
+        r0 = __builtin_amdgcn_alignbit(r1, r0, 2);
+        r1 = __builtin_amdgcn_alignbit(r2, r1, 2);
+        r2 = __builtin_amdgcn_alignbit(r3, r2, 2);
+        r3 = (r3 >> 2) | ((3u - c) << 30);
+    }
+    template <bool CANON>
+    DD_D uint64_t hash(int k) const {  // 49 <= k <= 64
+        const int hb = 2 * k - 96;  // bits of the k-mer in the top word, 2..32
+        const uint32_t mh = (hb == 32) ? ~0u : ((1u << hb) - 1u);
+        const uint64_t ah = pack64(f3 & mh, f2);
+        const uint64_t al = pack64(f1, f0);
+        if (!CANON) return wang64_fast<false>(fold128(ah, al));
+        const uint32_t s = 128u - 2u * (uint32_t)k;  // 0..30
+        const uint64_t bh = pack64(r3 >> s, __builtin_amdgcn_alignbit(r3, r2, s));
+        const uint64_t bl = pack64(__builtin_amdgcn_alignbit(r2, r1, s), __builtin_amdgcn_alignbit(r1, r0, s));
+        const bool f_lt = (ah < bh) | ((ah == bh) & (al < bl));  // bitwise: no exec-mask short circuit
+        return wang64_fast<false>(fold128(f_lt ? ah : bh, f_lt ? al : bl));
+    }
+};
+
+// The form each kernel family uses for k class KC.  sweep_kernel: the 128-bit class as 32-bit words (Windows<7>: 1.6 % at
+// log2m 16, 0.6 % at 14 on k 49..64); the 64- and 96-bit classes measure equal to slightly slower in that form there, where
+// one push serves several ks, and keep u64 members.  The scatter kernels: 32-bit words for every class.
+template <int KC>
+using SweepWindows = Windows<KC == 2 ? 7 : KC>;
+template <int KC>
+using ScatterWindows = Windows<KC == 1 ? 5 : (KC == 3 ? 6 : (KC == 2 ? 7 : KC))>;
+
+// a wave-uniform value that arrived through a vector load (a table entry): moved to scalar registers
+DD_D uint64_t uniform64(uint64_t v) {
+    // (the builtin returns int: without the casts the low half would be sign-extended over the high one)
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)), lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
+    return ((uint64_t)hi << 32) | lo;
+}
+template <typename T>
+DD_D T* uniform_ptr(T* q) { return reinterpret_cast<T*>(uniform64(reinterpret_cast<uint64_t>(q))); }
+
+// ---- a tile's input and the walk over a segment (the hashed kernels) ---------------------------------------------------
+// A thread's input for one tile: its segment (sc, sb) and the previous one (hc, hb: the halo that primes the windows;
+// segment 0 starts behind a BREAK).  A kernel issues the loads of tile t+1 before it processes tile t.  (fetch_tile fills
+// the caller's TileIn: returning one by value changed the code around the loads, profiles/k1_shared_walk.txt.)
+struct TileIn {
+    uint4 hc, sc;
+    uint2 hb, sb;
+    bool live;  // the segment lies inside the token stream
+};
+DD_D void fetch_tile(const SweepGenome& g, const SweepJob& job, unsigned long long ntok, unsigned tile, TileIn& t) {
+    const unsigned long long seg = (unsigned long long)tile * blockDim.x + threadIdx.x;
+    t.live = tile < job.tile_end && seg * kSegTokens < ntok;
+    t.hc = make_uint4(0, 0, 0, 0);
+    t.hb = make_uint2(~0u, ~0u);
+    t.sc = make_uint4(0, 0, 0, 0);  // a segment outside the stream is all BREAKs
+    t.sb = make_uint2(~0u, ~0u);
+    if (!t.live) return;
+    if (seg > 0) {
+        t.hc = gload16(g.codes + (seg - 1) * 4);
+        t.hb = gload8(g.bad + (seg - 1) * 2);
+    }
+    t.sc = gload16(g.codes + seg * 4);
+    t.sb = gload8(g.bad + seg * 2);
+}
+
+// The 64 tokens of a segment through the caller's windows `win` (primed here from the halo), reached by whole waves:
+// token(clean, run) is called behind every push.  clean is std::true_type on the path where no lane of the wave has a
+// BREAK within its halo or its segment (the common case away from record boundaries and N runs: every window of every
+// k <= 64 is valid; run is not kept there and passed as 0), else std::false_type with run = the clean tokens that end at
+// the current one.  (win is the caller's, and the token is taken from its word before run is updated: in both the compiler's
+// schedule of the token loops follows the order of the source, profiles/k1_shared_walk.txt.)
+template <typename Win, typename Token>
+DD_D void walk_segment(const TileIn& in, Win& win, const Token& token) {
+    const uint4 hc = in.hc, sc = in.sc;
+    const uint2 hb = in.hb, sb = in.sb;
+    const uint32_t cw[4] = {sc.x, sc.y, sc.z, sc.w};
+    win.prime(hc);
+    if (__all((hb.x | hb.y | sb.x | sb.y) == 0u)) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+#pragma unroll 1
+            for (int i = 0; i < 16; ++i) {
+                win.push((cw[w] >> (2 * i)) & 3u);
+                token(std::true_type{}, 0);
+            }
+        }
+        return;
+    }
+    // run enters as the clean tail of the halo
+    int run = hb.y ? __builtin_clz(hb.y) : 32 + (hb.x ? __builtin_clz(hb.x) : 32);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint32_t bw = ((w & 2) ? sb.y : sb.x) >> ((w & 1) * 16);
+#pragma unroll 1
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t c = (cw[w] >> (2 * i)) & 3u;
+            run = ((bw >> i) & 1u) ? 0 : run + 1;
+            win.push(c);
+            token(std::false_type{}, run);
+        }
+    }
+}
+
+// ---- the small-k classes' segment (bitmap_kernel, bigmap_kernel) -------------------------------------------------------
+// One 32-bit window pair.  WHOLE (bitmap_kernel): the newest 16 tokens, every k masks its own k-mer out; else (bigmap_kernel)
+// cut to the job's one k: mask = 4^k - 1, top = 2 k - 2.
+template <bool WHOLE>
+struct SmallWindows {
+    uint32_t mask;
+    int top;
+    uint32_t fw = 0, rc = 0;
+    DD_D void push(uint32_t c) {
+        fw = WHOLE ? (fw << 2) | c : ((fw << 2) | c) & mask;
+        rc = (rc >> 2) | ((3u - c) << (WHOLE ? 30 : top));
+    }
+};
+// A thread's segment, the windows primed from the last `prime` tokens of the halo (prime <= 10: its last code word), and
+// run = the clean tokens that end the halo, among those
+struct SmallIn {
+    uint4 sc;
+    uint2 sb;
+    int run;
+};
+template <typename Win>
+DD_D SmallIn fetch_small(const SweepGenome& g, unsigned long long seg, int prime, Win& win) {
+    SmallIn s;
+    s.run = 0;
+    if (seg > 0) {
+        const uint4 hc = gload16(g.codes + (seg - 1) * 4);
+        const uint2 hb = gload8(g.bad + (seg - 1) * 2);
+        const uint32_t cw = hc.w, bw = hb.y >> 16;
+#pragma unroll 1
+        for (int i = 16 - prime; i < 16; ++i) {
+            const uint32_t c = (cw >> (2 * i)) & 3u;
+            s.run = ((bw >> i) & 1u) ? 0 : s.run + 1;
+            win.push(c);
+        }
+    }
+    s.sc = gload16(g.codes + seg * 4);
+    s.sb = gload8(g.bad + seg * 2);
+    return s;
+}
+
+// ---- exact k-mer sets -> registers (bitmap_finish_kernel, bigmap_finish_kernel) and records -> registers (replay_kernel) --
+// LDS register a = max(., rho)
+DD_D void lds_raise(uint32_t a, uint32_t rho) {
+    const uint32_t w = RegsLds::load32(a);
+    if (rho > ((w >> RegsLds::shift(a)) & 0xFFu)) (void)cas_raise<RegsLds>(a, w, rho);
+}
+// f(32 w + bit) for every set bit of the nw words at bm, the words dealt round the workgroup
+template <typename F>
+DD_D void for_each_set_bit(const uint32_t* bm, uint32_t nw, const F& f) {
+    for (uint32_t w = threadIdx.x; w < nw; w += blockDim.x) {
+        uint32_t v = gload4(bm + w);
+        while (v) {
+            const uint32_t bit = (uint32_t)__builtin_ctz(v);
+            v &= v - 1;
+            f((w << 5) | bit);
+        }
+    }
+}
+// Index tile b (2^tile_log2 registers, at `out`) of a row built in LDS from ALL the k-mers of its set: for_each_kmer(emit)
+// calls emit(x) for every k-mer x (< 2^32) the workgroup's threads find; those whose register lies in another tile are dropped.
+template <typename ForEachKmer>
+DD_D void finish_tile(uint8_t* out, int tile_log2, uint32_t b, int p, const ForEachKmer& for_each_kmer) {
+    const uint32_t tile = 1u << tile_log2;
+    uint4* z = reinterpret_cast<uint4*>(g_lds);
+    for (uint32_t i = threadIdx.x; i < (tile >> 4); i += blockDim.x) z[i] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    for_each_kmer([&](uint32_t x) {
+        const Probe q = probe(wang64_fast<true>(x), p);
+        const uint32_t idx = q.hi >> (32 - p);
+        if ((idx >> tile_log2) != b) return;
+        lds_raise(idx & (tile - 1u), rho_of(q, p));
+    });
+    __syncthreads();
+    const uint4* l4 = reinterpret_cast<const uint4*>(g_lds);
+    for (uint32_t i = threadIdx.x; i < (tile >> 4); i += blockDim.x) gstore16(out + (size_t)i * 16, l4[i]);
+}
+
+// ---- host: pick the instantiation, launch it -----------------------------------------------------------------------------
+// f(std::bool_constant<b>)
+template <typename F>
+void dispatch_bool(bool b, const F& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// f(std::integral_constant<int, KC>, std::bool_constant<CANON>) for the k class and strand mode of a launch
+template <typename F>
+void dispatch_kc_canon(int kclass, bool canonical, const F& f) {
+    dispatch_bool(canonical, [&](auto cn) {
+        if (kclass == 0) f(std::integral_constant<int, 0>{}, cn);
+        else if (kclass == 1) f(std::integral_constant<int, 1>{}, cn);
+        else if (kclass == 3) f(std::integral_constant<int, 3>{}, cn);
+        else f(std::integral_constant<int, 2>{}, cn);
+    });
+}
+// Launch of a kernel whose dynamic LDS may exceed 64 KiB: that must be allowed per kernel AND per device (a process may hold
+// contexts on several GPUs), once, not on every launch; remembered in one bit per device id.  STATIC_LDS: the kernel's own
+// __shared__ bytes -- dynamic + static must stay within the CU's 160 KiB or the call is refused.
+template <auto Kern, int STATIC_LDS = 0, typename... Args>
+void launch_full_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, Args... args) {
+    static std::atomic<unsigned long long> allowed{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(allowed.load(std::memory_order_relaxed) & bit)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - STATIC_LDS) != hipSuccess)
+            (void)hipGetLastError();  // not sticky: a launch that needs the room will report it
+        allowed.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds_bytes, st, args...);
+}
+
+}  // namespace dd

@@ -197,13 +197,13 @@ std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbyte
             // Capacity of a row's stream.  Only the first epoch turns every token into a record; a later epoch that
             // starts after s tokens and is L long leaves about m L / s of them (m or fewer with the doubling schedule),
             // so four records per register cover it several times over -- and what should still not fit goes to the
-            // registers by compare-and-swap, exactly (dd_sweep.hip).  (Sized for the longest epoch's every token the areas
+            // registers by compare-and-swap, exactly (dd_scatter.hip).  (Sized for the longest epoch's every token the areas
             // of a 10 x 50 Mbp call at log2m 20 were 20 GB; 5.4 GB measure the same.)  A call with so many rows that even
             // the first epoch's worst case exceeds the budget gets what the budget allows.
             // (no epoch at all when every genome of the call is empty: epoch_edge is {0} then)
             const size_t first_tokens = nepochs ? (epoch_edge[1] - epoch_edge[0]) * kTileTokens : 0;
             const size_t per_row = std::min(std::max(first_tokens, 4 * m), bucket_row_tokens);
-            // (the first epoch's binned tiles take 70 chunks of stream per tile of tokens, not 64: dd_sweep.hip)
+            // (the first epoch's binned tiles take 70 chunks of stream per tile of tokens, not 64: dd_scatter.hip)
             sc.plan.cap_chunks = (unsigned)(knobs.bucket_cap_chunks ? knobs.bucket_cap_chunks
                                                 : (per_row + per_row / 8) / 1024 + max_jobs_row_epoch * (kThreads / 64) + 16);
             sc.plan.logg = bucket_logg;
@@ -271,7 +271,7 @@ std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbyte
             sc.plan.mode = 0;
             sc.plan.lds_bytes = kBigmapSliceWords * 4;
         } else if (bucket_mode) {
-            sc.plan.mode = kBucketMode;  // the 4-bit filter, then two 128-entry record queues per wave (dd_sweep.hip: scatter_kernel)
+            sc.plan.mode = kBucketMode;  // the 4-bit filter, then two 128-entry record queues per wave (dd_scatter.hip: scatter_kernel)
             sc.plan.lds_bytes = (int)((m >> bucket_logg) / 2) + (kThreads / 64) * 128 * 4 * 2;
         } else {
             sc.plan.mode = 0;

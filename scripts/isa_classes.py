@@ -2,8 +2,9 @@
 
     python scripts/isa_classes.py [--asm FILE] [--out profiles/r04_isa_classes.json]
 
-Without --asm the script compiles dandd_amd/csrc/dd_sweep.hip with the flags of dandd_amd/build.py plus -save-temps
-(hipcc cross-compiles gfx950 without a GPU) and reads the .s it leaves under build/isa/.
+Without --asm the script compiles K1's two sources, dandd_amd/csrc/dd_sweep.hip and dd_scatter.hip, with the flags of
+dandd_amd/build.py plus -save-temps (hipcc cross-compiles gfx950 without a GPU) and reads the .s files they leave under
+build/isa/.  --asm takes one file, or several separated by commas.
 
 What it counts.  A kernel's loops are found from the labels and backward branches of its function body; one pass of a loop
 is walked along its common path (hot_path: blocks guarded by `s_cbranch_execz` -- a register that must rise, the long form
@@ -23,6 +24,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+K1_SOURCES = ["dd_sweep", "dd_scatter"]   # dandd_amd/csrc/<stem>.hip: the log2m <= 16 family and the set classes; the record path
 CHEAP = {"v_xor_b32", "v_and_b32", "v_or_b32", "v_not_b32", "v_mov_b32", "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_lshrrev_b32"}
 
 
@@ -200,17 +202,19 @@ def main():
     ap.add_argument("--asm")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r04_isa_classes.json"))
     a = ap.parse_args()
-    asm_path = a.asm
-    if not asm_path:
+    asm_paths = a.asm.split(",") if a.asm else []
+    if not asm_paths:
         sys.path.insert(0, ROOT)
         from dandd_amd import build as b
         d = os.path.join(ROOT, "build", "isa")
         os.makedirs(d, exist_ok=True)
         flags = [f for f in b.FLAGS if f not in ("-shared",)]
-        subprocess.check_call([b.hipcc()] + flags + ["-save-temps", "-c", "-o", os.path.join(d, "dd_sweep.o"), os.path.join(b.CSRC, "dd_sweep.hip")], cwd=d)
-        asm_path = os.path.join(d, "dd_sweep-hip-amdgcn-amd-amdhsa-gfx950.s")
-    asm = open(asm_path).read()
-    fns = functions(asm)
+        for stem in K1_SOURCES:
+            subprocess.check_call([b.hipcc()] + flags + ["-save-temps", "-c", "-o", os.path.join(d, stem + ".o"), os.path.join(b.CSRC, stem + ".hip")], cwd=d)
+            asm_paths.append(os.path.join(d, stem + "-hip-amdgcn-amd-amdhsa-gfx950.s"))
+    fns = {}
+    for path in asm_paths:
+        fns.update(functions(open(path).read()))
     pretty = demangle(list(fns))
     costs = issue_costs(os.path.join(ROOT, "profiles", "r01_ubench_issue_costs.txt"))
     # kernels whose inner loop hashes: name pattern -> updates one pass of the hot loop makes
@@ -223,7 +227,7 @@ def main():
         (r"scatter_first_bin_kernel<(\d), true>", 1, "first epoch (log2m >= 17): one update per pass of the token loop -- the record's path (the rho = 1 lanes' ds_or block is the one skipped)", ("ds_add_rtn", "global_store"), (), ("ds_or",)),
     ]
     kc_name = {"0": "k <= 16 (32-bit windows)", "1": "k 17-32 (64-bit)", "3": "k 33-48 (96-bit)", "2": "k 49-64 (128-bit)"}
-    out = {"made_by": "scripts/isa_classes.py over `hipcc -save-temps` of dandd_amd/csrc/dd_sweep.hip (the flags of dandd_amd/build.py)",
+    out = {"made_by": "scripts/isa_classes.py over `hipcc -save-temps` of dandd_amd/csrc/dd_sweep.hip and dd_scatter.hip (the flags of dandd_amd/build.py)",
            "issue_costs": costs, "kernels": {}}
     for mangled, body in fns.items():
         name = re.sub(r"\(anonymous namespace\)::|dd::|void ", "", pretty[mangled]).split("(")[0]

@@ -4,7 +4,7 @@
 //   V 2: one 32-bit word per register, 16 384 registers per 64 KiB tile (the scatter would need 64 bins instead of 16), every
 //        record ONE ds_max_u32 that returns nothing -- no read, no compare, no retry;
 //   V 3: the same with 32 768 registers per tile (128 KiB of LDS: one workgroup per CU, 32 bins).
-// against V 1 = the shipped inner loop (RegsLds, cas_raise: this file INCLUDES dandd_amd/csrc/dd_sweep.hip), V 4 = V 1 without
+// against V 1 = the shipped inner loop (RegsLds, cas_raise: this file INCLUDES dandd_amd/csrc/dd_scatter.hip, and with it dd_k1.h), V 4 = V 1 without
 // the CAS (read + compare only: the floor of any byte-register form) and V 0 = the record loads alone.  Records are synthetic:
 // uniform indices inside the tile, rho geometric (half of them from 2 up: the rho = 1 bits of half the registers), ~4 records per
 // register as for 64 x 5 Mbp at log2m 20; a workgroup loads its tile's bytes, applies its records in pieces of 512 per wave (two
@@ -13,7 +13,7 @@
 //   run  : scripts/build/replay_probe [records_in_millions=2400]
 // Not part of the product; nothing here is linked into libdandd_hip.so.
 #ifndef REPLAY_PROBE_NO_MAIN   // (scripts/scatter_trace.hip includes this file for its overlap experiment: the kernels only)
-#include "../dandd_amd/csrc/dd_sweep.hip"
+#include "../dandd_amd/csrc/dd_scatter.hip"
 #endif
 
 #include <stdio.h>

@@ -1,14 +1,14 @@
 // scatter_trace.hip -- where the cycles of the first-epoch scatter go (VERDICT r05 #1a: "nobody has looked at an instruction-level
 // trace of one scatter workgroup").  There is no thread-trace decoder in this image (rocprofv3 --att needs
 // librocprof-trace-decoder, absent), so this is the other instrument the verdict names: the product's own inner loop -- this file
-// INCLUDES dandd_amd/csrc/dd_sweep.hip, so Windows<5>, wang64_fast, probe, rho_of are the shipped code -- rebuilt as a ladder of
+// INCLUDES dandd_amd/csrc/dd_scatter.hip (and with it dd_k1.h), so Windows<5>, wang64_fast, probe, rho_of are the shipped code -- rebuilt as a ladder of
 // variants that add one stage each, timed on the whole chip with the launch shape of scatter_first_bin_kernel<1, true> over
 // 64 x 5 Mbp at log2m 20 (78 848 tiles of 65 536 tokens, ~10 tiles per job, 1024 threads, two workgroups per CU), plus
 // s_memtime stamps around the stages of the full kernel (per wave: issue of hash / wait for the slot / issue of the store).
 //   build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I dandd_amd/csrc scripts/scatter_trace.hip -o scripts/build/scatter_trace
 //   run  : scripts/build/scatter_trace [tiles=78848] [tiles_per_job=10]      (needs ~23 GB of HBM for the record areas)
 // Not part of the product; nothing here is linked into libdandd_hip.so.
-#include "../dandd_amd/csrc/dd_sweep.hip"
+#include "../dandd_amd/csrc/dd_scatter.hip"
 #define REPLAY_PROBE_NO_MAIN
 #include "replay_probe.hip"   // fill_records, replay_probe<V>: the overlap experiment at the end of main
 

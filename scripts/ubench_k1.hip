@@ -19,7 +19,7 @@ __global__ __launch_bounds__(1024) void k1_model(uint32_t* out, int nk, int kfir
     uint32_t* z = reinterpret_cast<uint32_t*>(g_lds);
     for (uint32_t i = threadIdx.x; i < ((uint32_t)nk << p) / 4; i += blockDim.x) z[i] = fill;
     __syncthreads();
-    Windows<KC> win;
+    SweepWindows<KC> win;  // (the form sweep_kernel uses for the class: dd_k1.h)
     uint32_t s = seed ^ ((blockIdx.x * blockDim.x + threadIdx.x) * 2654435761u);
     uint64_t acc = 0;
     auto lds_slot = [](int j) { return RegsLds{(uint32_t)j}; };

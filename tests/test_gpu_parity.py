@@ -254,6 +254,53 @@ def test_sweep_parity_many_tiles(engine_factory, orc):
         assert abs(est - exact) / exact < 3 * 1.04 / np.sqrt(eng.m)
 
 
+def _edge_inputs():
+    """One record on one line of random ACGT, L bases.  L steps over the end of the first tile of 1024 x 64 tokens (the
+    header's BREAK token is absorbed by the range) and over a point in the middle of the second tile's second wave.
+    For one L of each range, two more inputs carry isolated Ns: at base 64 j - 1, and at base 64 j, for one j in the
+    first tile and one in the second -- a BREAK only in a lane's halo, or only in its first token, the segment
+    otherwise clean."""
+    rng = np.random.default_rng(SEED)
+    seq = rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=70_000)
+    tile, mid = 1024 * 64, 1024 * 64 + 4096 + 190
+    out = {}
+    for L in list(range(tile - 2, tile + 3)) + list(range(mid, mid + 5)):
+        out[f"L{L}"] = seq[:L]
+    for L, j2 in ((tile + 2, 1024), (mid + 2, 1024 + 65)):  # (j2 = 1089: a lane of the wave whose upper lanes are beyond the stream)
+        for d in (-1, 0):
+            s = seq[:L].copy()
+            s[64 * 517 + d] = s[64 * j2 + d] = ord("N")
+            out[f"L{L}_N{d}"] = s
+    return {name: np.concatenate([np.frombuffer(b">r\n", dtype=np.uint8), s, np.frombuffer(b"\n", dtype=np.uint8)]) for name, s in out.items()}
+
+
+EDGE_MODES = {
+    # log2m, knobs, [(kmin, kmax, canonical)]
+    "lds": (12, {}, [(9, 11, True), (15, 17, True), (32, 33, True), (48, 49, True), (15, 17, False), (48, 49, False)]),
+    "records": (17, {"DD_BUCKET_E0": "1"}, [(9, 11, True), (15, 17, True), (32, 33, True), (48, 49, True), (15, 17, False), (48, 49, False)]),
+    "exact_sets": (19, {"DD_BIGMAP_ANY_SIZE": "1"}, [(9, 11, True)]),
+}
+
+
+@pytest.mark.parametrize("mode", sorted(EDGE_MODES))
+def test_sweep_parity_at_tile_and_wave_edges(engine_factory, orc, monkeypatch, mode):
+    """Streams that end one token before, at and one token after the edge of a tile of 1024 x 64 tokens (the fetch of the next
+    tile beyond the stream; a second tile with one live lane), streams that end inside a wave of the second tile (live and
+    non-live lanes share a wave), and a BREAK that sits only in a lane's halo or only in its first token: every window class and
+    both class boundaries, registers in LDS (sweep_kernel, bitmap_kernel), on the record path with one tile per epoch
+    (scatter_first_bin_kernel takes the first tile, scatter_kernel the second) and the exact-set class (bigmap_kernel).
+    == the oracle, every register."""
+    p, knobs, cases = EDGE_MODES[mode]
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    for name, fa in _edge_inputs().items():
+        for kmin, kmax, canonical in cases:
+            try:
+                _sweep_check(engine_factory(p, canonical), orc, fa, kmin, kmax, canonical)
+            except AssertionError as e:
+                raise AssertionError(f"{name} k {kmin}..{kmax} log2m {p} canonical={canonical}: {e}") from None
+
+
 def test_union_and_card_match_oracle(engine_factory, orc):
     eng = engine_factory(14, True)
     fas = [orc.synth_fasta(SEED, g, 100000, 2) for g in range(4)]
