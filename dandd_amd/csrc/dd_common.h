@@ -63,6 +63,11 @@ DD_D void gor32(void* p, uint32_t bits) {
     (void)__hip_atomic_fetch_or((DD_GLOBAL uint32_t*)p, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// how many lanes below this one have their bit set in a wave-wide mask (a ballot): the lane's rank among them
+DD_D uint32_t lanes_below(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
 // Thomas Wang 64-bit integer mix.
 DD_HD uint64_t wang64(uint64_t key) {
     key = (~key) + (key << 21);

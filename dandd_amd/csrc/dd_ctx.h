@@ -59,7 +59,7 @@ struct TimedSpan { hipEvent_t a, b; };
 // bounce buffer for the results, the device decoders' inputs and tables, and the set's three events.
 struct PipeSet {
     DevBuf fasta, regs; HostBuf out;
-    // BGZF files inflated on the device (dd_ginflate.hip): compressed bytes, block table and error count of a batch
+    // BGZF files inflated on the device (dd_ginflate.hip; single-member files: dd_gunzip.hip): compressed bytes, block table and error count of a batch
     DevBuf gz, jobs, err; HostBuf jobs_host, err_host;
     // single-member gzip files inflated on the device: symbols, windows, the piece tables (RawFile[], starts, lens, offs,
     // chunk0, crcs) and their host copies

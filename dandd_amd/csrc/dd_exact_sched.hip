@@ -362,14 +362,6 @@ __global__ __launch_bounds__(kThreads) void sched_kernel(SortedView s, const uin
 // orderings one progressive launch takes: prefix masks + histogram within 40 KiB of LDS
 int max_orderings(int n) { return std::max(1, (40 << 10) / (12 * n)); }
 
-// once per process: every sched_kernel may take the dynamic LDS a CU has left beside the kernel's own (subsets asks for 128 KiB)
-template <class Acc>
-void allow_lds() {
-    for (const void* fn : {reinterpret_cast<const void*>(sched_kernel<true, Acc>), reinterpret_cast<const void*>(sched_kernel<false, Acc>)})
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)160 << 10) - kStaticLds)) != hipSuccess)
-            (void)hipGetLastError();   // (not sticky: a launch that needs the room reports it)
-}
-
 size_t sched_dyn_lds(int kind, int n, int norder) {
     switch (kind) {
         case kSchedPairwise: return (size_t)(kChunk / 64) * n * 8 + (size_t)n * (n + 1) + 16;
@@ -439,8 +431,6 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
     if (wide) hipLaunchKernelGGL(sched_summary_kernel<true>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
     else hipLaunchKernelGGL(sched_summary_kernel<false>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
     hipLaunchKernelGGL(sched_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, sum_f, sum_v, nchunks, carry);
-    static const bool lds_allowed = (allow_lds<AccPairwise>(), allow_lds<AccProgressive>(), allow_lds<AccLeaveOut>(), allow_lds<AccSubsets>(), true);
-    (void)lds_allowed;
     const int per = s.kind == kSchedProgressive ? max_orderings(s.n) : 1;
     for (int o0 = 0; o0 < (s.kind == kSchedProgressive ? s.norder : 1); o0 += per) {
         SchedArgs a{s.n, 0, s.ngroups, s.table, s.acc, o0 == 0, 1};
@@ -454,18 +444,17 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
         // persistent workgroups (the accumulators flush once each): as many as the CUs hold at this much LDS, 4 per CU at most
         const size_t per_cu = std::min<size_t>(4, std::max<size_t>(1, ((size_t)160 << 10) / (dyn + kStaticLds)));
         const unsigned grid = (unsigned)(std::min<size_t>(nchunks, 256 * per_cu) * a.slices);
-#define DD_SCHED(ACC)                                                                                                        \
-    do {                                                                                                                     \
-        if (wide) hipLaunchKernelGGL((sched_kernel<true, ACC>), dim3(grid), dim3(kThreads), dyn, st, v, carry, nchunks, a);  \
-        else hipLaunchKernelGGL((sched_kernel<false, ACC>), dim3(grid), dim3(kThreads), dyn, st, v, carry, nchunks, a);      \
-    } while (0)
-        switch (s.kind) {
-            case kSchedPairwise: DD_SCHED(AccPairwise); break;
-            case kSchedProgressive: DD_SCHED(AccProgressive); break;
-            case kSchedLeaveOut: DD_SCHED(AccLeaveOut); break;
-            default: DD_SCHED(AccSubsets); break;
-        }
-#undef DD_SCHED
+        // (every sched_kernel may take the dynamic LDS a CU has left beside the kernel's own: subsets asks for 128 KiB)
+        dispatch_bool(wide, [&](auto w) {
+            constexpr bool W = decltype(w)::value;
+            const dim3 g(grid), t(kThreads);
+            switch (s.kind) {
+                case kSchedPairwise: launch_full_lds<sched_kernel<W, AccPairwise>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
+                case kSchedProgressive: launch_full_lds<sched_kernel<W, AccProgressive>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
+                case kSchedLeaveOut: launch_full_lds<sched_kernel<W, AccLeaveOut>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
+                default: launch_full_lds<sched_kernel<W, AccSubsets>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
+            }
+        });
     }
     return hipGetLastError();
 }

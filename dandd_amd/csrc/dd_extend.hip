@@ -112,10 +112,9 @@ void launch_extend(const uint8_t* base_dev, const uint8_t* leaf_dev, int K, int 
     const int per_tile = kCorrTile / copies;
     const int ctiles = (nrows + per_tile - 1) / per_tile;
     const CorrShape sh = corr_shape(p, K, ctiles);
-    raise_dynamic_lds(extend_kernel, corr_lds_bytes(kCorrTile));
-    hipLaunchKernelGGL(extend_kernel, dim3((unsigned)((size_t)ctiles * K * sh.tiles)), dim3(sh.threads),
-                       corr_lds_bytes((nrows < per_tile ? nrows : per_tile) * copies), st, base_dev, leaf_dev, K, p,
-                       rows_dev, nrows, sh.tiles, copies, hist_dev);
+    launch_full_lds<extend_kernel>(dim3((unsigned)((size_t)ctiles * K * sh.tiles)), dim3(sh.threads),
+                                   corr_lds_bytes((nrows < per_tile ? nrows : per_tile) * copies), st, base_dev, leaf_dev, K, p,
+                                   rows_dev, nrows, sh.tiles, copies, hist_dev);
     launch_corr_finish(hist_dev, nrows, K, st);
 }
 

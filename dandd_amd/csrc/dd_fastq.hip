@@ -1,4 +1,4 @@
-// dd_fastq.hip -- FASTQ among the texts the device has inflated (dd_ginflate.hip), resolved where they are: in HBM.
+// dd_fastq.hip -- FASTQ among the texts the device has inflated (dd_ginflate.hip, dd_gunzip.hip), resolved where they are: in HBM.
 //
 // `dashing sketch` reads its inputs through klib's kseq.h, FASTA and FASTQ alike (/root/reference/lib/sketch_classes.py:358-365
 // hands it whatever the species directory holds; oracle/POLICIES.md P10).  K0 knows kseq's FASTA rules; a FASTQ record's

@@ -1,5 +1,5 @@
 // dd_ingest.hip -- the file-ingestion pipeline of the C ABI (dd_sketch_fasta, dd_sketch_files, dd_inflate_files,
-// dd_last_ingest_stats).  Host code only; the device decoders are dd_ginflate.hip and dd_fastq.hip.
+// dd_last_ingest_stats).  Host code only; the device decoders are dd_ginflate.hip, dd_gunzip.hip and dd_fastq.hip.
 // Many FASTA files (plain or .gz, as DandD's species directories hold them); regs is [nfiles][K][m] on the host.
 // A pipeline:
 //   loader threads   read + inflate into pinned host buffers of the context's pool, ahead of the GPU,
@@ -132,7 +132,7 @@ bool bgzf_for_device(const char* path, FileBuf& fb, std::vector<BgzfBlock>& blks
     fb.len = n;
     return true;
 }
-// One single-member gzip file for the device path (dd_ginflate.hip: launch_gunzip_members): the raw bytes into `fb`, where
+// One single-member gzip file for the device path (dd_gunzip.hip: launch_gunzip_members): the raw bytes into `fb`, where
 // the deflate data starts, the trailer's CRC-32 and ISIZE.  false: not a file that path takes (small, huge, not gzip,
 // FASTQ): the host decoder reads it.  (Whether the file is ONE member only the decoding shows: the device refuses a
 // stream whose final block is not followed by exactly the 8 trailer bytes.)
@@ -629,7 +629,7 @@ struct Ingest {
         }
         return e;
     }
-    // block starts -> piece lengths -> offsets -> symbols -> windows -> text -> CRC-32 of every 64 KiB (dd_ginflate.hip)
+    // block starts -> piece lengths -> offsets -> symbols -> windows -> text -> CRC-32 of every 64 KiB (dd_gunzip.hip)
     hipError_t issue_gunzip(PipeSet& ps, const BatchLayout& L, hipStream_t cs) const {
         const size_t nmem = L.members.size();
         if (!nmem) return hipSuccess;

@@ -356,7 +356,7 @@ inline uint32_t crc_x8n(uint32_t nbytes) {   // x^(8 nbytes) mod P
     return p;
 }
 
-// The gzip members of a file for the device decoder (dd_ginflate.hip): where each one's deflate data starts, where it ends,
+// The gzip members of a file for the device decoder (dd_gunzip.hip): where each one's deflate data starts, where it ends,
 // its trailer's CRC-32 and ISIZE.  `gzip` and the sequence archives write ONE member; `cat a.fa.gz b.fa.gz` (and pigz -i,
 // and a gzip run that appended) several: a member says nothing about its length, so the next one is looked for by its header
 // -- 1f 8b 08, a flag byte without reserved bits, an XFL and an OS byte of the values RFC 1952 knows, optional fields that

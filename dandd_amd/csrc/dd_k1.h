@@ -7,7 +7,6 @@
 #include "dd_kernels.h"
 
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 
 namespace dd {
@@ -530,12 +529,6 @@ DD_D void finish_tile(uint8_t* out, int tile_log2, uint32_t b, int p, const ForE
 }
 
 // ---- host: pick the instantiation, launch it -----------------------------------------------------------------------------
-// f(std::bool_constant<b>)
-template <typename F>
-void dispatch_bool(bool b, const F& f) {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
 // f(std::integral_constant<int, KC>, std::bool_constant<CANON>) for the k class and strand mode of a launch
 template <typename F>
 void dispatch_kc_canon(int kclass, bool canonical, const F& f) {
@@ -545,22 +538,6 @@ void dispatch_kc_canon(int kclass, bool canonical, const F& f) {
         else if (kclass == 3) f(std::integral_constant<int, 3>{}, cn);
         else f(std::integral_constant<int, 2>{}, cn);
     });
-}
-// Launch of a kernel whose dynamic LDS may exceed 64 KiB: that must be allowed per kernel AND per device (a process may hold
-// contexts on several GPUs), once, not on every launch; remembered in one bit per device id.  STATIC_LDS: the kernel's own
-// __shared__ bytes -- dynamic + static must stay within the CU's 160 KiB or the call is refused.
-template <auto Kern, int STATIC_LDS = 0, typename... Args>
-void launch_full_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, Args... args) {
-    static std::atomic<unsigned long long> allowed{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(allowed.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - STATIC_LDS) != hipSuccess)
-            (void)hipGetLastError();  // not sticky: a launch that needs the room will report it
-        allowed.fetch_or(bit, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL(Kern, grid, block, lds_bytes, st, args...);
 }
 
 }  // namespace dd

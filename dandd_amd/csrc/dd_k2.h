@@ -127,12 +127,4 @@ inline CorrShape corr_shape(int p, int K, int row_tiles) {
     return {threads, (int)tiles};
 }
 
-// host: a kernel may take more than the default 64 KiB of dynamic LDS once it is told so; called in front of every such
-// launch (a failure shows as the launch's own error)
-template <typename Kernel>
-inline void raise_dynamic_lds(Kernel kernel, size_t bytes) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-        (void)hipGetLastError();
-}
-
 }  // namespace dd

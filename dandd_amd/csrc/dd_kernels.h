@@ -1,11 +1,37 @@
 // dd_kernels.h -- host-callable launchers of the gfx950 kernels behind the C ABI.
 #pragma once
+#include <atomic>
+#include <type_traits>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 namespace dd {
+
+// ---- host: pick an instantiation, launch it ------------------------------------------------------------------------------
+// f(std::bool_constant<b>)
+template <typename F>
+void dispatch_bool(bool b, const F& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// Launch of a kernel whose dynamic LDS may exceed 64 KiB: that must be allowed per kernel AND per device (a process may hold
+// contexts on several GPUs), once, not on every launch; remembered in one bit per device id.  STATIC_LDS: the kernel's own
+// __shared__ bytes -- dynamic + static must stay within the CU's 160 KiB or the call is refused.
+template <auto Kern, int STATIC_LDS = 0, typename... Args>
+void launch_full_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, Args... args) {
+    static std::atomic<unsigned long long> allowed{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(allowed.load(std::memory_order_relaxed) & bit)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - STATIC_LDS) != hipSuccess)
+            (void)hipGetLastError();  // not sticky: a launch that needs the room will report it
+        allowed.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds_bytes, st, args...);
+}
 
 // ---------------------------------------------------------------------------------------
 // Token stream of one genome in HBM (output of K0, input of K1).
@@ -274,7 +300,8 @@ hipError_t launch_exact_sort_tagged(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt
 hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, const ExactSched& s, void* scratch, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
-// BGZF blocks inflated on the device (dd_ginflate.hip): one wave per block, text straight into the FASTA buffer
+// gzip inflated on the device: BGZF blocks (dd_ginflate.hip: one wave per block, text straight into the FASTA buffer) and
+// single-member files in pieces (dd_gunzip.hip around the same decoder)
 // ---------------------------------------------------------------------------------------
 struct InflateJob {
     const uint8_t* in;          // the block: a whole gzip member (header, deflate data, CRC-32, ISIZE)
@@ -282,7 +309,7 @@ struct InflateJob {
     uint32_t out_len;           // its ISIZE (<= 65536)
     uint8_t* out;               // where its text goes
 };
-// one single-member gzip file of a batch, inflated on the device in pieces (dd_ginflate.hip: launch_gunzip_members)
+// one single-member gzip file of a batch, inflated on the device in pieces (dd_gunzip.hip: launch_gunzip_members)
 struct RawFile {
     const uint8_t* in;          // the whole file on the device, 256-byte aligned
     uint32_t in_len;            // ... up to the end of THIS member (a file of several members: one RawFile each, same `in`)
@@ -295,7 +322,7 @@ struct RawFile {
                                 //   a piece that starts in range j and runs over r ranges owns r x range_syms of them
     uint32_t range_syms;
     uint16_t* arena;            // [isize]: the symbols of pieces too long for their ranges (counted first, then written here)
-    uint8_t* windows;           // what stands in the 32 KiB in front of every piece, in two levels (dd_ginflate.hip: piece_maps_kernel):
+    uint8_t* windows;           // what stands in the 32 KiB in front of every piece, in two levels (dd_gunzip.hip: piece_maps_kernel):
                                 //   u16 [nguess][32768] maps relative to the piece's group start, u16 [ngroups][32768] the groups' own maps,
                                 //   u8 [ngroups][32768] the windows at the groups' starts
     uint32_t group0, ngroups;   // groups of kPieceGroup ranges; group0 = this file's first group in the batch
@@ -329,6 +356,10 @@ void launch_gunzip_members(const RawFile* files_dev, int nfiles, int npieces, in
                            const uint32_t* chunk0_dev, uint32_t* crcs_dev, uint32_t* errors_dev, hipStream_t st);
 // *errors_dev += blocks that did not decode (the caller falls back to the host decoder)
 void launch_inflate_bgzf(const InflateJob* jobs_dev, int njobs, uint32_t* errors_dev, hipStream_t st);
+// the decoder over the pieces of single-member files, for launch_gunzip_members (dd_gunzip.hip).  mode 3: symbols into the pieces' own
+// ranges, lens / over written; 1: only count the text of the pieces marked in `over`; 2: write those into the arena at abase_dev
+void launch_inflate_pieces(int mode, const RawFile* files_dev, int nfiles, int npieces, const uint64_t* starts_dev, uint32_t* lens_dev, uint32_t* over_dev,
+                           const uint32_t* abase_dev, uint32_t* errors_dev, hipStream_t st);
 
 // synthetic FASTA
 void launch_synth(uint64_t seed, int gi, uint64_t nbases, int nrec, uint8_t* out_dev, hipStream_t st);

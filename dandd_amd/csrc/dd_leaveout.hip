@@ -130,11 +130,10 @@ void launch_leaveout(const uint8_t* leaf_dev, int K, int p, const int32_t* tab_d
     if (K <= 0 || G <= 0 || nslots <= 0) return;
     const int gtiles = (G + kCorrTile - 1) / kCorrTile;
     const CorrShape sh = corr_shape(p, K, gtiles);
-    raise_dynamic_lds(leaveout_kernel, corr_lds_bytes(kCorrTile));
     (void)hipMemsetAsync(hist_dev, 0, (size_t)(G + 1) * K * 64 * sizeof(uint32_t), st);
-    hipLaunchKernelGGL(leaveout_kernel, dim3((unsigned)((size_t)gtiles * K * sh.tiles)), dim3(sh.threads),
-                       corr_lds_bytes(G < kCorrTile ? G : kCorrTile), st, leaf_dev, K, p,
-                       tab_dev, nslots, G, sh.tiles, hist_dev);
+    launch_full_lds<leaveout_kernel>(dim3((unsigned)((size_t)gtiles * K * sh.tiles)), dim3(sh.threads),
+                                     corr_lds_bytes(G < kCorrTile ? G : kCorrTile), st, leaf_dev, K, p,
+                                     tab_dev, nslots, G, sh.tiles, hist_dev);
     launch_corr_finish(hist_dev, G, K, st);
 }
 

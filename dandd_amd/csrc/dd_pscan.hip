@@ -268,10 +268,10 @@ bool launch_progressive_pscan(const uint8_t* leaf_dev, int n, int K, int p, cons
         const int no = std::min(group, norder - o0);
         // (D = 4, 8, 16 or 32 plane words per row: one or two 16-byte groups per chunk of the scan; four groups -- 16
         // running ANDs beside the 32 counts -- spill)
-        const auto kernel = D >= 8 ? pscan_kernel<2> : pscan_kernel<1>;
-        raise_dynamic_lds(kernel, lds_bytes);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(K * RR)), dim3(PS_THREADS), lds_bytes, st, leaf_dev, n, K, p, ord_dev + (size_t)o0 * n, no,
-                           rng, RR, tiles, D, pitch, part);
+        dispatch_bool(D >= 8, [&](auto two) {
+            launch_full_lds<pscan_kernel<decltype(two)::value ? 2 : 1>>(dim3((unsigned)(K * RR)), dim3(PS_THREADS), lds_bytes, st, leaf_dev, n, K, p,
+                                                                        ord_dev + (size_t)o0 * n, no, rng, RR, tiles, D, pitch, part);
+        });
         const size_t jobs = (size_t)no * n * K;
         hipLaunchKernelGGL(pscan_finish_kernel, dim3((unsigned)((jobs + 3) / 4)), dim3(256), 0, st, part, n, K, p, no, rng, RR, pitch,
                            hist_dev + (size_t)o0 * n * K * 64);

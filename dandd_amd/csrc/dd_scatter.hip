@@ -94,7 +94,7 @@ DD_D void scatter_probe(const Scatter& s, uint32_t cand, uint32_t& waiting2, uin
     const unsigned long long mask = __builtin_amdgcn_ballot_w64(live);
     if (mask) {
         if (live) {
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+            const uint32_t rank = lanes_below(mask);
             lds32(s.queue + kQueueEntries * 4u + 4u * (waiting2 + rank)) = idx | ((rm1 + 1u) << 24);
         }
         waiting2 += (uint32_t)__builtin_popcountll(mask);
@@ -119,7 +119,7 @@ DD_D void scatter_update(const Scatter& s, uint32_t& waiting, uint32_t& waiting2
     const unsigned long long mask = __builtin_amdgcn_ballot_w64(cand);
     if (mask) {
         if (cand) {
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+            const uint32_t rank = lanes_below(mask);
             lds32(s.queue + 4u * (waiting + rank)) = (q.hi & s.himask) | (rho_of(q, p) - 1u);  // (scatter_probe's form)
         }
         waiting += (uint32_t)__builtin_popcountll(mask);

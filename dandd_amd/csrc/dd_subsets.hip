@@ -222,12 +222,8 @@ void launch_subsets(const uint8_t* leaf_dev, int n, int K, int p, int k0, int Kc
     const unsigned nwg = (unsigned)(pl.wg.size() / 3);
     if (nwg) {
         const dim3 grid(nwg, (unsigned)pl.RR);
-#define DD_SUBSETS_LAUNCH(HC)                                                                                                   \
-    do {                                                                                                                        \
-        raise_dynamic_lds(subsets_kernel<HC>, pl.lds_bytes);                                                                    \
-        hipLaunchKernelGGL((subsets_kernel<HC>), grid, dim3(SS_THREADS), pl.lds_bytes, st, leaf_dev, n, K, p, rng_dev, wg_dev,  \
-                           pl.nchunks, pl.D, pl.tiles, part_dev);                                                               \
-    } while (0)
+#define DD_SUBSETS_LAUNCH(HC) \
+    launch_full_lds<subsets_kernel<HC>>(grid, dim3(SS_THREADS), pl.lds_bytes, st, leaf_dev, n, K, p, rng_dev, wg_dev, pl.nchunks, pl.D, pl.tiles, part_dev)
         switch (pl.HC) {
             case 1: DD_SUBSETS_LAUNCH(1); break;
             case 2: DD_SUBSETS_LAUNCH(2); break;

@@ -490,12 +490,119 @@ def _bgzf(raw, level=1, strategy=0, block=65280):
     return bytes(out)
 
 
+def _long_code_parts():
+    """60 parts of 12 172 bytes: a header line of 20 bytes drawn from all of printable ASCII, then 12 000 random bases in 80-column
+    lines.  A deflate block that holds one part gives its header's rare bytes literal codes longer than the decoders' 10-bit tables,
+    and they stand among the block's first symbols, where the block-start finder's trial decoding looks too."""
+    import random
+    rnd = random.Random(7)
+    parts = []
+    for _ in range(60):
+        head = b">" + bytes(rnd.choice(bytes(range(33, 127))) for _ in range(20)) + b"\n"
+        bases = bytes(rnd.choice(b"ACGT") for _ in range(12000))
+        parts.append(head + b"".join(bases[i:i + 80] + b"\n" for i in range(0, 12000, 80)))
+    assert all(len(q) == 12172 for q in parts)
+    return parts
+
+
+def _long_codes(deflate):
+    """Raw deflate data -> for every dynamic-Huffman block (longest literal/length code among its first 24 symbols, longest distance
+    code it uses): which blocks take the decoders through their path for codes longer than the 10-bit tables."""
+    buf = cnt = at = 0
+
+    def fill(k):
+        nonlocal buf, cnt, at
+        while cnt < k:
+            buf |= (deflate[at] if at < len(deflate) else 0) << cnt
+            at += 1
+            cnt += 8
+
+    def take(k):
+        nonlocal buf, cnt
+        fill(k)
+        v = buf & ((1 << k) - 1)
+        buf >>= k
+        cnt -= k
+        return v
+
+    def table(lens):      # canonical code of these lengths: 15 bits of input -> (symbol, code length)
+        tab, code, prev = [None] * 32768, 0, 0
+        for n, sym in sorted((ln, sym) for sym, ln in enumerate(lens) if ln):
+            code <<= n - prev
+            tab[int(format(code, "0%db" % n)[::-1], 2)::1 << n] = [(sym, n)] * (32768 >> n)
+            code, prev = code + 1, n
+        return tab
+
+    def symbol(tab):
+        nonlocal buf, cnt
+        fill(15)
+        sym, n = tab[buf & 32767]
+        buf >>= n
+        cnt -= n
+        return sym, n
+
+    order = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+    len_extra = [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]
+    dist_extra = [max(0, d // 2 - 1) for d in range(30)]
+    out = []
+    while True:
+        final, btype = take(1), take(2)
+        assert btype != 3
+        if btype == 0:
+            take(cnt & 7)
+            n = take(16)
+            assert take(16) == n ^ 0xFFFF
+            for _ in range(n):
+                take(8)
+        else:
+            if btype == 1:
+                ll, dd = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8, [5] * 30
+            else:
+                hlit, hdist, hclen = take(5) + 257, take(5) + 1, take(4) + 4
+                cl = [0] * 19
+                for i in range(hclen):
+                    cl[order[i]] = take(3)
+                ct, lens = table(cl), []
+                while len(lens) < hlit + hdist:
+                    sym, _ = symbol(ct)
+                    lens += [sym] if sym < 16 else [lens[-1]] * (3 + take(2)) if sym == 16 else [0] * (3 + take(3)) if sym == 17 else [0] * (11 + take(7))
+                assert len(lens) == hlit + hdist
+                ll, dd = lens[:hlit], lens[hlit:]
+            lt, dt = table(ll), table(dd)
+            seen = long_ll = long_d = 0
+            while True:
+                sym, n = symbol(lt)
+                if seen < 24:
+                    long_ll = max(long_ll, n)
+                seen += 1
+                if sym == 256:
+                    break
+                if sym > 256:
+                    take(len_extra[sym - 257])
+                    d, n = symbol(dt)
+                    long_d = max(long_d, n)
+                    take(dist_extra[d])
+            if btype == 2:
+                out.append((long_ll, long_d))
+        if final:
+            return out
+
+
+def _assert_long_codes(blocks, level):
+    """the condition under which the long_l* cases test what they are for (another zlib may compress otherwise: then this fails,
+    visibly, instead of the cases passing without having met a long code)"""
+    assert sum(1 for ll, _ in blocks if ll > 10) >= 40, (level, len(blocks))
+    if level > 1:      # (level 1 uses no long distance code, and none is claimed there)
+        assert sum(1 for _, d in blocks if d > 10) >= 5, (level, len(blocks))
+
+
 def test_bgzf_files_are_inflated_on_the_device(engine_factory, orc, tmp_path, monkeypatch):
     """dd_sketch_files over BGZF files: the compressed bytes cross PCIe and dd_ginflate.hip inflates the blocks into the FASTA
     buffer K0 reads.  Every kind of deflate block -- dynamic codes at levels 1 / 6 / 9, fixed codes (Z_FIXED), stored
     blocks (level 0), Huffman-only (no matches: an empty distance tree), run-length (distance 1 only), blocks of 1 byte and
-    of the full 64 KiB, repeat-rich text with long far matches -- gives the registers of the uncompressed bytes; a damaged
-    block makes the call fall back to the host decoder, which reports it."""
+    of the full 64 KiB, repeat-rich text with long far matches, blocks whose first symbols and whose distances have codes longer
+    than the decoder's 10-bit tables (long_l*: decode_slow, behind litlen_code of dd_deflate.h and behind the distance look-ups) -- gives the registers
+    of the uncompressed bytes; a damaged block makes the call fall back to the host decoder, which reports it."""
     import zlib
     eng = engine_factory(14, True)
     uniform, real = orc.synth_fasta(SEED, 0, 3_000_000, 4).tobytes(), orc.synth_realistic(SEED, 1, 2_000_000).tobytes()
@@ -508,6 +615,18 @@ def test_bgzf_files_are_inflated_on_the_device(engine_factory, orc, tmp_path, mo
         path = tmp_path / f"{name}.fa.gz"
         path.write_bytes(_bgzf(raw, **kw))
         cases.append((name, str(path), np.frombuffer(raw, dtype=np.uint8)))
+    longtext = b"".join(_long_code_parts())
+    for level in (1, 6, 9):                                        # one BGZF block per part
+        data = _bgzf(longtext, level=level, block=12172)
+        blocks, off = [], 0
+        while off < len(data):
+            size = int.from_bytes(data[off + 16:off + 18], "little") + 1
+            blocks += _long_codes(data[off + 18:off + size - 8])
+            off += size
+        _assert_long_codes(blocks, level)
+        path = tmp_path / f"long_l{level}.fa.gz"
+        path.write_bytes(data)
+        cases.append((f"long_l{level}", str(path), np.frombuffer(longtext, dtype=np.uint8)))
     monkeypatch.setenv("DD_INFLATE_STRICT", "1")                 # a block the device refuses fails the call: no silent host fallback here
     got = eng.sketch_files([p for _, p, _ in cases], 19, 21)
     # ... and the inflated BYTES (dd_inflate_files: the text as K0 is about to read it, copied back from the device) are zlib's:
@@ -547,7 +666,7 @@ def test_damaged_bgzf_blocks_are_refused_or_read_like_zlib(orc, torch_cuda, tmp_
     """Bit flips and overwritten bytes in the deflate data, in the CRC-32 and in the ISIZE of single BGZF blocks (the
     container's size fields intact, so the file still goes to the device decoder): the call either raises -- exactly when
     zlib refuses the file -- or gives the registers of the text zlib reads.  The device checks the deflate structure, the
-    member's length AND its CRC-32 (dd_ginflate.hip: text_crc); what it refuses is run again on the host."""
+    member's length AND its CRC-32 (dd_deflate.h: text_crc); what it refuses is run again on the host."""
     import gzip
     import zlib
     from dandd_amd.engine import Engine, EngineError
@@ -600,11 +719,13 @@ def test_damaged_bgzf_blocks_are_refused_or_read_like_zlib(orc, torch_cuda, tmp_
 
 def test_single_member_gzip_files_are_inflated_on_the_device(engine_factory, orc, tmp_path, monkeypatch):
     """What `gzip` writes -- ONE member, deflate blocks of any size with 32 KiB of history across them -- through
-    dd_sketch_files on the device (dd_ginflate.hip: launch_gunzip_members): block starts found by trial, every piece decoded
+    dd_sketch_files on the device (dd_gunzip.hip: launch_gunzip_members): block starts found by trial, every piece decoded
     without its history into 16-bit symbols, placeholders resolved along the chain of windows, CRC-32 checked.  Levels 1 / 6 / 9
     on uniform and repeat-rich text, a header with FNAME, files whose blocks are all stored or all fixed-Huffman (no dynamic
     block start to find: one piece), Huffman-only and RLE strategies, files of two and three members, small and large finder
-    ranges: registers == the sketch of the plain bytes and the inflated bytes == zlib's, with DD_INFLATE_STRICT=1 (a refused
+    ranges, dynamic blocks whose first symbols and whose distances have codes longer than the 10-bit tables (long_l*: a full flush
+    behind every part of _long_code_parts, so that the finder's trial decoding and the decoder both meet them): registers == the
+    sketch of the plain bytes and the inflated bytes == zlib's, with DD_INFLATE_STRICT=1 (a refused
     piece fails the test; nothing goes to the host decoder).  A file of many small members is not for this path (the host reads it)."""
     import gzip
     import io
@@ -635,6 +756,12 @@ def test_single_member_gzip_files_are_inflated_on_the_device(engine_factory, orc
              # behind the other) -- two of different levels, three with a named header in the middle and a stored-only one at the end
              ("two_members", uniform[:1_500_000], member(uniform[:800_000], 6) + member(uniform[800_000:1_500_000], 1)),
              ("three_members", real[:2_400_000], member(real[:900_000], 9) + member(real[900_000:1_700_000], 6, name="part2.fa") + member(real[1_700_000:2_400_000], 0))]
+    parts = _long_code_parts()
+    for level in (1, 6, 9):                                        # a dynamic block starts at every part's header line
+        co = zlib.compressobj(level, zlib.DEFLATED, 31, 8, 0)
+        data = b"".join(co.compress(q) + co.flush(zlib.Z_FULL_FLUSH) for q in parts) + co.flush()
+        _assert_long_codes(_long_codes(data[10:-8]), level)
+        cases.append((f"long_l{level}", b"".join(parts), data))
     paths = []
     for name, raw, data in cases:
         (tmp_path / f"{name}.fa.gz").write_bytes(data)
