@@ -1,6 +1,7 @@
 // dd_ctx.h -- the context behind the C ABI's opaque dd_ctx, and the host-side helpers the ABI's sources share
-// (dd_api.hip: context, sketch, timing, synth, comm; dd_k2_api.hip: union, card and the HLL schedules; dd_exact_api.hip:
-// exact count and schedules; dd_ingest.hip: the file-ingestion pipeline).  Callers see dandd_hip.h only.
+// (dd_api.hip: context, timing and stats, synth, dd_plan_sweep; dd_sketch_api.hip: sketch; dd_k2_api.hip: union, card and the
+// HLL schedules; dd_exact_api.hip: exact count and schedules; dd_ingest.hip: the file-ingestion pipeline; dd_comm.hip: RCCL).
+// Callers see dandd_hip.h only.
 #pragma once
 #include "../../include/dandd_hip.h"
 #include <sched.h>
@@ -100,6 +101,13 @@ struct IngestState {
     }
 };
 
+// Pinned staging for the tables of one sketch call -- genome/pack tables, K1 job tables (their size is only known once K0
+// is launched, and growing a buffer frees it) and the bucket rows -- and the event signalled when the last upload from
+// them completed.  A context has two and dd_sketch_device alternates, so that a call can be issued while the uploads of the
+// call before it are still queued behind work of other streams (the ingestion pipeline issues batch b + 1 while batch b
+// waits for its files to be copied or inflated).
+struct StageSet { HostBuf tables, jobs, rows; hipEvent_t free = nullptr; };
+
 struct dd_ctx {
     int device = 0, p = 14, canonical = 1;
     hipStream_t stream = nullptr;
@@ -108,7 +116,8 @@ struct dd_ctx {
     std::vector<hipEvent_t> pool;
     // workspaces
     DevBuf tokens, scratch, tables, fasta, regs, ptrs, hist, est, ord, bitmaps, bigmaps, exact, buckets, gram, synth;
-    HostBuf stage, stage_jobs, stage_rows;  // genome/pack tables and K1 job tables are uploaded in two steps
+    StageSet stage[2];
+    int stage_cur = 0;  // the set of the running (or last) sketch call
     // the job tables of the last few sketch calls: a call over genomes of the same sizes and the same k range (a
     // pipeline sketching batches of a few recurring shapes, a benchmark loop) reuses them, on the host and in HBM
     struct PlanEntry {
@@ -123,12 +132,6 @@ struct dd_ctx {
     };
     PlanEntry plans[8];
     unsigned long long plan_clock = 0;
-    hipEvent_t stage_free = nullptr;  // signalled when the last upload from `stage` completed
-    // a second set of staging buffers: dd_sketch_device alternates, so that a call can be issued while the uploads of
-    // the call before it are still queued behind work of other streams (the ingestion pipeline issues batch b + 1
-    // while batch b waits for its files to be copied or inflated)
-    HostBuf stage_alt, stage_jobs_alt, stage_rows_alt;
-    hipEvent_t stage_free_alt = nullptr;
     IngestState ingest;  // dd_sketch_files
     hipStream_t side[8] = {};  // k classes of a small call run side by side
     hipEvent_t side_done[8] = {}, side_go = nullptr;
@@ -210,16 +213,17 @@ inline int upload(dd_ctx* c, HostBuf& stage, void* dst_dev, const void* src, siz
     return DD_OK;
 }
 
-// A host table into `dst` (grown to hold it) through c->stage.  The staging buffer may not be rewritten while the upload
-// before this one is in flight: stage_free is waited for first and recorded behind the copy.  (dd_sketch_device alternates
-// two staging sets around its launches and keeps its own sequence.)
+// A host table into `dst` (grown to hold it) through the current staging set.  The staging buffer may not be rewritten while
+// the upload before this one is in flight: `free` is waited for first and recorded behind the copy.  (dd_sketch_device
+// alternates the two sets around its launches and keeps its own sequence.)
 inline int stage_table(dd_ctx* c, DevBuf& dst, const void* src, size_t bytes) {
+    StageSet& s = c->stage[c->stage_cur];
     int rc;
     if ((rc = dst.reserve(bytes))) return rc;
-    DD_HIP(hipEventSynchronize(c->stage_free));
-    if ((rc = c->stage.reserve(bytes))) return rc;
-    if ((rc = upload(c, c->stage, dst.p, src, bytes, 0))) return rc;
-    DD_HIP(hipEventRecord(c->stage_free, c->stream));
+    DD_HIP(hipEventSynchronize(s.free));
+    if ((rc = s.tables.reserve(bytes))) return rc;
+    if ((rc = upload(c, s.tables, dst.p, src, bytes, 0))) return rc;
+    DD_HIP(hipEventRecord(s.free, c->stream));
     return DD_OK;
 }
 

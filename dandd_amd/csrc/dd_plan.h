@@ -1,6 +1,6 @@
-// dd_plan.h -- the K1 job tables: which workgroup sketches which (genome, k-group, tile range).
-// Pure host code, no HIP calls: dd_sketch_device (dd_api.hip) uploads the tables, tests inspect them
-// through dd_plan_sweep (include/dandd_hip.h) without a GPU.
+// dd_plan.h -- the K1 job tables: which workgroup sketches which (genome, k-group, tile range), and where the record
+// path's rows lie in HBM.  Pure host code, no HIP calls: dd_sketch_device (dd_sketch_api.hip) uploads the tables, tests
+// inspect them through dd_plan_sweep (include/dandd_hip.h) and tests/native/sanitize_host.cpp without a GPU.
 #pragma once
 #include <stddef.h>
 
@@ -44,5 +44,26 @@ struct PlanKnobs {
 bool plan_bigmap_range(int log2m, int kmin, int kmax, const PlanKnobs& knobs, const size_t* nbytes, int ngenomes, int* ka, int* kb);
 std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbytes, int ngenomes, int kmin,
                                    int kmax, const PlanKnobs& knobs);
+
+// Where the record path (log2m >= 17) keeps what in its ONE allocation, as byte offsets from its start.  The regions lie
+// in this order: the BucketRow table; one cursor per (genome, k) row, each in a 256-byte slot of its own (every block of a
+// row is reserved by an atomic add on it, and neighbouring rows are written from other XCDs); then, for the bucketed rows
+// only -- those whose k belongs to a class of plan.mode == kBucketMode --, the 4-bit filters of (m >> logg) / 2 bytes
+// (16-aligned), the rho = 1 bits of the first epoch (m / 8 bytes: one bit per register instead of a record each,
+// dd_scatter.hip, scatter_first_bin_kernel), fill (cap_chunks * 4 bytes) + seg (cap_chunks * 32 bytes, at seg_off) each
+// 256-aligned, and the record areas of cap_chunks * 4096 bytes (1024 records per chunk).  Bucketed row (g, kk) is number
+// g * per_genome + slot[kk] of its regions.  [zero_begin, zero_begin + zero_bytes) = cursors, filters and bits must start
+// a call at zero: nothing handed out, every register's lower bound 0.  A wrong offset here does not crash: one row's
+// records land in another row's stream and the registers come out slightly low (tests/native/sanitize_host.cpp).
+struct BucketLayout {
+    int K = 0, per_genome = 0;  // rows of a genome; how many of them are bucketed
+    std::vector<int> slot;      // [K]: -1 = the row is not bucketed
+    size_t table = 0, cursors = 0, filters = 0, ones = 0, fills = 0, areas = 0;                                 // region starts
+    size_t cursor_stride = 256, filter_bytes = 0, ones_bytes = 0, fill_bytes = 0, seg_off = 0, area_bytes = 0;  // per row
+    size_t zero_begin = 0, zero_bytes = 0, total = 0;  // (total 0: the call has no bucket class)
+};
+BucketLayout bucket_layout(const std::vector<SweepClass>& classes, int log2m, int ngenomes, int kmin, int kmax);
+// the call's row table over an allocation at `base`, row (g, kk)'s registers at regs + (g * K + kk) * m
+void bucket_rows(const BucketLayout& lay, char* base, uint8_t* regs, int log2m, int ngenomes, BucketRow* rows);
 
 }  // namespace dd

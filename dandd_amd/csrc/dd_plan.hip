@@ -27,6 +27,7 @@ constexpr int kThreads = 1024;
 constexpr size_t kTileTokens = (size_t)kThreads * kSegTokens;
 
 size_t tiles_of(size_t nbytes) { return (nbytes + kTileTokens - 1) / kTileTokens; }  // tokens <= bytes
+size_t align_to(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 SweepJob make_job(int genome, int kfirst, int nk, int kmin, size_t t0, size_t t1) {
     SweepJob j;
@@ -77,6 +78,11 @@ std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbyte
     int big_ka = 0, big_kb = 0;
     const bool use_big = plan_bigmap_range(p, kmin, kmax, knobs, nbytes, ngenomes, &big_ka, &big_kb);
 
+    const int lo0 = use_big ? big_kb + 1 : (use_bitmaps ? kBitmapMaxK + 1 : 1);
+    const struct { int kc, ka, kb; } class_tab[6] = {
+        {kBitmapClass, 1, use_bitmaps ? kBitmapMaxK : 0}, {kBigmapClass, big_ka, use_big ? big_kb : 0},
+        {0, lo0, 16}, {1, 17, 32}, {3, 33, 48}, {2, 49, 64}};
+
     size_t total_tiles = 0, max_tiles = 0;
     for (int g = 0; g < ngenomes; ++g) {
         total_tiles += tiles_of(nbytes[g]);
@@ -94,9 +100,10 @@ std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbyte
     std::vector<size_t> epoch_edge;           // epoch e covers tiles [epoch_edge[e], epoch_edge[e+1])
     size_t epoch_longest = 0, bucket_row_tokens = 0;
     if (bucket_mode) {
-        int first_hashed = use_bitmaps ? std::max(kmin, kBitmapMaxK + 1) : kmin;
-        if (use_big) first_hashed = std::max(first_hashed, big_kb + 1);
-        const size_t nrows = (size_t)ngenomes * (size_t)std::max(0, kmax - first_hashed + 1);
+        int bucketed_ks = 0;  // the ks of the classes that will be bucket classes (bucket_layout goes by the same classes)
+        for (const auto& ct : class_tab)
+            if (ct.kc >= 0) bucketed_ks += std::max(0, std::min(kmax, ct.kb) - std::max(kmin, ct.ka) + 1);
+        const size_t nrows = (size_t)ngenomes * (size_t)bucketed_ks;
         // (the first epoch runs unfiltered and cheaply -- every register is zero, every update a record --, so it is
         // made four tokens per register long, 8 tiles at least: measured best at log2m 18, 19 and 20 with the
         // dense record stream; two per register before that)
@@ -120,10 +127,6 @@ std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbyte
         }
     }
 
-    const int lo0 = use_big ? big_kb + 1 : (use_bitmaps ? kBitmapMaxK + 1 : 1);
-    const struct { int kc, ka, kb; } class_tab[6] = {
-        {kBitmapClass, 1, use_bitmaps ? kBitmapMaxK : 0}, {kBigmapClass, big_ka, use_big ? big_kb : 0},
-        {0, lo0, 16}, {1, 17, 32}, {3, 33, 48}, {2, 49, 64}};
     for (const auto& ct : class_tab) {
         const int kc = ct.kc;
         const int ka = std::max(kmin, ct.ka), kb = std::min(kmax, ct.kb);
@@ -286,6 +289,48 @@ std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbyte
     for (SweepClass& sc : classes)
         if (sc.plan.mode == kBucketMode) sc.plan.cap_chunks = cap;
     return classes;
+}
+
+BucketLayout bucket_layout(const std::vector<SweepClass>& classes, int log2m, int ngenomes, int kmin, int kmax) {
+    BucketLayout lay;
+    const SweepPlan* bplan = nullptr;
+    lay.K = kmax - kmin + 1;
+    lay.slot.assign(lay.K, -1);
+    for (const SweepClass& sc : classes)
+        for (int k = sc.kfirst; sc.plan.mode == kBucketMode && k <= sc.klast; ++k) lay.slot[k - kmin] = 0, bplan = &sc.plan;
+    if (!bplan) return lay;
+    for (int& s : lay.slot)
+        if (s == 0) s = lay.per_genome++;
+    const size_t m = (size_t)1 << log2m, nrows = (size_t)ngenomes * lay.K, nbucketed = (size_t)ngenomes * lay.per_genome;
+    lay.filter_bytes = align_to((m >> bplan->logg) / 2, 16);
+    lay.ones_bytes = m / 8;
+    lay.seg_off = align_to((size_t)bplan->cap_chunks * 4, 256);
+    lay.fill_bytes = lay.seg_off + align_to((size_t)bplan->cap_chunks * 32, 256);
+    lay.area_bytes = (size_t)bplan->cap_chunks * 4096;
+    lay.cursors = lay.table + align_to(sizeof(BucketRow) * nrows, 256);
+    lay.filters = lay.cursors + align_to(nrows * lay.cursor_stride, 256);
+    lay.ones = lay.filters + align_to(nbucketed * lay.filter_bytes, 256);
+    lay.fills = lay.ones + align_to(nbucketed * lay.ones_bytes, 256);
+    lay.areas = lay.fills + nbucketed * lay.fill_bytes;
+    lay.total = lay.areas + nbucketed * lay.area_bytes;
+    lay.zero_begin = lay.cursors;
+    lay.zero_bytes = lay.fills - lay.cursors;
+    return lay;
+}
+
+void bucket_rows(const BucketLayout& lay, char* base, uint8_t* regs, int log2m, int ngenomes, BucketRow* rows) {
+    for (size_t r = 0; r < (size_t)ngenomes * lay.K; ++r) {
+        const int s = lay.slot[r % lay.K];
+        const size_t h = r / lay.K * lay.per_genome + (s < 0 ? 0 : s);
+        char* fill = base + lay.fills + h * lay.fill_bytes;
+        rows[r].regs = regs + (r << log2m);
+        rows[r].cursor = reinterpret_cast<uint32_t*>(base + lay.cursors + r * lay.cursor_stride);
+        rows[r].filter = s < 0 ? nullptr : reinterpret_cast<uint8_t*>(base + lay.filters + h * lay.filter_bytes);
+        rows[r].ones = s < 0 ? nullptr : reinterpret_cast<uint32_t*>(base + lay.ones + h * lay.ones_bytes);
+        rows[r].fill = s < 0 ? nullptr : reinterpret_cast<uint32_t*>(fill);
+        rows[r].seg = s < 0 ? nullptr : reinterpret_cast<uint16_t*>(fill + lay.seg_off);
+        rows[r].area = s < 0 ? nullptr : reinterpret_cast<uint32_t*>(base + lay.areas + h * lay.area_bytes);
+    }
 }
 
 }  // namespace dd

@@ -1,6 +1,7 @@
 // Host-only sanitizer build of the engine's CPU-side code ("race detection / sanitizers"):
 //   * dd_plan.hip  -- the K1 job tables (pure host code): every (genome, k, tile) covered exactly once, for every
-//                     register mode, under AddressSanitizer + UBSan;
+//                     register mode, under AddressSanitizer + UBSan; the record path's HBM layout: every row's regions
+//                     inside the allocation, disjoint, aligned, and bucketed exactly when a bucket class owns the row's k;
 //   * dd_io.h      -- the loader used by the ingestion pipeline: many threads reading plain / gzip / multi-member
 //                     files into pooled, reused, growing buffers (the access pattern of dd_sketch_files), under
 //                     ASan + UBSan and again under ThreadSanitizer.
@@ -37,10 +38,71 @@ static int failures = 0;
         }                                     \
     } while (0)
 
+// The record path's layout for a plan (dd::bucket_layout + dd::bucket_rows).  A wrong offset on the device would not crash:
+// one row's records would land in another row's stream and the registers come out slightly low.  Returns the total.
+static size_t check_layout(const std::vector<dd::SweepClass>& classes, int log2m, int ngenomes, int kmin, int kmax) {
+    const int K = kmax - kmin + 1;
+    const dd::SweepPlan* bp = nullptr;
+    std::vector<char> bucketed(K, 0);
+    for (const dd::SweepClass& sc : classes)
+        for (int k = sc.kfirst; sc.plan.mode == dd::kBucketMode && k <= sc.klast; ++k) bucketed[k - kmin] = 1, bp = &sc.plan;
+    const dd::BucketLayout lay = dd::bucket_layout(classes, log2m, ngenomes, kmin, kmax);
+    if (!bp) {
+        CHECK(lay.total == 0, "log2m %d: a layout of %zu bytes without a bucket class", log2m, lay.total);
+        return 0;
+    }
+    const size_t m = (size_t)1 << log2m, cap = bp->cap_chunks, nrows = (size_t)ngenomes * K;
+    char* const base = reinterpret_cast<char*>((uintptr_t)1 << 40);     // (never dereferenced)
+    uint8_t* const regs = reinterpret_cast<uint8_t*>((uintptr_t)1 << 50);
+    std::vector<dd::BucketRow> rows(nrows);
+    dd::bucket_rows(lay, base, regs, log2m, ngenomes, rows.data());
+    struct Region { size_t a, n, align; bool zeroed; };   // sizes and alignments as the kernels use them (dd_kernels.h, dd_scatter.hip)
+    std::vector<Region> regions{{lay.table, sizeof(dd::BucketRow) * nrows, 256, false}};
+    auto off = [&](const void* q) { return (size_t)(static_cast<const char*>(q) - base); };
+    size_t nbucketed = 0;
+    const int failures_before = failures;   // (one wrong offset repeats in every row: the first report says it)
+    for (size_t r = 0; r < nrows && failures == failures_before; ++r) {
+        const dd::BucketRow& w = rows[r];
+        const bool b = bucketed[r % K] != 0;
+        nbucketed += b;
+        CHECK(w.regs == regs + r * m && w.cursor, "row %zu: registers or cursor", r);
+        CHECK(!w.area == !b && !w.fill == !b && !w.seg == !b && !w.filter == !b && !w.ones == !b, "log2m %d row %zu (k %d): bucketed %d, but its regions say otherwise",
+              log2m, r, kmin + (int)(r % K), (int)b);
+        regions.push_back({off(w.cursor), 256, 256, true});
+        if (!w.area || !w.fill || !w.seg || !w.filter || !w.ones) continue;
+        regions.push_back({off(w.filter), (m >> bp->logg) / 2, 16, true});
+        regions.push_back({off(w.ones), m / 8, 16, true});
+        regions.push_back({off(w.fill), cap * 4, 256, false});
+        regions.push_back({off(w.seg), cap * 32, 256, false});
+        regions.push_back({off(w.area), cap * 4096, 256, false});
+    }
+    std::sort(regions.begin(), regions.end(), [](const Region& x, const Region& y) { return x.a < y.a; });
+    size_t zlo = lay.total, zhi = 0;
+    for (size_t i = 0; i < regions.size() && failures == failures_before; ++i) {
+        const Region& g = regions[i];
+        CHECK(g.n > 0 && g.a % g.align == 0 && g.a < lay.total && g.n <= lay.total - g.a, "log2m %d: region [%zu, +%zu) outside [0, %zu) or not %zu-aligned", log2m, g.a, g.n,
+              lay.total, g.align);
+        CHECK(i == 0 || regions[i - 1].a + regions[i - 1].n <= g.a, "log2m %d: regions at %zu and %zu overlap", log2m, i ? regions[i - 1].a : 0, g.a);
+        const bool inside = g.a >= lay.zero_begin && g.a + g.n <= lay.zero_begin + lay.zero_bytes;
+        const bool apart = g.a + g.n <= lay.zero_begin || g.a >= lay.zero_begin + lay.zero_bytes;
+        CHECK(g.zeroed ? inside : apart, "log2m %d: region at %zu and the zero span [%zu, +%zu)", log2m, g.a, lay.zero_begin, lay.zero_bytes);
+        if (g.zeroed) zlo = std::min(zlo, g.a), zhi = std::max(zhi, g.a + g.n);
+    }
+    auto up = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
+    if (failures != failures_before) return lay.total;
+    CHECK(lay.zero_begin == zlo && up(zhi, 256) == lay.zero_begin + lay.zero_bytes, "log2m %d: the zero span is not cursors + filters + ones", log2m);
+    // the size the allocation had when dd_sketch_device computed it in place: the region sizes above, each group 256-aligned
+    const size_t want = up(sizeof(dd::BucketRow) * nrows, 256) + nrows * 256 + up(nbucketed * up((m >> bp->logg) / 2, 16), 256) + up(nbucketed * (m / 8), 256) +
+                        nbucketed * (up(cap * 4, 256) + up(cap * 32, 256) + cap * 4096);
+    CHECK(lay.total == want, "log2m %d: layout of %zu bytes, %zu expected", log2m, lay.total, want);
+    return lay.total;
+}
+
 static void check_plan(int log2m, const std::vector<size_t>& sizes, int kmin, int kmax, const dd::PlanKnobs& knobs) {
     const std::vector<dd::SweepClass> classes = dd::plan_sweep(log2m, 1, sizes.data(), (int)sizes.size(), kmin, kmax, knobs);
     const size_t tile = 1024 * 64;
     const int K = kmax - kmin + 1;
+    check_layout(classes, log2m, (int)sizes.size(), kmin, kmax);
     std::vector<std::vector<int>> cover(sizes.size());
     for (size_t g = 0; g < sizes.size(); ++g) cover[g].assign(((sizes[g] + tile - 1) / tile) * K, 0);
     for (const dd::SweepClass& sc : classes) {
@@ -558,6 +620,22 @@ int main(int argc, char** argv) {
     k2 = base;
     k2.bucket_budget = (size_t)1 << 30;            // (a budget that cuts the first epoch short)
     check_plan(20, ragged, 2, 20, k2);
+    // the record path's layout (check_layout): with and without the bitmap and big-bitmap classes in front of the hashed ones,
+    // an empty genome among the rows, and streams of a single chunk
+    k2 = base;
+    k2.bucket_cap_chunks = 1;
+    for (int log2m : {17, 18, 19, 20})
+        for (auto kr : {std::pair<int, int>{4, 40}, {12, 20}, {10, 11}})
+            for (const std::vector<size_t>& sizes : {std::vector<size_t>{50000000}, std::vector<size_t>{50000000, 0, 70000, 12345678, 1000000}})
+                for (const dd::PlanKnobs& kn : {base, k2}) check_plan(log2m, sizes, kr.first, kr.second, kn);
+    // three calls' totals (profiles/sketch_device_split.txt), with the 48 GiB budget a context gives itself on a 288 GB device
+    k2 = base;
+    k2.bucket_budget = (size_t)48 << 30;
+    const struct { std::vector<size_t> sizes; int kmin, kmax, log2m; } shapes[3] = {
+        {std::vector<size_t>(10, 50600000), 4, 40, 20}, {std::vector<size_t>(64, 5000000), 4, 40, 20}, {std::vector<size_t>(5, 200000), 15, 18, 17}};
+    for (const auto& sh : shapes)
+        printf("layout total: %zu genomes, k %d-%d, log2m %d: %zu bytes\n", sh.sizes.size(), sh.kmin, sh.kmax, sh.log2m,
+               check_layout(dd::plan_sweep(sh.log2m, 1, sh.sizes.data(), (int)sh.sizes.size(), sh.kmin, sh.kmax, k2), sh.log2m, (int)sh.sizes.size(), sh.kmin, sh.kmax));
     check_loaders(argv[1]);
     check_gzip_edges(argv[1]);
     check_parallel_inflate();

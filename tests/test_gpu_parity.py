@@ -1130,7 +1130,34 @@ def test_device_resident_schedules_and_stream(engine_factory, torch_cuda, orc):
         eng.set_stream(0)
 
 
-def test_timing_spans_and_call_statistics(engine_factory, orc):
+@pytest.mark.parametrize("p", [14, 17])
+def test_sketch_calls_back_to_back_over_many_shapes(engine_factory, torch_cuda, orc, monkeypatch, p):
+    """Twelve sketch calls queued on one context without a synchronise in between: ten shapes (the plan cache holds eight, so
+    the last two replace plans whose tables queued kernels may still read; from the third call on a staging set is reused),
+    then shape 0 again (evicted: planned and uploaded again) and shape 9 again (a hit).  Single genomes of more than one
+    65 536-token tile, k 8-18 = the bitmap class and two hashed classes: on side streams at log2m 14, and at log2m 17 with a
+    one-tile first epoch as record pipelines on side streams.  Every slab == the oracle."""
+    torch = torch_cuda
+    if p == 17:
+        monkeypatch.setenv("DD_BUCKET_E0", "1")
+    eng = engine_factory(p, True)
+    kmin, kmax = 8, 18
+    fas = [orc.synth_fasta(SEED, 40 + i, 70_000 + 10_000 * i, 1 + i % 3) for i in range(10)]
+    assert len({f.size for f in fas}) == 10
+    bufs = [torch.from_numpy(f.copy()).cuda() for f in fas]
+    order = list(range(10)) + [0, 9]
+    regs = torch.empty((len(order), kmax - kmin + 1, eng.m), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    for slot, i in enumerate(order):
+        eng.sketch_device([bufs[i].data_ptr()], [fas[i].size], kmin, kmax, regs[slot].data_ptr())
+    eng.synchronize()
+    got = regs.cpu().numpy()
+    want = [orc.sketch_sweep(f, kmin, kmax, p) for f in fas]
+    for slot, i in enumerate(order):
+        assert np.array_equal(got[slot], want[i]), (slot, i)
+
+
+def test_timing_spans_and_call_statistics(engine_factory, orc, monkeypatch):
     from dandd_amd.engine import KERNEL_PACK, KERNEL_SWEEP, KERNEL_UNION
     eng = engine_factory(14, True)
     fa = orc.synth_fasta(SEED, 9, 200000, 2)
@@ -1148,6 +1175,17 @@ def test_timing_spans_and_call_statistics(engine_factory, orc):
     eng.timing_enable(False)
     tokens, updates, blocks = eng.last_sketch_stats()
     assert tokens == fa.size and updates == fa.size * 37 and blocks > 0
+    # log2m 17 with a filtered epoch: the bitmap class and the two record pipelines run side by side, timed as one span too
+    monkeypatch.setenv("DD_BUCKET_E0", "1")
+    eng = engine_factory(17, True)
+    eng.timing_enable(True)
+    eng.timing_reset()
+    eng.sketch_buffer(fa, 8, 18)
+    assert eng.timing_read(KERNEL_PACK)[1] == 1 and eng.timing_read(KERNEL_SWEEP)[1] == 1
+    eng.timing_reset()
+    eng.timing_enable(False)
+    tokens, updates, blocks = eng.last_sketch_stats()
+    assert tokens == fa.size and updates == fa.size * 11 and blocks > 0
 
 
 def _random_slab(rng, n, K, p, kind):

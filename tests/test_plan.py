@@ -24,6 +24,9 @@ SIZES = {
 
 def check(log2m, sizes, kmin, kmax):
     jobs = plan_sweep(log2m, sizes, kmin, kmax)
+    # dd_sketch_device launches the classes in table order, LDS classes on side streams and the record pipelines (mode 5)
+    # behind their joins: every job of another mode comes before the first of mode 5
+    assert np.all(np.diff((jobs["mode"] == 5).astype(np.int8)) >= 0), (log2m, kmin, kmax)
     m = 1 << log2m
     ntiles = [(n + TILE - 1) // TILE for n in sizes]
     cover = [np.zeros((kmax - kmin + 1, nt), dtype=np.int32) for nt in ntiles]
@@ -141,6 +144,7 @@ def test_knobs_change_the_plan_not_the_coverage(monkeypatch):
             monkeypatch.setenv(k, v)
         for log2m in (14, 18):
             jobs = plan_sweep(log2m, SIZES["ragged"], 2, 40)
+            assert np.all(np.diff((jobs["mode"] == 5).astype(np.int8)) >= 0), env
             ntiles = [(n + TILE - 1) // TILE for n in SIZES["ragged"]]
             cover = [np.zeros((39, nt), dtype=np.int32) for nt in ntiles]
             for j in jobs:
