@@ -1,6 +1,7 @@
-// dd_exact_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h): dd_exact_count* and the exact union
-// schedules (dd_exact_pairwise / _progressive / _leave_out / _subsets).  Host-side orchestration only; the kernels are in
-// dd_exact.hip and dd_exact_sched.hip.
+// dd_exact_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h): dd_exact_count*, the exact union
+// schedules (dd_exact_pairwise / _progressive / _leave_out / _subsets) and the exact intersection schedules
+// (dd_exact_spectrum / _core_progressive / _select).  Host-side orchestration only; the kernels are in dd_exact.hip and
+// dd_exact_sched.hip.
 #include <functional>
 #include "dd_ctx.h"
 
@@ -268,7 +269,7 @@ int dd_exact_count(dd_ctx* c, const char* const* paths, int n, int k, uint64_t* 
 // dd_exact_sched.hip: one sort of the universe per k, a membership mask per distinct k-mer, one accumulator per schedule.
 namespace {
 
-// The driver behind the four schedules: K0 once, then for every k extract (with the genome's index) -> sort -> reduce +
+// The driver behind every schedule: K0 once, then for every k extract (with the genome's index) -> sort -> reduce +
 // accumulate through exact_passes.  out[kk] receives the accumulator's exact_sched_acc_words() counts of k = kmin + kk.
 int exact_schedule(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, dd::ExactSched s,
                    const std::vector<uint64_t>& table, std::vector<std::vector<unsigned long long>>& out) {
@@ -373,6 +374,19 @@ int subsets_from_hist(const unsigned long long* hist, int n, uint64_t* card, siz
     return DD_OK;
 }
 
+// select's argument rules -> the (all, none) pairs its accumulator reads
+int select_table(const uint64_t* all, const uint64_t* none, int nq, int n, std::vector<uint64_t>& table) {
+    if (!all || !none) return fail(DD_EINVAL, "null argument");
+    if (nq < 1) return fail(DD_EINVAL, "nq=%d: at least one query", nq);
+    const uint64_t outside = n == 64 ? 0ull : ~((1ull << n) - 1ull);
+    table.resize((size_t)2 * nq);
+    for (int q = 0; q < nq; ++q) {
+        if ((all[q] | none[q]) & outside) return fail(DD_EINVAL, "query %d: a bit outside 0..%d is set", q, n - 1);
+        table[(size_t)2 * q] = all[q], table[(size_t)2 * q + 1] = none[q];
+    }
+    return DD_OK;
+}
+
 // a path form: the files read and uploaded, then the device form (which checks the schedule's own arguments)
 extern "C++" template <class DeviceForm>
 int exact_path_form(dd_ctx* c, const char* const* paths, int n, DeviceForm device_form) {
@@ -453,6 +467,80 @@ int dd_exact_subsets_device(dd_ctx* c, const uint8_t* const* fasta_dev, const si
     const size_t K = acc.size();
     for (size_t kk = 0; kk < K; ++kk) subsets_from_hist(acc[kk].data() + 1, n, card + kk, K);
     return DD_OK;
+}
+
+// ---------------------------------------------------------------- exact intersection schedules
+int dd_exact_spectrum_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, uint64_t* spec) {
+    if (exact_sched_args(c, fasta_dev, n, 64, kmin, kmax, spec)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedSpectrum, n, 0, 0, nullptr, nullptr}, {}, acc))) return rc;
+    const size_t K = acc.size();
+    for (size_t kk = 0; kk < K; ++kk)
+        for (int j = 0; j <= n; ++j) spec[(size_t)j * K + kk] = acc[kk][1 + j];
+    return DD_OK;
+}
+
+int dd_exact_core_progressive_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax,
+                                     const int32_t* orderings, int norder, uint64_t* core) {
+    if (exact_sched_args(c, fasta_dev, n, 64, kmin, kmax, core)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    std::vector<uint64_t> table;
+    if (progressive_table(orderings, norder, n, table)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedCoreProgressive, n, norder, 0, nullptr, nullptr}, table, acc))) return rc;
+    const size_t K = acc.size();
+    for (size_t kk = 0; kk < K; ++kk)
+        for (int o = 0; o < norder; ++o) {
+            uint64_t run = 0;   // |core of the first j+1| = k-mers whose last contained prefix stands at a position >= j
+            for (int j = n - 1; j >= 0; --j) {
+                run += acc[kk][1 + (size_t)o * n + j];
+                core[((size_t)o * n + j) * K + kk] = run;
+            }
+        }
+    return DD_OK;
+}
+
+int dd_exact_select_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax,
+                           const uint64_t* all, const uint64_t* none, int nq, uint64_t* count) {
+    if (exact_sched_args(c, fasta_dev, n, 64, kmin, kmax, count)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    std::vector<uint64_t> table;
+    if (select_table(all, none, nq, n, table)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedSelect, n, nq, 0, nullptr, nullptr}, table, acc))) return rc;
+    const size_t K = acc.size();
+    for (size_t kk = 0; kk < K; ++kk)
+        for (int q = 0; q < nq; ++q) count[(size_t)q * K + kk] = acc[kk][1 + q];
+    return DD_OK;
+}
+
+int dd_exact_spectrum(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, uint64_t* spec) {
+    if (exact_sched_args(c, paths, n, 64, kmin, kmax, spec)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) { return dd_exact_spectrum_device(c, p, s, n, kmin, kmax, spec); });
+}
+
+int dd_exact_core_progressive(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, const int32_t* orderings, int norder, uint64_t* core) {
+    if (exact_sched_args(c, paths, n, 64, kmin, kmax, core)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) {
+        return dd_exact_core_progressive_device(c, p, s, n, kmin, kmax, orderings, norder, core);
+    });
+}
+
+int dd_exact_select(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, const uint64_t* all, const uint64_t* none, int nq, uint64_t* count) {
+    if (exact_sched_args(c, paths, n, 64, kmin, kmax, count)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) {
+        return dd_exact_select_device(c, p, s, n, kmin, kmax, all, none, nq, count);
+    });
 }
 
 int dd_exact_subsets_from_hist(const uint64_t* hist, int n, uint64_t* card) {

@@ -21,6 +21,13 @@
 //                   leave-out    lowest set bit -> its group -> is the mask inside the group? one counter per group
 //                   subsets      histogram of the masks over 2^n bins in LDS (u32; n = 16: two halves by the top bit, on
 //                                alternate workgroups)
+//                 and the intersection schedules, which ask whether a mask CONTAINS a set and how many bits it has:
+//                   spectrum     popcount(mask) over n + 1 bins in LDS; bins 1 and n (where related genomes put almost
+//                                every mask) are counted in registers and added once at the flush
+//                   core-progressive  the prefix masks of progressive; binary search for the LAST prefix the mask contains;
+//                                the full mask is the last bin of every ordering and is counted once, in a register
+//                   select       (all, none) pairs in LDS; a thread owns up to 4 queries and a stripe of the tile and
+//                                counts its hits in registers
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
@@ -35,6 +42,7 @@ constexpr int kThreads = 256, kItems = 8, kChunk = kThreads * kItems;  // slots 
 constexpr int kCarryThreads = 1024;
 constexpr size_t kStaticLds = (size_t)kChunk * 8 + 128;   // sched_kernel's own LDS: the tile of masks, the scan's wave totals
 constexpr int kPairSlots = 9;   // ceil(64 * 65 / 2 / 256): (i, j) pairs a thread of the pairwise accumulator owns
+constexpr int kSelectSlots = 4, kSelectBatch = kSelectSlots * kThreads;   // queries a thread owns; queries of one select launch
 
 struct SortedView {
     const uint64_t* lo;
@@ -172,9 +180,10 @@ DD_D void agg_add(uint32_t* base, uint32_t idx, bool valid) {
 
 struct SchedArgs {
     int n;
-    int norder;                       // progressive: orderings of this launch
+    int norder;                       // progressive, core-progressive: orderings of this launch; select: its queries
     int ngroups;                      // leave-out
-    const uint64_t* table;            // progressive: prefix masks [norder][n]; leave-out: group of bit [64], group masks [ngroups]
+    const uint64_t* table;            // progressive, core-progressive: prefix masks [norder][n]; leave-out: group of bit [64],
+                                      // group masks [ngroups]; select: (all, none) [norder][2]
     unsigned long long* acc;          // [0] = M (masks seen), then the schedule's counts
     int add_m;
     int slices;                       // subsets, n = 16: workgroup w counts the masks whose top bit is w % 2 (every chunk is reduced twice)
@@ -313,6 +322,121 @@ struct AccPairwise {
     }
 };
 
+struct AccSpectrum {
+    uint32_t* bins;     // [65]: k-mers held by exactly j genomes
+    uint32_t one, all;  // this thread's masks of 1 and of n bits: the two bins related genomes fill, kept off the LDS atomics
+    DD_D void init(const SchedArgs&, uint64_t* dyn) {
+        bins = reinterpret_cast<uint32_t*>(dyn);
+        if (threadIdx.x <= 64) bins[threadIdx.x] = 0;
+        one = all = 0;
+    }
+    DD_D void consume(const SchedArgs& a, const uint64_t* tile, uint32_t cnt, uint32_t) {
+        for (uint32_t i = threadIdx.x; i < cnt; i += kThreads) {
+            const int pc = __builtin_popcountll(tile[i]);
+            if (pc == a.n) ++all;
+            else if (pc == 1) ++one;
+            else atomicAdd(&bins[pc], 1u);
+        }
+    }
+    DD_D void flush(const SchedArgs& a, uint32_t) {
+        if (all) atomicAdd(&bins[a.n], all);
+        if (one) atomicAdd(&bins[1], one);
+        __syncthreads();
+        if ((int)threadIdx.x <= a.n && bins[threadIdx.x]) atomicAdd(&a.acc[1 + threadIdx.x], (unsigned long long)bins[threadIdx.x]);
+    }
+};
+
+struct AccCoreProgressive {
+    uint64_t* prefix;   // [norder][n]
+    uint32_t* hist;     // [norder][n]: k-mers that hold genomes 0..j of ordering o and not genome j+1
+    uint32_t* fulls;    // [1]: the workgroup's full masks
+    uint32_t full;      // this thread's full masks: position n-1 of every ordering
+    DD_D void init(const SchedArgs& a, uint64_t* dyn) {
+        prefix = dyn;
+        hist = reinterpret_cast<uint32_t*>(dyn + (size_t)a.norder * a.n);
+        fulls = hist + (size_t)a.norder * a.n;
+        for (int i = threadIdx.x; i < a.norder * a.n; i += kThreads) prefix[i] = a.table[i], hist[i] = 0;
+        if (threadIdx.x == 0) *fulls = 0;
+        full = 0;
+    }
+    DD_D void consume(const SchedArgs& a, const uint64_t* tile, uint32_t cnt, uint32_t) {
+        const uint64_t every = a.n == 64 ? ~0ull : ((1ull << a.n) - 1ull);
+        for (uint32_t base = 0; base < cnt; base += kThreads) {
+            const uint32_t i = base + threadIdx.x;
+            const uint64_t m = i < cnt ? tile[i] : 0ull;
+            const bool search = m != 0 && m != every;
+            full += m == every;
+            for (int o = 0; o < a.norder; ++o) {
+                const uint64_t* p = prefix + (size_t)o * a.n;
+                const bool valid = search && (m & p[0]) == p[0];   // (without the ordering's first genome: in no core)
+                int lo = 0, hi = a.n - 1;
+                if (valid)
+                    while (lo < hi) {
+                        const int mid = (lo + hi + 1) >> 1;
+                        if ((m & p[mid]) == p[mid]) lo = mid;
+                        else hi = mid - 1;
+                    }
+                agg_add(hist + (size_t)o * a.n, (uint32_t)lo, valid);
+            }
+        }
+    }
+    DD_D void flush(const SchedArgs& a, uint32_t) {
+        if (full) atomicAdd(fulls, full);
+        __syncthreads();
+        const uint32_t f = *fulls;
+        for (int i = threadIdx.x; i < a.norder * a.n; i += kThreads) {
+            const uint32_t h = hist[i] + ((i % a.n) == a.n - 1 ? f : 0u);
+            if (h) atomicAdd(&a.acc[1 + i], (unsigned long long)h);
+        }
+    }
+};
+
+struct AccSelect {
+    uint64_t* pair;     // [norder][2]: (all, none)
+    uint32_t* hits;     // [norder]
+    uint32_t width;     // threads that share one stripe of the tile: a power of two >= the queries, kThreads at most
+    uint32_t c[kSelectSlots];   // hits of queries (threadIdx.x % width) + r * kThreads among the masks of this thread's stripe
+    DD_D void init(const SchedArgs& a, uint64_t* dyn) {
+        pair = dyn;
+        hits = reinterpret_cast<uint32_t*>(dyn + 2 * (size_t)a.norder);
+        for (int i = threadIdx.x; i < 2 * a.norder; i += kThreads) pair[i] = a.table[i];
+        for (int i = threadIdx.x; i < a.norder; i += kThreads) hits[i] = 0;
+        width = 1;
+        while (width < (uint32_t)a.norder && width < (uint32_t)kThreads) width <<= 1;
+#pragma unroll
+        for (int r = 0; r < kSelectSlots; ++r) c[r] = 0;
+    }
+    DD_D void consume(const SchedArgs& a, const uint64_t* tile, uint32_t cnt, uint32_t) {
+        const uint32_t q0 = threadIdx.x & (width - 1), step = kThreads / width;
+        const int rounds = (a.norder + kThreads - 1) / kThreads;
+        uint64_t all[kSelectSlots], none[kSelectSlots];
+#pragma unroll
+        for (int r = 0; r < kSelectSlots; ++r) {
+            const uint32_t q = q0 + (uint32_t)r * kThreads;
+            const bool live = q < (uint32_t)a.norder;   // (all = none = ~0 matches no mask)
+            all[r] = live ? pair[2 * q] : ~0ull;
+            none[r] = live ? pair[2 * q + 1] : ~0ull;
+        }
+        for (uint32_t i = threadIdx.x / width; i < cnt; i += step) {
+            const uint64_t m = tile[i];
+#pragma unroll
+            for (int r = 0; r < kSelectSlots; ++r)
+                if (r < rounds) c[r] += (m & all[r]) == all[r] && (m & none[r]) == 0;
+        }
+    }
+    DD_D void flush(const SchedArgs& a, uint32_t) {
+        const uint32_t q0 = threadIdx.x & (width - 1);
+#pragma unroll
+        for (int r = 0; r < kSelectSlots; ++r) {
+            const uint32_t q = q0 + (uint32_t)r * kThreads;
+            if (q < (uint32_t)a.norder && c[r]) atomicAdd(&hits[q], c[r]);
+        }
+        __syncthreads();
+        for (int q = threadIdx.x; q < a.norder; q += kThreads)
+            if (hits[q]) atomicAdd(&a.acc[1 + q], (unsigned long long)hits[q]);
+    }
+};
+
 template <bool WIDE, class Acc>
 __global__ __launch_bounds__(kThreads) void sched_kernel(SortedView s, const uint64_t* __restrict__ carry, size_t nchunks,
                                                        SchedArgs a) {
@@ -359,7 +483,7 @@ __global__ __launch_bounds__(kThreads) void sched_kernel(SortedView s, const uin
     if (threadIdx.x == 0 && a.add_m && seen) atomicAdd(&a.acc[0], seen);
 }
 
-// orderings one progressive launch takes: prefix masks + histogram within 40 KiB of LDS
+// orderings one progressive or core-progressive launch takes: prefix masks + histogram within 40 KiB of LDS
 int max_orderings(int n) { return std::max(1, (40 << 10) / (12 * n)); }
 
 size_t sched_dyn_lds(int kind, int n, int norder) {
@@ -367,6 +491,9 @@ size_t sched_dyn_lds(int kind, int n, int norder) {
         case kSchedPairwise: return (size_t)(kChunk / 64) * n * 8 + (size_t)n * (n + 1) + 16;
         case kSchedProgressive: return (size_t)norder * n * 12 + 16;
         case kSchedLeaveOut: return 64 * 8 + 64 * 4 + 64 * 4;
+        case kSchedSpectrum: return 65 * 4 + 12;
+        case kSchedCoreProgressive: return (size_t)norder * n * 12 + 16;
+        case kSchedSelect: return (size_t)norder * 20 + 16;
         default: return (size_t)4 << std::min(n, kExactSubsetsLdsN);
     }
 }
@@ -378,6 +505,9 @@ size_t exact_sched_acc_words(const ExactSched& s) {
         case kSchedPairwise: return 1 + (size_t)s.n * (s.n + 1) / 2;
         case kSchedProgressive: return 1 + (size_t)s.norder * s.n;
         case kSchedLeaveOut: return 1 + (size_t)s.ngroups;
+        case kSchedSpectrum: return 1 + (size_t)s.n + 1;
+        case kSchedCoreProgressive: return 1 + (size_t)s.norder * s.n;
+        case kSchedSelect: return 1 + (size_t)s.norder;
         default: return 1 + ((size_t)1 << s.n);
     }
 }
@@ -431,14 +561,17 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
     if (wide) hipLaunchKernelGGL(sched_summary_kernel<true>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
     else hipLaunchKernelGGL(sched_summary_kernel<false>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
     hipLaunchKernelGGL(sched_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, sum_f, sum_v, nchunks, carry);
-    const int per = s.kind == kSchedProgressive ? max_orderings(s.n) : 1;
-    for (int o0 = 0; o0 < (s.kind == kSchedProgressive ? s.norder : 1); o0 += per) {
+    // progressive and core-progressive take their orderings, select its queries, in batches that fit the LDS of a launch
+    const bool by_order = s.kind == kSchedProgressive || s.kind == kSchedCoreProgressive, by_query = s.kind == kSchedSelect;
+    const int items = (by_order || by_query) ? s.norder : 1, per = by_order ? max_orderings(s.n) : (by_query ? kSelectBatch : 1);
+    const size_t tstride = by_order ? (size_t)s.n : 2, astride = by_order ? (size_t)s.n : 1;
+    for (int o0 = 0; o0 < items; o0 += per) {
         SchedArgs a{s.n, 0, s.ngroups, s.table, s.acc, o0 == 0, 1};
         if (s.kind == kSchedSubsets && s.n > kExactSubsetsLdsN) a.slices = 1 << (s.n - kExactSubsetsLdsN);
-        if (s.kind == kSchedProgressive) {
-            a.norder = std::min(per, s.norder - o0);
-            a.table = s.table + (size_t)o0 * s.n;
-            a.acc = s.acc + (size_t)o0 * s.n;   // (acc[0] of a later launch is never written: add_m = 0)
+        if (by_order || by_query) {
+            a.norder = std::min(per, items - o0);
+            a.table = s.table + (size_t)o0 * tstride;
+            a.acc = s.acc + (size_t)o0 * astride;   // (acc[0] of a later launch is never written: add_m = 0)
         }
         const size_t dyn = sched_dyn_lds(s.kind, s.n, a.norder);
         // persistent workgroups (the accumulators flush once each): as many as the CUs hold at this much LDS, 4 per CU at most
@@ -452,6 +585,9 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
                 case kSchedPairwise: launch_full_lds<sched_kernel<W, AccPairwise>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
                 case kSchedProgressive: launch_full_lds<sched_kernel<W, AccProgressive>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
                 case kSchedLeaveOut: launch_full_lds<sched_kernel<W, AccLeaveOut>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
+                case kSchedSpectrum: launch_full_lds<sched_kernel<W, AccSpectrum>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
+                case kSchedCoreProgressive: launch_full_lds<sched_kernel<W, AccCoreProgressive>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
+                case kSchedSelect: launch_full_lds<sched_kernel<W, AccSelect>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
                 default: launch_full_lds<sched_kernel<W, AccSubsets>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
             }
         });

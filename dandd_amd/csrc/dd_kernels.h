@@ -274,7 +274,8 @@ hipError_t launch_exact_sort_count(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt,
 // byte array next to the keys (k = 29..32, 61..64)
 inline constexpr int exact_tag_mode(int k) { return (k <= 32 ? 2 * k : 2 * k - 64) <= 56 ? 1 : 2; }
 constexpr int kExactSubsetsLdsN = 15;   // subsets: 2^n histogram bins in LDS (u32, 128 KiB at 15); n = 16 as two halves by the top bit
-enum { kSchedPairwise = 0, kSchedProgressive = 1, kSchedLeaveOut = 2, kSchedSubsets = 3 };
+enum { kSchedPairwise = 0, kSchedProgressive = 1, kSchedLeaveOut = 2, kSchedSubsets = 3,
+       kSchedSpectrum = 4, kSchedCoreProgressive = 5, kSchedSelect = 6 };   // 4..6: the intersection schedules
 struct ExactSorted {            // where launch_exact_sort_tagged left the sorted k-mers
     const uint64_t* lo;
     const uint64_t* hi;         // k > 32
@@ -282,15 +283,19 @@ struct ExactSorted {            // where launch_exact_sort_tagged left the sorte
 };
 struct ExactSched {
     int kind, n;
-    int norder;                 // progressive
+    int norder;                 // progressive, core-progressive: orderings; select: queries (any number >= 1)
     int ngroups;                // leave-out
     const uint64_t* table;      // device; progressive: prefix masks [norder][n]; leave-out: group of bit i [64] (~0: never left out),
-                                //         then the groups' masks [ngroups]
+                                //         then the groups' masks [ngroups]; core-progressive: the prefix masks of progressive;
+                                //         select: (all, none) [norder][2]
     unsigned long long* acc;    // device, exact_sched_acc_words() of them, zeroed by the caller: [0] = M, the number of distinct k-mers,
                                 //   pairwise: then |A_i n A_j| for i <= j, row by row (the diagonal: |A_i|)
                                 //   progressive: then [norder][n] k-mers whose first genome of ordering o stands at position j
                                 //   leave-out: then [ngroups] k-mers no genome outside group g holds
                                 //   subsets: then [2^n] k-mers per membership mask
+                                //   spectrum: then [n+1] k-mers held by exactly j genomes
+                                //   core-progressive: then [norder][n] k-mers that hold genomes 0..j of ordering o and not genome j+1
+                                //   select: then [norder] k-mers whose mask contains all[q] and meets none[q] nowhere
 };
 size_t exact_sched_acc_words(const ExactSched& s);
 size_t exact_sched_temp_bytes(size_t n, int k);

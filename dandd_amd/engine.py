@@ -31,6 +31,8 @@ EXPORTS = [
     "dd_exact_pairwise", "dd_exact_progressive", "dd_exact_leave_out", "dd_exact_subsets",
     "dd_exact_pairwise_device", "dd_exact_progressive_device", "dd_exact_leave_out_device", "dd_exact_subsets_device",
     "dd_exact_subsets_from_hist",
+    "dd_exact_spectrum", "dd_exact_core_progressive", "dd_exact_select",
+    "dd_exact_spectrum_device", "dd_exact_core_progressive_device", "dd_exact_select_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
     "dd_comm_unique_id", "dd_comm_init", "dd_comm_destroy", "dd_comm_info", "dd_allreduce_max_u8", "dd_allgather_u8",
@@ -155,7 +157,11 @@ def load_library(path=None):
     for name, src, extra in (("dd_exact_pairwise", [paths_t], []), ("dd_exact_progressive", [paths_t], [vp, i32]),
                              ("dd_exact_leave_out", [paths_t], [vp, i32]), ("dd_exact_subsets", [paths_t], []),
                              ("dd_exact_pairwise_device", [ptrs_t, sizes_t], []), ("dd_exact_progressive_device", [ptrs_t, sizes_t], [vp, i32]),
-                             ("dd_exact_leave_out_device", [ptrs_t, sizes_t], [vp, i32]), ("dd_exact_subsets_device", [ptrs_t, sizes_t], [])):
+                             ("dd_exact_leave_out_device", [ptrs_t, sizes_t], [vp, i32]), ("dd_exact_subsets_device", [ptrs_t, sizes_t], []),
+                             ("dd_exact_spectrum", [paths_t], []), ("dd_exact_core_progressive", [paths_t], [vp, i32]),
+                             ("dd_exact_select", [paths_t], [vp, vp, i32]), ("dd_exact_spectrum_device", [ptrs_t, sizes_t], []),
+                             ("dd_exact_core_progressive_device", [ptrs_t, sizes_t], [vp, i32]),
+                             ("dd_exact_select_device", [ptrs_t, sizes_t], [vp, vp, i32])):
         fn = getattr(lib, name)
         fn.restype = i32
         fn.argtypes = [vp] + src + [i32, i32, i32] + extra + [vp]
@@ -634,6 +640,46 @@ class Engine:
 
     def exact_subsets_device(self, fasta_ptrs, nbytes, kmin, kmax):
         return self._exact_subsets(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax)
+
+    # -- exact intersection schedules: the same sort, masks asked what they contain ---------------
+    def _exact_spectrum(self, src, kmin, kmax):
+        return self._exact_sched("spectrum", src, lambda n: (min(max(n, 0), 64) + 1,), kmin, kmax)
+
+    def _exact_core_progressive(self, src, kmin, kmax, orderings):
+        n = src[1]
+        ords = np.ascontiguousarray(orderings, dtype=np.int32).reshape(-1, max(n, 1))
+        return self._exact_sched("core_progressive", src, lambda n: (ords.shape[0], n), kmin, kmax, ords.ctypes.data, ords.shape[0])
+
+    def _exact_select(self, src, kmin, kmax, all_masks, none_masks):
+        al = np.ascontiguousarray([int(x) for x in all_masks], dtype=np.uint64).reshape(-1)
+        no = np.ascontiguousarray([int(x) for x in none_masks], dtype=np.uint64).reshape(-1)
+        if al.size != no.size:
+            raise ValueError("all_masks and none_masks must have the same length")
+        nq = al.size
+        if nq == 0:   # (the library rejects nq = 0 by its own rule; it still wants two pointers)
+            al = no = np.zeros(1, dtype=np.uint64)
+        return self._exact_sched("select", src, lambda n: (nq,), kmin, kmax, al.ctypes.data, no.ctypes.data, nq)
+
+    def exact_spectrum(self, paths, kmin, kmax):
+        """FASTA files (n <= 64) -> uint64 [n+1][K]: row j the distinct k-mers held by exactly j of the files (row 0: 0)."""
+        return self._exact_spectrum(self._exact_src(paths=paths), kmin, kmax)
+
+    def exact_spectrum_device(self, fasta_ptrs, nbytes, kmin, kmax):
+        return self._exact_spectrum(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax)
+
+    def exact_core_progressive(self, paths, kmin, kmax, orderings):
+        """-> uint64 [o][n][K]: distinct k-mers held by every one of the first j+1 files of every ordering (a permutation of 0..n-1)."""
+        return self._exact_core_progressive(self._exact_src(paths=paths), kmin, kmax, orderings)
+
+    def exact_core_progressive_device(self, fasta_ptrs, nbytes, kmin, kmax, orderings):
+        return self._exact_core_progressive(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, orderings)
+
+    def exact_select(self, paths, kmin, kmax, all_masks, none_masks):
+        """-> uint64 [nq][K]: row q the distinct k-mers held by every file of all_masks[q] and by no file of none_masks[q] (bit i: file i)."""
+        return self._exact_select(self._exact_src(paths=paths), kmin, kmax, all_masks, none_masks)
+
+    def exact_select_device(self, fasta_ptrs, nbytes, kmin, kmax, all_masks, none_masks):
+        return self._exact_select(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, all_masks, none_masks)
 
     # -- measurement ----------------------------------------------------------------------
     def timing_enable(self, on=True):

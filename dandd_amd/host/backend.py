@@ -303,6 +303,32 @@ class HipExactBackend:
         self._seed_leaves(leaf_paths, dbs, files, table[[1 << i for i in range(len(files))]])
         return table.astype(np.float64)
 
+    # ---- intersection schedules (`core`): what the masks contain, from the same sort.  Counts stay uint64: nothing here is
+    # a cardinality estimate, and no object path stands behind them -- None (more than 64 leaves) ends the command.
+    def spectrum_counts(self, leaf_paths):
+        """distinct k-mers held by exactly j of the leaves: uint64 [n+1][K], row 0 all 0"""
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, kmin, kmax = win
+        return self.engine.exact_spectrum(files, kmin, kmax)
+
+    def core_progressive_counts(self, leaf_paths, orderings):
+        """k-mers held by every one of the first j+1 leaves of ordering o: uint64 [o][n][K]"""
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, kmin, kmax = win
+        return self.engine.exact_core_progressive(files, kmin, kmax, orderings)
+
+    def select_counts(self, leaf_paths, all_masks, none_masks):
+        """k-mers held by every leaf of all_masks[q] and by no leaf of none_masks[q] (bit i: leaf i): uint64 [nq][K]"""
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, kmin, kmax = win
+        return self.engine.exact_select(files, kmin, kmax, all_masks, none_masks)
+
     def close(self):
         self.engine.close()
 

@@ -1,4 +1,4 @@
-"""`dandd tree | progressive | kij | deltadelta | abba | greedy` on the MI355X engine: same sub-commands, flags, defaults and
+"""`dandd tree | progressive | kij | deltadelta | abba | greedy | core` on the MI355X engine: same sub-commands, flags, defaults and
 output files as /root/reference/lib/dandd_cmd.py (flags :141-286, handlers :43-132); only the
 sketching backend differs.  Run as  python -m dandd_amd.host.cli <subcommand> ...
 """
@@ -133,32 +133,37 @@ def _leaf_lookup(tree, cmd, tree_path):
     return leaf_of
 
 
+def _lines(path):
+    with open(path) as fh:
+        return [line.rstrip("\n") for line in fh if line.strip()]
+
+
+def _read_groups(cmd, path, leaf_of):
+    """-> (groups as lists of leaf FASTAs, their labels in order of first appearance) from 'fasta<TAB>group' lines"""
+    groups, labels = [], []
+    for n, line in enumerate(_lines(path), 1):
+        parts = line.split("\t")
+        if len(parts) != 2 or not parts[0].strip() or not parts[1].strip():
+            sys.exit(f"{cmd}: {path}:{n}: expected 'fasta<TAB>group', found {line!r}")
+        f, label = leaf_of(parts[0].strip()), parts[1].strip()
+        if label not in labels:
+            labels.append(label)
+            groups.append([])
+        groups[labels.index(label)].append(f)
+    return groups, labels
+
+
 def _deltadelta_groups(tree, args):
     """-> (groups as lists of leaf FASTAs, their labels) from -f / -g, or every leaf on its own in tree order"""
     leaves = tree.leaf_nodes()
     leaf_of = _leaf_lookup(tree, "deltadelta", args.delta_tree)
-
-    def lines(path):
-        with open(path) as fh:
-            return [line.rstrip("\n") for line in fh if line.strip()]
-
     if args.flist_loc and args.groups_loc:
         sys.exit("deltadelta: -f/--fastas and -g/--groups are mutually exclusive")
     if args.groups_loc:
-        groups, labels = [], []
-        for n, line in enumerate(lines(args.groups_loc), 1):
-            parts = line.split("\t")
-            if len(parts) != 2 or not parts[0].strip() or not parts[1].strip():
-                sys.exit(f"deltadelta: {args.groups_loc}:{n}: expected 'fasta<TAB>group', found {line!r}")
-            f, label = leaf_of(parts[0].strip()), parts[1].strip()
-            if label not in labels:
-                labels.append(label)
-                groups.append([])
-            groups[labels.index(label)].append(f)
-        return groups, labels
+        return _read_groups("deltadelta", args.groups_loc, leaf_of)
     if args.flist_loc:
         seen, groups = set(), []
-        for name in lines(args.flist_loc):
+        for name in _lines(args.flist_loc):
             f = leaf_of(name.strip())
             if f not in seen:
                 seen.add(f)
@@ -337,6 +342,81 @@ def greedy_command(args):
             fh.write("".join(f + "\n" for f in r["order"]))
     _write_csv(outfile + ".greedy.csv", ["mode", "ngen", "fasta", "delta", "kval", "gain", "fastas"], rows)
     _write_csv(outfile + ".greedysummary.csv", ["mode", "ngen", "kval", "card", "delta_pos"], summary)
+    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
+    tree.speciesinfo.save_references(fast=False)
+
+
+def core_command(args):
+    """The intersection side of a pan-genome study, exact: how many k-mers 1, 2, ... n genomes hold (the spectrum), the core
+    of every prefix of an ordering next to its union (the second curve of a pan/core plot), and per group of genomes its
+    core, its private k-mers and its signature (in every member, in nobody else).  All of it sums over the membership
+    masks of an exact tree; sketches have no such sums (inclusion-exclusion over 2^n union estimates amplifies their error)."""
+    tree = _load_tree(args.delta_tree)
+    tree.speciesinfo.update(tool=tree.experiment["tool"])
+    if tree.experiment["tool"] != "kmc":
+        sys.exit(f"core: {args.delta_tree} is a tree of sketches: build it with `tree --exact` -- intersections are sums over exact "
+                 "membership masks, and inclusion-exclusion over HyperLogLog union estimates amplifies their error")
+    if not args.tag:
+        args.tag = tree.speciesinfo.tag
+    outfile = tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
+    if args.ksweep:
+        window = (int(args.mink), int(args.maxk))
+    elif tree.experiment.get("ksweep") is not None:
+        window = tuple(int(v) for v in tree.experiment["ksweep"])
+    else:
+        sys.exit("core: a k window is needed: give --ksweep --mink --maxk, or a tree built with --ksweep")
+    if args.safety:
+        tree.experiment["safety"] = True
+    leaf_of = _leaf_lookup(tree, "core", args.delta_tree)
+    fastas = tree.progressive_fastas(args.flist_loc)
+    n = len(fastas)
+    if n < 1:
+        sys.exit(f"core: {n} genomes in the universe: at least 1 is needed")
+    if n > 64:
+        sys.exit(f"core: {n} genomes in the universe: at most 64 (a membership mask has one bit per genome); choose them with -f/--fastas")
+    orderings = [tuple(range(n))]
+    if args.ordering_file or args.norderings:
+        try:
+            fastas, orderings = tree.orderings_list(ordering_file=args.ordering_file, flist_loc=args.flist_loc, count=args.norderings)
+        except ValueError as e:
+            sys.exit(f"core: {e}")
+    for o in orderings:
+        if sorted(o) != list(range(n)):
+            sys.exit(f"core: an ordering of {len(o)} entries does not order the {n} genomes of the universe")
+    groups, labels = [], []
+    if args.groups_loc:
+        groups, labels = _read_groups("core", args.groups_loc, leaf_of)
+        for g in groups:
+            for f in g:
+                if f not in fastas:
+                    sys.exit(f"core: {f} (-g) is not in the universe of this run (-f)")
+    os.makedirs(args.outdir, exist_ok=True)
+    try:
+        res = tree.core_tables(fastas, *window, orderings, groups)
+    except ValueError as e:
+        sys.exit(f"core: {e}")
+    ks = res["ks"]
+    delta_of = deltatree._window_delta
+    spec = res["spectrum"]
+    _write_csv(outfile + ".core_spectrum.csv", ["k", "ngen", "kmers"],
+               [[k, j, int(spec[j, kk])] for kk, k in enumerate(ks) for j in range(1, n + 1)])
+    rows, summary = [], []
+    for o, order in enumerate(orderings):
+        for j, g in enumerate(order):
+            pan, core = [int(v) for v in res["pan"][o, j]], [int(v) for v in res["core"][o, j]]
+            rows.extend([o + 1, j + 1, fastas[g], k, p, c] for k, p, c in zip(ks, pan, core))
+            summary.append([o + 1, j + 1, fastas[g], *delta_of(pan, ks), *delta_of(core, ks)])
+    _write_csv(outfile + ".core_growth.csv", ["ordering", "step", "fasta", "k", "pan", "core"], rows)
+    _write_csv(outfile + ".core_growthsummary.csv", ["ordering", "step", "fasta", "pan_delta", "pan_k", "core_delta", "core_k"], summary)
+    if groups:
+        rows, summary = [], []
+        for gi, (label, g) in enumerate(zip(labels, groups)):
+            cols = [[int(v) for v in res["groups"][gi, c]] for c in range(3)]
+            rows.extend([label, len(set(g)), k, *(col[kk] for col in cols)] for kk, k in enumerate(ks))
+            summary.append([label, len(set(g)), *(v for col in cols for v in delta_of(col, ks))])
+        _write_csv(outfile + ".core_groups.csv", ["group", "ngen", "k", "core", "private", "signature"], rows)
+        _write_csv(outfile + ".core_groupsummary.csv", ["group", "ngen", "core_delta", "core_k", "private_delta", "private_k",
+                                                        "signature_delta", "signature_k"], summary)
     tree.speciesinfo.save_cardkey(tree.experiment["tool"])
     tree.speciesinfo.save_references(fast=False)
 
@@ -535,6 +615,21 @@ def build_parser():
     gr.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     gr.add_argument("-l", "--label", dest="label", default="")
     gr.set_defaults(func=greedy_command)
+
+    co = subs.add_parser("core", parents=[common, sweep],
+                         description="exact core genome, k-mer frequency spectrum and group markers of up to 64 genomes of a `tree --exact`")
+    co.add_argument("-d", "--dtree", dest="delta_tree", required=True)
+    co.add_argument("-s", "--tag", dest="tag", type=str)
+    co.add_argument("-f", "--fastas", dest="flist_loc", default=None, type=str,
+                    help="the genomes of the universe (default: every leaf), in the order `progressive -f` takes them")
+    co.add_argument("-r", "--orderings", dest="ordering_file", type=str, default=None)
+    co.add_argument("-n", "--norderings", dest="norderings", default=0, type=int,
+                    help="with neither -r nor -n: one ordering, the genomes as listed")
+    co.add_argument("-g", "--groups", dest="groups_loc", default=None, type=str,
+                    help="'fasta<TAB>group' lines: per group its core, its private k-mers and its signature")
+    co.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
+    co.add_argument("-l", "--label", dest="label", default="")
+    co.set_defaults(func=core_command)
 
     # (not in the reference: its every command is a fresh process that shells out to fresh `dashing` processes)
     sv = subs.add_parser("serve", description="keep the GPU context alive and run the commands dandd_amd.host.client forwards")

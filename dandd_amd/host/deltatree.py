@@ -1050,6 +1050,64 @@ class DeltaTree:
                              delta=[d for d, _ in picked], kval=[k for _, k in picked])
         return out
 
+    # ---- core genome, k-mer spectrum and group markers (`dandd core`) -----------------------------------------------------
+    def core_tables(self, fastas, lo, hi, orderings, groups=None):
+        """What the exact membership masks of `fastas` (1..64 leaf FASTAs of an exact tree, the universe; bit i is fastas[i])
+        say over k in [max(1, lo), hi], each table from ONE backend call:
+          spectrum [n+1][K]   k-mers held by exactly j genomes (spectrum_counts)
+          core [o][n][K]      k-mers held by every one of the first j+1 genomes of each ordering (core_progressive_counts)
+          pan [o][n][K]       the union of the same prefixes: progressive_cards where the backend has that table, else one
+                              SubSpider per prefix (the object path of `progressive`)
+          groups [g][3][K]    with `groups` (lists of FASTAs): core (G, 0), private (0, full ^ G) and signature
+                              (G, full ^ G) of every group, three queries each in one select_counts call
+        There is no object path behind the three new tables: a backend without them, or without a table for these leaves,
+        is a ValueError.  -> dict: ks and the tables as integer arrays"""
+        by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
+        nodes = [by_fasta[f] for f in fastas]
+        n = len(nodes)
+        lo, hi = max(1, int(lo)), int(hi)
+        if hi < lo:
+            raise ValueError(f"empty k window {lo}..{hi}")
+        ks = list(range(lo, hi + 1))
+        exp = dict(self.experiment, ksweep=(lo, hi))
+        be = backend_for(exp)
+        for entry in ("spectrum_counts", "core_progressive_counts", "select_counts"):
+            if not hasattr(be, entry):
+                raise ValueError(f"the backend {getattr(be, 'name', type(be).__name__)} has no {entry}: intersections need exact membership masks")
+        paths = self._leaf_files(nodes, lo, hi)
+        orderings = [[int(i) for i in o] for o in orderings]
+
+        def table(got, shape):
+            if got is None:
+                raise ValueError(f"the backend has no membership masks for {n} genomes")
+            return np.asarray(got).astype(np.uint64).reshape(shape)
+        out = {"ks": ks}
+        out["spectrum"] = table(be.spectrum_counts(paths), (n + 1, len(ks)))
+        out["core"] = table(be.core_progressive_counts(paths, orderings), (len(orderings), n, len(ks)))
+        pan = None
+        if hasattr(be, "progressive_cards") and not exp.get("safety") and not os.environ.get("DD_NO_PREFETCH"):
+            pan = be.progressive_cards(paths, orderings)
+        if pan is None:
+            pan = np.zeros((len(orderings), n, len(ks)))
+            seen = {}
+            for o, order in enumerate(orderings):
+                for j in range(n):
+                    key = frozenset(order[:j + 1])
+                    if key not in seen:
+                        sub = SubSpider([nodes[i] for i in sorted(key)], self.speciesinfo, exp)
+                        sub.root.node_ksweep(lo, hi)
+                        seen[key] = [sub.root.ksketches[k].card for k in ks]
+                    pan[o, j] = seen[key]
+        out["pan"] = np.rint(np.asarray(pan, dtype=np.float64)).astype(np.uint64).reshape(len(orderings), n, len(ks))
+        if groups:
+            index = {f: i for i, f in enumerate(fastas)}
+            full = (1 << n) - 1
+            masks = [sum(1 << index[f] for f in set(g)) for g in groups]
+            alls = [m for G in masks for m in (G, 0, G)]
+            nones = [m for G in masks for m in (0, full ^ G, full ^ G)]
+            out["groups"] = table(be.select_counts(paths, alls, nones), (len(groups), 3, len(ks)))
+        return out
+
     # ---- batched GPU union schedules ------------------------------------------------------------------
     def _table_window(self, experiment):
         """[lo, hi] of a union table for climbs over this tree's leaves: the --ksweep window, or a hill-climb's guess -- the

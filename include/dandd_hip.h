@@ -229,6 +229,32 @@ int dd_exact_subsets_device(dd_ctx *, const uint8_t *const *fasta_dev, const siz
  * card[s] = total - (k-mers whose mask avoids s), by a subset-sum transform of the histogram. */
 int dd_exact_subsets_from_hist(const uint64_t *hist /*[2^n]*/, int n, uint64_t *card /*[2^n]*/);
 
+/* ---- exact intersection schedules: core genome, k-mer spectrum, marker k-mers ------------------------------
+ * What the union schedules cannot give and HyperLogLog sketches cannot estimate (inclusion-exclusion over 2^n union
+ * estimates amplifies their error): counts of the distinct k-mers whose membership mask CONTAINS a set of inputs, or has
+ * a given number of bits.  Same sort, same masks, same argument rules (1 <= n <= 64, k in 1..64), budget and passes as
+ * the union schedules above; an empty input, or one without a k-mer of length k, holds nothing, so every core that
+ * includes it is 0.
+ *   spectrum          spec[j][kk] = distinct k-mers held by exactly j of the n inputs; spec[0][kk] = 0; the rows add
+ *                     up to dd_exact_count of all inputs, spec[n] is the core of all
+ *   core_progressive  core[o][j][kk] = k-mers held by every one of inputs ord[o][0..j]; every ordering a permutation of
+ *                     0..n-1 (the rules of dd_exact_progressive); core[o][0] = |input ord[o][0]|, core[o][n-1] = spec[n]
+ *   select            count[q][kk] = k-mers held by every input of all[q] and by no input of none[q] (bit i: input i);
+ *                     any nq >= 1; a bit >= n set in all[q] or none[q]: DD_EINVAL; all = none = 0 counts every distinct
+ *                     k-mer; all & none != 0 is legal and counts 0.  A group G of a clade: core (G, 0), private
+ *                     (0, full ^ G), signature (G, full ^ G). */
+int dd_exact_spectrum(dd_ctx *, const char *const *paths, int n, int kmin, int kmax, uint64_t *spec /*[n+1][K]*/);
+int dd_exact_core_progressive(dd_ctx *, const char *const *paths, int n, int kmin, int kmax,
+                              const int32_t *orderings /*[norder][n]*/, int norder, uint64_t *core /*[norder][n][K]*/);
+int dd_exact_select(dd_ctx *, const char *const *paths, int n, int kmin, int kmax, const uint64_t *all /*[nq]*/,
+                    const uint64_t *none /*[nq]*/, int nq, uint64_t *count /*[nq][K]*/);
+int dd_exact_spectrum_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
+                             uint64_t *spec);
+int dd_exact_core_progressive_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin,
+                                     int kmax, const int32_t *orderings, int norder, uint64_t *core);
+int dd_exact_select_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
+                           const uint64_t *all, const uint64_t *none, int nq, uint64_t *count);
+
 /* ---- measurement hooks (bench.py) -------------------------------------------------
  * When enabled, every launch of kernel `which` is bracketed by HIP events on the
  * context's stream.  dd_timing_read synchronises the stream and returns the summed
