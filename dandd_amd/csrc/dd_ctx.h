@@ -1,6 +1,6 @@
 // dd_ctx.h -- the context behind the C ABI's opaque dd_ctx, and the host-side helpers the ABI's sources share
 // (dd_api.hip: context, timing and stats, synth, dd_plan_sweep; dd_sketch_api.hip: sketch; dd_k2_api.hip: union, card and the
-// HLL schedules; dd_exact_api.hip: exact count and schedules; dd_ingest.hip: the file-ingestion pipeline; dd_comm.hip: RCCL).
+// HLL schedules; dd_exact_api.hip: exact count, schedules and greedy; dd_ingest.hip: the file-ingestion pipeline; dd_comm.hip: RCCL).
 // Callers see dandd_hip.h only.
 #pragma once
 #include "../../include/dandd_hip.h"
@@ -116,6 +116,7 @@ struct dd_ctx {
     std::vector<hipEvent_t> pool;
     // workspaces
     DevBuf tokens, scratch, tables, fasta, regs, ptrs, hist, est, ord, bitmaps, bigmaps, exact, buckets, gram, synth;
+    DevBuf masks;  // dd_exact_greedy: cursor and overflow word | gains [64][64] | the mask streams of every k of the call
     StageSet stage[2];
     int stage_cur = 0;  // the set of the running (or last) sketch call
     // the job tables of the last few sketch calls: a call over genomes of the same sizes and the same k range (a
@@ -270,6 +271,43 @@ inline int layout_tokens(dd_ctx* c, const uint8_t* const* fasta_dev, const size_
         max_chunks = std::max(max_chunks, ptab[g].nchunks);
     }
     return DD_OK;
+}
+
+// the walk rules that the HLL and the exact greedy share: mode, cand[] over n rows, nfixed <= nsteps <= ncand
+inline int check_greedy_walk(int n, int mode, const int32_t* cand, int ncand, int nfixed, int nsteps) {
+    if (mode != DD_GREEDY_MAX && mode != DD_GREEDY_MIN) return fail(DD_EINVAL, "mode=%d: DD_GREEDY_MAX (0) or DD_GREEDY_MIN (1)", mode);
+    if (ncand < 1 || ncand > n) return fail(DD_EINVAL, "ncand=%d outside 1..%d", ncand, n);
+    std::vector<char> seen(n, 0);
+    for (int i = 0; i < ncand; ++i) {
+        if (cand[i] < 0 || cand[i] >= n) return fail(DD_EINVAL, "cand[%d]=%d outside 0..%d", i, cand[i], n - 1);
+        if (seen[cand[i]]) return fail(DD_EINVAL, "cand[%d]=%d is a repeat: candidates are distinct", i, cand[i]);
+        seen[cand[i]] = 1;
+    }
+    if (nfixed < 0 || nfixed > nsteps) return fail(DD_EINVAL, "nfixed=%d outside 0..nsteps=%d", nfixed, nsteps);
+    if (nsteps < 1 || nsteps > ncand) return fail(DD_EINVAL, "nsteps=%d outside 1..ncand=%d", nsteps, ncand);
+    return DD_OK;
+}
+
+// the selection rule of include/dandd_hip.h (dd_greedy): the largest card / k of the window, a later k winning a tie
+inline double window_delta(const double* card, int K, int kmin) {
+    double best = 0.0;
+    for (int kk = 0; kk < K; ++kk) {
+        const double v = card[kk] / (double)(kmin + kk);
+        if (best <= v) best = v;
+    }
+    return best;
+}
+
+// ... and between candidates: the row of cards[nrows][K] with the largest (DD_GREEDY_MAX) or smallest window delta, the
+// first of equals
+inline int greedy_pick(const double* cards, int nrows, int K, int kmin, int mode) {
+    int pick = 0;
+    double best = window_delta(cards, K, kmin);
+    for (int r = 1; r < nrows; ++r) {
+        const double d = window_delta(cards + (size_t)r * K, K, kmin);
+        if (mode == DD_GREEDY_MAX ? d > best : d < best) best = d, pick = r;
+    }
+    return pick;
 }
 
 // the group[] / ngroups rules that the HLL and the exact leave-out share

@@ -1,7 +1,7 @@
 // dd_exact_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h): dd_exact_count*, the exact union
-// schedules (dd_exact_pairwise / _progressive / _leave_out / _subsets) and the exact intersection schedules
-// (dd_exact_spectrum / _core_progressive / _select).  Host-side orchestration only; the kernels are in dd_exact.hip and
-// dd_exact_sched.hip.
+// schedules (dd_exact_pairwise / _progressive / _leave_out / _subsets), the exact intersection schedules
+// (dd_exact_spectrum / _core_progressive / _select) and the exact greedy walk (dd_exact_greedy).  Host-side orchestration
+// only; the kernels are in dd_exact.hip, dd_exact_sched.hip and dd_exact_greedy.hip.
 #include <functional>
 #include "dd_ctx.h"
 
@@ -269,10 +269,17 @@ int dd_exact_count(dd_ctx* c, const char* const* paths, int n, int k, uint64_t* 
 // dd_exact_sched.hip: one sort of the universe per k, a membership mask per distinct k-mer, one accumulator per schedule.
 namespace {
 
+// what a caller of exact_schedule does around the loop over k (dd_exact_greedy: its mask store)
+struct ScheduleHooks {
+    std::function<int(const ExactInputs&, dd::ExactSched&)> begin;                             // the inputs are packed and hold a token
+    std::function<int(int kk, const std::vector<unsigned long long>& acc)> after_k;            // k = kmin + kk is done and waited for
+};
+
 // The driver behind every schedule: K0 once, then for every k extract (with the genome's index) -> sort -> reduce +
 // accumulate through exact_passes.  out[kk] receives the accumulator's exact_sched_acc_words() counts of k = kmin + kk.
 int exact_schedule(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, dd::ExactSched s,
-                   const std::vector<uint64_t>& table, std::vector<std::vector<unsigned long long>>& out) {
+                   const std::vector<uint64_t>& table, std::vector<std::vector<unsigned long long>>& out,
+                   const ScheduleHooks* hooks = nullptr) {
     hipStream_t st = c->stream;
     int rc;
     const size_t words = dd::exact_sched_acc_words(s);
@@ -287,6 +294,7 @@ int exact_schedule(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nby
         if ((rc = stage_table(c, c->ord, table.data(), table.size() * sizeof(uint64_t)))) return rc;
         s.table = static_cast<const uint64_t*>(c->ord.p);
     }
+    if (hooks && (rc = hooks->begin(in, s))) return rc;
     int most_passes = 0;
     for (int k = kmin; k <= kmax; ++k) {
         DD_HIP(hipMemsetAsync(s.acc, 0, words * sizeof(unsigned long long), st));
@@ -301,6 +309,7 @@ int exact_schedule(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nby
         DD_HIP(hipMemcpyAsync(out[(size_t)(k - kmin)].data(), s.acc, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         DD_HIP(hipStreamSynchronize(st));
         most_passes = std::max(most_passes, c->st_blocks);
+        if (hooks && (rc = hooks->after_k(k - kmin, out[(size_t)(k - kmin)]))) return rc;
     }
     c->st_blocks = most_passes;   // (dd_last_sketch_stats: the passes of the k that took the most)
     return DD_OK;
@@ -522,6 +531,111 @@ int dd_exact_select_device(dd_ctx* c, const uint8_t* const* fasta_dev, const siz
     for (size_t kk = 0; kk < K; ++kk)
         for (int q = 0; q < nq; ++q) count[(size_t)q * K + kk] = acc[kk][1 + q];
     return DD_OK;
+}
+
+// ------------------------------------------------------------------------ exact greedy
+// dd_exact_greedy.hip: the masks of every k kept in HBM (kSchedStream), one gains launch per step, the pick on the host.
+namespace {
+
+size_t exact_masks_budget() {
+    size_t budget = (size_t)24 << 30;
+    if (const char* e = getenv("DD_EXACT_MASKS_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
+    return budget;
+}
+
+// c->masks: cursor, overflow word (256 B) | gains [64][64] u64 | the streams, k = kmin first
+constexpr size_t kMaskHeadBytes = 256, kGainBytes = (size_t)dd::kGreedyMaxK * 64 * sizeof(unsigned long long);
+
+}  // namespace
+
+int dd_exact_greedy_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, int mode,
+                           const int32_t* cand, int ncand, int nfixed, int nsteps, int32_t* order, uint64_t* card) {
+    if (exact_sched_args(c, fasta_dev, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    if (!nbytes || !cand || !order) return fail(DD_EINVAL, "null argument");
+    if (check_greedy_walk(n, mode, cand, ncand, nfixed, nsteps)) return DD_EINVAL;
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    const int K = kmax - kmin + 1;
+    const size_t budget = exact_masks_budget();
+    dd::GreedySegments seg{};   // off[kk]: where the stream of k = kmin + kk starts = the cursor when the k before it was done
+    seg.K = K;
+    size_t cap = 0;
+    ScheduleHooks hooks;
+    hooks.begin = [&](const ExactInputs& in, dd::ExactSched& s) -> int {
+        cap = std::min(budget / sizeof(uint64_t), (size_t)K * in.slots);   // (a k holds no more distinct k-mers than the inputs have slots)
+        if (c->masks.reserve(kMaskHeadBytes + kGainBytes + cap * sizeof(uint64_t)))
+            return fail(DD_ENOMEM, "exact greedy: no device memory for a mask store of %zu masks (DD_EXACT_MASKS_MB sets its budget, %zu MiB now)",
+                        cap, budget >> 20);
+        char* mb = static_cast<char*>(c->masks.p);
+        DD_HIP(hipMemsetAsync(mb, 0, kMaskHeadBytes, st));
+        s.cursor = reinterpret_cast<unsigned long long*>(mb);
+        s.overflow = s.cursor + 1;
+        s.store = reinterpret_cast<uint64_t*>(mb + kMaskHeadBytes + kGainBytes);
+        s.cap = cap;
+        return DD_OK;
+    };
+    hooks.after_k = [&](int kk, const std::vector<unsigned long long>& acc) -> int {
+        unsigned long long h[2] = {0, 0};   // cursor, overflow
+        DD_HIP(hipMemcpyAsync(h, c->masks.p, sizeof h, hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+        if (h[1])
+            return fail(DD_ENOMEM, "exact greedy: the mask streams of k = %d..%d need %llu masks, the store holds %zu (DD_EXACT_MASKS_MB sets its budget, %zu MiB now)",
+                        kmin, kmin + kk, h[0], cap, budget >> 20);
+        if (h[0] - seg.off[kk] != acc[0])
+            return fail(DD_EHIP, "exact greedy: k=%d appended %llu masks to its stream, %llu distinct k-mers were counted", kmin + kk,
+                        h[0] - seg.off[kk], acc[0]);
+        seg.off[kk + 1] = h[0];
+        return DD_OK;
+    };
+    std::vector<std::vector<unsigned long long>> acc;
+    int rc;
+    if ((rc = exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedStream, n, 0, 0, nullptr, nullptr}, {}, acc, &hooks))) return rc;
+
+    // the walk: per step the gains of every input at every k, then dd_greedy's rule on |C|_k + gain
+    const unsigned long long total = seg.off[K];   // (0: no input holds a token, every union is empty)
+    const size_t gbytes = (size_t)K * 64 * sizeof(unsigned long long);
+    unsigned long long* gain_dev = total ? reinterpret_cast<unsigned long long*>(static_cast<char*>(c->masks.p) + kMaskHeadBytes) : nullptr;
+    const uint64_t* store = total ? reinterpret_cast<const uint64_t*>(static_cast<char*>(c->masks.p) + kMaskHeadBytes + kGainBytes) : nullptr;
+    std::vector<unsigned long long> gain((size_t)K * 64, 0ull), running((size_t)K, 0ull);
+    std::vector<int32_t> left(cand + nfixed, cand + ncand), chosen_order((size_t)nsteps);   // left: in tie-break order throughout
+    std::vector<uint64_t> cards((size_t)nsteps * K);
+    std::vector<double> rows((size_t)ncand * K);
+    uint64_t chosen = 0;
+    for (int j = 0; j < nsteps; ++j) {
+        if (total) {
+            DD_HIP(hipMemsetAsync(gain_dev, 0, gbytes, st));
+            {
+                Span sp(c, DD_KERNEL_EXACT);
+                dd::launch_exact_greedy_gains(store, seg, n, chosen, gain_dev, st);
+            }
+            DD_HIP(hipGetLastError());
+            DD_HIP(hipMemcpyAsync(gain.data(), gain_dev, gbytes, hipMemcpyDeviceToHost, st));
+            DD_HIP(hipStreamSynchronize(st));
+        }
+        const bool given = j < nfixed;
+        const int32_t* from = given ? cand + j : left.data();
+        const int nrows = given ? 1 : (int)left.size();
+        for (int r = 0; r < nrows; ++r)
+            for (int kk = 0; kk < K; ++kk) rows[(size_t)r * K + kk] = (double)(running[kk] + gain[(size_t)kk * 64 + from[r]]);
+        const int pick = greedy_pick(rows.data(), nrows, K, kmin, mode);
+        const int32_t g = from[pick];
+        chosen_order[j] = g;
+        for (int kk = 0; kk < K; ++kk) cards[(size_t)j * K + kk] = running[kk] += gain[(size_t)kk * 64 + g];
+        chosen |= 1ull << g;
+        if (!given) left.erase(left.begin() + pick);
+    }
+    memcpy(order, chosen_order.data(), sizeof(int32_t) * nsteps);   // (nothing is written before everything is known)
+    memcpy(card, cards.data(), sizeof(uint64_t) * cards.size());
+    return DD_OK;
+}
+
+int dd_exact_greedy(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, int mode, const int32_t* cand, int ncand, int nfixed,
+                    int nsteps, int32_t* order, uint64_t* card) {
+    if (exact_sched_args(c, paths, n, 64, kmin, kmax, card)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) {
+        return dd_exact_greedy_device(c, p, s, n, kmin, kmax, mode, cand, ncand, nfixed, nsteps, order, card);
+    });
 }
 
 int dd_exact_spectrum(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, uint64_t* spec) {

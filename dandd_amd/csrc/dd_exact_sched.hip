@@ -3,7 +3,7 @@
 // The exact counterparts of dd_pairwise / dd_progressive / dd_leave_out / dd_subsets.  Every k-mer occurrence of all n
 // genomes is extracted with the index of its genome (dd_exact.hip, TAG), radix-sorted by the k-mer, and the sorted
 // run of each distinct k-mer is OR-ed into a 64-bit MEMBERSHIP MASK (bit i: genome i holds it).  Every schedule is an
-// additive statistic of those masks, so the masks never reach HBM: a workgroup reduces a chunk of the sorted array
+// additive statistic of those masks, so the masks never reach HBM (but for the stream, below): a workgroup reduces a chunk of the sorted array
 // into an LDS tile of masks and hands the tile to the schedule's accumulator, whose u64 counts add up over chunks,
 // passes and bins of the k-mer space.
 //
@@ -28,6 +28,10 @@
 //                                the full mask is the last bin of every ordering and is counted once, in a register
 //                   select       (all, none) pairs in LDS; a thread owns up to 4 queries and a stripe of the tile and
 //                                counts its hits in registers
+//                 and the one that is no statistic: a walk that picks by the masks of EVERY k at once (dd_exact_greedy.hip)
+//                 needs them to outlive their sort
+//                   stream       the tile appended to a store in HBM, 8 bytes per distinct k-mer, at a position reserved
+//                                with one atomicAdd per tile
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
@@ -187,6 +191,10 @@ struct SchedArgs {
     unsigned long long* acc;          // [0] = M (masks seen), then the schedule's counts
     int add_m;
     int slices;                       // subsets, n = 16: workgroup w counts the masks whose top bit is w % 2 (every chunk is reduced twice)
+    uint64_t* store;                  // stream: where the masks go, the device cursor they are reserved on, the word a tile
+    unsigned long long* cursor;       //   that would pass `cap` masks sets
+    unsigned long long* overflow;
+    unsigned long long cap;
 };
 
 // ---- accumulators: init (LDS state), consume (one tile of masks; whole workgroup), flush (once per workgroup) ----
@@ -437,6 +445,23 @@ struct AccSelect {
     }
 };
 
+struct AccStream {
+    unsigned long long* at;   // [1]: where this tile goes, from the thread that reserved it to the others (no state: rewritten per tile)
+    DD_D void init(const SchedArgs&, uint64_t* dyn) { at = reinterpret_cast<unsigned long long*>(dyn); }
+    DD_D void consume(const SchedArgs& a, const uint64_t* tile, uint32_t cnt, uint32_t) {
+        if (!cnt) return;   // (cnt is the same in every thread)
+        if (threadIdx.x == 0) *at = atomicAdd(a.cursor, (unsigned long long)cnt);
+        __syncthreads();
+        const unsigned long long base = *at;
+        if (base + cnt <= a.cap) {
+            for (uint32_t i = threadIdx.x; i < cnt; i += kThreads) a.store[base + i] = tile[i];
+        } else if (threadIdx.x == 0) {
+            *a.overflow = 1ull;
+        }
+    }
+    DD_D void flush(const SchedArgs&, uint32_t) {}
+};
+
 template <bool WIDE, class Acc>
 __global__ __launch_bounds__(kThreads) void sched_kernel(SortedView s, const uint64_t* __restrict__ carry, size_t nchunks,
                                                        SchedArgs a) {
@@ -494,6 +519,7 @@ size_t sched_dyn_lds(int kind, int n, int norder) {
         case kSchedSpectrum: return 65 * 4 + 12;
         case kSchedCoreProgressive: return (size_t)norder * n * 12 + 16;
         case kSchedSelect: return (size_t)norder * 20 + 16;
+        case kSchedStream: return 16;
         default: return (size_t)4 << std::min(n, kExactSubsetsLdsN);
     }
 }
@@ -508,6 +534,7 @@ size_t exact_sched_acc_words(const ExactSched& s) {
         case kSchedSpectrum: return 1 + (size_t)s.n + 1;
         case kSchedCoreProgressive: return 1 + (size_t)s.norder * s.n;
         case kSchedSelect: return 1 + (size_t)s.norder;
+        case kSchedStream: return 1;
         default: return 1 + ((size_t)1 << s.n);
     }
 }
@@ -566,7 +593,7 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
     const int items = (by_order || by_query) ? s.norder : 1, per = by_order ? max_orderings(s.n) : (by_query ? kSelectBatch : 1);
     const size_t tstride = by_order ? (size_t)s.n : 2, astride = by_order ? (size_t)s.n : 1;
     for (int o0 = 0; o0 < items; o0 += per) {
-        SchedArgs a{s.n, 0, s.ngroups, s.table, s.acc, o0 == 0, 1};
+        SchedArgs a{s.n, 0, s.ngroups, s.table, s.acc, o0 == 0, 1, s.store, s.cursor, s.overflow, s.cap};
         if (s.kind == kSchedSubsets && s.n > kExactSubsetsLdsN) a.slices = 1 << (s.n - kExactSubsetsLdsN);
         if (by_order || by_query) {
             a.norder = std::min(per, items - o0);
@@ -588,6 +615,7 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
                 case kSchedSpectrum: launch_full_lds<sched_kernel<W, AccSpectrum>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
                 case kSchedCoreProgressive: launch_full_lds<sched_kernel<W, AccCoreProgressive>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
                 case kSchedSelect: launch_full_lds<sched_kernel<W, AccSelect>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
+                case kSchedStream: launch_full_lds<sched_kernel<W, AccStream>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
                 default: launch_full_lds<sched_kernel<W, AccSubsets>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
             }
         });

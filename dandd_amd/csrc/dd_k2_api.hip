@@ -332,27 +332,8 @@ int greedy_args(dd_ctx* c, const uint8_t* leaf, int n, int K, int kmin, int mode
     if (check_ctx(c)) return DD_EINVAL;
     if (n < 1 || K < 1 || !leaf || !cand || !order || !card) return fail(DD_EINVAL, "bad argument");
     if (kmin < 1 || kmin + K - 1 > 64) return fail(DD_EINVAL, "k window %d..%d outside 1..64", kmin, kmin + K - 1);
-    if (mode != DD_GREEDY_MAX && mode != DD_GREEDY_MIN) return fail(DD_EINVAL, "mode=%d: DD_GREEDY_MAX (0) or DD_GREEDY_MIN (1)", mode);
-    if (ncand < 1 || ncand > n) return fail(DD_EINVAL, "ncand=%d outside 1..%d", ncand, n);
-    std::vector<char> seen(n, 0);
-    for (int i = 0; i < ncand; ++i) {
-        if (cand[i] < 0 || cand[i] >= n) return fail(DD_EINVAL, "cand[%d]=%d outside 0..%d", i, cand[i], n - 1);
-        if (seen[cand[i]]) return fail(DD_EINVAL, "cand[%d]=%d is a repeat: candidates are distinct", i, cand[i]);
-        seen[cand[i]] = 1;
-    }
-    if (nfixed < 0 || nfixed > nsteps) return fail(DD_EINVAL, "nfixed=%d outside 0..nsteps=%d", nfixed, nsteps);
-    if (nsteps < 1 || nsteps > ncand) return fail(DD_EINVAL, "nsteps=%d outside 1..ncand=%d", nsteps, ncand);
+    if (check_greedy_walk(n, mode, cand, ncand, nfixed, nsteps)) return DD_EINVAL;
     return DD_OK;
-}
-
-// the selection rule of include/dandd_hip.h: the largest card / k of the window, a later k winning a tie
-double window_delta(const double* card, int K, int kmin) {
-    double best = 0.0;
-    for (int kk = 0; kk < K; ++kk) {
-        const double v = card[kk] / (double)(kmin + kk);
-        if (best <= v) best = v;
-    }
-    return best;
 }
 
 }  // namespace
@@ -400,12 +381,7 @@ int dd_greedy_device(dd_ctx* c, const uint8_t* leaf_dev, int n, int K, int kmin,
         const int32_t* rows = given ? cand + j : left.data();
         const int nrows = given ? 1 : (int)left.size();
         if ((rc = extend_step(c, j ? base : nullptr, leaf_dev, K, rows, nrows, cards.data()))) return rc;
-        int pick = 0;
-        double best = window_delta(cards.data(), K, kmin);
-        for (int r = 1; r < nrows; ++r) {
-            const double d = window_delta(cards.data() + (size_t)r * K, K, kmin);
-            if (mode == DD_GREEDY_MAX ? d > best : d < best) best = d, pick = r;
-        }
+        const int pick = greedy_pick(cards.data(), nrows, K, kmin, mode);
         order[j] = rows[pick];
         memcpy(card + (size_t)j * K, cards.data() + (size_t)pick * K, sizeof(double) * K);
         if (!given) left.erase(left.begin() + pick);

@@ -275,7 +275,8 @@ hipError_t launch_exact_sort_count(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt,
 inline constexpr int exact_tag_mode(int k) { return (k <= 32 ? 2 * k : 2 * k - 64) <= 56 ? 1 : 2; }
 constexpr int kExactSubsetsLdsN = 15;   // subsets: 2^n histogram bins in LDS (u32, 128 KiB at 15); n = 16 as two halves by the top bit
 enum { kSchedPairwise = 0, kSchedProgressive = 1, kSchedLeaveOut = 2, kSchedSubsets = 3,
-       kSchedSpectrum = 4, kSchedCoreProgressive = 5, kSchedSelect = 6 };   // 4..6: the intersection schedules
+       kSchedSpectrum = 4, kSchedCoreProgressive = 5, kSchedSelect = 6,    // 4..6: the intersection schedules
+       kSchedStream = 7 };   // the masks themselves, kept in HBM for a walk that needs every k's masks at once (dd_exact_greedy.hip)
 struct ExactSorted {            // where launch_exact_sort_tagged left the sorted k-mers
     const uint64_t* lo;
     const uint64_t* hi;         // k > 32
@@ -296,6 +297,14 @@ struct ExactSched {
                                 //   spectrum: then [n+1] k-mers held by exactly j genomes
                                 //   core-progressive: then [norder][n] k-mers that hold genomes 0..j of ordering o and not genome j+1
                                 //   select: then [norder] k-mers whose mask contains all[q] and meets none[q] nowhere
+                                //   stream: nothing more
+    // stream: every mask is appended to store[] at a position reserved on *cursor (one reservation per tile of masks, so their
+    // order is whatever the reservations give); a tile that would pass `cap` sets *overflow and is not written, the cursor
+    // still advances: it says how many masks the store would have had to hold
+    uint64_t* store = nullptr;
+    unsigned long long* cursor = nullptr;
+    unsigned long long* overflow = nullptr;
+    unsigned long long cap = 0;
 };
 size_t exact_sched_acc_words(const ExactSched& s);
 size_t exact_sched_temp_bytes(size_t n, int k);
@@ -303,6 +312,19 @@ size_t exact_sched_scratch_bytes(size_t count);
 hipError_t launch_exact_sort_tagged(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, uint8_t* g, uint8_t* g_alt,
                                     size_t n, int k, void* temp, size_t temp_bytes, hipStream_t st, ExactSorted* out);
 hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, const ExactSched& s, void* scratch, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
+// exact greedy walk (dd_exact_greedy.hip) over the mask streams of kSchedStream: one launch per step of the walk reads
+// every stream once.  gain[kk][b] += masks of stream kk (store[seg.off[kk] .. seg.off[kk + 1])) that meet `chosen` nowhere
+// and hold bit b, for every b < 64 (a bit of `chosen` gains 0).  gain_dev [K][64], zeroed by the caller.
+// ---------------------------------------------------------------------------------------
+constexpr int kGreedyMaxK = 64;
+struct GreedySegments {
+    int K;
+    unsigned long long off[kGreedyMaxK + 1];   // ascending; off[K] = masks in the store
+};
+void launch_exact_greedy_gains(const uint64_t* store, const GreedySegments& seg, int n, uint64_t chosen, unsigned long long* gain_dev,
+                               hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // gzip inflated on the device: BGZF blocks (dd_ginflate.hip: one wave per block, text straight into the FASTA buffer) and

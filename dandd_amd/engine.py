@@ -33,6 +33,7 @@ EXPORTS = [
     "dd_exact_subsets_from_hist",
     "dd_exact_spectrum", "dd_exact_core_progressive", "dd_exact_select",
     "dd_exact_spectrum_device", "dd_exact_core_progressive_device", "dd_exact_select_device",
+    "dd_exact_greedy", "dd_exact_greedy_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
     "dd_comm_unique_id", "dd_comm_init", "dd_comm_destroy", "dd_comm_info", "dd_allreduce_max_u8", "dd_allgather_u8",
@@ -41,7 +42,10 @@ COMM_ID_BYTES = 128   # include/dandd_hip.h: DD_COMM_ID_BYTES
 
 
 class EngineError(RuntimeError):
-    pass
+    code = None   # the library's DD_E* code, where the library raised it
+
+
+ENOMEM = -5   # include/dandd_hip.h: DD_ENOMEM
 
 
 _lib = None
@@ -165,6 +169,10 @@ def load_library(path=None):
         fn = getattr(lib, name)
         fn.restype = i32
         fn.argtypes = [vp] + src + [i32, i32, i32] + extra + [vp]
+    for name, src in (("dd_exact_greedy", [paths_t]), ("dd_exact_greedy_device", [ptrs_t, sizes_t])):
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = [vp] + src + [i32, i32, i32, i32, vp, i32, i32, i32, vp, vp]
     lib.dd_exact_subsets_from_hist.restype = i32
     lib.dd_exact_subsets_from_hist.argtypes = [vp, i32, vp]
     lib.dd_timing_enable.restype = i32
@@ -327,7 +335,9 @@ class Engine:
 
     def _check(self, rc):
         if rc != 0:
-            raise EngineError(f"libdandd_hip error {rc}: {self._lib.dd_last_error().decode()}")
+            err = EngineError(f"libdandd_hip error {rc}: {self._lib.dd_last_error().decode()}")
+            err.code = rc
+            raise err
 
     def set_stream(self, hip_stream):
         self._check(self._lib.dd_set_stream(self._ctx, C.c_void_p(int(hip_stream) if hip_stream else 0)))
@@ -680,6 +690,28 @@ class Engine:
 
     def exact_select_device(self, fasta_ptrs, nbytes, kmin, kmax, all_masks, none_masks):
         return self._exact_select(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, all_masks, none_masks)
+
+    # -- exact greedy: the masks of every k kept on the device, one read of them per step (dd_exact_greedy.hip) ---------
+    def _exact_greedy(self, src, kmin, kmax, mode, cand, nfixed, nsteps):
+        args, n, suffix = src
+        K = max(int(kmax) - int(kmin) + 1, 1)
+        cand = np.ascontiguousarray(np.arange(n) if cand is None else cand, dtype=np.int32).reshape(-1)
+        nsteps = cand.size if nsteps is None else int(nsteps)
+        order = np.zeros(max(nsteps, 0), dtype=np.int32)
+        card = np.zeros((max(nsteps, 0), K), dtype=np.uint64)
+        self._check(getattr(self._lib, f"dd_exact_greedy{suffix}")(self._ctx, *args, n, int(kmin), int(kmax), int(mode), cand.ctypes.data,
+                                                                  cand.size, int(nfixed), nsteps, order.ctypes.data, card.ctypes.data))
+        return order, card
+
+    def exact_greedy(self, paths, kmin, kmax, mode, cand=None, nfixed=0, nsteps=None):
+        """FASTA files (n <= 64); mode GREEDY_MAX / GREEDY_MIN; cand: distinct files in tie-break order (None: all), the first
+        nfixed of them a given start -> (order int32 [nsteps], card uint64 [nsteps][K]): the steepest (flattest) ordering by the
+        selection rule of include/dandd_hip.h and the distinct k-mers of its prefix unions.  EngineError with code ENOMEM when
+        the masks of the window do not fit DD_EXACT_MASKS_MB."""
+        return self._exact_greedy(self._exact_src(paths=paths), kmin, kmax, mode, cand, nfixed, nsteps)
+
+    def exact_greedy_device(self, fasta_ptrs, nbytes, kmin, kmax, mode, cand=None, nfixed=0, nsteps=None):
+        return self._exact_greedy(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, mode, cand, nfixed, nsteps)
 
     # -- measurement ----------------------------------------------------------------------
     def timing_enable(self, on=True):

@@ -329,6 +329,28 @@ class HipExactBackend:
         _, files, kmin, kmax = win
         return self.engine.exact_select(files, kmin, kmax, all_masks, none_masks)
 
+    def greedy_cards(self, leaf_paths, mode, nfixed, nsteps, kmin):
+        """HipBackend.greedy_cards on exact counts (dd_exact_greedy): -> (order [nsteps] as indices into leaf_paths, cards
+        float64 [nsteps][K]), ties going to the leaf the caller lists first.  None -- the caller goes on as without this
+        entry -- for n <= 16 (the table of all subsets answers every step there), for more leaves than a mask has bits, and
+        when the masks of the window do not fit their store (DD_EXACT_MASKS_MB)."""
+        from ..engine import ENOMEM, GREEDY_MAX, GREEDY_MIN, EngineError
+        if len(leaf_paths) <= self.MAX_SUBSET_LEAVES:
+            return None
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, first, last = win
+        if int(kmin) != first:
+            raise ValueError(f"the leaf databases start at k={first}, the walk at k={kmin}")
+        try:
+            order, cards = self.engine.exact_greedy(files, first, last, {"max": GREEDY_MAX, "min": GREEDY_MIN}[mode], None, nfixed, nsteps)
+        except EngineError as e:
+            if e.code == ENOMEM:
+                return None
+            raise
+        return order, cards.astype(np.float64)
+
     def close(self):
         self.engine.close()
 

@@ -1001,10 +1001,12 @@ class DeltaTree:
         order) and then adds at each step the genome whose union with the chosen ones has the largest (smallest) window delta
         over k in [max(1, lo), hi], until `steps` genomes stand (default: all).  The rule is _greedy_pick's -- the largest
         card / k, ties between k to the larger k, ties between genomes to the earlier one of `fastas` -- on every path:
-          * Schedule path (a backend with greedy_cards, the GPU): one call per mode over the leaf slab.
+          * Schedule path (a backend with greedy_cards, the GPU): one call per mode -- over the leaf slab, or, on exact trees
+            of 17..64 genomes, over the membership masks of one sort per k.
           * n <= 16 and a backend with subset_cards (exact trees on the GPU): a walk over that one table.
-          * Object path (--safe, DD_NO_PREFETCH, a backend with neither, the CPU checkers, exact trees of n > 16): one
-            SubSpider per (step, candidate), through the cardinality cache.
+          * Object path (--safe, DD_NO_PREFETCH, a backend with neither, the CPU checkers, exact trees of more than 64
+            genomes or whose masks do not fit their store): one SubSpider per (step, candidate), through the cardinality
+            cache.
         -> dict: ks, and per mode dict(order: FASTAs [steps], cards [steps][K], delta [steps], kval [steps])"""
         by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
         base = list(base)

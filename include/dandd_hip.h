@@ -255,6 +255,29 @@ int dd_exact_core_progressive_device(dd_ctx *, const uint8_t *const *fasta_dev, 
 int dd_exact_select_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
                            const uint64_t *all, const uint64_t *none, int nq, uint64_t *count);
 
+/* ---- exact greedy orderings -----------------------------------------------------------------------------------
+ * dd_greedy on exact counts, for `dandd greedy` on trees built with `--exact`: the same walk, the same SELECTION RULE
+ * (above, word for word: the largest card[kk] / (kmin + kk) in IEEE double, ties between k to the LARGER k, ties between
+ * candidates to the one that comes FIRST in cand), over numbers of distinct k-mers instead of estimates.
+ * cand[ncand]: distinct inputs in 0..n-1, in tie-break order; order[j] = cand[j] for j < nfixed; nfixed <= nsteps <= ncand,
+ * nsteps >= 1; mode DD_GREEDY_MAX or DD_GREEDY_MIN.  card[j][kk] = |union of inputs order[0..j]| at k = kmin + kk, exact.
+ * Inputs that are not in cand are never chosen and contribute nothing.  1 <= n <= 64 and k in 1..64, as for the schedules
+ * above; an empty input, or one without a k-mer of length k, holds nothing at that k.
+ * The k-mers are sorted ONCE per k, as for the schedules (same budget and passes: DD_EXACT_MB), and what the sort leaves --
+ * one 64-bit membership mask per distinct k-mer -- is kept in HBM for every k of the window, because a step picks by the
+ * largest card / k over the WHOLE window: with C the inputs chosen so far,
+ *     |C U c|_k = |C|_k + #{ masks m of k : m & C == 0 and bit c of m }
+ * so a step is one read of the stored masks (dd_exact_greedy.hip) and no further sort.  The store has a budget of its own,
+ * 24 GiB (DD_EXACT_MASKS_MB overrides; 8 bytes per distinct k-mer and k).  When the masks of the window do not fit it the
+ * call returns DD_ENOMEM -- the message gives the masks needed so far and the budget -- and writes nothing to order or card:
+ * there is no partial result. */
+int dd_exact_greedy(dd_ctx *, const char *const *paths, int n, int kmin, int kmax, int mode,
+                    const int32_t *cand /*[ncand]*/, int ncand, int nfixed, int nsteps,
+                    int32_t *order /*[nsteps]*/, uint64_t *card /*[nsteps][K]*/);
+int dd_exact_greedy_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
+                           int mode, const int32_t *cand, int ncand, int nfixed, int nsteps, int32_t *order,
+                           uint64_t *card);
+
 /* ---- measurement hooks (bench.py) -------------------------------------------------
  * When enabled, every launch of kernel `which` is bracketed by HIP events on the
  * context's stream.  dd_timing_read synchronises the stream and returns the summed
@@ -262,7 +285,7 @@ int dd_exact_select_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules */
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy */
 #define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);
