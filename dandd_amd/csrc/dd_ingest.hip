@@ -542,7 +542,11 @@ struct Ingest {
         // (device-inflated batches: no small batch at the end -- a launch of the inflate kernel over two files' pieces takes as
         // long as one over five, with a quarter of the chip: ten gzip -1 files went out as 4 + 4 + 2 and the last two cost
         // 22 of the call's 60 ms.  What would be left is fewer than half a batch: it joins this one, waited for.)
-        if (pl.full_batches && i + count < nfiles && nfiles - (i + count) < (want + 1) / 2) {
+        // (Only where the loaders can bring those files NOW.  A file beyond the window gets its buffer when a batch in flight
+        // is retired, and that happens after this returns: waiting for it here is waiting for ever -- ten BGZF files in
+        // batches of three with three loaders, a window of nine: the third batch waited for file 9.  Such a call ends
+        // with a small batch instead.)
+        if (pl.full_batches && i + count < nfiles && nfiles - (i + count) < (want + 1) / 2 && nfiles <= consumed + pl.window) {
             cv.wait(lk, [&] { return all_done(i + count, nfiles); });
             count = nfiles - i;
         }
@@ -750,11 +754,23 @@ struct Ingest {
         lk.unlock();
         cv.notify_all();
     }
+    // error path: the batches in flight give their buffers back (once nothing reads them) BEFORE any later file does.  `consumed`
+    // may only pass files whose buffers are back in the pool: the window then never admits more files than there are
+    // buffers, which is what keeps a later file from taking the buffer the next file to be drained still waits for.
+    void drop_in_flight() {
+        if (!fly[0].count && !fly[1].count) return;
+        sync_copy_streams(), (void)hipStreamSynchronize(c->stream), (void)hipStreamSynchronize(in.out_stream);
+        for (int k2 = 0; k2 < 2; ++k2) {   // (the older of the two first)
+            BatchLayout& f = fly[(nbatches + k2) & 1];
+            if (f.count) give_back(f.first, f.count), f.count = 0;
+        }
+    }
     // a batch that could not be sent: its error is the call's, its buffers go back (once nothing reads them, if it was issued)
     void abandon(int first, int count, bool issued) {
         first_err = g_err;
         if (issued)  // nothing may still read the host buffers
             sync_copy_streams(), (void)hipStreamSynchronize(c->stream), (void)hipStreamSynchronize(in.out_stream);
+        drop_in_flight();
         give_back(first, count);
     }
     // hand a finished batch's results to the caller and its host buffers back to the pool
@@ -797,6 +813,7 @@ struct Ingest {
             for (int j = i; j < i + count && rc == DD_OK; ++j)
                 if (!slots[j].ok) rc = DD_EIO, first_err = slots[j].err;
             if (rc != DD_OK) {  // drain: give every buffer back as its file arrives
+                drop_in_flight();
                 give_back(i, count), i += count;
                 continue;
             }

@@ -19,6 +19,8 @@ FUZZ = [
     ("fuzz_damage.py", 300, 508, "damaged .gz files: the call raises exactly when zlib's gzread fails, else the registers of gzread's text"),
     ("fuzz_fastq.py", 250, 510, "FASTQ-like texts in .gz / BGZF / two members, clean and broken: whichever of the device's rules or the host's kseq state machine takes a text, registers == the oracle's kseq reading"),
     ("fuzz_k2.py", 50, 509, "Gram all-pairs == streaming kernel, bit-plane progressive scan == streaming kernel"),
+    # (40 draws: 1 123 files in 225 batches, 5.9 s on the MI355X)
+    ("fuzz_ingest.py", 40, 512, "the ingestion pipeline around the decoders: 1-60 files of six kinds, DD_BATCH_MB 1 / 2 / unset, 1-16 loaders, engines kept across draws, a missing path in every eighth draw: every file's registers == oracle, batches >= the plan's guarantee (strict)"),
     ("fuzz_cli.py", 40, 511, "the command-line boundary through one `dashing serve`: k-batches via dandd_amd/bin/fused/parallel == one `dashing sketch` per k == oracle, unions, multi-path card, three sketch containers"),
 ]
 

@@ -477,17 +477,7 @@ def test_sketch_files_fastq_read_in_pieces(engine_factory, orc, tmp_path):
         assert np.array_equal(g, orc.sketch_sweep(np.frombuffer(raw, np.uint8), 15, 18, 12)), name
 
 
-def _bgzf(raw, level=1, strategy=0, block=65280):
-    """bgzip's container: <= 64 KiB gzip members with a 'BC' extra subfield that holds the member's size - 1, + the empty EOF block"""
-    import zlib
-    out = bytearray()
-    for a in list(range(0, len(raw), block)) + [len(raw)]:
-        part = raw[a:a + block] if a < len(raw) else b""
-        c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
-        body = c.compress(part) + c.flush()
-        out += (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + (len(body) + 25).to_bytes(2, "little") + body +
-                zlib.crc32(part).to_bytes(4, "little") + len(part).to_bytes(4, "little"))
-    return bytes(out)
+from ingest_worker import bgzf as _bgzf  # noqa: E402  (bgzip's container; shared with tests/test_gpu_ingest.py)
 
 
 def _long_code_parts():
