@@ -1,6 +1,6 @@
 // dd_ctx.h -- the context behind the C ABI's opaque dd_ctx, and the host-side helpers the ABI's sources share
 // (dd_api.hip: context, timing and stats, synth, dd_plan_sweep; dd_sketch_api.hip: sketch; dd_k2_api.hip: union, card and the
-// HLL schedules; dd_exact_api.hip: exact count, schedules and greedy; dd_ingest.hip: the file-ingestion pipeline; dd_comm.hip: RCCL).
+// HLL schedules; dd_exact_api.hip: exact count, schedules, greedy and the selected k-mers; dd_ingest.hip: the file-ingestion pipeline; dd_comm.hip: RCCL).
 // Callers see dandd_hip.h only.
 #pragma once
 #include "../../include/dandd_hip.h"
@@ -117,6 +117,7 @@ struct dd_ctx {
     // workspaces
     DevBuf tokens, scratch, tables, fasta, regs, ptrs, hist, est, ord, bitmaps, bigmaps, exact, buckets, gram, synth;
     DevBuf masks;  // dd_exact_greedy: cursor and overflow word | gains [64][64] | the mask streams of every k of the call
+    DevBuf emit;   // dd_exact_select_kmers: cursor (256 B) | lo | hi | mask, `cap` records each
     StageSet stage[2];
     int stage_cur = 0;  // the set of the running (or last) sketch call
     // the job tables of the last few sketch calls: a call over genomes of the same sizes and the same k range (a

@@ -1,6 +1,7 @@
 // dd_exact_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h): dd_exact_count*, the exact union
 // schedules (dd_exact_pairwise / _progressive / _leave_out / _subsets), the exact intersection schedules
-// (dd_exact_spectrum / _core_progressive / _select) and the exact greedy walk (dd_exact_greedy).  Host-side orchestration
+// (dd_exact_spectrum / _core_progressive / _select), the exact greedy walk (dd_exact_greedy) and the selected k-mers
+// themselves (dd_exact_select_kmers).  Host-side orchestration
 // only; the kernels are in dd_exact.hip, dd_exact_sched.hip and dd_exact_greedy.hip.
 #include <functional>
 #include "dd_ctx.h"
@@ -635,6 +636,90 @@ int dd_exact_greedy(dd_ctx* c, const char* const* paths, int n, int kmin, int km
     if (exact_sched_args(c, paths, n, 64, kmin, kmax, card)) return DD_EINVAL;
     return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) {
         return dd_exact_greedy_device(c, p, s, n, kmin, kmax, mode, cand, ncand, nfixed, nsteps, order, card);
+    });
+}
+
+// ------------------------------------------------------------------- the selected k-mers
+// dd_exact_sched.hip, emit_kernel: the sort of the schedules for ONE k, then the k-mers whose mask matches a query leave for
+// c->emit (cursor | lo | hi | mask) instead of being counted.  The chunks of the sort finish in any order and the passes
+// each hold an arbitrary part of the k-mer space, so the records are sorted here, on the host, after the copy-back.
+int dd_exact_select_kmers_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int k, const uint64_t* all,
+                                 const uint64_t* none, int nq, uint64_t* kmers, uint64_t* masks, size_t cap, uint64_t* found) {
+    if (exact_sched_args(c, fasta_dev, n, 64, k, k, found)) return DD_EINVAL;
+    if (!nbytes || (cap && (!kmers || !masks))) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    if (nq > dd::kEmitMaxQueries)
+        return fail(DD_EINVAL, "nq=%d: at most %d queries in one call (what one launch holds); split them over calls", nq, dd::kEmitMaxQueries);
+    std::vector<uint64_t> table;
+    if (select_table(all, none, nq, n, table)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    *found = 0;
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n, in))) return rc;
+    c->st_blocks = 0;
+    if (!in.slots) return DD_OK;
+    const size_t dcap = std::min(cap, in.slots), stride = align_up(dcap * sizeof(uint64_t), 256);   // (no more distinct k-mers than slots)
+    if (c->emit.reserve(256 + 3 * stride))
+        return fail(DD_ENOMEM, "exact select k-mers: no device memory for an output of %zu records (24 bytes each); ask with a smaller cap", dcap);
+    char* eb = static_cast<char*>(c->emit.p);
+    dd::ExactEmit e{n, nq, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<unsigned long long*>(eb), dcap};
+    if (dcap) {
+        e.lo = reinterpret_cast<uint64_t*>(eb + 256);
+        e.hi = reinterpret_cast<uint64_t*>(eb + 256 + stride);
+        e.mask = reinterpret_cast<uint64_t*>(eb + 256 + 2 * stride);
+    }
+    DD_HIP(hipMemsetAsync(eb, 0, 256, st));
+    if ((rc = stage_table(c, c->ord, table.data(), table.size() * sizeof(uint64_t)))) return rc;
+    e.table = static_cast<const uint64_t*>(c->ord.p);
+    rc = exact_passes(c, in, n, k, ExactLayout{"exact select k-mers", dd::exact_tag_mode(k), dd::exact_sched_temp_bytes, dd::exact_sched_scratch_bytes},
+                      [&](const ExactArrays& a, size_t count) -> int {
+                          dd::ExactSorted sorted{};
+                          DD_HIP(dd::launch_exact_sort_tagged(a.lo, a.hi, a.lo_alt, a.hi_alt, a.g, a.g_alt, count, k, a.temp, a.temp_bytes, st, &sorted));
+                          DD_HIP(dd::launch_exact_emit(sorted, count, k, e, a.scratch, st));
+                          return DD_OK;
+                      });
+    if (rc) return rc;
+    unsigned long long total = 0;
+    DD_HIP(hipMemcpyAsync(&total, e.cursor, sizeof total, hipMemcpyDeviceToHost, st));
+    DD_HIP(hipStreamSynchronize(st));
+    *found = total;
+    if (!total || total > cap) return DD_OK;   // (more than the caller has room for: the count is the answer, nothing was kept whole)
+    const bool wide = k > 32;
+    const size_t m = (size_t)total;
+    std::vector<uint64_t> lo(m), hi(wide ? m : 0), mk(m);
+    DD_HIP(hipMemcpyAsync(lo.data(), e.lo, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (wide) DD_HIP(hipMemcpyAsync(hi.data(), e.hi, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    DD_HIP(hipMemcpyAsync(mk.data(), e.mask, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    DD_HIP(hipStreamSynchronize(st));
+    // ascending in the 2k-bit key: hi, then lo.  The keys are distinct, so the order is total and two calls agree byte for byte.
+    struct Rec { uint64_t hi, lo, mask; };
+    std::vector<Rec> rec(m);
+    for (size_t i = 0; i < m; ++i) rec[i] = Rec{wide ? hi[i] : 0ull, lo[i], mk[i]};
+    const auto before = [](const Rec& x, const Rec& y) { return x.hi != y.hi ? x.hi < y.hi : x.lo < y.lo; };
+    // slices sorted side by side, then merged in pairs (every distinct k-mer of 16 x 5 Mbp is 20 M records)
+    size_t parts = 1;
+    while (parts * 2 <= (size_t)std::min(usable_cpus(), 16) && m / (parts * 2) >= ((size_t)1 << 16)) parts *= 2;
+    const auto cut = [&](size_t i) { return rec.begin() + (ptrdiff_t)(m / parts * i + std::min(i, m % parts)); };
+    const auto side_by_side = [](size_t jobs, const std::function<void(size_t)>& job) {
+        std::vector<std::thread> th;
+        for (size_t j = 1; j < jobs; ++j) th.emplace_back(job, j);
+        job(0);
+        for (std::thread& t : th) t.join();
+    };
+    side_by_side(parts, [&](size_t j) { std::sort(cut(j), cut(j + 1), before); });
+    for (size_t w = 1; w < parts; w *= 2)
+        side_by_side(parts / (2 * w), [&](size_t j) { std::inplace_merge(cut(2 * w * j), cut(2 * w * j + w), cut(2 * w * j + 2 * w), before); });
+    for (size_t i = 0; i < m; ++i) kmers[2 * i] = rec[i].lo, kmers[2 * i + 1] = rec[i].hi, masks[i] = rec[i].mask;
+    return DD_OK;
+}
+
+int dd_exact_select_kmers(dd_ctx* c, const char* const* paths, int n, int k, const uint64_t* all, const uint64_t* none, int nq,
+                          uint64_t* kmers, uint64_t* masks, size_t cap, uint64_t* found) {
+    if (exact_sched_args(c, paths, n, 64, k, k, found)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) {
+        return dd_exact_select_kmers_device(c, p, s, n, k, all, none, nq, kmers, masks, cap, found);
     });
 }
 

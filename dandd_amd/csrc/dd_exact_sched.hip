@@ -32,6 +32,8 @@
 //                 needs them to outlive their sort
 //                   stream       the tile appended to a store in HBM, 8 bytes per distinct k-mer, at a position reserved
 //                                with one atomicAdd per tile
+//   emit_kernel   (at the end of this file) sched_kernel's sibling for the selected k-mers themselves: no accumulator, the keys
+//                 and masks of the runs that match a query leave for HBM
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
@@ -620,6 +622,103 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
             }
         });
     }
+    return hipGetLastError();
+}
+
+// ---- emit: the selected k-mers themselves -------------------------------------------------------------------------------
+// A sibling of sched_kernel behind the same two pre-passes.  The same segmented OR-scan of a chunk; at the last slot of a
+// run whose mask is non-zero the mask is tested against the (all, none) pairs in LDS, and the first hit is enough: a k-mer
+// that matches several queries leaves once.  A hit stages (lo, hi, mask) in LDS -- the slot's key under mlo / mhi, so the
+// genome of tag mode 1 never leaves, and hi only for k > 32 -- at a position from one ballot and one LDS counter per wave,
+// as the tile of sched_kernel is filled; the workgroup then reserves its range of the output with ONE atomicAdd on the
+// device cursor per chunk and writes it with plain stores.  The cursor keeps counting past `cap`: a range that would pass
+// it is not written, and the caller reads from the cursor how many records there were.  Ranges land in the order the
+// chunks finish; who wants an order sorts (dd_exact_api.hip does).
+namespace {
+
+constexpr size_t kEmitStaticLds = 128;   // emit_kernel's own LDS: the scan's wave totals, the counter, the reserved position
+
+template <bool WIDE>
+__global__ __launch_bounds__(kThreads) void emit_kernel(SortedView s, const uint64_t* __restrict__ carry, size_t nchunks, ExactEmit a) {
+    extern __shared__ uint64_t dyn[];
+    __shared__ uint32_t sf[kThreads / 64];
+    __shared__ uint64_t sv[kThreads / 64];
+    __shared__ uint32_t cnt;
+    __shared__ unsigned long long at;
+    uint64_t* pair = dyn;                          // [nq][2]: (all, none)
+    uint64_t* st_mask = dyn + 2 * (size_t)a.nq;    // [kChunk] each: a chunk has no more run ends than slots
+    uint64_t* st_lo = st_mask + kChunk;
+    uint64_t* st_hi = st_lo + kChunk;              // WIDE only
+    for (int i = threadIdx.x; i < 2 * a.nq; i += kThreads) pair[i] = a.table[i];
+    const uint32_t lane = threadIdx.x & 63;
+    for (size_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        if (threadIdx.x == 0) cnt = 0;
+        uint32_t head, tail, f, ef, tf;
+        uint64_t bit[kItems], v, ev, tv;
+        const size_t first = chunk * kChunk + (size_t)threadIdx.x * kItems;
+        load_items<WIDE>(s, first, head, tail, bit);
+        thread_summary(head, bit, f, v);
+        block_seg_scan<kThreads / 64>(f, v, sf, sv, ef, ev, tf, tv);   // (its barrier also publishes cnt = 0 and the pairs)
+        uint64_t run = ef ? ev : (ev | carry[chunk]);
+#pragma unroll
+        for (int j = 0; j < kItems; ++j) {
+            if ((head >> j) & 1u) run = 0;
+            run |= bit[j];
+            bool hit = false;
+            if (((tail >> j) & 1u) && run != 0)
+                for (int q = 0; q < a.nq && !hit; ++q) hit = (run & pair[2 * q]) == pair[2 * q] && (run & pair[2 * q + 1]) == 0;
+            const unsigned long long em = __ballot(hit);
+            if (em) {
+                const int leader = __builtin_ctzll(em);
+                uint32_t p = 0;
+                if ((int)lane == leader) p = atomicAdd(&cnt, (uint32_t)__builtin_popcountll(em));
+                p = __shfl(p, leader);
+                if (hit) {   // (a tail's slot is inside the array: load_items sets the bit only behind a valid slot)
+                    p += __builtin_popcountll(em & ((1ull << lane) - 1ull));
+                    st_mask[p] = run;
+                    st_lo[p] = s.lo[first + j] & s.mlo;
+                    if (WIDE) st_hi[p] = s.hi[first + j] & s.mhi;
+                }
+            }
+        }
+        __syncthreads();
+        const uint32_t have = cnt;   // (the same in every thread)
+        if (have) {
+            if (threadIdx.x == 0) at = atomicAdd(a.cursor, (unsigned long long)have);
+            __syncthreads();
+            const unsigned long long base = at;
+            if (base + have <= a.cap)
+                for (uint32_t i = threadIdx.x; i < have; i += kThreads) {
+                    a.mask[base + i] = st_mask[i];
+                    a.lo[base + i] = st_lo[i];
+                    if (WIDE) a.hi[base + i] = st_hi[i];
+                }
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+hipError_t launch_exact_emit(const ExactSorted& sorted, size_t count, int k, const ExactEmit& e, void* scratch, hipStream_t st) {
+    if (!count) return hipSuccess;
+    const size_t nchunks = exact_sched_chunks(count);
+    char* sb = static_cast<char*>(scratch);   // (the layout of launch_exact_sched)
+    uint64_t* sum_v = reinterpret_cast<uint64_t*>(sb);
+    uint64_t* carry = sum_v + nchunks;
+    uint32_t* sum_f = reinterpret_cast<uint32_t*>(carry + nchunks);
+    const bool wide = k > 32;
+    SortedView v{sorted.lo, sorted.hi, sorted.g, (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1ull),
+                 (k <= 32) ? 0ull : ((k == 64) ? ~0ull : ((1ull << (2 * k - 64)) - 1ull)), count, e.n};
+    if (wide) hipLaunchKernelGGL(sched_summary_kernel<true>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
+    else hipLaunchKernelGGL(sched_summary_kernel<false>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
+    hipLaunchKernelGGL(sched_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, sum_f, sum_v, nchunks, carry);
+    // the pairs, then a staging area of kChunk records (all = none = 0 hits every distinct k-mer): 48 KiB + 16 KiB at the most
+    const size_t dyn = ((size_t)2 * e.nq + (size_t)(wide ? 3 : 2) * kChunk) * sizeof(uint64_t);
+    const size_t per_cu = std::min<size_t>(4, std::max<size_t>(1, ((size_t)160 << 10) / (dyn + kEmitStaticLds)));
+    const dim3 g((unsigned)std::min<size_t>(nchunks, 256 * per_cu)), t(kThreads);   // persistent workgroups, as launch_exact_sched sizes them
+    if (wide) launch_full_lds<emit_kernel<true>, (int)kEmitStaticLds>(g, t, dyn, st, v, carry, nchunks, e);
+    else launch_full_lds<emit_kernel<false>, (int)kEmitStaticLds>(g, t, dyn, st, v, carry, nchunks, e);
     return hipGetLastError();
 }
 

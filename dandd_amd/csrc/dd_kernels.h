@@ -312,6 +312,20 @@ size_t exact_sched_scratch_bytes(size_t count);
 hipError_t launch_exact_sort_tagged(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, uint8_t* g, uint8_t* g_alt,
                                     size_t n, int k, void* temp, size_t temp_bytes, hipStream_t st, ExactSorted* out);
 hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, const ExactSched& s, void* scratch, hipStream_t st);
+// The selected k-mers themselves (emit_kernel of dd_exact_sched.hip), behind launch_exact_sort_tagged and with the scratch
+// of launch_exact_sched: every distinct k-mer whose mask matches at least one of the nq <= kEmitMaxQueries (all, none) pairs
+// is appended once -- key in lo / hi (hi written for k > 32 only), mask in mask -- at a position reserved on *cursor, one
+// reservation per chunk of the sorted array, so the order is whatever the reservations give.  A range that would pass `cap`
+// records is not written; the cursor still advances and says how many records there were.
+constexpr int kEmitMaxQueries = 1024;
+struct ExactEmit {
+    int n, nq;
+    const uint64_t* table;       // device: (all, none) [nq][2]
+    uint64_t *lo, *hi, *mask;    // device, [cap] each (null when cap = 0)
+    unsigned long long* cursor;  // device, zeroed by the caller before the first pass; runs on across passes
+    unsigned long long cap;
+};
+hipError_t launch_exact_emit(const ExactSorted& sorted, size_t count, int k, const ExactEmit& e, void* scratch, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // exact greedy walk (dd_exact_greedy.hip) over the mask streams of kSchedStream: one launch per step of the walk reads

@@ -34,6 +34,7 @@ EXPORTS = [
     "dd_exact_spectrum", "dd_exact_core_progressive", "dd_exact_select",
     "dd_exact_spectrum_device", "dd_exact_core_progressive_device", "dd_exact_select_device",
     "dd_exact_greedy", "dd_exact_greedy_device",
+    "dd_exact_select_kmers", "dd_exact_select_kmers_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
     "dd_comm_unique_id", "dd_comm_init", "dd_comm_destroy", "dd_comm_info", "dd_allreduce_max_u8", "dd_allgather_u8",
@@ -43,6 +44,7 @@ COMM_ID_BYTES = 128   # include/dandd_hip.h: DD_COMM_ID_BYTES
 
 class EngineError(RuntimeError):
     code = None   # the library's DD_E* code, where the library raised it
+    found = None  # exact_select_kmers with a cap that was too small: the number of k-mers that match
 
 
 ENOMEM = -5   # include/dandd_hip.h: DD_ENOMEM
@@ -173,6 +175,10 @@ def load_library(path=None):
         fn = getattr(lib, name)
         fn.restype = i32
         fn.argtypes = [vp] + src + [i32, i32, i32, i32, vp, i32, i32, i32, vp, vp]
+    for name, src in (("dd_exact_select_kmers", [paths_t]), ("dd_exact_select_kmers_device", [ptrs_t, sizes_t])):
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = [vp] + src + [i32, i32, vp, vp, i32, vp, vp, sz, C.POINTER(u64)]
     lib.dd_exact_subsets_from_hist.restype = i32
     lib.dd_exact_subsets_from_hist.argtypes = [vp, i32, vp]
     lib.dd_timing_enable.restype = i32
@@ -220,6 +226,20 @@ def exact_subsets_from_hist(hist, n):
     if rc != 0:
         raise EngineError(f"libdandd_hip error {rc}: {lib.dd_last_error().decode()}")
     return card
+
+
+def kmer_text(kmers, k):
+    """Host-side (no device needed): uint64 [m][2] (lo, hi) records of dd_exact_select_kmers -> list of m strings of k bases,
+    two bits per base, A = 0, C = 1, G = 2, T = 3, the first base most significant."""
+    k = int(k)
+    if not 1 <= k <= 64:
+        raise ValueError(f"k={k} outside 1..64")
+    rec = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, 2)
+    pos = 2 * (k - 1 - np.arange(k))                                   # base j of the text: bits pos[j], pos[j] + 1 of the key
+    word = np.where(pos >= 64, 1, 0)                                   # ... which lie in hi (column 1) from bit 64 on
+    codes = (rec[:, word] >> (pos % 64).astype(np.uint64)) & np.uint64(3)
+    text = np.frombuffer(b"ACGT", dtype=np.uint8)[codes.astype(np.intp)].reshape(-1, k)
+    return [row.tobytes().decode("ascii") for row in text]
 
 
 def synth_realistic_size(seed, nbases):
@@ -690,6 +710,44 @@ class Engine:
 
     def exact_select_device(self, fasta_ptrs, nbytes, kmin, kmax, all_masks, none_masks):
         return self._exact_select(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, all_masks, none_masks)
+
+    # -- the selected k-mers themselves: the same sort for one k, the matching k-mers written out (emit_kernel) ------------
+    KMERS_FIRST_CAP = 1 << 20
+
+    def _exact_select_kmers(self, src, k, all_masks, none_masks, cap):
+        args, n, suffix = src
+        al = np.ascontiguousarray([int(x) for x in all_masks], dtype=np.uint64).reshape(-1)
+        no = np.ascontiguousarray([int(x) for x in none_masks], dtype=np.uint64).reshape(-1)
+        if al.size != no.size:
+            raise ValueError("all_masks and none_masks must have the same length")
+        nq = al.size
+        if nq == 0:   # (the library rejects nq = 0 by its own rule; it still wants two pointers)
+            al = no = np.zeros(1, dtype=np.uint64)
+        fn = getattr(self._lib, f"dd_exact_select_kmers{suffix}")
+        room = self.KMERS_FIRST_CAP if cap is None else int(cap)
+        for _ in range(2):
+            kmers, masks = np.zeros((room, 2), dtype=np.uint64), np.zeros(room, dtype=np.uint64)
+            found = C.c_uint64()
+            self._check(fn(self._ctx, *args, n, int(k), al.ctypes.data, no.ctypes.data, nq, kmers.ctypes.data if room else None,
+                           masks.ctypes.data if room else None, room, C.byref(found)))
+            if found.value <= room:
+                return kmers[:found.value], masks[:found.value]
+            if cap is not None:
+                err = EngineError(f"exact_select_kmers: {found.value} k-mers match, cap={room} records were asked for")
+                err.found = found.value
+                raise err
+            room = found.value
+        raise EngineError(f"exact_select_kmers: {found.value} k-mers match on the second call, {room} on the first")
+
+    def exact_select_kmers(self, paths, k, all_masks, none_masks, cap=None):
+        """FASTA files (n <= 64), one k, at most 1024 queries -> (kmers uint64 [found][2] (lo, hi), masks uint64 [found]): the
+        distinct k-mers held by every file of all_masks[q] and by no file of none_masks[q] for at least one q, ascending
+        (alphabetical; kmer_text decodes them), each with its membership mask.  cap=None: room for 2^20 records, and one more
+        call with the count when there are more; a given cap that is too small raises EngineError naming the count."""
+        return self._exact_select_kmers(self._exact_src(paths=paths), k, all_masks, none_masks, cap)
+
+    def exact_select_kmers_device(self, fasta_ptrs, nbytes, k, all_masks, none_masks, cap=None):
+        return self._exact_select_kmers(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), k, all_masks, none_masks, cap)
 
     # -- exact greedy: the masks of every k kept on the device, one read of them per step (dd_exact_greedy.hip) ---------
     def _exact_greedy(self, src, kmin, kmax, mode, cand, nfixed, nsteps):

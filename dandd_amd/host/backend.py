@@ -329,6 +329,25 @@ class HipExactBackend:
         _, files, kmin, kmax = win
         return self.engine.exact_select(files, kmin, kmax, all_masks, none_masks)
 
+    def select_kmers(self, leaf_paths, k, all_masks, none_masks, limit):
+        """the k-mers select_counts counts at one k of the window, themselves: (kmers uint64 [m][2] (lo, hi), masks uint64 [m]),
+        ascending, a k-mer that matches several queries once.  More than `limit` of them is a ValueError that carries the count."""
+        from ..engine import EngineError
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, kmin, kmax = win
+        if not kmin <= int(k) <= kmax:
+            raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
+        try:
+            return self.engine.exact_select_kmers(files, int(k), all_masks, none_masks, cap=int(limit))
+        except EngineError as e:
+            if getattr(e, "found", None) is None:
+                raise
+            err = ValueError(f"{e.found} k-mers match at k={k}, more than the limit of {limit}")
+            err.found = e.found
+            raise err from None
+
     def greedy_cards(self, leaf_paths, mode, nfixed, nsteps, kmin):
         """HipBackend.greedy_cards on exact counts (dd_exact_greedy): -> (order [nsteps] as indices into leaf_paths, cards
         float64 [nsteps][K]), ties going to the leaf the caller lists first.  None -- the caller goes on as without this

@@ -390,11 +390,29 @@ def core_command(args):
             for f in g:
                 if f not in fastas:
                     sys.exit(f"core: {f} (-g) is not in the universe of this run (-f)")
+    if not args.kmers and (args.kmers_k or args.kmers_max is not None):
+        sys.exit("core: --kmers-k and --kmers-max go with --kmers")
+    kmers_max = 1_000_000 if args.kmers_max is None else int(args.kmers_max)
+    if args.kmers:
+        for k in args.kmers_k or []:
+            if not max(1, window[0]) <= k <= window[1]:
+                sys.exit(f"core: --kmers-k {k} is outside the k window {max(1, window[0])}..{window[1]}")
+        if kmers_max < 0:
+            sys.exit(f"core: --kmers-max {kmers_max}: a number of k-mers")
+        if not groups:                                               # the whole universe: its core is the core genome
+            groups, labels = [list(fastas)], ["all"]
     os.makedirs(args.outdir, exist_ok=True)
     try:
         res = tree.core_tables(fastas, *window, orderings, groups)
     except ValueError as e:
         sys.exit(f"core: {e}")
+    lists = []
+    if args.kmers:
+        try:
+            lists = tree.core_kmers(fastas, groups, args.kmers, ks=sorted(set(args.kmers_k or [])) or None, limit=kmers_max,
+                                    window=window, counts=res["groups"])
+        except ValueError as e:
+            sys.exit(f"core: {e} (--kmers-max {kmers_max}: raise it, or narrow the class)" if "more than the limit" in str(e) else f"core: {e}")
     ks = res["ks"]
     delta_of = deltatree._window_delta
     spec = res["spectrum"]
@@ -417,6 +435,17 @@ def core_command(args):
         _write_csv(outfile + ".core_groups.csv", ["group", "ngen", "k", "core", "private", "signature"], rows)
         _write_csv(outfile + ".core_groupsummary.csv", ["group", "ngen", "core_delta", "core_k", "private_delta", "private_k",
                                                         "signature_delta", "signature_k"], summary)
+    if args.kmers:
+        from ..engine import kmer_text
+        index = []
+        for cell in lists:                                           # (nothing is written before every list is there)
+            gi, cls, k = cell["group"], cell["cls"], cell["k"]
+            path = f"{outfile}.core_kmers.g{gi + 1}.{cls}.k{k}.fasta"
+            with open(path, "w") as fh:
+                for j, (text, m) in enumerate(zip(kmer_text(cell["kmers"], k), cell["masks"]), 1):
+                    fh.write(f">{labels[gi]}.{cls}.k{k}.{j} ngen={bin(int(m)).count('1')}\n{text}\n")
+            index.append([labels[gi], cls, k, len(cell["masks"]), os.path.basename(path)])
+        _write_csv(outfile + ".core_kmers.csv", ["group", "class", "k", "kmers", "file"], index)
     tree.speciesinfo.save_cardkey(tree.experiment["tool"])
     tree.speciesinfo.save_references(fast=False)
 
@@ -627,6 +656,13 @@ def build_parser():
                     help="with neither -r nor -n: one ordering, the genomes as listed")
     co.add_argument("-g", "--groups", dest="groups_loc", default=None, type=str,
                     help="'fasta<TAB>group' lines: per group its core, its private k-mers and its signature")
+    co.add_argument("--kmers", dest="kmers", action="append", choices=["core", "private", "signature"], default=None, metavar="CLASS",
+                    help="also write the k-mers of this class (core, private, signature; repeatable) of every group as FASTA, at the k "
+                         "the group summary reports for it; without -g: of one group `all`, the whole universe")
+    co.add_argument("--kmers-k", dest="kmers_k", action="append", type=int, default=None, metavar="K",
+                    help="write the k-mers at this k of the window (repeatable) instead of each class's own")
+    co.add_argument("--kmers-max", dest="kmers_max", type=int, default=None, metavar="N",
+                    help="most k-mers of one group, class and k (default 1000000): more ends the command before anything is written")
     co.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     co.add_argument("-l", "--label", dest="label", default="")
     co.set_defaults(func=core_command)

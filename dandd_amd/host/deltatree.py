@@ -1110,6 +1110,75 @@ class DeltaTree:
             out["groups"] = table(be.select_counts(paths, alls, nones), (len(groups), 3, len(ks)))
         return out
 
+    KMER_CLASSES = ("core", "private", "signature")       # the columns of core_tables' groups, in that order
+
+    def core_kmers(self, fastas, groups, wanted, ks=None, limit=1_000_000, window=None, counts=None):
+        """The k-mers behind the cells of core_tables' `groups`: for every group (lists of FASTAs of the universe `fastas`) and
+        every class of `wanted` (core (G, 0), private (0, full ^ G), signature (G, full ^ G)) the k-mers themselves at the k
+        where count / k is largest over the window (_window_delta's rule: the *_k of the group summary), or at every k of
+        `ks`.  window: (lo, hi), default the tree's --ksweep; counts: core_tables(...)["groups"] of the same window where the
+        caller has it, else one select_counts call.  ONE select_kmers call per distinct k carries every query of that k; the
+        records come back once each, ascending, and go to their queries by their masks, here.  A cell of more than `limit`
+        k-mers is a ValueError that names it, before any k-mer is asked for.
+        -> list of dict(group, cls, k, kmers uint64 [m][2] (lo, hi), masks uint64 [m]) in (group, class as KMER_CLASSES, k) order"""
+        by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
+        nodes = [by_fasta[f] for f in fastas]
+        n = len(nodes)
+        wanted = [c for c in self.KMER_CLASSES if c in set(wanted)]
+        if window is None:
+            window = self.experiment.get("ksweep")
+        if window is None:
+            raise ValueError("a k window is needed")
+        lo, hi = max(1, int(window[0])), int(window[1])
+        if hi < lo:
+            raise ValueError(f"empty k window {lo}..{hi}")
+        window_ks = list(range(lo, hi + 1))
+        for k in ks or []:
+            if int(k) not in window_ks:
+                raise ValueError(f"k={k} is outside the window {lo}..{hi}")
+        exp = dict(self.experiment, ksweep=(lo, hi))
+        be = backend_for(exp)
+        for entry in ("select_counts", "select_kmers"):
+            if not hasattr(be, entry):
+                raise ValueError(f"the backend {getattr(be, 'name', type(be).__name__)} has no {entry}: intersections need exact membership masks")
+        paths = self._leaf_files(nodes, lo, hi)
+        index = {f: i for i, f in enumerate(fastas)}
+        full = (1 << n) - 1
+        gmasks = [sum(1 << index[f] for f in set(g)) for g in groups]
+        query = {"core": lambda G: (G, 0), "private": lambda G: (0, full ^ G), "signature": lambda G: (G, full ^ G)}
+        if counts is None:
+            alls = [m for G in gmasks for m in (G, 0, G)]
+            nones = [m for G in gmasks for m in (0, full ^ G, full ^ G)]
+            counts = be.select_counts(paths, alls, nones)
+            if counts is None:
+                raise ValueError(f"the backend has no membership masks for {n} genomes")
+        counts = np.asarray(counts).astype(np.uint64).reshape(len(groups), 3, len(window_ks))
+        cells = []                                                     # (group, class, k, all, none, count)
+        for gi, G in enumerate(gmasks):
+            for cls in wanted:
+                col = [int(v) for v in counts[gi, self.KMER_CLASSES.index(cls)]]
+                for k in ([int(k) for k in ks] if ks else [_window_delta(col, window_ks)[1]]):
+                    count = col[k - lo]
+                    if count > limit:
+                        raise ValueError(f"group {gi + 1}, {cls}, k={k}: {count} k-mers, more than the limit of {limit}")
+                    cells.append((gi, cls, k, *query[cls](G), count))
+        got = {}
+        for k in sorted({cell[2] for cell in cells}):
+            mine = sorted({(a, b) for _, _, kk, a, b, _ in cells if kk == k})
+            room = sum(count for _, _, kk, _, _, count in cells if kk == k)     # (the union of the queries holds no more)
+            res = be.select_kmers(paths, k, [a for a, _ in mine], [b for _, b in mine], room)
+            if res is None:
+                raise ValueError(f"the backend has no membership masks for {n} genomes")
+            got[k] = (np.asarray(res[0], dtype=np.uint64).reshape(-1, 2), np.asarray(res[1], dtype=np.uint64).reshape(-1))
+        out = []
+        for gi, cls, k, a, b, count in cells:
+            kmers, masks = got[k]
+            keep = ((masks & np.uint64(a)) == np.uint64(a)) & ((masks & np.uint64(b)) == np.uint64(0))
+            if int(keep.sum()) != count:
+                raise ValueError(f"group {gi + 1}, {cls}, k={k}: {int(keep.sum())} k-mers came back, {count} were counted")
+            out.append(dict(group=gi, cls=cls, k=k, kmers=kmers[keep], masks=masks[keep]))
+        return out
+
     # ---- batched GPU union schedules ------------------------------------------------------------------
     def _table_window(self, experiment):
         """[lo, hi] of a union table for climbs over this tree's leaves: the --ksweep window, or a hill-climb's guess -- the

@@ -255,6 +255,30 @@ int dd_exact_core_progressive_device(dd_ctx *, const uint8_t *const *fasta_dev, 
 int dd_exact_select_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
                            const uint64_t *all, const uint64_t *none, int nq, uint64_t *count);
 
+/* ---- the selected k-mers themselves ---------------------------------------------------------------------------
+ * dd_exact_select says how many k-mers match a query; this writes them.  ONE k per call (a range would need ragged
+ * outputs), the sort and the masks of the schedules above, and the bit rules of dd_exact_select: a bit >= n set in all[q]
+ * or none[q] is DD_EINVAL, all & none != 0 is legal and matches nothing, all = none = 0 matches every distinct k-mer.
+ * 1 <= n <= 64, 1 <= k <= 64, 1 <= nq <= 1024 (what one launch holds; more is DD_EINVAL: split the queries over calls).
+ * `found` must not be null; kmers and masks may be null only when cap == 0, which makes the call a pure count.
+ *   *found    the number of distinct k-mers whose mask matches AT LEAST ONE query (a k-mer that matches several is one)
+ *   found <= cap:  records 0 .. found-1 hold those k-mers in ASCENDING order of the 2k-bit key -- kmers[i][1] (hi: bits
+ *             64 and up, 0 for k <= 32), then kmers[i][0] (lo), unsigned: two bits per base, A = 0, C = 1, G = 2, T = 3, the
+ *             first base most significant, so the order is alphabetical -- and masks[i] is the membership mask of record i
+ *             (bit j: input j holds it).  Two calls on the same inputs return identical bytes.
+ *   found > cap:   the call still returns DD_OK; the contents of kmers and masks are then UNSPECIFIED (not a prefix of
+ *             the answer), and the caller comes back with cap >= found.
+ * The records wait in 24 bytes x min(cap, k-mer slots of the inputs) of HBM beside the exact workspace (DD_ENOMEM with a
+ * message when that cannot be had); budget and passes are those of dd_exact_count (DD_EXACT_MB), the count runs on across
+ * passes, dd_last_sketch_stats' third value is the number of passes, and kernel time is DD_KERNEL_EXACT's.  An empty
+ * input, or one without a k-mer of length k, holds nothing. */
+int dd_exact_select_kmers(dd_ctx *, const char *const *paths, int n, int k, const uint64_t *all /*[nq]*/,
+                          const uint64_t *none /*[nq]*/, int nq, uint64_t *kmers /*[cap][2]: lo, hi*/,
+                          uint64_t *masks /*[cap]*/, size_t cap, uint64_t *found);
+int dd_exact_select_kmers_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int k,
+                                 const uint64_t *all, const uint64_t *none, int nq, uint64_t *kmers, uint64_t *masks,
+                                 size_t cap, uint64_t *found);
+
 /* ---- exact greedy orderings -----------------------------------------------------------------------------------
  * dd_greedy on exact counts, for `dandd greedy` on trees built with `--exact`: the same walk, the same SELECTION RULE
  * (above, word for word: the largest card[kk] / (kmin + kk) in IEEE double, ties between k to the LARGER k, ties between
@@ -285,7 +309,7 @@ int dd_exact_greedy_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy */
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission of dd_exact_select_kmers */
 #define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);
