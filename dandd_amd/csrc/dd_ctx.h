@@ -118,6 +118,7 @@ struct dd_ctx {
     DevBuf tokens, scratch, tables, fasta, regs, ptrs, hist, est, ord, bitmaps, bigmaps, exact, buckets, gram, synth;
     DevBuf masks;  // dd_exact_greedy: cursor and overflow word | gains [64][64] | the mask streams of every k of the call
     DevBuf emit;   // dd_exact_select_kmers: cursor (256 B) | lo | hi | mask, `cap` records each
+    DevBuf hits;   // dd_exact_locate: the jobs' hit bitmaps, off[njobs] words
     StageSet stage[2];
     int stage_cur = 0;  // the set of the running (or last) sketch call
     // the job tables of the last few sketch calls: a call over genomes of the same sizes and the same k range (a

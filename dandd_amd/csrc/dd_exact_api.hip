@@ -1,8 +1,8 @@
 // dd_exact_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h): dd_exact_count*, the exact union
 // schedules (dd_exact_pairwise / _progressive / _leave_out / _subsets), the exact intersection schedules
-// (dd_exact_spectrum / _core_progressive / _select), the exact greedy walk (dd_exact_greedy) and the selected k-mers
-// themselves (dd_exact_select_kmers).  Host-side orchestration
-// only; the kernels are in dd_exact.hip, dd_exact_sched.hip and dd_exact_greedy.hip.
+// (dd_exact_spectrum / _core_progressive / _select), the exact greedy walk (dd_exact_greedy), the selected k-mers
+// themselves (dd_exact_select_kmers) and their positions (dd_exact_locate).  Host-side orchestration
+// only; the kernels are in dd_exact.hip, dd_exact_sched.hip, dd_exact_greedy.hip and dd_exact_locate.hip.
 #include <functional>
 #include "dd_ctx.h"
 
@@ -15,6 +15,7 @@ namespace {
 struct ExactInputs {
     const dd::ExactGenome* etab_dev = nullptr;
     size_t slots = 0, max_segments = 0;   // slots = 0: no input has a token
+    std::vector<dd::ExactGenome> etab;    // the host's copy of etab_dev (dd_exact_locate: where each stream and its ntok lie)
 };
 
 int exact_check_inputs(const uint8_t* const* fasta_dev, const size_t* nbytes, int n) {
@@ -45,6 +46,7 @@ int exact_prepare(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbyt
     memcpy(image.data(), ptab.data(), sizeof(dd::PackGenome) * n);
     dd::ExactGenome* etab = reinterpret_cast<dd::ExactGenome*>(image.data() + pbytes);
     for (int g = 0; g < n; ++g) etab[g] = dd::ExactGenome{ptab[g].out.codes, ptab[g].out.bad, ptab[g].out.ntok, base[g]};
+    in.etab.assign(etab, etab + n);
     if ((rc = stage_table(c, c->tables, image.data(), image.size()))) return rc;
     char* tdev = static_cast<char*>(c->tables.p);
     {
@@ -723,6 +725,130 @@ int dd_exact_select_kmers(dd_ctx* c, const char* const* paths, int n, int k, con
     });
 }
 
+// ------------------------------------------------------------------- where the selected k-mers lie
+// dd_exact_locate.hip: dd_exact_select_kmers' sort and emission with the jobs' distinct (all, none) pairs as queries, the
+// records of all passes put in key order on the device (c->exact, free by then, is the sort's other half and temp), then
+// one walk of every painted genome that looks each k-mer up in them.  Nothing but the bitmaps comes back.
+int dd_exact_locate_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int k, const uint64_t* all,
+                           const uint64_t* none, const int32_t* genome, int njobs, const uint64_t* off, uint64_t* hits, uint64_t* found) {
+    if (exact_sched_args(c, fasta_dev, n, 64, k, k, found)) return DD_EINVAL;
+    if (!nbytes || !all || !none || !genome || !off) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n)) return DD_EINVAL;
+    if (njobs < 1 || njobs > dd::kEmitMaxQueries)
+        return fail(DD_EINVAL, "njobs=%d outside 1..%d (what one launch holds); split the jobs over calls", njobs, dd::kEmitMaxQueries);
+    const uint64_t outside = n == 64 ? 0ull : ~((1ull << n) - 1ull);
+    for (int j = 0; j < njobs; ++j) {
+        if (genome[j] < 0 || genome[j] >= n) return fail(DD_EINVAL, "job %d: genome %d outside 0..%d", j, genome[j], n - 1);
+        if ((all[j] | none[j]) & outside) return fail(DD_EINVAL, "job %d: a bit outside 0..%d is set", j, n - 1);
+    }
+    if (off[njobs] < off[0]) return fail(DD_EINVAL, "off[] must ascend");
+    const uint64_t words = off[njobs] - off[0];   // (each job's own share is checked once the inputs' token counts are known)
+    if (words && !hits) return fail(DD_EINVAL, "null argument");
+    // the queries of the emission: the jobs' distinct pairs
+    std::vector<std::pair<uint64_t, uint64_t>> pairs((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) pairs[(size_t)j] = {all[j], none[j]};
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    const int nq = (int)pairs.size();
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    *found = 0;
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n, in))) return rc;
+    c->st_blocks = 0;
+    // every genome's ntok, for the shape of the answer
+    std::vector<unsigned long long> ntok((size_t)n, 0ull);
+    if (in.slots) {
+        for (int g = 0; g < n; ++g) DD_HIP(hipMemcpyAsync(&ntok[(size_t)g], in.etab[(size_t)g].ntok, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+    }
+    size_t max_segments = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const uint64_t want = (ntok[(size_t)genome[j]] + dd::kSegTokens - 1) / dd::kSegTokens;
+        if (off[j + 1] - off[j] != want)
+            return fail(DD_EINVAL, "job %d: off[%d] - off[%d] = %llu words, %llu expected (input %d holds %llu tokens, 64 to a word)", j, j + 1, j,
+                        (unsigned long long)(off[j + 1] - off[j]), (unsigned long long)want, genome[j], ntok[(size_t)genome[j]]);
+        max_segments = std::max(max_segments, (size_t)want);
+    }
+    if (!in.slots) return DD_OK;   // (no input holds a token)
+    // the emission of dd_exact_select_kmers_device, with room for every distinct k-mer the inputs can hold
+    const size_t dcap = in.slots, stride = align_up(dcap * sizeof(uint64_t), 256);
+    if (c->emit.reserve(256 + 3 * stride))
+        return fail(DD_ENOMEM, "exact locate: no device memory for the %zu bytes of the record area (24 bytes per k-mer slot of the inputs)", 256 + 3 * stride);
+    char* eb = static_cast<char*>(c->emit.p);
+    dd::ExactEmit e{n, nq, nullptr, reinterpret_cast<uint64_t*>(eb + 256), reinterpret_cast<uint64_t*>(eb + 256 + stride),
+                    reinterpret_cast<uint64_t*>(eb + 256 + 2 * stride), reinterpret_cast<unsigned long long*>(eb), dcap};
+    DD_HIP(hipMemsetAsync(eb, 0, 256, st));
+    // one image for both tables: (all, none) [nq][2] | LocateUnit[] -- the jobs of a genome, kLocateJobs to a unit
+    std::vector<int> order((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) order[(size_t)j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return genome[x] < genome[y]; });
+    std::vector<dd::LocateUnit> units;
+    for (int j : order) {
+        const dd::ExactGenome& eg = in.etab[(size_t)genome[j]];
+        if (!ntok[(size_t)genome[j]]) continue;   // (an empty bitmap)
+        if (units.empty() || units.back().ntok != eg.ntok || units.back().nj == dd::kLocateJobs) {
+            units.push_back(dd::LocateUnit{});
+            units.back().codes = eg.codes, units.back().bad = eg.bad, units.back().ntok = eg.ntok;
+        }
+        dd::LocateUnit& u = units.back();
+        u.all[u.nj] = all[j], u.none[u.nj] = none[j], u.out[u.nj] = off[j] - off[0];
+        ++u.nj;
+    }
+    const size_t pbytes = align_up(sizeof(uint64_t) * 2 * (size_t)nq, 256);
+    std::vector<char> image(pbytes + sizeof(dd::LocateUnit) * units.size(), 0);
+    for (int q = 0; q < nq; ++q) {
+        uint64_t* t = reinterpret_cast<uint64_t*>(image.data()) + 2 * (size_t)q;
+        t[0] = pairs[(size_t)q].first, t[1] = pairs[(size_t)q].second;
+    }
+    memcpy(image.data() + pbytes, units.data(), sizeof(dd::LocateUnit) * units.size());
+    if ((rc = stage_table(c, c->ord, image.data(), image.size()))) return rc;
+    e.table = static_cast<const uint64_t*>(c->ord.p);
+    const dd::LocateUnit* units_dev = reinterpret_cast<const dd::LocateUnit*>(static_cast<const char*>(c->ord.p) + pbytes);
+    if ((rc = c->hits.reserve(words * sizeof(uint64_t)))) return rc;
+    uint64_t* hits_dev = static_cast<uint64_t*>(c->hits.p);
+    rc = exact_passes(c, in, n, k, ExactLayout{"exact locate", dd::exact_tag_mode(k), dd::exact_sched_temp_bytes, dd::exact_sched_scratch_bytes},
+                      [&](const ExactArrays& a, size_t count) -> int {
+                          dd::ExactSorted sorted{};
+                          DD_HIP(dd::launch_exact_sort_tagged(a.lo, a.hi, a.lo_alt, a.hi_alt, a.g, a.g_alt, count, k, a.temp, a.temp_bytes, st, &sorted));
+                          DD_HIP(dd::launch_exact_emit(sorted, count, k, e, a.scratch, st));
+                          return DD_OK;
+                      });
+    if (rc) return rc;
+    unsigned long long total = 0;
+    DD_HIP(hipMemcpyAsync(&total, e.cursor, sizeof total, hipMemcpyDeviceToHost, st));
+    DD_HIP(hipStreamSynchronize(st));
+    if (total > dcap) return fail(DD_EHIP, "exact locate: %llu records emitted, the inputs have %zu k-mer slots", total, dcap);
+    if (!total || !words) {
+        if (words) DD_HIP(hipMemsetAsync(hits_dev, 0, words * sizeof(uint64_t), st));   // nothing matches: no search
+    } else {
+        // (a pass holds an arbitrary part of the k-mer space and its chunks finish in any order: one ordering, after the last)
+        if (c->exact.reserve(dd::exact_locate_order_bytes((size_t)total, k)))
+            return fail(DD_ENOMEM, "exact locate: no device memory for the %zu bytes that put %llu records in order",
+                        dd::exact_locate_order_bytes((size_t)total, k), total);
+        Span sp(c, DD_KERNEL_EXACT);
+        dd::LocateSet set{};
+        DD_HIP(dd::launch_exact_locate_order(e.lo, e.hi, e.mask, (size_t)total, k, c->exact.p, st, &set));
+        dd::launch_exact_locate(units_dev, (int)units.size(), max_segments, k, c->canonical, set, hits_dev, st);
+        DD_HIP(hipGetLastError());
+    }
+    std::vector<uint64_t> host((size_t)words);
+    if (words) DD_HIP(hipMemcpyAsync(host.data(), hits_dev, words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    DD_HIP(hipStreamSynchronize(st));
+    if (words) memcpy(hits + off[0], host.data(), words * sizeof(uint64_t));   // (nothing is written before everything is known)
+    *found = total;
+    return DD_OK;
+}
+
+int dd_exact_locate(dd_ctx* c, const char* const* paths, int n, int k, const uint64_t* all, const uint64_t* none, const int32_t* genome,
+                    int njobs, const uint64_t* off, uint64_t* hits, uint64_t* found) {
+    if (exact_sched_args(c, paths, n, 64, k, k, found)) return DD_EINVAL;
+    return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) {
+        return dd_exact_locate_device(c, p, s, n, k, all, none, genome, njobs, off, hits, found);
+    });
+}
+
 int dd_exact_spectrum(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, uint64_t* spec) {
     if (exact_sched_args(c, paths, n, 64, kmin, kmax, spec)) return DD_EINVAL;
     return exact_path_form(c, paths, n, [&](const uint8_t* const* p, const size_t* s) { return dd_exact_spectrum_device(c, p, s, n, kmin, kmax, spec); });
@@ -747,6 +873,25 @@ int dd_exact_subsets_from_hist(const uint64_t* hist, int n, uint64_t* card) {
     if (!hist || !card) return fail(DD_EINVAL, "null argument");
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "u64");
     return subsets_from_hist(reinterpret_cast<const unsigned long long*>(hist), n, card, 1);
+}
+
+// host only: dd_io.h's record index of one file, in the caller's arrays
+int dd_fasta_index(const char* path, uint64_t* seq_len, uint64_t* tok_start, size_t cap, uint64_t* nrec, char* names, size_t names_cap,
+                   size_t* names_need, uint64_t* ntok) {
+    if (!path || !nrec || !names_need || !ntok || (cap && (!seq_len || !tok_start)) || (names_cap && !names)) return fail(DD_EINVAL, "null argument");
+    dd::FastaIndex ix;
+    std::string err;
+    if (!dd::fasta_index_file(path, ix, err, usable_cpus())) return fail(DD_EIO, "%s", err.c_str());
+    size_t need = 0;
+    for (const std::string& s : ix.names) need += s.size() + 1;
+    *nrec = ix.seq_len.size(), *names_need = need, *ntok = ix.ntok;
+    if (ix.seq_len.size() <= cap && !ix.seq_len.empty()) {
+        memcpy(seq_len, ix.seq_len.data(), sizeof(uint64_t) * ix.seq_len.size());
+        memcpy(tok_start, ix.tok_start.data(), sizeof(uint64_t) * ix.tok_start.size());
+    }
+    if (need <= names_cap)
+        for (const std::string& s : ix.names) memcpy(names, s.c_str(), s.size() + 1), names += s.size() + 1;
+    return DD_OK;
 }
 
 int dd_exact_pairwise(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, uint64_t* card) {

@@ -251,7 +251,13 @@ inline bool piece_has_plus_line(const uint8_t* p, size_t off, size_t len) {
 inline bool plus_at_piece_start(const uint8_t* p, size_t off) { return off > 0 && p[off] == '+' && p[off - 1] == '\n'; }
 // src[0..n) -> dst (at least n + 2 bytes; may be src itself: the output never runs ahead of the input by more than two
 // bytes, which memmove tolerates); returns the bytes written
-inline size_t fastq_to_fasta(const uint8_t* src, size_t n, uint8_t* dst) {
+// (names: the first word of every record's header line, for the record index below -- the rewritten headers are bare)
+inline void header_name(const uint8_t* p, size_t n, std::string& out) {
+    size_t e = 0;
+    while (e < n && p[e] != ' ' && !(p[e] >= '\t' && p[e] <= '\r')) ++e;
+    out.assign(reinterpret_cast<const char*>(p), e);
+}
+inline size_t fastq_to_fasta(const uint8_t* src, size_t n, uint8_t* dst, std::vector<std::string>* names = nullptr) {
     size_t i = 0, o = 0;
     bool have_header = false;  // kseq's last_char: the next record's header character has been consumed
     for (;;) {
@@ -261,7 +267,9 @@ inline size_t fastq_to_fasta(const uint8_t* src, size_t n, uint8_t* dst) {
             ++i;
         }
         have_header = false;
+        const size_t name_at = i;
         while (i < n && src[i] != '\n') ++i;
+        if (names) names->emplace_back(), header_name(src + name_at, i - name_at, names->back());   // (before the output reaches these bytes)
         const bool header_closed = i < n;
         if (i < n) ++i;
         // (in place: everything read so far is at least as long as what goes out, except for a header cut short by the
@@ -301,7 +309,10 @@ inline size_t fastq_to_fasta(const uint8_t* src, size_t n, uint8_t* dst) {
         // `while (kseq_read(ks) >= 0)` then drops this record and everything behind it; one quality line is read even for
         // an empty sequence (kseq tests the length after the read).  oracle/POLICIES.md P10, oracle/dd_oracle.c: orc_records.
         while (i < n && src[i] != '\n') ++i;  // the rest of the '+' line
-        if (i >= n) return o_rec;
+        if (i >= n) {
+            if (names) names->pop_back();
+            return o_rec;
+        }
         ++i;
         size_t qual_len = 0;
         do {
@@ -313,7 +324,10 @@ inline size_t fastq_to_fasta(const uint8_t* src, size_t n, uint8_t* dst) {
             qual_len += len;
             i = e < n ? e + 1 : e;
         } while (qual_len < seq_len);
-        if (qual_len != seq_len) return o_rec;
+        if (qual_len != seq_len) {
+            if (names) names->pop_back();
+            return o_rec;
+        }
     }
     return o;
 }
@@ -518,5 +532,59 @@ inline bool read_file_bytes(const char* path, FileBuf& out, std::string& err, in
     return true;
 }
 
+// ---- record index --------------------------------------------------------------------------------------------------
+// Where the records of a file lie in K0's token stream (dd_pack.hip), from the bytes K0 reads (read_fasta_file's): what
+// stands in front of the first '>' or '@' is skipped; a line that starts with '>' or '@' is a header line and yields ONE
+// BREAK token where it ends (at its newline, or at the end of the buffer when that cuts it short) -- so a record's BREAK
+// stands IN FRONT of its bases, and an empty record is a BREAK followed by the next one's --; of every other line each
+// byte is a token (ambiguous ones a BREAK each) but the newline and a '\r' right in front of it (or of the end of the
+// buffer).  tok_start[r]: the token behind record r's BREAK; ntok = records + bases.
+struct FastaIndex {
+    std::vector<std::string> names;            // first word of each header line
+    std::vector<uint64_t> seq_len, tok_start;
+    uint64_t ntok = 0;
+};
+// names: those of a FASTQ buffer before fastq_to_fasta rewrote it (null: the header lines of p itself)
+inline void index_records(const uint8_t* p, size_t n, FastaIndex& ix, const std::vector<std::string>* names = nullptr) {
+    ix = FastaIndex();
+    size_t i = 0;
+    while (i < n && p[i] != '>' && p[i] != '@') ++i;
+    uint64_t tok = 0;
+    while (i < n) {   // i: the first byte of a line
+        const uint8_t* nl = static_cast<const uint8_t*>(memchr(p + i, '\n', n - i));
+        const size_t e = nl ? (size_t)(nl - p) : n;
+        if (p[i] == '>' || p[i] == '@') {
+            const size_t r = ix.seq_len.size();
+            ix.names.emplace_back();
+            if (names && r < names->size()) ix.names.back() = (*names)[r];
+            else header_name(p + i + 1, e - i - 1, ix.names.back());
+            ++tok;
+            ix.seq_len.push_back(0);
+            ix.tok_start.push_back(tok);
+        } else {
+            size_t len = e - i;
+            if (len && p[e - 1] == '\r') --len;
+            tok += len;
+            ix.seq_len.back() += len;   // (the first line of the walk is a header line: there is a record)
+        }
+        i = nl ? e + 1 : n;
+    }
+    ix.ntok = tok;
+}
+inline bool fasta_index_file(const char* path, FastaIndex& ix, std::string& err, int par = 1) {
+    FileBuf fb;
+    if (!read_file_bytes(path, fb, err, par)) return false;
+    std::vector<std::string> names;
+    const bool fastq = has_plus_line(fb.p, fb.len);
+    if (fastq) {
+        if (!fb.reserve(fb.len + 16)) {
+            err = std::string("out of host memory reading ") + path;
+            return false;
+        }
+        fb.len = fastq_to_fasta(fb.p, fb.len, fb.p, &names);
+    }
+    index_records(fb.p, fb.len, ix, fastq ? &names : nullptr);
+    return true;
+}
 
 }  // namespace dd

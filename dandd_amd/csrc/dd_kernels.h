@@ -328,6 +328,33 @@ struct ExactEmit {
 hipError_t launch_exact_emit(const ExactSorted& sorted, size_t count, int k, const ExactEmit& e, void* scratch, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// the positions of the selected k-mers (dd_exact_locate.hip), behind launch_exact_emit: the emitted records put in ascending
+// key order on the device, then every token of a painted genome looked up in them.
+// ---------------------------------------------------------------------------------------
+constexpr int kLocateJobs = 8;      // jobs one walk of a genome serves (a hit word each, in registers); more jobs: more units
+struct LocateUnit {                 // one per gridDim.y of a launch, device-resident table
+    const uint32_t* codes;          // the genome's token stream (ExactGenome)
+    const uint32_t* bad;
+    const unsigned long long* ntok;
+    int nj, pad;                    // jobs of this unit, 1..kLocateJobs
+    uint64_t all[kLocateJobs], none[kLocateJobs];
+    unsigned long long out[kLocateJobs];   // first word of each job's bitmap in the hit buffer; ceil(ntok / 64) words follow
+};
+struct LocateSet {                  // where launch_exact_locate_order left the records, ascending in (hi, lo)
+    const uint64_t* lo;
+    const uint64_t* hi;             // k > 32
+    const uint64_t* mask;
+    unsigned long long found;
+};
+// `work`: exact_locate_order_bytes(found, k) of device memory; lo / hi / mask [found] are the emit area and are overwritten
+size_t exact_locate_order_bytes(size_t found, int k);
+hipError_t launch_exact_locate_order(uint64_t* lo, uint64_t* hi, uint64_t* mask, size_t found, int k, void* work, hipStream_t st,
+                                     LocateSet* out);
+// every live thread writes its word of every job: the bitmaps need no zeroing.  Nothing is launched for an empty set.
+void launch_exact_locate(const LocateUnit* units_dev, int nunits, size_t max_segments, int k, int canonical, const LocateSet& set,
+                         uint64_t* hits_dev, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // exact greedy walk (dd_exact_greedy.hip) over the mask streams of kSchedStream: one launch per step of the walk reads
 // every stream once.  gain[kk][b] += masks of stream kk (store[seg.off[kk] .. seg.off[kk + 1])) that meet `chosen` nowhere
 // and hold bit b, for every b < 64 (a bit of `chosen` gains 0).  gain_dev [K][64], zeroed by the caller.

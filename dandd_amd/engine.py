@@ -35,6 +35,7 @@ EXPORTS = [
     "dd_exact_spectrum_device", "dd_exact_core_progressive_device", "dd_exact_select_device",
     "dd_exact_greedy", "dd_exact_greedy_device",
     "dd_exact_select_kmers", "dd_exact_select_kmers_device",
+    "dd_exact_locate", "dd_exact_locate_device", "dd_fasta_index",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
     "dd_comm_unique_id", "dd_comm_init", "dd_comm_destroy", "dd_comm_info", "dd_allreduce_max_u8", "dd_allgather_u8",
@@ -181,6 +182,12 @@ def load_library(path=None):
         fn.argtypes = [vp] + src + [i32, i32, vp, vp, i32, vp, vp, sz, C.POINTER(u64)]
     lib.dd_exact_subsets_from_hist.restype = i32
     lib.dd_exact_subsets_from_hist.argtypes = [vp, i32, vp]
+    for name, src in (("dd_exact_locate", [paths_t]), ("dd_exact_locate_device", [ptrs_t, sizes_t])):
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = [vp] + src + [i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(u64)]
+    lib.dd_fasta_index.restype = i32
+    lib.dd_fasta_index.argtypes = [C.c_char_p, vp, vp, sz, C.POINTER(u64), vp, sz, C.POINTER(sz), C.POINTER(u64)]
     lib.dd_timing_enable.restype = i32
     lib.dd_timing_enable.argtypes = [vp, i32]
     lib.dd_timing_read.restype = i32
@@ -226,6 +233,55 @@ def exact_subsets_from_hist(hist, n):
     if rc != 0:
         raise EngineError(f"libdandd_hip error {rc}: {lib.dd_last_error().decode()}")
     return card
+
+
+def fasta_index(path):
+    """Host-side (no device needed): the records of one FASTA / FASTQ file, plain or gzip, as the exact calls read it ->
+    (names list of str, seq_len uint64 [r], tok_start uint64 [r], ntok): tok_start[r] is the index in the file's token stream
+    of the first base of record r (every record's BREAK token stands in front of it), ntok the stream's length
+    (dd_fasta_index)."""
+    lib = load_library()
+    cap, names_cap = 1024, 1 << 16
+    for _ in range(2):
+        seq_len, tok_start = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+        names = C.create_string_buffer(max(names_cap, 1))
+        nrec, need, ntok = C.c_uint64(), C.c_size_t(), C.c_uint64()
+        rc = lib.dd_fasta_index(os.fsencode(path), seq_len.ctypes.data, tok_start.ctypes.data, cap, C.byref(nrec), names, names_cap,
+                                C.byref(need), C.byref(ntok))
+        if rc != 0:
+            err = EngineError(f"libdandd_hip error {rc}: {lib.dd_last_error().decode()}")
+            err.code = rc
+            raise err
+        if nrec.value <= cap and need.value <= names_cap:
+            r = int(nrec.value)
+            text = names.raw[:need.value].split(b"\0")[:r]
+            return [t.decode("utf-8", "replace") for t in text], seq_len[:r].copy(), tok_start[:r].copy(), int(ntok.value)
+        cap, names_cap = max(cap, int(nrec.value)), max(names_cap, int(need.value))
+    raise EngineError(f"dd_fasta_index: {path} changed between two reads")
+
+
+def regions_from_hits(words, k, tok_start, seq_len):
+    """Host-side, pure numpy: one job's hit bitmap of exact_locate (uint64 words, bit b of word w = token 64 w + b: a marked
+    k-mer ENDS there) and the file's record index (fasta_index) -> per record an int64 [m][2] array of 0-based half-open
+    (start, end) base intervals: the union of the spans [t - k + 1, t] of its hits, two hits merging iff they overlap or abut
+    (t2 - t1 <= k).  A k-mer holds no BREAK, so a span lies inside its record; hits of different records never merge."""
+    k = int(k)
+    w = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    bits = np.unpackbits(w.astype("<u8").view(np.uint8), bitorder="little")   # (little-endian bytes: byte i holds bits 8 i ..)
+    t = np.flatnonzero(bits).astype(np.int64)
+    starts, lens = np.asarray(tok_start, dtype=np.int64).reshape(-1), np.asarray(seq_len, dtype=np.int64).reshape(-1)
+    rec = np.searchsorted(starts, t, side="right") - 1                  # the last record that starts at or before the hit
+    out = []
+    for r in range(starts.size):
+        e = t[rec == r] - starts[r] + 1                                   # ends of the spans, in the record's bases
+        if e.size and (e[0] < k or e[-1] > lens[r]):
+            raise ValueError(f"record {r}: a hit outside the record's k-mers (k={k}, {int(lens[r])} bases)")
+        fresh = np.ones(e.size, dtype=bool)
+        fresh[1:] = np.diff(e) > k
+        first = np.flatnonzero(fresh)
+        last = np.append(first[1:], e.size) - 1
+        out.append(np.stack([e[first] - k, e[last]], axis=1) if e.size else np.zeros((0, 2), dtype=np.int64))
+    return out
 
 
 def kmer_text(kmers, k):
@@ -748,6 +804,39 @@ class Engine:
 
     def exact_select_kmers_device(self, fasta_ptrs, nbytes, k, all_masks, none_masks, cap=None):
         return self._exact_select_kmers(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), k, all_masks, none_masks, cap)
+
+    # -- where the selected k-mers lie: the same sort and emission, then every position looked up (dd_exact_locate.hip) ---
+    last_locate_found = None   # of the last exact_locate call: the distinct k-mers that match at least one job's query
+    def _exact_locate(self, src, k, jobs, ntok):
+        args, n, suffix = src
+        jobs = [(int(a), int(b), int(g)) for a, b, g in jobs]
+        nj = len(jobs)
+        al = np.array([a for a, _, _ in jobs] or [0], dtype=np.uint64)
+        no = np.array([b for _, b, _ in jobs] or [0], dtype=np.uint64)
+        ge = np.array([g for _, _, g in jobs] or [0], dtype=np.int32)
+        off = np.zeros(nj + 1, dtype=np.uint64)
+        for j, (_, _, g) in enumerate(jobs):
+            off[j + 1] = off[j] + np.uint64((int(ntok[g]) + 63) // 64 if 0 <= g < len(ntok) else 0)
+        hits = np.zeros(max(int(off[nj]), 1), dtype=np.uint64)
+        found = C.c_uint64()
+        self._check(getattr(self._lib, f"dd_exact_locate{suffix}")(self._ctx, *args, n, int(k), al.ctypes.data, no.ctypes.data, ge.ctypes.data, nj,
+                                                                  off.ctypes.data, hits.ctypes.data, C.byref(found)))
+        self.last_locate_found = int(found.value)
+        return [hits[int(off[j]):int(off[j + 1])].copy() for j in range(nj)]
+
+    def exact_locate(self, paths, k, jobs, ntok=None):
+        """FASTA files (n <= 64), one k, at most 1024 jobs (all_mask, none_mask, file index) -> list of uint64 arrays, one per
+        job: a bitmap over the tokens of that file (fasta_index gives the records' places in it), bit b of word w set iff a
+        valid k-mer ends at token 64 w + b and its membership mask contains all_mask and meets none_mask nowhere
+        (regions_from_hits turns one into base intervals).  ntok: the files' token counts where the caller has them, else one
+        fasta_index per file.  last_locate_found: the distinct k-mers that match at least one job's query."""
+        if ntok is None:                                              # the shape of the answer: the inputs' token counts
+            ntok = [fasta_index(p)[3] for p in paths]
+        return self._exact_locate(self._exact_src(paths=paths), k, jobs, ntok)
+
+    def exact_locate_device(self, fasta_ptrs, nbytes, k, jobs, ntok):
+        """exact_locate over FASTA bytes on the device; ntok: every input's token count (the library checks them)."""
+        return self._exact_locate(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), k, jobs, ntok)
 
     # -- exact greedy: the masks of every k kept on the device, one read of them per step (dd_exact_greedy.hip) ---------
     def _exact_greedy(self, src, kmin, kmax, mode, cand, nfixed, nsteps):

@@ -348,6 +348,20 @@ class HipExactBackend:
             err.found = e.found
             raise err from None
 
+    def locate_hits(self, leaf_paths, k, jobs):
+        """where the k-mers select_kmers writes lie, at one k of the window: jobs = (all_mask, none_mask, leaf index) ->
+        ([(names, seq_len, tok_start, ntok)] per leaf, [uint64 bitmap over the leaf's tokens] per job); bit t of a
+        bitmap: a k-mer of the job's query ends at token t of that leaf's file (engine.regions_from_hits makes intervals)."""
+        from ..engine import fasta_index
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, kmin, kmax = win
+        if not kmin <= int(k) <= kmax:
+            raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
+        index = [fasta_index(f) for f in files]
+        return index, self.engine.exact_locate(files, int(k), jobs, ntok=[ix[3] for ix in index])
+
     def greedy_cards(self, leaf_paths, mode, nfixed, nsteps, kmin):
         """HipBackend.greedy_cards on exact counts (dd_exact_greedy): -> (order [nsteps] as indices into leaf_paths, cards
         float64 [nsteps][K]), ties going to the leaf the caller lists first.  None -- the caller goes on as without this

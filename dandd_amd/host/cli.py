@@ -401,6 +401,14 @@ def core_command(args):
             sys.exit(f"core: --kmers-max {kmers_max}: a number of k-mers")
         if not groups:                                               # the whole universe: its core is the core genome
             groups, labels = [list(fastas)], ["all"]
+    if not args.regions and args.regions_k:
+        sys.exit("core: --regions-k goes with --regions")
+    if args.regions:
+        for k in args.regions_k or []:
+            if not max(1, window[0]) <= k <= window[1]:
+                sys.exit(f"core: --regions-k {k} is outside the k window {max(1, window[0])}..{window[1]}")
+        if not groups:
+            groups, labels = [list(fastas)], ["all"]
     os.makedirs(args.outdir, exist_ok=True)
     try:
         res = tree.core_tables(fastas, *window, orderings, groups)
@@ -413,6 +421,13 @@ def core_command(args):
                                     window=window, counts=res["groups"])
         except ValueError as e:
             sys.exit(f"core: {e} (--kmers-max {kmers_max}: raise it, or narrow the class)" if "more than the limit" in str(e) else f"core: {e}")
+    regions = []
+    if args.regions:
+        try:
+            regions = tree.core_regions(fastas, groups, args.regions, ks=sorted(set(args.regions_k or [])) or None, window=window,
+                                        counts=res["groups"])
+        except ValueError as e:
+            sys.exit(f"core: {e}")
     ks = res["ks"]
     delta_of = deltatree._window_delta
     spec = res["spectrum"]
@@ -446,6 +461,17 @@ def core_command(args):
                     fh.write(f">{labels[gi]}.{cls}.k{k}.{j} ngen={bin(int(m)).count('1')}\n{text}\n")
             index.append([labels[gi], cls, k, len(cell["masks"]), os.path.basename(path)])
         _write_csv(outfile + ".core_kmers.csv", ["group", "class", "k", "kmers", "file"], index)
+    if args.regions:
+        index = []
+        for cell in regions:                                         # (nothing is written before every cell is there)
+            gi, cls, k = cell["group"], cell["cls"], cell["k"]
+            path = f"{outfile}.core_regions.g{gi + 1}.{cls}.k{k}.bed"
+            with open(path, "w") as fh:
+                for fasta, rows in cell["genomes"]:
+                    base = os.path.basename(fasta)
+                    fh.write("".join(f"{name}\t{start}\t{end}\t{base}\n" for name, start, end in rows))
+                    index.append([labels[gi], cls, k, base, len(rows), sum(end - start for _, start, end in rows), os.path.basename(path)])
+        _write_csv(outfile + ".core_regions.csv", ["group", "class", "k", "fasta", "regions", "bases", "file"], index)
     tree.speciesinfo.save_cardkey(tree.experiment["tool"])
     tree.speciesinfo.save_references(fast=False)
 
@@ -663,6 +689,12 @@ def build_parser():
                     help="write the k-mers at this k of the window (repeatable) instead of each class's own")
     co.add_argument("--kmers-max", dest="kmers_max", type=int, default=None, metavar="N",
                     help="most k-mers of one group, class and k (default 1000000): more ends the command before anything is written")
+    co.add_argument("--regions", dest="regions", action="append", choices=["core", "private", "signature"], default=None, metavar="CLASS",
+                    help="also write where the k-mers of this class (core, private, signature; repeatable) lie in every genome of the "
+                         "group, as BED (record, start, end, fasta), at the k the group summary reports for it; without -g: of one "
+                         "group `all`, the whole universe")
+    co.add_argument("--regions-k", dest="regions_k", action="append", type=int, default=None, metavar="K",
+                    help="write the regions at this k of the window (repeatable) instead of each class's own")
     co.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     co.add_argument("-l", "--label", dest="label", default="")
     co.set_defaults(func=core_command)

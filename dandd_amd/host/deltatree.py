@@ -1112,15 +1112,11 @@ class DeltaTree:
 
     KMER_CLASSES = ("core", "private", "signature")       # the columns of core_tables' groups, in that order
 
-    def core_kmers(self, fastas, groups, wanted, ks=None, limit=1_000_000, window=None, counts=None):
-        """The k-mers behind the cells of core_tables' `groups`: for every group (lists of FASTAs of the universe `fastas`) and
-        every class of `wanted` (core (G, 0), private (0, full ^ G), signature (G, full ^ G)) the k-mers themselves at the k
-        where count / k is largest over the window (_window_delta's rule: the *_k of the group summary), or at every k of
-        `ks`.  window: (lo, hi), default the tree's --ksweep; counts: core_tables(...)["groups"] of the same window where the
-        caller has it, else one select_counts call.  ONE select_kmers call per distinct k carries every query of that k; the
-        records come back once each, ascending, and go to their queries by their masks, here.  A cell of more than `limit`
-        k-mers is a ValueError that names it, before any k-mer is asked for.
-        -> list of dict(group, cls, k, kmers uint64 [m][2] (lo, hi), masks uint64 [m]) in (group, class as KMER_CLASSES, k) order"""
+    def _core_cells(self, fastas, groups, wanted, ks, window, counts, entry):
+        """What core_kmers and core_regions share: the window, the backend (which must have select_counts and `entry`), the leaf
+        files, and one cell per group, class of `wanted` and k -- the class's argmax of count / k over the window
+        (_window_delta's rule: the *_k of the group summary), or every k of `ks`.
+        -> (backend, leaf files, n, members [g] (indices into fastas), cells [(group, class, k, all, none, count)])"""
         by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
         nodes = [by_fasta[f] for f in fastas]
         n = len(nodes)
@@ -1138,13 +1134,14 @@ class DeltaTree:
                 raise ValueError(f"k={k} is outside the window {lo}..{hi}")
         exp = dict(self.experiment, ksweep=(lo, hi))
         be = backend_for(exp)
-        for entry in ("select_counts", "select_kmers"):
-            if not hasattr(be, entry):
-                raise ValueError(f"the backend {getattr(be, 'name', type(be).__name__)} has no {entry}: intersections need exact membership masks")
+        for name in ("select_counts", entry):
+            if not hasattr(be, name):
+                raise ValueError(f"the backend {getattr(be, 'name', type(be).__name__)} has no {name}: intersections need exact membership masks")
         paths = self._leaf_files(nodes, lo, hi)
         index = {f: i for i, f in enumerate(fastas)}
         full = (1 << n) - 1
-        gmasks = [sum(1 << index[f] for f in set(g)) for g in groups]
+        members = [sorted({index[f] for f in g}) for g in groups]
+        gmasks = [sum(1 << i for i in m) for m in members]
         query = {"core": lambda G: (G, 0), "private": lambda G: (0, full ^ G), "signature": lambda G: (G, full ^ G)}
         if counts is None:
             alls = [m for G in gmasks for m in (G, 0, G)]
@@ -1153,15 +1150,27 @@ class DeltaTree:
             if counts is None:
                 raise ValueError(f"the backend has no membership masks for {n} genomes")
         counts = np.asarray(counts).astype(np.uint64).reshape(len(groups), 3, len(window_ks))
-        cells = []                                                     # (group, class, k, all, none, count)
+        cells = []
         for gi, G in enumerate(gmasks):
             for cls in wanted:
                 col = [int(v) for v in counts[gi, self.KMER_CLASSES.index(cls)]]
                 for k in ([int(k) for k in ks] if ks else [_window_delta(col, window_ks)[1]]):
-                    count = col[k - lo]
-                    if count > limit:
-                        raise ValueError(f"group {gi + 1}, {cls}, k={k}: {count} k-mers, more than the limit of {limit}")
-                    cells.append((gi, cls, k, *query[cls](G), count))
+                    cells.append((gi, cls, k, *query[cls](G), col[k - lo]))
+        return be, paths, n, members, cells
+
+    def core_kmers(self, fastas, groups, wanted, ks=None, limit=1_000_000, window=None, counts=None):
+        """The k-mers behind the cells of core_tables' `groups`: for every group (lists of FASTAs of the universe `fastas`) and
+        every class of `wanted` (core (G, 0), private (0, full ^ G), signature (G, full ^ G)) the k-mers themselves at the k
+        where count / k is largest over the window (_window_delta's rule: the *_k of the group summary), or at every k of
+        `ks`.  window: (lo, hi), default the tree's --ksweep; counts: core_tables(...)["groups"] of the same window where the
+        caller has it, else one select_counts call.  ONE select_kmers call per distinct k carries every query of that k; the
+        records come back once each, ascending, and go to their queries by their masks, here.  A cell of more than `limit`
+        k-mers is a ValueError that names it, before any k-mer is asked for.
+        -> list of dict(group, cls, k, kmers uint64 [m][2] (lo, hi), masks uint64 [m]) in (group, class as KMER_CLASSES, k) order"""
+        be, paths, n, _, cells = self._core_cells(fastas, groups, wanted, ks, window, counts, "select_kmers")
+        for gi, cls, k, _, _, count in cells:
+            if count > limit:
+                raise ValueError(f"group {gi + 1}, {cls}, k={k}: {count} k-mers, more than the limit of {limit}")
         got = {}
         for k in sorted({cell[2] for cell in cells}):
             mine = sorted({(a, b) for _, _, kk, a, b, _ in cells if kk == k})
@@ -1177,6 +1186,35 @@ class DeltaTree:
             if int(keep.sum()) != count:
                 raise ValueError(f"group {gi + 1}, {cls}, k={k}: {int(keep.sum())} k-mers came back, {count} were counted")
             out.append(dict(group=gi, cls=cls, k=k, kmers=kmers[keep], masks=masks[keep]))
+        return out
+
+    def core_regions(self, fastas, groups, wanted, ks=None, window=None, counts=None):
+        """Where the k-mers of core_kmers' cells lie in the genomes: for every group, every class of `wanted` and the k of
+        core_kmers' rule (the class's argmax of count / k over the window, or every k of `ks`), the query is painted onto every
+        genome OF ITS GROUP and the hit positions become 0-based half-open base intervals per record -- the union of the
+        k-mers' spans, overlapping and abutting ones merged (engine.regions_from_hits).  ONE locate_hits call per distinct k
+        carries every job of that k.  window, counts: as for core_kmers.
+        -> list of dict(group, cls, k, genomes [(fasta, [(record name, start, end)])]) in (group, class as KMER_CLASSES, k)
+        order; a cell's genomes in the universe's order, a genome's rows by record, then start"""
+        from ..engine import regions_from_hits
+        be, paths, n, members, cells = self._core_cells(fastas, groups, wanted, ks, window, counts, "locate_hits")
+        got = {}                                                       # (k, all, none, genome) -> intervals per record
+        names = {}                                                     # genome -> its records' names
+        for k in sorted({cell[2] for cell in cells}):
+            jobs = sorted({(a, b, g) for gi, _, kk, a, b, _ in cells if kk == k for g in members[gi]})
+            res = be.locate_hits(paths, k, jobs)
+            if res is None:
+                raise ValueError(f"the backend has no membership masks for {n} genomes")
+            recs, hits = res
+            for (a, b, g), words in zip(jobs, hits):
+                rec_names, seq_len, tok_start, _ = recs[g]
+                names[g] = list(rec_names)
+                got[(k, a, b, g)] = regions_from_hits(words, k, tok_start, seq_len)
+        out = []
+        for gi, cls, k, a, b, _ in cells:
+            per = [(fastas[g], [(name, int(s), int(e)) for name, spans in zip(names[g], got[(k, a, b, g)]) for s, e in spans])
+                   for g in members[gi]]
+            out.append(dict(group=gi, cls=cls, k=k, genomes=per))
         return out
 
     # ---- batched GPU union schedules ------------------------------------------------------------------

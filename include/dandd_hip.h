@@ -279,6 +279,44 @@ int dd_exact_select_kmers_device(dd_ctx *, const uint8_t *const *fasta_dev, cons
                                  const uint64_t *all, const uint64_t *none, int nq, uint64_t *kmers, uint64_t *masks,
                                  size_t cap, uint64_t *found);
 
+/* ---- where the selected k-mers lie -----------------------------------------------------------------------------
+ * dd_exact_select_kmers writes the k-mers that match a query; this says WHERE they stand in an input, without the k-mers
+ * leaving the device (dd_exact_locate.hip).  ONE k per call, over the n inputs of the universe and a list of JOBS: job j
+ * paints query (all[j], none[j]) onto input genome[j].  The bit rules are dd_exact_select's: a bit >= n set in all[j] or
+ * none[j] is DD_EINVAL, all & none != 0 is legal and paints nothing, all = none = 0 paints every position where a valid
+ * k-mer ends.  1 <= n <= 64, 1 <= k <= 64, 1 <= njobs <= 1024 (more is DD_EINVAL: split the jobs over calls), genome[j] in
+ * 0..n-1.
+ *   hits      job j owns the words off[j] .. off[j+1]-1: a bitmap over the tokens of input genome[j] as K0 lays them out
+ *             (dd_fasta_index below), word w, bit b = token 64 w + b.  The bit is set iff a valid k-mer (no BREAK among its k
+ *             tokens; canonical per the context) ENDS at that token and its membership mask m has (m & all) == all and
+ *             (m & none) == 0.  Bits at or beyond the input's ntok are 0.  off[j+1] - off[j] must be ceil(ntok / 64) of
+ *             input genome[j], else DD_EINVAL with a message naming the job and the number expected; hits may be null only
+ *             when no word is asked for.  Nothing is written to hits unless the call returns DD_OK.
+ *   *found    the number of distinct k-mers whose mask matches at least one job's query (dd_exact_select_kmers' meaning)
+ * Two calls on the same inputs return identical bytes.  An input that is empty or shorter than k gets an all-zero bitmap.
+ * The sort, the masks and the emission are dd_exact_select_kmers' (the jobs' distinct (all, none) pairs are its queries), so
+ * are budget and passes (DD_EXACT_MB), dd_last_sketch_stats' third value and the DD_KERNEL_EXACT timer.  The records wait in
+ * 24 bytes x the k-mer slots of the inputs of HBM (DD_ENOMEM with a message naming the bytes when that cannot be had) and
+ * are put in key order there once, after the last pass, with the exact workspace as the sort's other half. */
+int dd_exact_locate(dd_ctx *, const char *const *paths, int n, int k, const uint64_t *all /*[njobs]*/,
+                    const uint64_t *none /*[njobs]*/, const int32_t *genome /*[njobs]*/, int njobs,
+                    const uint64_t *off /*[njobs+1], in 64-bit words*/, uint64_t *hits /*[off[njobs]]*/, uint64_t *found);
+int dd_exact_locate_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int k,
+                           const uint64_t *all, const uint64_t *none, const int32_t *genome, int njobs,
+                           const uint64_t *off, uint64_t *hits, uint64_t *found);
+/* Host only, no context and no device: names, sequence lengths and token starts of the records of one FASTA / FASTQ file,
+ * plain or gzip, read by the loaders and record rules the exact calls and dd_sketch_files use.  K0 puts one BREAK token
+ * where each header line ends -- IN FRONT of its record's bases -- and one for every ambiguous byte, so
+ *   tok_start[r]  the index in the file's token stream of the first base of record r (of where it would be: an empty
+ *                 record's is the next record's BREAK, or ntok); tok_start[0] = 1
+ *   seq_len[r]    its bases, ambiguous ones included
+ *   *ntok         the length of the stream = records + bases
+ *   names         the first words of the header lines, NUL-terminated, one after the other; *names_need their bytes
+ * *nrec > cap or *names_need > names_cap is DD_OK and a count, as found > cap is for dd_exact_select_kmers: the array that
+ * lacks room is not written and the caller comes back with room. */
+int dd_fasta_index(const char *path, uint64_t *seq_len /*[cap]*/, uint64_t *tok_start /*[cap]*/, size_t cap, uint64_t *nrec,
+                   char *names, size_t names_cap, size_t *names_need, uint64_t *ntok);
+
 /* ---- exact greedy orderings -----------------------------------------------------------------------------------
  * dd_greedy on exact counts, for `dandd greedy` on trees built with `--exact`: the same walk, the same SELECTION RULE
  * (above, word for word: the largest card[kk] / (kmin + kk) in IEEE double, ties between k to the LARGER k, ties between
@@ -309,7 +347,7 @@ int dd_exact_greedy_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission of dd_exact_select_kmers */
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate */
 #define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);
