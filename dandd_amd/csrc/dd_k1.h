@@ -167,6 +167,92 @@ DD_D void hll_update2(const R& r0, uint64_t h0, const R& r1, uint64_t h1, int p)
     }
 }
 
+// ---- sweep_kernel's raises: queued per wave, applied 64 at a time ------------------------------------------------------
+// A candidate (lz >= the register's byte) does not run raise()'s load / compare-and-swap sequence -- some twenty wave
+// instructions and two LDS round trips for, typically, one lane: the lane appends a record
+// (LDS byte address | (rho - 1) << 24) to its WAVE's queue behind the group's registers (dd_plan.hip makes the room), and once
+// 64 wait they are applied one per lane.  Exact: cas_raise is a byte-max, so a record that names a register raised since,
+// or one named twice, changes nothing; probes in between see a stale (lower) byte, which only makes more candidates.
+// Capacity: a wave applies 64 records as soon as 64 wait, so an append finds at most 63, and one step (a k pair) adds at
+// most 31 -- kRaiseDense or more candidate lanes, as in every step of a cold job, are applied at once, not queued: never
+// more than 94 of the kRaiseQueueRecords (dd_kernels.h).  Every function here is reached by whole waves.
+constexpr uint32_t kRaiseDense = 32;
+static_assert(63 + (kRaiseDense - 1) <= kRaiseQueueRecords, "raise queue capacity");
+
+struct RaiseQueue {
+    uint32_t base;     // LDS byte address of this wave's records
+    uint32_t dense;    // kRaiseDense, or 0: no queue (the 32-bit class; a group that left no room), every raise is applied at once
+    uint32_t waiting;  // records in the queue (wave-uniform)
+};
+DD_D uint32_t lds_load32(uint32_t a) { return *(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)a; }  // (absolute, as RegsLds)
+DD_D void lds_store32(uint32_t a, uint32_t v) { *(__attribute__((address_space(3))) uint32_t*)(uintptr_t)a = v; }
+DD_D void raise_record(uint32_t rec) {
+    const uint32_t a = rec & 0xFFFFFFu;
+    (void)cas_raise<RegsLds>(a, RegsLds::load32(a), (rec >> 24) + 1u);
+}
+// rho - 1 from a probe, in its long form where the 32 bits after the index are all zero (rho_of)
+DD_D uint32_t rho_minus_1(const Probe& q, int p) {
+    return q.lz != ~0u ? q.lz : 32u + (uint32_t)__builtin_clz((q.lo << p) | (1u << (p - 1)));
+}
+// Behind the wave-level "any candidate" branch of one or two updates: the lanes of m0 (c0: this lane is one) must raise
+// their register at a to rho(qa), those of m1 theirs at b to rho(qb).
+template <bool QUEUE>
+DD_D void sweep_raise(RaiseQueue& s, int p, unsigned long long m0, bool c0, uint32_t a, const Probe& qa,
+                      unsigned long long m1, bool c1, uint32_t b, const Probe& qb) {
+    uint32_t z0 = qa.lz, z1 = qb.lz;
+    if (__builtin_expect(__any((int32_t)(z0 | z1) < 0), 0)) {  // (lz is <= 31 or 0xFFFFFFFF)
+        z0 = rho_minus_1(qa, p);
+        z1 = rho_minus_1(qb, p);
+    }
+    const uint32_t n0 = (uint32_t)__builtin_popcountll(m0), n = n0 + (uint32_t)__builtin_popcountll(m1);
+    if (QUEUE && n < s.dense) {
+        // (one scalar, so that a lane's slot is one v_lshl_add of its rank)
+        const uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane(s.base + 4u * s.waiting);
+        if (c0) lds_store32(at + 4u * lanes_below(m0), a | (z0 << 24));
+        if (c1) lds_store32((uint32_t)__builtin_amdgcn_readfirstlane(at + 4u * n0) + 4u * lanes_below(m1), b | (z1 << 24));
+        s.waiting += n;
+        if (s.waiting >= 64u) {
+            s.waiting -= 64u;
+            raise_record(lds_load32(s.base + 4u * (s.waiting + lanes_below(~0ull))));
+        }
+        return;
+    }
+    if (c0) (void)cas_raise<RegsLds>(a, RegsLds::load32(a), z0 + 1u);
+    if (c1) (void)cas_raise<RegsLds>(b, RegsLds::load32(b), z1 + 1u);
+}
+// what still waits when the job's tiles are done
+DD_D void sweep_drain(RaiseQueue& s) {
+    const uint32_t lane = lanes_below(~0ull);
+    if (lane < s.waiting) raise_record(lds_load32(s.base + 4u * lane));
+    s.waiting = 0;
+}
+// hll_update / hll_update2 on the group's LDS registers.  MASKED (the walk's CHECK variant): only for the lanes with ok
+// (okm: its ballot, taken by the caller beside the compare).
+// The candidate masks are the ballots of the plain compares, combined as scalars: the ballot of a combined condition
+// costs a v_cndmask + v_cmp pair per update, in the loop every update runs.
+template <bool QUEUE, bool MASKED>
+DD_D void sweep_update(RaiseQueue& s, uint32_t slot, uint64_t h, unsigned long long okm, bool ok, int p) {
+    const RegsLds regs{slot};
+    const Probe q = probe(h, p);
+    const uint32_t a = regs.at(q.hi, p);
+    const bool r = q.lz >= regs.bound(a);
+    unsigned long long mask = __builtin_amdgcn_ballot_w64(r);
+    if (MASKED) mask &= okm;
+    if (mask) sweep_raise<QUEUE>(s, p, mask, MASKED ? (ok & r) : r, a, q, 0ull, false, 0u, Probe{0u, 0u, 0u, 0u});
+}
+template <bool QUEUE, bool MASKED>
+DD_D void sweep_update2(RaiseQueue& s, uint32_t slot0, uint64_t h0, unsigned long long okm0, bool ok0,
+                        uint32_t slot1, uint64_t h1, unsigned long long okm1, bool ok1, int p) {
+    const RegsLds r0{slot0}, r1{slot1};
+    const Probe qa = probe(h0, p), qb = probe(h1, p);
+    const uint32_t a = r0.at(qa.hi, p), b = r1.at(qb.hi, p);
+    const uint32_t v0 = r0.bound(a), v1 = r1.bound(b);
+    const bool c0 = qa.lz >= v0, c1 = qb.lz >= v1;
+    unsigned long long m0 = __builtin_amdgcn_ballot_w64(c0), m1 = __builtin_amdgcn_ballot_w64(c1);
+    if (MASKED) m0 &= okm0, m1 &= okm1;
+    if (m0 | m1) sweep_raise<QUEUE>(s, p, m0, MASKED ? (ok0 & c0) : c0, a, qa, m1, MASKED ? (ok1 & c1) : c1, b, qb);
+}
+
 // Reverse the order of the 16 2-bit fields of a code word: the token stream stores token j at bits
 // [2j, 2j+1] (oldest lowest), the forward window wants the newest token lowest.
 DD_D uint32_t pairrev32(uint32_t x) {

@@ -121,11 +121,14 @@ struct SweepJob {               // one per workgroup, device-resident table
 };
 constexpr int kBucketMode = 5;
 constexpr int kBucketFromLog2m = 17;  // registers stay in HBM (scatter + replay) from this log2m on
+constexpr unsigned kRaiseQueueRecords = 128;                        // sweep_kernel's raise queue (dd_k1.h, RaiseQueue): records per wave
+constexpr unsigned kRaiseQueueBytes = 16 * kRaiseQueueRecords * 4;  // ... bytes per 1024-thread workgroup
 struct SweepPlan {
     int log2m;
     int canonical;
     int threads;                // workgroup size
     int lds_bytes;              // dynamic LDS per workgroup
+    int queue_off = 0;          // mode 0, k classes 1 / 3 / 2: LDS byte offset of the raise queues behind the group's registers (dd_k1.h), 0 = none
     int mode;                   // 0: registers in LDS (log2m <= 16); 5 (kBucketMode): in HBM, scatter to buckets + replay (below)
     // kBucketMode only
     int logg = 0;               // one 4-bit filter entry (bounds saturate at 15, two entries per byte) per 2^logg registers

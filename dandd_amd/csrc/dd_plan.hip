@@ -279,6 +279,12 @@ std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbyte
         } else {
             sc.plan.mode = 0;
             sc.plan.lds_bytes = (int)((size_t)max_nk * m);
+            // The 64-, 96- and 128-bit classes queue their register raises per wave (dd_k1.h, RaiseQueue) behind the group's
+            // registers while that keeps two workgroups per CU; the 32-bit class stays at three of 48 KiB without.
+            if (kc != 0 && (size_t)sc.plan.lds_bytes + kRaiseQueueBytes <= lds_budget) {
+                sc.plan.queue_off = sc.plan.lds_bytes;
+                sc.plan.lds_bytes += (int)kRaiseQueueBytes;
+            }
         }
         classes.push_back(std::move(sc));
     }

@@ -32,27 +32,34 @@
 namespace dd {
 namespace {
 
-// every k of the group for the token just pushed
-template <int KC, bool CANON, bool CHECK, typename Win, typename MakeRegs>
-DD_D void sweep_token(const Win& win, int run, int kfirst, int nk, int p, const MakeRegs& slot) {
+// every k of the group for the token just pushed; reached by whole waves (the raise queue's count is wave-uniform)
+template <int KC, bool CANON, bool CHECK, typename Win>
+DD_D void sweep_token(const Win& win, int run, int kfirst, int nk, int p, RaiseQueue& s) {
     // The loop counter stays wave-uniform in both variants (k-dependent masks and shifts are then
-    // scalar); in the CHECK variant lanes whose run is too short for k are simply predicated off.
+    // scalar); in the CHECK variant lanes whose run is too short for k hash their window all the same and are
+    // left out of the update (ok), and the ks no lane of the wave has a window for are skipped.
+    constexpr bool QUEUE = KC != 0;
     int j = 0;
 #pragma unroll 1
     for (; j + 1 < nk; j += 2) {
         const int k = kfirst + j;
-        if (!CHECK || run >= k + 1)
-            hll_update2(slot(j), win.template hash<CANON>(k), slot(j + 1), win.template hash<CANON>(k + 1), p);
-        else if (run >= k)
-            hll_update(slot(j), win.template hash<CANON>(k), p);
+        const bool ok0 = !CHECK || run >= k, ok1 = !CHECK || run > k;
+        const unsigned long long okm0 = CHECK ? __builtin_amdgcn_ballot_w64(run >= k) : ~0ull, okm1 = CHECK ? __builtin_amdgcn_ballot_w64(run > k) : ~0ull;
+        if (CHECK && !okm0) return;
+        sweep_update2<QUEUE, CHECK>(s, (uint32_t)j, win.template hash<CANON>(k), okm0, ok0,
+                                    (uint32_t)j + 1u, win.template hash<CANON>(k + 1), okm1, ok1, p);
     }
-    if (j < nk && (!CHECK || run >= kfirst + j)) hll_update(slot(j), win.template hash<CANON>(kfirst + j), p);
+    if (j < nk) {
+        const int k = kfirst + j;
+        const unsigned long long okm = CHECK ? __builtin_amdgcn_ballot_w64(run >= k) : ~0ull;
+        if (!CHECK || okm) sweep_update<QUEUE, CHECK>(s, (uint32_t)j, win.template hash<CANON>(k), okm, !CHECK || run >= k, p);
+    }
 }
 
 // The registers of the job's k-group live in LDS (2^p * nk bytes <= 160 KiB): log2m <= 16.
 template <int KC, bool CANON>
 __global__ __launch_bounds__(1024) void sweep_kernel(const SweepGenome* __restrict__ genomes,
-                                                    const SweepJob* __restrict__ jobs, int p) {
+                                                    const SweepJob* __restrict__ jobs, int p, uint32_t queue_off) {
     lds_starts_at_zero();
     const SweepJob job = jobs[blockIdx.x];
     const SweepGenome g = genomes[job.genome];
@@ -80,23 +87,30 @@ __global__ __launch_bounds__(1024) void sweep_kernel(const SweepGenome* __restri
     __syncthreads();
 
     const int kmaxg = kfirst + nk - 1;
-    auto lds_slot = [](int j) { return RegsLds{(uint32_t)j}; };
+    // (queue_off: where the plan put the workgroup's raise queues, 0 = it had no room for them)
+    RaiseQueue s;
+    s.base = queue_off + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kRaiseQueueRecords * 4u);
+    s.dense = (KC != 0 && queue_off) ? kRaiseDense : 0u;
+    s.waiting = 0;
 
     for (unsigned tile = job.tile_begin; tile < job.tile_end; ++tile) {
         const TileIn cur = next;
         fetch_tile(g, job, ntok, tile + 1, next);
-        if (!cur.live) continue;  // (a lane beyond the stream just skips the tile: it shares no state with its wave)
+        // Lanes beyond the stream stay in the loop as all-BREAK segments while any lane of their wave has tokens: the
+        // raise queue is the wave's, and every append and flush must be reached by the whole wave.
+        if (!__any(cur.live)) continue;
         SweepWindows<KC> win;
         walk_segment(cur, win, [&](auto clean, int run) {
             if constexpr (decltype(clean)::value) {
-                sweep_token<KC, CANON, false>(win, 0, kfirst, nk, p, lds_slot);
+                sweep_token<KC, CANON, false>(win, 0, kfirst, nk, p, s);
             } else {
                 // wave-uniform fast path: no lane of the wave is within kmaxg tokens of a BREAK
-                if (__all(run >= kmaxg)) sweep_token<KC, CANON, false>(win, run, kfirst, nk, p, lds_slot);
-                else sweep_token<KC, CANON, true>(win, run, kfirst, nk, p, lds_slot);
+                if (__all(run >= kmaxg)) sweep_token<KC, CANON, false>(win, run, kfirst, nk, p, s);
+                else sweep_token<KC, CANON, true>(win, run, kfirst, nk, p, s);
             }
         });
     }
+    if (s.dense) sweep_drain(s);
     __syncthreads();
 
     // merge the group's registers into the genome's slab (rows krow .. krow+nk-1 are contiguous)
@@ -420,7 +434,7 @@ void launch_sweep(const SweepGenome* genomes, const SweepJob* jobs, int njobs, i
     if (njobs <= 0) return;
     dispatch_kc_canon(kclass, plan.canonical, [&](auto kc, auto cn) {
         launch_full_lds<sweep_kernel<decltype(kc)::value, decltype(cn)::value>>(dim3((unsigned)njobs), dim3((unsigned)plan.threads), (size_t)plan.lds_bytes, st,
-                                                                                genomes, jobs, plan.log2m);
+                                                                                genomes, jobs, plan.log2m, (uint32_t)plan.queue_off);
     });
 }
 
