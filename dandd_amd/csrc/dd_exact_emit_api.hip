@@ -1,0 +1,203 @@
+// dd_exact_emit_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h) that hand k-mers out instead of counting
+// them: the selected k-mers themselves (dd_exact_select_kmers), where they lie in each genome (dd_exact_locate) and the
+// record index of a file that turns those places into names (dd_fasta_index).  Both exact entries are one emission
+// (exact_emit_records, dd_exact_host.h) and one ordering of its records on the device (launch_exact_emit_order).
+// Host-side orchestration only; the kernels are in dd_exact_sched.hip (emit_kernel) and dd_exact_locate.hip.
+#include "dd_exact_host.h"
+
+extern "C" {
+
+// ------------------------------------------------------------------- the selected k-mers
+// The sort of the schedules for ONE k, then the k-mers whose mask matches a query leave for c->emit instead of being counted.
+// Chunks finish in any order and a pass holds an arbitrary part of the k-mer space, so the records are put in order afterwards,
+// on the device: ascending in the 2k-bit key, hi then lo.  The keys are distinct: the order is total, two calls agree byte for byte.
+int dd_exact_select_kmers_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int k, const uint64_t* all,
+                                 const uint64_t* none, int nq, uint64_t* kmers, uint64_t* masks, size_t cap, uint64_t* found) {
+    if (exact_frame(c, fasta_dev, nbytes, n, 64, k, k, found, cap && (!kmers || !masks))) return DD_EINVAL;
+    if (nq > dd::kEmitMaxQueries)
+        return fail(DD_EINVAL, "nq=%d: at most %d queries in one call (what one launch holds); split them over calls", nq, dd::kEmitMaxQueries);
+    std::vector<uint64_t> table;
+    if (select_table(all, none, nq, n, table)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    *found = 0;
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n, in))) return rc;
+    c->st_blocks = 0;
+    if (!in.slots) return DD_OK;
+    const size_t dcap = std::min(cap, in.slots);   // (no more distinct k-mers than slots)
+    if (c->emit.reserve(exact_emit_bytes(dcap)))
+        return fail(DD_ENOMEM, "exact select k-mers: no device memory for an output of %zu records (24 bytes each); ask with a smaller cap", dcap);
+    dd::ExactEmit e{};
+    unsigned long long total = 0;
+    if ((rc = exact_emit_records(c, in, n, k, "exact select k-mers", nq, table.data(), table.size() * sizeof(uint64_t), dcap, e, &total))) return rc;
+    *found = total;
+    if (!total || total > cap) return DD_OK;   // (more than the caller has room for: the count is the answer, nothing was kept whole)
+    if ((rc = exact_emit_order_room(c, "exact select k-mers", total, k))) return rc;
+    dd::LocateSet set{};
+    {
+        Span sp(c, DD_KERNEL_EXACT);
+        DD_HIP(dd::launch_exact_emit_order(e.lo, e.hi, e.mask, (size_t)total, k, c->exact.p, st, &set));
+    }
+    const bool wide = k > 32;
+    const size_t m = (size_t)total;
+    std::vector<uint64_t> lo(m), hi(wide ? m : 0), mk(m);
+    DD_HIP(hipMemcpyAsync(lo.data(), set.lo, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (wide) DD_HIP(hipMemcpyAsync(hi.data(), set.hi, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    DD_HIP(hipMemcpyAsync(mk.data(), set.mask, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    DD_HIP(hipStreamSynchronize(st));
+    for (size_t i = 0; i < m; ++i) kmers[2 * i] = lo[i], kmers[2 * i + 1] = wide ? hi[i] : 0ull, masks[i] = mk[i];
+    return DD_OK;
+}
+
+int dd_exact_select_kmers(dd_ctx* c, const char* const* paths, int n, int k, const uint64_t* all, const uint64_t* none, int nq,
+                          uint64_t* kmers, uint64_t* masks, size_t cap, uint64_t* found) {
+    return exact_path_form(c, paths, n, 64, k, k, found, [&](auto p, auto s) {
+        return dd_exact_select_kmers_device(c, p, s, n, k, all, none, nq, kmers, masks, cap, found);
+    });
+}
+
+// ------------------------------------------------------------------- where the selected k-mers lie
+// dd_exact_locate.hip: the emission with the jobs' distinct (all, none) pairs as queries and room for every distinct k-mer
+// the inputs can hold, the records put in key order, then one walk of every painted genome that looks each k-mer up in
+// them.  Nothing but the bitmaps comes back.
+namespace {
+
+// every genome's ntok, for the shape of the answer: each job's share of off[] checked against it
+int locate_shape(dd_ctx* c, const ExactInputs& in, int n, const int32_t* genome, int njobs, const uint64_t* off,
+                 std::vector<unsigned long long>& ntok, size_t& max_segments) {
+    ntok.assign((size_t)n, 0ull);
+    if (in.slots) {
+        for (int g = 0; g < n; ++g)
+            DD_HIP(hipMemcpyAsync(&ntok[(size_t)g], in.etab[(size_t)g].ntok, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        DD_HIP(hipStreamSynchronize(c->stream));
+    }
+    max_segments = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const uint64_t want = (ntok[(size_t)genome[j]] + dd::kSegTokens - 1) / dd::kSegTokens;
+        if (off[j + 1] - off[j] != want)
+            return fail(DD_EINVAL, "job %d: off[%d] - off[%d] = %llu words, %llu expected (input %d holds %llu tokens, 64 to a word)", j, j + 1, j,
+                        (unsigned long long)(off[j + 1] - off[j]), (unsigned long long)want, genome[j], ntok[(size_t)genome[j]]);
+        max_segments = std::max(max_segments, (size_t)want);
+    }
+    return DD_OK;
+}
+
+// the jobs of a genome, kLocateJobs to a unit
+void locate_units(const ExactInputs& in, const std::vector<unsigned long long>& ntok, const uint64_t* all, const uint64_t* none,
+                  const int32_t* genome, int njobs, const uint64_t* off, std::vector<dd::LocateUnit>& units) {
+    std::vector<int> order((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) order[(size_t)j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return genome[x] < genome[y]; });
+    for (int j : order) {
+        const dd::ExactGenome& eg = in.etab[(size_t)genome[j]];
+        if (!ntok[(size_t)genome[j]]) continue;   // (an empty bitmap)
+        if (units.empty() || units.back().ntok != eg.ntok || units.back().nj == dd::kLocateJobs) {
+            units.push_back(dd::LocateUnit{});
+            units.back().codes = eg.codes, units.back().bad = eg.bad, units.back().ntok = eg.ntok;
+        }
+        dd::LocateUnit& u = units.back();
+        u.all[u.nj] = all[j], u.none[u.nj] = none[j], u.out[u.nj] = off[j] - off[0];
+        ++u.nj;
+    }
+}
+
+}  // namespace
+
+int dd_exact_locate_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int k, const uint64_t* all,
+                           const uint64_t* none, const int32_t* genome, int njobs, const uint64_t* off, uint64_t* hits, uint64_t* found) {
+    if (exact_frame(c, fasta_dev, nbytes, n, 64, k, k, found, !all || !none || !genome || !off)) return DD_EINVAL;
+    if (njobs < 1 || njobs > dd::kEmitMaxQueries)
+        return fail(DD_EINVAL, "njobs=%d outside 1..%d (what one launch holds); split the jobs over calls", njobs, dd::kEmitMaxQueries);
+    const uint64_t outside = n == 64 ? 0ull : ~((1ull << n) - 1ull);
+    for (int j = 0; j < njobs; ++j) {
+        if (genome[j] < 0 || genome[j] >= n) return fail(DD_EINVAL, "job %d: genome %d outside 0..%d", j, genome[j], n - 1);
+        if ((all[j] | none[j]) & outside) return fail(DD_EINVAL, "job %d: a bit outside 0..%d is set", j, n - 1);
+    }
+    if (off[njobs] < off[0]) return fail(DD_EINVAL, "off[] must ascend");
+    const uint64_t words = off[njobs] - off[0];   // (each job's own share is checked once the inputs' token counts are known)
+    if (words && !hits) return fail(DD_EINVAL, "null argument");
+    // the queries of the emission: the jobs' distinct pairs
+    std::vector<std::pair<uint64_t, uint64_t>> pairs((size_t)njobs);
+    for (int j = 0; j < njobs; ++j) pairs[(size_t)j] = {all[j], none[j]};
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    const int nq = (int)pairs.size();
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    *found = 0;
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n, in))) return rc;
+    c->st_blocks = 0;
+    std::vector<unsigned long long> ntok;
+    size_t max_segments = 0;
+    if ((rc = locate_shape(c, in, n, genome, njobs, off, ntok, max_segments))) return rc;
+    if (!in.slots) return DD_OK;   // (no input holds a token)
+    const size_t dcap = in.slots;
+    if (c->emit.reserve(exact_emit_bytes(dcap)))
+        return fail(DD_ENOMEM, "exact locate: no device memory for the %zu bytes of the record area (24 bytes per k-mer slot of the inputs)",
+                    exact_emit_bytes(dcap));
+    // one image for both tables: (all, none) [nq][2] | LocateUnit[]
+    std::vector<dd::LocateUnit> units;
+    locate_units(in, ntok, all, none, genome, njobs, off, units);
+    const size_t pbytes = align_up(sizeof(uint64_t) * 2 * (size_t)nq, 256);
+    std::vector<char> image(pbytes + sizeof(dd::LocateUnit) * units.size(), 0);
+    for (int q = 0; q < nq; ++q) {
+        uint64_t* t = reinterpret_cast<uint64_t*>(image.data()) + 2 * (size_t)q;
+        t[0] = pairs[(size_t)q].first, t[1] = pairs[(size_t)q].second;
+    }
+    memcpy(image.data() + pbytes, units.data(), sizeof(dd::LocateUnit) * units.size());
+    if ((rc = c->hits.reserve(words * sizeof(uint64_t)))) return rc;
+    uint64_t* hits_dev = static_cast<uint64_t*>(c->hits.p);
+    dd::ExactEmit e{};
+    unsigned long long total = 0;
+    if ((rc = exact_emit_records(c, in, n, k, "exact locate", nq, image.data(), image.size(), dcap, e, &total))) return rc;
+    if (total > dcap) return fail(DD_EHIP, "exact locate: %llu records emitted, the inputs have %zu k-mer slots", total, dcap);
+    if (!total || !words) {
+        if (words) DD_HIP(hipMemsetAsync(hits_dev, 0, words * sizeof(uint64_t), st));   // nothing matches: no search
+    } else {
+        if ((rc = exact_emit_order_room(c, "exact locate", total, k))) return rc;
+        Span sp(c, DD_KERNEL_EXACT);
+        dd::LocateSet set{};
+        DD_HIP(dd::launch_exact_emit_order(e.lo, e.hi, e.mask, (size_t)total, k, c->exact.p, st, &set));
+        const dd::LocateUnit* units_dev = reinterpret_cast<const dd::LocateUnit*>(static_cast<const char*>(c->ord.p) + pbytes);
+        dd::launch_exact_locate(units_dev, (int)units.size(), max_segments, k, c->canonical, set, hits_dev, st);
+        DD_HIP(hipGetLastError());
+    }
+    std::vector<uint64_t> host((size_t)words);
+    if (words) DD_HIP(hipMemcpyAsync(host.data(), hits_dev, words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    DD_HIP(hipStreamSynchronize(st));
+    if (words) memcpy(hits + off[0], host.data(), words * sizeof(uint64_t));   // (nothing is written before everything is known)
+    *found = total;
+    return DD_OK;
+}
+
+int dd_exact_locate(dd_ctx* c, const char* const* paths, int n, int k, const uint64_t* all, const uint64_t* none, const int32_t* genome,
+                    int njobs, const uint64_t* off, uint64_t* hits, uint64_t* found) {
+    return exact_path_form(c, paths, n, 64, k, k, found, [&](auto p, auto s) {
+        return dd_exact_locate_device(c, p, s, n, k, all, none, genome, njobs, off, hits, found);
+    });
+}
+
+// host only: dd_io.h's record index of one file, in the caller's arrays
+int dd_fasta_index(const char* path, uint64_t* seq_len, uint64_t* tok_start, size_t cap, uint64_t* nrec, char* names, size_t names_cap,
+                   size_t* names_need, uint64_t* ntok) {
+    if (!path || !nrec || !names_need || !ntok || (cap && (!seq_len || !tok_start)) || (names_cap && !names)) return fail(DD_EINVAL, "null argument");
+    dd::FastaIndex ix;
+    std::string err;
+    if (!dd::fasta_index_file(path, ix, err, usable_cpus())) return fail(DD_EIO, "%s", err.c_str());
+    size_t need = 0;
+    for (const std::string& s : ix.names) need += s.size() + 1;
+    *nrec = ix.seq_len.size(), *names_need = need, *ntok = ix.ntok;
+    if (ix.seq_len.size() <= cap && !ix.seq_len.empty()) {
+        memcpy(seq_len, ix.seq_len.data(), sizeof(uint64_t) * ix.seq_len.size());
+        memcpy(tok_start, ix.tok_start.data(), sizeof(uint64_t) * ix.tok_start.size());
+    }
+    if (need <= names_cap)
+        for (const std::string& s : ix.names) memcpy(names, s.c_str(), s.size() + 1), names += s.size() + 1;
+    return DD_OK;
+}
+
+}  // extern "C"

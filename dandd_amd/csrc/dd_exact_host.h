@@ -1,0 +1,69 @@
+// dd_exact_host.h -- what the exact entry points share on the host (defined in dd_exact_passes.hip; called by dd_exact_api.hip
+// and dd_exact_emit_api.hip): the call frame, the path forms' upload, K0 over the inputs, the pass driver and the emission.
+#pragma once
+#include <functional>
+#include "dd_ctx.h"
+
+// What every entry checks first, in this order: the context, n against the entry's limit (64; 16: all subsets), inputs and
+// `out` for null, the k range.  exact_frame, the device forms': then nbytes (and what else may not be null), then the buffers.
+int exact_args(dd_ctx* c, const void* inputs, int n, int nmax, int kmin, int kmax, const void* out);
+int exact_frame(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int nmax, int kmin, int kmax,
+                const void* out, bool more_null = false);
+int exact_check_inputs(const uint8_t* const* fasta_dev, const size_t* nbytes, int n);
+// select's argument rules -> the (all, none) pairs its accumulator and the emission read
+int select_table(const uint64_t* all, const uint64_t* none, int nq, int n, std::vector<uint64_t>& table);
+using ExactDeviceForm = std::function<int(const uint8_t* const* fasta_dev, const size_t* nbytes)>;
+// the files of a path form read, uploaded into the context's FASTA buffer and handed to the device form, on the context's device
+int exact_upload_files(dd_ctx* c, const char* const* paths, int n, const ExactDeviceForm& device_form);
+// a path form: exact_args, no null path, exact_upload_files (the device form checks the entry's own arguments)
+int exact_path_form(dd_ctx* c, const char* const* paths, int n, int nmax, int kmin, int kmax, const void* out, const ExactDeviceForm& device_form);
+
+// K0 over the n inputs of an exact call (once per call, whatever the number of ks) and where each genome's k-mers go
+struct ExactInputs {
+    const dd::ExactGenome* etab_dev = nullptr;
+    size_t slots = 0, max_segments = 0;   // slots = 0: no input has a token
+    std::vector<dd::ExactGenome> etab;    // the host's copy of etab_dev (dd_exact_locate: where each stream and its ntok lie)
+};
+int exact_prepare(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, ExactInputs& in);
+size_t exact_budget(const char* env_mb = "DD_EXACT_MB");   // bytes of k-mers a pass may hold: 24 GiB, or what the variable says
+
+// What a caller of exact_passes says about its part of the k-mer workspace.
+struct ExactLayout {
+    const char* what;                           // "exact count" / "exact schedule", for the messages
+    int tag;                                    // launch_kmer_extract's tag mode; 2 adds the g | g_alt arrays (a byte per slot each)
+    size_t (*temp_bytes)(size_t keys, int k);   // of the caller's sort
+    size_t (*scratch_bytes)(size_t keys);       // what the caller wants behind the sort's temp (null: nothing)
+};
+
+// c->exact carved for `keys` k-mers:
+// counters (256 B) | bin histogram (32 KiB) | lo | lo_alt [| hi | hi_alt] [| g | g_alt] | sort temp | scratch
+struct ExactArrays {
+    unsigned long long *counters, *hist;
+    uint64_t *lo, *lo_alt, *hi, *hi_alt;   // hi: k > 32
+    uint8_t *g, *g_alt;                    // tag mode 2
+    void *temp, *scratch;
+    size_t temp_bytes;
+};
+int exact_carve(dd_ctx* c, const ExactLayout& L, int k, size_t keys, ExactArrays& a);
+
+// a pass is extracted: launch the sort of its `count` k-mers and what follows
+using ExactConsume = std::function<int(const ExactArrays& a, size_t count)>;
+// the counters of a pass, read back (dd_kernels.h, launch_kmer_extract); single: the pass held every slot of the inputs
+using ExactCounted = std::function<void(const unsigned long long* h, bool single)>;
+int exact_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const ExactLayout& L, const ExactConsume& consume,
+                 const ExactCounted& counted = nullptr);
+
+// exact_passes with the consumer of the schedules and the emission: launch_exact_sort_tagged, then `then` on what it left
+using ExactSortedThen = std::function<hipError_t(const dd::ExactSorted& sorted, size_t count, void* scratch)>;
+int exact_sorted_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, const ExactSortedThen& then);
+
+// The distinct k-mers of one k whose mask matches a query, left in c->emit (cursor (256 B) | lo | hi | mask, dcap records
+// each; the caller has reserved exact_emit_bytes(dcap)) in the order the chunks of the sort finished, over all passes.
+// `image` is staged into c->ord: its first 2 nq words are the (all, none) pairs, what the caller appended follows there.
+// *found = the cursor: it counts on past dcap, and then no record was kept whole.  `what` names the entry in the messages.
+inline size_t exact_emit_bytes(size_t dcap) { return 256 + 3 * align_up(dcap * sizeof(uint64_t), 256); }
+int exact_emit_records(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, int nq, const void* image, size_t image_bytes,
+                       size_t dcap, dd::ExactEmit& e, unsigned long long* found);
+// room in c->exact -- free after the last pass, grown if a multi-pass call found more than a pass holds -- for
+// launch_exact_emit_order to put `found` records in ascending (hi, lo) order
+int exact_emit_order_room(dd_ctx* c, const char* what, unsigned long long found, int k);

@@ -1,13 +1,11 @@
 // dd_exact_locate.hip -- where the selected k-mers lie: every position of a genome looked up in the emitted set.
 //
-// dd_exact_select_kmers leaves the distinct k-mers whose membership mask matches a query in HBM (emit_kernel of
-// dd_exact_sched.hip: lo | hi | mask, in the order the chunks of the sort finished, over all passes).  Two steps turn that
-// set into positions, and neither leaves the device:
+// The emission leaves the distinct k-mers whose membership mask matches a query in HBM (emit_kernel of dd_exact_sched.hip:
+// lo | hi | mask, in the order the chunks of the sort finished, over all passes).  Two steps turn that set into positions,
+// and neither leaves the device:
 //
-//   order    launch_exact_locate_order: the records radix-sorted by their 2k-bit key (rocPRIM, the mask rides as the value;
-//            k > 32: the two stable passes of launch_exact_sort_tagged, low word first, and -- a pair sort carries ONE value
-//            array -- each pass run once per array that has to follow, the same keys giving the same permutation).  The
-//            exact workspace is free by then and holds the other halves of the double buffers and the sort's temp.
+//   order    launch_exact_emit_order (dd_exact_sched.hip, shared with dd_exact_select_kmers): the records in ascending
+//            (hi, lo) order.  The exact workspace is free by then and holds the sort's other halves and temp.
 //   locate   locate_kernel: one thread per 64-token segment of a painted genome, the token walk of kmer_extract_kernel
 //            (dd_exact.hip: the segment in front warms the windows up, run >= k, canonical per the context).  At every
 //            valid window the key is formed under mlo / mhi and looked up with a lower_bound on (hi, lo): ceil(log2 found)
@@ -22,10 +20,6 @@
 // and its top levels stay in L2.
 // (The walk is a copy of kmer_extract_kernel's, not shared code: that kernel keeps every lane in the token loop for its
 // wave-level append, so a common walk would have to be threaded through its hot loop.)
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include <algorithm>
-
 #include "dd_common.h"
 #include "dd_kernels.h"
 
@@ -122,44 +116,7 @@ __global__ __launch_bounds__(256) void locate_kernel(const LocateUnit* __restric
         if (j < nj) hits[sout[j] + seg] = word[j];
 }
 
-size_t order_temp_bytes(size_t found) {
-    size_t b = 0;
-    uint64_t* nul = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul, nul, found, 0, 64);
-    return b + 256;
-}
-
 }  // namespace
-
-// the other halves of the double buffers (lo, mask[, hi]), then the sort's temp
-size_t exact_locate_order_bytes(size_t found, int k) {
-    return (size_t)(k > 32 ? 3 : 2) * ((found * sizeof(uint64_t) + 255) / 256 * 256) + order_temp_bytes(found);
-}
-
-hipError_t launch_exact_locate_order(uint64_t* lo, uint64_t* hi, uint64_t* mask, size_t found, int k, void* work, hipStream_t st,
-                                     LocateSet* out) {
-    const size_t stride = (found * sizeof(uint64_t) + 255) / 256 * 256;
-    size_t tb = order_temp_bytes(found);
-    char* wb = static_cast<char*>(work);
-    uint64_t* lo_alt = reinterpret_cast<uint64_t*>(wb);
-    uint64_t* mask_alt = reinterpret_cast<uint64_t*>(wb + stride);
-    hipError_t e;
-    if (k <= 32) {
-        void* temp = wb + 2 * stride;
-        e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, mask, mask_alt, found, 0, (unsigned)(2 * k), st);
-        *out = LocateSet{lo_alt, nullptr, mask_alt, found};
-        return e;
-    }
-    uint64_t* hi_alt = reinterpret_cast<uint64_t*>(wb + 2 * stride);
-    void* temp = wb + 3 * stride;
-    const unsigned bits = (unsigned)(2 * k - 64);
-    if ((e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, mask, mask_alt, found, 0, 64, st)) != hipSuccess) return e;
-    if ((e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, hi, hi_alt, found, 0, 64, st)) != hipSuccess) return e;
-    if ((e = rocprim::radix_sort_pairs(temp, tb, hi_alt, hi, mask_alt, mask, found, 0, bits, st)) != hipSuccess) return e;
-    if ((e = rocprim::radix_sort_pairs(temp, tb, hi_alt, hi, lo_alt, lo, found, 0, bits, st)) != hipSuccess) return e;
-    *out = LocateSet{lo, hi, mask, found};
-    return hipSuccess;
-}
 
 void launch_exact_locate(const LocateUnit* units_dev, int nunits, size_t max_segments, int k, int canonical, const LocateSet& set,
                          uint64_t* hits_dev, hipStream_t st) {

@@ -33,7 +33,7 @@
 //                   stream       the tile appended to a store in HBM, 8 bytes per distinct k-mer, at a position reserved
 //                                with one atomicAdd per tile
 //   emit_kernel   (at the end of this file) sched_kernel's sibling for the selected k-mers themselves: no accumulator, the keys
-//                 and masks of the runs that match a query leave for HBM
+//                 and masks of the runs that match a query leave for HBM; launch_exact_emit_order then puts them in key order
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
@@ -526,6 +526,38 @@ size_t sched_dyn_lds(int kind, int n, int norder) {
     }
 }
 
+// the masks of a k's key words: the low 2k bits of lo, the low 2k - 64 of hi
+uint64_t key_mask_lo(int k) { return (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1ull); }
+uint64_t key_mask_hi(int k) { return (k <= 32) ? 0ull : ((k == 64) ? ~0ull : ((1ull << (2 * k - 64)) - 1ull)); }
+size_t exact_sched_chunks(size_t count) { return (count + kChunk - 1) / kChunk; }
+
+// What sched_kernel and emit_kernel both stand on: the scratch carved (open-run ORs | carries | flags, one per chunk), the
+// view of the sorted array, and the two pre-passes launched.
+struct SortedHead {
+    SortedView v;
+    const uint64_t* carry;   // per chunk: what the run that crosses into it has collected
+    size_t nchunks;
+};
+
+SortedHead sorted_head(const ExactSorted& sorted, size_t count, int k, int n, void* scratch, hipStream_t st) {
+    const size_t nchunks = exact_sched_chunks(count);
+    uint64_t* sum_v = static_cast<uint64_t*>(scratch);
+    uint64_t* carry = sum_v + nchunks;
+    uint32_t* sum_f = reinterpret_cast<uint32_t*>(carry + nchunks);
+    const SortedView v{sorted.lo, sorted.hi, sorted.g, key_mask_lo(k), key_mask_hi(k), count, n};
+    if (k > 32) hipLaunchKernelGGL(sched_summary_kernel<true>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
+    else hipLaunchKernelGGL(sched_summary_kernel<false>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
+    hipLaunchKernelGGL(sched_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, sum_f, sum_v, nchunks, carry);
+    return SortedHead{v, carry, nchunks};
+}
+
+size_t order_temp_bytes(size_t found) {   // of launch_exact_emit_order's sort
+    size_t b = 0;
+    uint64_t* nul = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul, nul, found, 0, 64);
+    return b + 256;
+}
+
 }  // namespace
 
 size_t exact_sched_acc_words(const ExactSched& s) {
@@ -541,7 +573,6 @@ size_t exact_sched_acc_words(const ExactSched& s) {
     }
 }
 
-size_t exact_sched_chunks(size_t count) { return (count + kChunk - 1) / kChunk; }
 // per chunk: flag (u32), open-run OR (u64), carry (u64)
 size_t exact_sched_scratch_bytes(size_t count) { return exact_sched_chunks(count) * 24 + 512; }
 
@@ -579,17 +610,8 @@ hipError_t launch_exact_sort_tagged(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt
 
 hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, const ExactSched& s, void* scratch, hipStream_t st) {
     if (!count) return hipSuccess;
-    const size_t nchunks = exact_sched_chunks(count);
-    char* sb = static_cast<char*>(scratch);
-    uint64_t* sum_v = reinterpret_cast<uint64_t*>(sb);
-    uint64_t* carry = sum_v + nchunks;
-    uint32_t* sum_f = reinterpret_cast<uint32_t*>(carry + nchunks);
     const bool wide = k > 32;
-    SortedView v{sorted.lo, sorted.hi, sorted.g, (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1ull),
-                 (k <= 32) ? 0ull : ((k == 64) ? ~0ull : ((1ull << (2 * k - 64)) - 1ull)), count, s.n};
-    if (wide) hipLaunchKernelGGL(sched_summary_kernel<true>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
-    else hipLaunchKernelGGL(sched_summary_kernel<false>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
-    hipLaunchKernelGGL(sched_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, sum_f, sum_v, nchunks, carry);
+    const SortedHead h = sorted_head(sorted, count, k, s.n, scratch, st);
     // progressive and core-progressive take their orderings, select its queries, in batches that fit the LDS of a launch
     const bool by_order = s.kind == kSchedProgressive || s.kind == kSchedCoreProgressive, by_query = s.kind == kSchedSelect;
     const int items = (by_order || by_query) ? s.norder : 1, per = by_order ? max_orderings(s.n) : (by_query ? kSelectBatch : 1);
@@ -605,20 +627,20 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
         const size_t dyn = sched_dyn_lds(s.kind, s.n, a.norder);
         // persistent workgroups (the accumulators flush once each): as many as the CUs hold at this much LDS, 4 per CU at most
         const size_t per_cu = std::min<size_t>(4, std::max<size_t>(1, ((size_t)160 << 10) / (dyn + kStaticLds)));
-        const unsigned grid = (unsigned)(std::min<size_t>(nchunks, 256 * per_cu) * a.slices);
+        const unsigned grid = (unsigned)(std::min<size_t>(h.nchunks, 256 * per_cu) * a.slices);
         // (every sched_kernel may take the dynamic LDS a CU has left beside the kernel's own: subsets asks for 128 KiB)
         dispatch_bool(wide, [&](auto w) {
             constexpr bool W = decltype(w)::value;
             const dim3 g(grid), t(kThreads);
             switch (s.kind) {
-                case kSchedPairwise: launch_full_lds<sched_kernel<W, AccPairwise>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
-                case kSchedProgressive: launch_full_lds<sched_kernel<W, AccProgressive>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
-                case kSchedLeaveOut: launch_full_lds<sched_kernel<W, AccLeaveOut>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
-                case kSchedSpectrum: launch_full_lds<sched_kernel<W, AccSpectrum>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
-                case kSchedCoreProgressive: launch_full_lds<sched_kernel<W, AccCoreProgressive>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
-                case kSchedSelect: launch_full_lds<sched_kernel<W, AccSelect>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
-                case kSchedStream: launch_full_lds<sched_kernel<W, AccStream>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
-                default: launch_full_lds<sched_kernel<W, AccSubsets>, kStaticLds>(g, t, dyn, st, v, carry, nchunks, a); break;
+                case kSchedPairwise: launch_full_lds<sched_kernel<W, AccPairwise>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
+                case kSchedProgressive: launch_full_lds<sched_kernel<W, AccProgressive>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
+                case kSchedLeaveOut: launch_full_lds<sched_kernel<W, AccLeaveOut>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
+                case kSchedSpectrum: launch_full_lds<sched_kernel<W, AccSpectrum>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
+                case kSchedCoreProgressive: launch_full_lds<sched_kernel<W, AccCoreProgressive>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
+                case kSchedSelect: launch_full_lds<sched_kernel<W, AccSelect>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
+                case kSchedStream: launch_full_lds<sched_kernel<W, AccStream>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
+                default: launch_full_lds<sched_kernel<W, AccSubsets>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
             }
         });
     }
@@ -633,7 +655,7 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
 // as the tile of sched_kernel is filled; the workgroup then reserves its range of the output with ONE atomicAdd on the
 // device cursor per chunk and writes it with plain stores.  The cursor keeps counting past `cap`: a range that would pass
 // it is not written, and the caller reads from the cursor how many records there were.  Ranges land in the order the
-// chunks finish; who wants an order sorts (dd_exact_api.hip does).
+// chunks finish; who wants an order calls launch_exact_emit_order behind the last pass (both callers do).
 namespace {
 
 constexpr size_t kEmitStaticLds = 128;   // emit_kernel's own LDS: the scan's wave totals, the counter, the reserved position
@@ -702,24 +724,49 @@ __global__ __launch_bounds__(kThreads) void emit_kernel(SortedView s, const uint
 
 hipError_t launch_exact_emit(const ExactSorted& sorted, size_t count, int k, const ExactEmit& e, void* scratch, hipStream_t st) {
     if (!count) return hipSuccess;
-    const size_t nchunks = exact_sched_chunks(count);
-    char* sb = static_cast<char*>(scratch);   // (the layout of launch_exact_sched)
-    uint64_t* sum_v = reinterpret_cast<uint64_t*>(sb);
-    uint64_t* carry = sum_v + nchunks;
-    uint32_t* sum_f = reinterpret_cast<uint32_t*>(carry + nchunks);
     const bool wide = k > 32;
-    SortedView v{sorted.lo, sorted.hi, sorted.g, (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1ull),
-                 (k <= 32) ? 0ull : ((k == 64) ? ~0ull : ((1ull << (2 * k - 64)) - 1ull)), count, e.n};
-    if (wide) hipLaunchKernelGGL(sched_summary_kernel<true>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
-    else hipLaunchKernelGGL(sched_summary_kernel<false>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
-    hipLaunchKernelGGL(sched_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, sum_f, sum_v, nchunks, carry);
+    const SortedHead h = sorted_head(sorted, count, k, e.n, scratch, st);
     // the pairs, then a staging area of kChunk records (all = none = 0 hits every distinct k-mer): 48 KiB + 16 KiB at the most
     const size_t dyn = ((size_t)2 * e.nq + (size_t)(wide ? 3 : 2) * kChunk) * sizeof(uint64_t);
     const size_t per_cu = std::min<size_t>(4, std::max<size_t>(1, ((size_t)160 << 10) / (dyn + kEmitStaticLds)));
-    const dim3 g((unsigned)std::min<size_t>(nchunks, 256 * per_cu)), t(kThreads);   // persistent workgroups, as launch_exact_sched sizes them
-    if (wide) launch_full_lds<emit_kernel<true>, (int)kEmitStaticLds>(g, t, dyn, st, v, carry, nchunks, e);
-    else launch_full_lds<emit_kernel<false>, (int)kEmitStaticLds>(g, t, dyn, st, v, carry, nchunks, e);
+    const dim3 g((unsigned)std::min<size_t>(h.nchunks, 256 * per_cu)), t(kThreads);   // persistent workgroups, as launch_exact_sched sizes them
+    if (wide) launch_full_lds<emit_kernel<true>, (int)kEmitStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, e);
+    else launch_full_lds<emit_kernel<false>, (int)kEmitStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, e);
     return hipGetLastError();
+}
+
+// ---- the emitted records in ascending key order ------------------------------------------------------------------------
+// The records radix-sorted by their 2k-bit key, the mask riding as the value; k > 32: the two stable passes of
+// launch_exact_sort_tagged, low word first, and -- a pair sort carries ONE value array -- each pass run once per array that
+// has to follow, the same keys giving the same permutation.  `work`: the other halves of the double buffers (lo, mask[, hi]),
+// then the sort's temp.
+size_t exact_emit_order_bytes(size_t found, int k) {
+    return (size_t)(k > 32 ? 3 : 2) * ((found * sizeof(uint64_t) + 255) / 256 * 256) + order_temp_bytes(found);
+}
+
+hipError_t launch_exact_emit_order(uint64_t* lo, uint64_t* hi, uint64_t* mask, size_t found, int k, void* work, hipStream_t st,
+                                   LocateSet* out) {
+    const size_t stride = (found * sizeof(uint64_t) + 255) / 256 * 256;
+    size_t tb = order_temp_bytes(found);
+    char* wb = static_cast<char*>(work);
+    uint64_t* lo_alt = reinterpret_cast<uint64_t*>(wb);
+    uint64_t* mask_alt = reinterpret_cast<uint64_t*>(wb + stride);
+    hipError_t e;
+    if (k <= 32) {
+        void* temp = wb + 2 * stride;
+        e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, mask, mask_alt, found, 0, (unsigned)(2 * k), st);
+        *out = LocateSet{lo_alt, nullptr, mask_alt, found};
+        return e;
+    }
+    uint64_t* hi_alt = reinterpret_cast<uint64_t*>(wb + 2 * stride);
+    void* temp = wb + 3 * stride;
+    const unsigned bits = (unsigned)(2 * k - 64);
+    if ((e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, mask, mask_alt, found, 0, 64, st)) != hipSuccess) return e;
+    if ((e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, hi, hi_alt, found, 0, 64, st)) != hipSuccess) return e;
+    if ((e = rocprim::radix_sort_pairs(temp, tb, hi_alt, hi, mask_alt, mask, found, 0, bits, st)) != hipSuccess) return e;
+    if ((e = rocprim::radix_sort_pairs(temp, tb, hi_alt, hi, lo_alt, lo, found, 0, bits, st)) != hipSuccess) return e;
+    *out = LocateSet{lo, hi, mask, found};
+    return hipSuccess;
 }
 
 }  // namespace dd

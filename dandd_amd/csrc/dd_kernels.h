@@ -329,10 +329,23 @@ struct ExactEmit {
     unsigned long long cap;
 };
 hipError_t launch_exact_emit(const ExactSorted& sorted, size_t count, int k, const ExactEmit& e, void* scratch, hipStream_t st);
+// ... and put in ascending key order behind the last pass, for who wants an order (dd_exact_select_kmers) or searches them
+// (dd_exact_locate).  `work`: exact_emit_order_bytes(found, k) of device memory; lo / hi / mask [found] are the emit area and
+// are overwritten.
+struct LocateSet {                  // where launch_exact_emit_order left the records, ascending in (hi, lo)
+                                    // (named for its first user: locate_kernel takes it by value, a new name would change the kernel's symbol)
+    const uint64_t* lo;
+    const uint64_t* hi;             // k > 32
+    const uint64_t* mask;
+    unsigned long long found;
+};
+size_t exact_emit_order_bytes(size_t found, int k);
+hipError_t launch_exact_emit_order(uint64_t* lo, uint64_t* hi, uint64_t* mask, size_t found, int k, void* work, hipStream_t st,
+                                   LocateSet* out);
 
 // ---------------------------------------------------------------------------------------
-// the positions of the selected k-mers (dd_exact_locate.hip), behind launch_exact_emit: the emitted records put in ascending
-// key order on the device, then every token of a painted genome looked up in them.
+// the positions of the selected k-mers (dd_exact_locate.hip), behind launch_exact_emit_order: every token of a painted
+// genome looked up in the ordered records.
 // ---------------------------------------------------------------------------------------
 constexpr int kLocateJobs = 8;      // jobs one walk of a genome serves (a hit word each, in registers); more jobs: more units
 struct LocateUnit {                 // one per gridDim.y of a launch, device-resident table
@@ -343,16 +356,6 @@ struct LocateUnit {                 // one per gridDim.y of a launch, device-res
     uint64_t all[kLocateJobs], none[kLocateJobs];
     unsigned long long out[kLocateJobs];   // first word of each job's bitmap in the hit buffer; ceil(ntok / 64) words follow
 };
-struct LocateSet {                  // where launch_exact_locate_order left the records, ascending in (hi, lo)
-    const uint64_t* lo;
-    const uint64_t* hi;             // k > 32
-    const uint64_t* mask;
-    unsigned long long found;
-};
-// `work`: exact_locate_order_bytes(found, k) of device memory; lo / hi / mask [found] are the emit area and are overwritten
-size_t exact_locate_order_bytes(size_t found, int k);
-hipError_t launch_exact_locate_order(uint64_t* lo, uint64_t* hi, uint64_t* mask, size_t found, int k, void* work, hipStream_t st,
-                                     LocateSet* out);
 // every live thread writes its word of every job: the bitmaps need no zeroing.  Nothing is launched for an empty set.
 void launch_exact_locate(const LocateUnit* units_dev, int nunits, size_t max_segments, int k, int canonical, const LocateSet& set,
                          uint64_t* hits_dev, hipStream_t st);

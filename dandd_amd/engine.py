@@ -736,14 +736,19 @@ class Engine:
         ords = np.ascontiguousarray(orderings, dtype=np.int32).reshape(-1, max(n, 1))
         return self._exact_sched("core_progressive", src, lambda n: (ords.shape[0], n), kmin, kmax, ords.ctypes.data, ords.shape[0])
 
-    def _exact_select(self, src, kmin, kmax, all_masks, none_masks):
+    @staticmethod
+    def _query_masks(all_masks, none_masks):
+        """-> (all, none, nq): the queries of select and select_kmers as two uint64 arrays the library can read."""
         al = np.ascontiguousarray([int(x) for x in all_masks], dtype=np.uint64).reshape(-1)
         no = np.ascontiguousarray([int(x) for x in none_masks], dtype=np.uint64).reshape(-1)
         if al.size != no.size:
             raise ValueError("all_masks and none_masks must have the same length")
-        nq = al.size
-        if nq == 0:   # (the library rejects nq = 0 by its own rule; it still wants two pointers)
-            al = no = np.zeros(1, dtype=np.uint64)
+        if al.size == 0:   # (the library rejects nq = 0 by its own rule; it still wants two pointers)
+            return np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64), 0
+        return al, no, al.size
+
+    def _exact_select(self, src, kmin, kmax, all_masks, none_masks):
+        al, no, nq = self._query_masks(all_masks, none_masks)
         return self._exact_sched("select", src, lambda n: (nq,), kmin, kmax, al.ctypes.data, no.ctypes.data, nq)
 
     def exact_spectrum(self, paths, kmin, kmax):
@@ -772,13 +777,7 @@ class Engine:
 
     def _exact_select_kmers(self, src, k, all_masks, none_masks, cap):
         args, n, suffix = src
-        al = np.ascontiguousarray([int(x) for x in all_masks], dtype=np.uint64).reshape(-1)
-        no = np.ascontiguousarray([int(x) for x in none_masks], dtype=np.uint64).reshape(-1)
-        if al.size != no.size:
-            raise ValueError("all_masks and none_masks must have the same length")
-        nq = al.size
-        if nq == 0:   # (the library rejects nq = 0 by its own rule; it still wants two pointers)
-            al = no = np.zeros(1, dtype=np.uint64)
+        al, no, nq = self._query_masks(all_masks, none_masks)
         fn = getattr(self._lib, f"dd_exact_select_kmers{suffix}")
         room = self.KMERS_FIRST_CAP if cap is None else int(cap)
         for _ in range(2):

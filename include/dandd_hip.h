@@ -268,10 +268,11 @@ int dd_exact_select_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
  *             (bit j: input j holds it).  Two calls on the same inputs return identical bytes.
  *   found > cap:   the call still returns DD_OK; the contents of kmers and masks are then UNSPECIFIED (not a prefix of
  *             the answer), and the caller comes back with cap >= found.
- * The records wait in 24 bytes x min(cap, k-mer slots of the inputs) of HBM beside the exact workspace (DD_ENOMEM with a
- * message when that cannot be had); budget and passes are those of dd_exact_count (DD_EXACT_MB), the count runs on across
- * passes, dd_last_sketch_stats' third value is the number of passes, and kernel time is DD_KERNEL_EXACT's.  An empty
- * input, or one without a k-mer of length k, holds nothing. */
+ * The records wait in 24 bytes x min(cap, k-mer slots of the inputs) of HBM beside the exact workspace and are put in
+ * order there, in the workspace itself (DD_ENOMEM with a message when either cannot be had); budget and passes are
+ * those of dd_exact_count (DD_EXACT_MB), the count runs on across passes, dd_last_sketch_stats' third value is the
+ * number of passes, and kernel time is DD_KERNEL_EXACT's.  An empty input, or one without a k-mer of length k, holds
+ * nothing. */
 int dd_exact_select_kmers(dd_ctx *, const char *const *paths, int n, int k, const uint64_t *all /*[nq]*/,
                           const uint64_t *none /*[nq]*/, int nq, uint64_t *kmers /*[cap][2]: lo, hi*/,
                           uint64_t *masks /*[cap]*/, size_t cap, uint64_t *found);
@@ -347,7 +348,7 @@ int dd_exact_greedy_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate */
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate */
 #define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
-KS = [1, 5, 21, 28, 29, 32, 33, 48, 60, 61, 64]    # tag in the top byte for 2k <= 56 and 2k - 64 <= 56, in g[] otherwise
+KS = [1, 5, 21, 28, 29, 32, 33, 48, 56, 57, 60, 61, 64]    # tag in the top byte for 2k <= 56 and 2k - 64 <= 56, in g[] otherwise
 NS = [1, 3, 8, 64]
 U64 = (1 << 64) - 1
 DD_EINVAL = -1
@@ -83,13 +83,18 @@ def test_records_match_masks(engine_factory, tmp_path, n, canonical):
 
 
 # ---- 2. everything: the staging area of every chunk is full ----------------------------------------------------------------
-def test_every_distinct_kmer(engine_factory, tmp_path):
+ORDER_KS = [21, 32, 33, 56, 57, 64]    # the records are ordered on the device: one key word up to 32, 2k - 64 bits of hi above
+
+
+@pytest.mark.parametrize("k", ORDER_KS)
+def test_every_distinct_kmer(engine_factory, tmp_path, k):
     eng = engine_factory()
     fas = sched.genomes(1, 4000, 1001)
     paths = sched.write(tmp_path, fas)
-    kmers, masks = eng.exact_select_kmers(paths, 21, [0], [0])
-    assert len(masks) == eng.exact_count(paths, 21) == len(set(pyref.kmers(fas[0], 21)))
-    assert [int(lo) for lo in kmers[:, 0]] == sorted(set(pyref.kmers(fas[0], 21))) and not kmers[:, 1].any()
+    kmers, masks = eng.exact_select_kmers(paths, k, [0], [0])
+    want = sorted(set(pyref.kmers(fas[0], k)))
+    assert len(masks) == eng.exact_count(paths, k) == len(want)
+    assert [int(lo) | int(hi) << 64 for lo, hi in kmers] == want and (k > 32 or not kmers[:, 1].any())
     assert set(int(m) for m in masks) == {1}
 
 
@@ -140,13 +145,15 @@ def _raw(eng, paths, k, al, no, nq, kmers, masks, cap, found):
                                           None if found is None else ctypes.byref(found))
 
 
-@pytest.mark.parametrize("k", [21, 33])
+@pytest.mark.parametrize("k", ORDER_KS)
 def test_capacity_protocol(engine_factory, tmp_path, k):
     eng = engine_factory()
     fas = sched.genomes(3, 2500, 1003)
     paths = sched.write(tmp_path, fas)
     part = [(1, 2), (2, 1)]
-    want = want_arrays(cpuc.masks_of(fas, k, True), part)
+    ref = cpuc.masks_of(fas, k, True)
+    want = want_arrays(ref, part)
+    same(eng.exact_select_kmers(paths, k, [0], [0]), want_arrays(ref, [(0, 0)]), ("every k-mer", k))
     m = len(want[1])
     assert m > 2
     al, no = np.array([a for a, _ in part], dtype=np.uint64), np.array([b for _, b in part], dtype=np.uint64)
