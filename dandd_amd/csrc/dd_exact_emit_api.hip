@@ -1,8 +1,9 @@
 // dd_exact_emit_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h) that hand k-mers out instead of counting
-// them: the selected k-mers themselves (dd_exact_select_kmers), where they lie in each genome (dd_exact_locate) and the
-// record index of a file that turns those places into names (dd_fasta_index).  Both exact entries are one emission
-// (exact_emit_records, dd_exact_host.h) and one ordering of its records on the device (launch_exact_emit_order).
-// Host-side orchestration only; the kernels are in dd_exact_sched.hip (emit_kernel) and dd_exact_locate.hip.
+// them: the selected k-mers themselves (dd_exact_select_kmers), where they lie in each genome (dd_exact_locate), the
+// record index of a file that turns those places into names (dd_fasta_index), and what samples that are no inputs hold of
+// them (dd_exact_screen).  The three exact entries are one emission (exact_emit_records, dd_exact_host.h) and one ordering
+// of its records on the device (launch_exact_emit_order).  Host-side orchestration only; the kernels are in
+// dd_exact_sched.hip (emit_kernel), dd_exact_locate.hip and dd_exact_screen.hip.
 #include "dd_exact_host.h"
 
 extern "C" {
@@ -178,6 +179,111 @@ int dd_exact_locate(dd_ctx* c, const char* const* paths, int n, int k, const uin
                     int njobs, const uint64_t* off, uint64_t* hits, uint64_t* found) {
     return exact_path_form(c, paths, n, 64, k, k, found, [&](auto p, auto s) {
         return dd_exact_locate_device(c, p, s, n, k, all, none, genome, njobs, off, hits, found);
+    });
+}
+
+// ------------------------------------------------------------------- samples screened against the universe
+// dd_exact_screen.hip: K0 over the universe's inputs AND the samples, the sort and the emission of dd_exact_locate over the
+// universe alone (the samples stay out of the sort and out of the slot count that sizes the record area) with the single
+// query (0, 0), the records put in key order, one walk of every sample that marks the records it holds, one tally of the
+// marks.  The ordered set may lie in the exact workspace: no sort runs there before the tally has finished.
+namespace {
+
+int screen_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const uint64_t* all, const uint64_t* none, int nq,
+                const uint64_t* shared, const uint64_t* match, const uint64_t* found) {
+    if (exact_args(c, inputs, n, 64, k, k, found)) return DD_EINVAL;
+    if (ns < 1 || ns > 1024) return fail(DD_EINVAL, "ns=%d outside 1..1024 samples in one call; split them over calls", ns);
+    if (nq < 0 || nq > dd::kScreenMaxQueries)
+        return fail(DD_EINVAL, "nq=%d outside 0..%d (what one launch holds); split the queries over calls", nq, dd::kScreenMaxQueries);
+    if (!shared || (nq && (!all || !none || !match))) return fail(DD_EINVAL, "null argument");
+    const uint64_t outside = n == 64 ? 0ull : ~((1ull << n) - 1ull);
+    for (int q = 0; q < nq; ++q)
+        if ((all[q] | none[q]) & outside) return fail(DD_EINVAL, "query %d: a bit outside 0..%d is set", q, n - 1);
+    return DD_OK;
+}
+
+}  // namespace
+
+int dd_exact_screen_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns, int k, const uint64_t* all,
+                           const uint64_t* none, int nq, uint64_t* shared, uint64_t* match, uint64_t* found) {
+    if (screen_args(c, fasta_dev, n, ns, k, all, none, nq, shared, match, found)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n + ns)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n + ns, in))) return rc;   // K0 over everything, once
+    c->st_blocks = 0;
+    const bool tokens = in.slots != 0;
+    // the sort sees the universe only
+    in.slots = 0, in.max_segments = 0;
+    size_t sample_segments = 0;
+    for (int g = 0; g < n + ns; ++g) {
+        const size_t segs = (nbytes[g] + dd::kSegTokens - 1) / dd::kSegTokens;
+        if (g < n) in.slots += segs * dd::kSegTokens, in.max_segments = std::max(in.max_segments, segs);
+        else sample_segments = std::max(sample_segments, segs);
+    }
+    const size_t rows = (size_t)ns + 1, ncount = rows * ((size_t)n + (size_t)nq);
+    std::vector<unsigned long long> host(ncount, 0ull);
+    unsigned long long total = 0;
+    dd::ExactEmit e{};
+    if (tokens && in.slots) {
+        const size_t dcap = in.slots;
+        if (c->emit.reserve(exact_emit_bytes(dcap)))
+            return fail(DD_ENOMEM, "exact screen: no device memory for the %zu bytes of the record area (24 bytes per k-mer slot of the universe)",
+                        exact_emit_bytes(dcap));
+        // one image for both tables: the emission's single query (0, 0) | the caller's (all, none) [nq][2]
+        const size_t pbytes = 256;
+        std::vector<char> image(pbytes + sizeof(uint64_t) * 2 * (size_t)nq, 0);
+        for (int q = 0; q < nq; ++q) {
+            uint64_t* t = reinterpret_cast<uint64_t*>(image.data() + pbytes) + 2 * (size_t)q;
+            t[0] = all[q], t[1] = none[q];
+        }
+        if ((rc = exact_emit_records(c, in, n, k, "exact screen", 1, image.data(), image.size(), dcap, e, &total))) return rc;
+        if (total > dcap) return fail(DD_EHIP, "exact screen: %llu records emitted, the universe has %zu k-mer slots", total, dcap);
+    }
+    if (total) {
+        // counters [ns + 1][n] | [ns + 1][nq], then the seen bitmaps [ns][words]
+        const size_t words = ((size_t)total + 31) / 32, cbytes = align_up(ncount * sizeof(unsigned long long), 256),
+                     sbytes = (size_t)ns * words * sizeof(uint32_t);
+        if (c->hits.reserve(cbytes + sbytes))
+            return fail(DD_ENOMEM, "exact screen: no device memory for the %zu bytes of the samples' seen bitmaps (%d samples x %zu words of 32 records)",
+                        sbytes, ns, words);
+        if ((rc = exact_emit_order_room(c, "exact screen", total, k))) return rc;
+        unsigned long long* shared_dev = static_cast<unsigned long long*>(c->hits.p);
+        unsigned long long* match_dev = shared_dev + rows * (size_t)n;
+        uint32_t* seen_dev = reinterpret_cast<uint32_t*>(static_cast<char*>(c->hits.p) + cbytes);
+        DD_HIP(hipMemsetAsync(c->hits.p, 0, cbytes + sbytes, st));
+        {
+            Span sp(c, DD_KERNEL_EXACT);
+            dd::LocateSet set{};
+            DD_HIP(dd::launch_exact_emit_order(e.lo, e.hi, e.mask, (size_t)total, k, c->exact.p, st, &set));
+            dd::launch_exact_screen(in.etab_dev + n, ns, sample_segments, k, c->canonical, set, seen_dev, words, st);
+            DD_HIP(hipGetLastError());
+            const uint64_t* pairs_dev = reinterpret_cast<const uint64_t*>(static_cast<const char*>(c->ord.p) + 256);
+            dd::launch_exact_tally(set, seen_dev, words, ns, n, nq, pairs_dev, shared_dev, match_dev, st);
+            DD_HIP(hipGetLastError());
+        }
+        DD_HIP(hipMemcpyAsync(host.data(), shared_dev, ncount * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+    }
+    // (nothing is written before everything is known)
+    for (size_t i = 0; i < rows * (size_t)n; ++i) shared[i] = host[i];
+    for (size_t i = 0; i < rows * (size_t)nq; ++i) match[i] = host[rows * (size_t)n + i];
+    *found = total;
+    return DD_OK;
+}
+
+int dd_exact_screen(dd_ctx* c, const char* const* paths, int n, const char* const* samples, int ns, int k, const uint64_t* all,
+                    const uint64_t* none, int nq, uint64_t* shared, uint64_t* match, uint64_t* found) {
+    if (screen_args(c, paths, n, ns, k, all, none, nq, shared, match, found)) return DD_EINVAL;
+    if (!samples) return fail(DD_EINVAL, "null argument");
+    std::vector<const char*> files((size_t)(n + ns));
+    for (int i = 0; i < n + ns; ++i)
+        if (!(files[(size_t)i] = i < n ? paths[i] : samples[i - n])) return fail(DD_EINVAL, "null argument");
+    return exact_upload_files(c, files.data(), n + ns, [&](auto p, auto s) {
+        return dd_exact_screen_device(c, p, s, n, ns, k, all, none, nq, shared, match, found);
     });
 }
 

@@ -361,6 +361,20 @@ void launch_exact_locate(const LocateUnit* units_dev, int nunits, size_t max_seg
                          uint64_t* hits_dev, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// samples that are no leaves, screened against the ordered records (dd_exact_screen.hip), behind launch_exact_emit_order.
+// ---------------------------------------------------------------------------------------
+constexpr int kScreenMaxQueries = 1024;   // (all, none) pairs one tally holds in LDS
+// samples_dev[ns]: the samples' token streams (`base` is not read).  seen_dev [ns][words] u32, words >= ceil(found / 32),
+// zeroed by the caller: bit r of row s is set iff sample s holds record r.  Nothing is launched for an empty set.
+void launch_exact_screen(const ExactGenome* samples_dev, int ns, size_t max_segments, int k, int canonical, const LocateSet& set,
+                         uint32_t* seen_dev, size_t words, hipStream_t st);
+// shared_dev [ns + 1][n] += records of the row that hold bit i; match_dev [ns + 1][nq] += records of the row whose mask has
+// (m & all) == all && (m & none) == 0 for pair q of table_dev [nq][2].  Row s < ns: the records seen by sample s; row ns:
+// every record.  Both zeroed by the caller.
+void launch_exact_tally(const LocateSet& set, const uint32_t* seen_dev, size_t words, int ns, int n, int nq, const uint64_t* table_dev,
+                        unsigned long long* shared_dev, unsigned long long* match_dev, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // exact greedy walk (dd_exact_greedy.hip) over the mask streams of kSchedStream: one launch per step of the walk reads
 // every stream once.  gain[kk][b] += masks of stream kk (store[seg.off[kk] .. seg.off[kk + 1])) that meet `chosen` nowhere
 // and hold bit b, for every b < 64 (a bit of `chosen` gains 0).  gain_dev [K][64], zeroed by the caller.

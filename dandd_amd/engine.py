@@ -36,6 +36,7 @@ EXPORTS = [
     "dd_exact_greedy", "dd_exact_greedy_device",
     "dd_exact_select_kmers", "dd_exact_select_kmers_device",
     "dd_exact_locate", "dd_exact_locate_device", "dd_fasta_index",
+    "dd_exact_screen", "dd_exact_screen_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
     "dd_comm_unique_id", "dd_comm_init", "dd_comm_destroy", "dd_comm_info", "dd_allreduce_max_u8", "dd_allgather_u8",
@@ -186,6 +187,10 @@ def load_library(path=None):
         fn = getattr(lib, name)
         fn.restype = i32
         fn.argtypes = [vp] + src + [i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(u64)]
+    lib.dd_exact_screen.restype = i32
+    lib.dd_exact_screen.argtypes = [vp, paths_t, i32, paths_t, i32, i32, vp, vp, i32, vp, vp, C.POINTER(u64)]
+    lib.dd_exact_screen_device.restype = i32
+    lib.dd_exact_screen_device.argtypes = [vp, ptrs_t, sizes_t, i32, i32, i32, vp, vp, i32, vp, vp, C.POINTER(u64)]
     lib.dd_fasta_index.restype = i32
     lib.dd_fasta_index.argtypes = [C.c_char_p, vp, vp, sz, C.POINTER(u64), vp, sz, C.POINTER(sz), C.POINTER(u64)]
     lib.dd_timing_enable.restype = i32
@@ -836,6 +841,35 @@ class Engine:
     def exact_locate_device(self, fasta_ptrs, nbytes, k, jobs, ntok):
         """exact_locate over FASTA bytes on the device; ntok: every input's token count (the library checks them)."""
         return self._exact_locate(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), k, jobs, ntok)
+
+    # -- samples that are no leaves, screened against the universe's records (dd_exact_screen.hip) ------------------------
+    last_screen_found = None   # of the last exact_screen call: the distinct k-mers of the universe
+    def _exact_screen(self, call, n, ns, k, all_masks, none_masks):
+        al, no, nq = self._query_masks(all_masks, none_masks)
+        shared = np.zeros((max(ns, 0) + 1, max(n, 0)), dtype=np.uint64)
+        match = np.zeros((max(ns, 0) + 1, nq), dtype=np.uint64)
+        found = C.c_uint64()
+        self._check(call(int(k), al.ctypes.data if nq else None, no.ctypes.data if nq else None, nq, shared.ctypes.data,
+                         match.ctypes.data if nq else None, C.byref(found)))
+        self.last_screen_found = int(found.value)
+        return shared, match
+
+    def exact_screen(self, paths, samples, k, all_masks, none_masks):
+        """FASTA files (n <= 64: the universe), sample files (FASTA / FASTQ, plain or gzip, ns <= 1024), one k, at most 1024
+        queries -> (shared uint64 [ns+1][n], match uint64 [ns+1][nq]): shared[s][i] the distinct k-mers of sample s that
+        file i also holds, match[s][q] those whose universe mask contains all_masks[q] and meets none_masks[q] nowhere; row
+        ns is the universe itself (|file i|; what exact_select counts).  last_screen_found: the universe's distinct k-mers."""
+        pa = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+        sa = (C.c_char_p * max(len(samples), 1))(*[os.fsencode(p) for p in samples])
+        return self._exact_screen(lambda *rest: self._lib.dd_exact_screen(self._ctx, pa, len(paths), sa, len(samples), *rest),
+                                  len(paths), len(samples), k, all_masks, none_masks)
+
+    def exact_screen_device(self, fasta_ptrs, nbytes, n, k, all_masks, none_masks):
+        """exact_screen over FASTA bytes on the device: the n universe inputs first, the samples behind them."""
+        args, total, _ = self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes)
+        ns = total - int(n)
+        return self._exact_screen(lambda *rest: self._lib.dd_exact_screen_device(self._ctx, *args, int(n), ns, *rest),
+                                  int(n), ns, k, all_masks, none_masks)
 
     # -- exact greedy: the masks of every k kept on the device, one read of them per step (dd_exact_greedy.hip) ---------
     def _exact_greedy(self, src, kmin, kmax, mode, cand, nfixed, nsteps):

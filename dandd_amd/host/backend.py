@@ -362,6 +362,19 @@ class HipExactBackend:
         index = [fasta_index(f) for f in files]
         return index, self.engine.exact_locate(files, int(k), jobs, ntok=[ix[3] for ix in index])
 
+    def screen_counts(self, leaf_paths, k, sample_files, all_masks, none_masks):
+        """files that are no leaves screened against the leaves' k-mers at one k of the window (dd_exact_screen): ->
+        (shared uint64 [ns+1][n], match uint64 [ns+1][nq]); shared[s][i]: the distinct k-mers of sample s that leaf i also
+        holds, match[s][q]: those whose membership mask contains all_masks[q] and meets none_masks[q] nowhere; row ns: the
+        leaves themselves (|leaf i|; what select_counts counts)."""
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, kmin, kmax = win
+        if not kmin <= int(k) <= kmax:
+            raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
+        return self.engine.exact_screen(files, [str(f) for f in sample_files], int(k), all_masks, none_masks)
+
     def greedy_cards(self, leaf_paths, mode, nfixed, nsteps, kmin):
         """HipBackend.greedy_cards on exact counts (dd_exact_greedy): -> (order [nsteps] as indices into leaf_paths, cards
         float64 [nsteps][K]), ties going to the leaf the caller lists first.  None -- the caller goes on as without this

@@ -1,4 +1,4 @@
-"""`dandd tree | progressive | kij | deltadelta | abba | greedy | core` on the MI355X engine: same sub-commands, flags, defaults and
+"""`dandd tree | progressive | kij | deltadelta | abba | greedy | core | screen` on the MI355X engine: same sub-commands, flags, defaults and
 output files as /root/reference/lib/dandd_cmd.py (flags :141-286, handlers :43-132); only the
 sketching backend differs.  Run as  python -m dandd_amd.host.cli <subcommand> ...
 """
@@ -476,6 +476,86 @@ def core_command(args):
     tree.speciesinfo.save_references(fast=False)
 
 
+def screen_command(args):
+    """New samples -- assemblies or read sets that are no leaves -- against the genomes of an exact tree: how much of each
+    genome a sample contains and the other way round, which genome it is closest to, how much of it is in the pan-genome and
+    the core, and with -g which group's core, private k-mers and signature it carries.  Counts are over distinct k-mers;
+    the samples enter no sort and change none of the collection's numbers."""
+    tree = _load_tree(args.delta_tree)
+    tree.speciesinfo.update(tool=tree.experiment["tool"])
+    if tree.experiment["tool"] != "kmc":
+        sys.exit(f"screen: {args.delta_tree} is a tree of sketches: build it with `tree --exact` -- intersections are sums over exact "
+                 "membership masks, and inclusion-exclusion over HyperLogLog union estimates amplifies their error")
+    if not args.tag:
+        args.tag = tree.speciesinfo.tag
+    outfile = tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
+    ks = sorted(set(int(k) for k in args.ks)) if args.ks else [int(tree.root_k())]
+    for k in ks:
+        if not 1 <= k <= 64:
+            sys.exit(f"screen: -k {k} is outside 1..64")
+    names = list(args.samples)
+    if args.query_loc:
+        if not os.path.isfile(args.query_loc):
+            sys.exit(f"screen: {args.query_loc} (-q) not found")
+        names.extend(line.strip() for line in _lines(args.query_loc))
+    samples = []
+    for f in names:
+        if f not in samples:
+            samples.append(f)
+    if not samples:
+        sys.exit("screen: no sample: give files, or -q with one path per line")
+    for f in samples:
+        if not os.path.isfile(f):
+            sys.exit(f"screen: {f} not found")
+    leaf_of = _leaf_lookup(tree, "screen", args.delta_tree)
+    fastas = tree.progressive_fastas(args.flist_loc)
+    n, ns = len(fastas), len(samples)
+    if n < 1:
+        sys.exit(f"screen: {n} genomes in the universe: at least 1 is needed")
+    if n > 64:
+        sys.exit(f"screen: {n} genomes in the universe: at most 64 (a membership mask has one bit per genome); choose them with -f/--fastas")
+    groups, labels = [], []
+    if args.groups_loc:
+        groups, labels = _read_groups("screen", args.groups_loc, leaf_of)
+        for g in groups:
+            for f in g:
+                if f not in fastas:
+                    sys.exit(f"screen: {f} (-g) is not in the universe of this run (-f)")
+    try:
+        res = tree.screen_tables(fastas, samples, ks, groups)
+    except (ValueError, OSError) as e:
+        sys.exit("screen: " + " ".join(str(e).split()))
+
+    def ratio(a, b):
+        return a / b if b else None
+    rows, summary, marks = [], [], []
+    for s, sample in enumerate(samples):                                 # (nothing is written before every table is there)
+        for kk, k in enumerate(ks):
+            q = int(res["sample_kmers"][kk, s])
+            best = None
+            for i, fasta in enumerate(fastas):
+                g, sh = int(res["shared"][kk, ns, i]), int(res["shared"][kk, s, i])
+                jac = ratio(sh, g + q - sh)
+                rows.append([sample, k, fasta, g, q, sh, ratio(sh, g), ratio(sh, q), jac])
+                if sh and (best is None or jac > best[1]):               # (ties: the earlier genome of the universe)
+                    best = (fasta, jac, ratio(sh, g))
+            in_pan, in_core = int(res["match"][kk, s, 0]), int(res["match"][kk, s, 1])
+            summary.append([sample, k, q, in_pan, q - in_pan, in_core, *(best or (None, None, None))])
+            for gi, label in enumerate(labels):
+                for c, cls in enumerate(tree.KMER_CLASSES):
+                    total, hits = int(res["match"][kk, ns, 2 + 3 * gi + c]), int(res["match"][kk, s, 2 + 3 * gi + c])
+                    marks.append([sample, k, label, cls, total, hits, ratio(hits, total)])
+    os.makedirs(args.outdir, exist_ok=True)
+    _write_csv(outfile + ".screen.csv", ["sample", "k", "fasta", "genome_kmers", "sample_kmers", "shared", "genome_containment",
+                                         "sample_containment", "jaccard"], rows)
+    _write_csv(outfile + ".screen_summary.csv", ["sample", "k", "sample_kmers", "in_pan", "novel", "in_core", "best_fasta", "best_jaccard",
+                                                 "best_genome_containment"], summary)
+    if groups:
+        _write_csv(outfile + ".screen_groups.csv", ["sample", "k", "group", "class", "marker_kmers", "hits", "fraction"], marks)
+    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
+    tree.speciesinfo.save_references(fast=False)
+
+
 def serve_command(args):
     """A resident `dandd`: commands arrive over a unix socket (dandd_amd.host.client), run one at a time in THIS process --
     whose backends (deltatree._backends: GPU context, kernel modules, pinned buffers, job-table cache) outlive them -- with the
@@ -698,6 +778,22 @@ def build_parser():
     co.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     co.add_argument("-l", "--label", dest="label", default="")
     co.set_defaults(func=core_command)
+
+    sc = subs.add_parser("screen", parents=[common],
+                         description="exact containment of new samples (assemblies, read sets) in up to 64 genomes of a `tree --exact`")
+    sc.add_argument("-d", "--dtree", dest="delta_tree", required=True)
+    sc.add_argument("-s", "--tag", dest="tag", type=str)
+    sc.add_argument("-f", "--fastas", dest="flist_loc", default=None, type=str,
+                    help="the genomes of the universe (default: every leaf), in the order `progressive -f` takes them")
+    sc.add_argument("-g", "--groups", dest="groups_loc", default=None, type=str,
+                    help="'fasta<TAB>group' lines: per group the share of its core, private and signature k-mers each sample holds")
+    sc.add_argument("-q", "--queries", dest="query_loc", default=None, type=str, help="a file of sample paths, one per line")
+    sc.add_argument("-k", dest="ks", action="append", type=int, default=None, metavar="K",
+                    help="screen at this k (1..64, repeatable; default: the k of the tree's root)")
+    sc.add_argument("samples", nargs="*", metavar="SAMPLE", help="FASTA / FASTQ files, plain or gzip, that are no leaves of the tree")
+    sc.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
+    sc.add_argument("-l", "--label", dest="label", default="")
+    sc.set_defaults(func=screen_command)
 
     # (not in the reference: its every command is a fresh process that shells out to fresh `dashing` processes)
     sv = subs.add_parser("serve", description="keep the GPU context alive and run the commands dandd_amd.host.client forwards")

@@ -1217,6 +1217,65 @@ class DeltaTree:
             out.append(dict(group=gi, cls=cls, k=k, genomes=per))
         return out
 
+    # ---- samples that are no leaves (`dandd screen`) ---------------------------------------------------------------------
+    SCREEN_BATCH_FILES, SCREEN_BATCH_BYTES = 64, 4 << 30    # samples of one screen_counts call: files, bytes of their files
+
+    def screen_tables(self, fastas, samples, ks, groups=None):
+        """Exact containment of `samples` (files that are no leaves: FASTA / FASTQ, plain or gzip) in the universe `fastas`
+        (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]) at every k of `ks`.  The queries are (0, 0) -- in the
+        pan-genome at all --, (full, 0) -- in the core --, then core (G, 0), private (0, full ^ G) and signature
+        (G, full ^ G) of every group of `groups` (lists of FASTAs), in KMER_CLASSES order.  The samples go to the backend's
+        screen_counts in batches of at most SCREEN_BATCH_FILES files or SCREEN_BATCH_BYTES bytes, whichever comes first; each
+        batch sorts the universe again, which is cheap next to reading the samples.  A sample's own distinct k-mers are a
+        leaf database of its own, made in a temporary directory and counted by the backend's card.  There is no object path:
+        a backend without screen_counts, or without a table for these leaves, is a ValueError.
+        -> dict: ks, shared [K][ns+1][n], match [K][ns+1][nq] (row ns: the universe itself), sample_kmers [K][ns]"""
+        import tempfile
+        by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
+        nodes = [by_fasta[f] for f in fastas]
+        n, ns = len(nodes), len(samples)
+        ks = [int(k) for k in ks]
+        for k in ks:
+            if not 1 <= k <= 64:
+                raise ValueError(f"k={k} is outside 1..64")
+        index = {f: i for i, f in enumerate(fastas)}
+        full = (1 << n) - 1
+        gmasks = [sum(1 << index[f] for f in set(g)) for g in groups or []]
+        alls = [0, full] + [m for G in gmasks for m in (G, 0, G)]
+        nones = [0, 0] + [m for G in gmasks for m in (0, full ^ G, full ^ G)]
+        nq = len(alls)
+        batches, size = [[]], 0
+        for j, f in enumerate(samples):
+            b = os.path.getsize(f)
+            if batches[-1] and (len(batches[-1]) >= self.SCREEN_BATCH_FILES or size + b > self.SCREEN_BATCH_BYTES):
+                batches.append([])
+                size = 0
+            batches[-1].append(j)
+            size += b
+        out = {"ks": ks, "shared": np.zeros((len(ks), ns + 1, n), dtype=np.uint64), "match": np.zeros((len(ks), ns + 1, nq), dtype=np.uint64),
+               "sample_kmers": np.zeros((len(ks), ns), dtype=np.uint64)}
+        for kk, k in enumerate(ks):
+            exp = dict(self.experiment, ksweep=(k, k))
+            be = backend_for(exp)
+            if not hasattr(be, "screen_counts"):
+                raise ValueError(f"the backend {getattr(be, 'name', type(be).__name__)} has no screen_counts: containment needs exact membership masks")
+            paths = self._leaf_files(nodes, k, k)
+            for batch in batches:
+                got = be.screen_counts(paths, k, [samples[j] for j in batch], alls, nones)
+                if got is None:
+                    raise ValueError(f"the backend has no membership masks for {n} genomes")
+                shared = np.asarray(got[0]).astype(np.uint64).reshape(len(batch) + 1, n)
+                match = np.asarray(got[1]).astype(np.uint64).reshape(len(batch) + 1, nq)
+                out["shared"][kk, batch] = shared[:-1]
+                out["match"][kk, batch] = match[:-1]
+                out["shared"][kk, ns], out["match"][kk, ns] = shared[-1], match[-1]      # (the same in every batch)
+            with tempfile.TemporaryDirectory(prefix="dandd_screen_") as tmp:
+                for j, f in enumerate(samples):
+                    db = os.path.join(tmp, f"s{j}.k{k}")
+                    be.leaf(f, [k], [db])
+                    out["sample_kmers"][kk, j] = int(be.card(db))
+        return out
+
     # ---- batched GPU union schedules ------------------------------------------------------------------
     def _table_window(self, experiment):
         """[lo, hi] of a union table for climbs over this tree's leaves: the --ksweep window, or a hill-climb's guess -- the

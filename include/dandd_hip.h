@@ -305,6 +305,35 @@ int dd_exact_locate(dd_ctx *, const char *const *paths, int n, int k, const uint
 int dd_exact_locate_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int k,
                            const uint64_t *all, const uint64_t *none, const int32_t *genome, int njobs,
                            const uint64_t *off, uint64_t *hits, uint64_t *found);
+/* ---- samples screened against the universe ----------------------------------------------------------------------
+ * Exact containment of files that are NOT inputs of the universe (dd_exact_screen.hip): which of the universe's k-mers a
+ * sample holds, counted per input and per query, without the sample becoming a 65th mask bit, without its k-mers entering
+ * the sort and without the universe's own numbers changing.  ONE k per call, 1 <= k <= 64, 1 <= n <= 64 universe inputs,
+ * 1 <= ns <= 1024 samples, 0 <= nq <= 1024 queries (nq == 0: all, none and match may be null).  The bit rules are
+ * dd_exact_select's: a bit >= n set in all[q] or none[q] is DD_EINVAL, all & none != 0 is legal and matches nothing,
+ * all = none = 0 matches every record.  Counts are over DISTINCT k-mers (canonical per the context): a read set at 30x
+ * coverage counts each k-mer once.
+ *   shared[s][i]  s < ns: the distinct k-mers of sample s that universe input i also holds
+ *   match[s][q]   s < ns: the distinct k-mers of sample s whose universe mask m has (m & all[q]) == all[q] and
+ *                 (m & none[q]) == 0; with (0, 0): the k-mers of sample s that the universe holds at all
+ *   row ns        of both arrays is the universe itself: shared[ns][i] = the distinct k-mers of input i, match[ns][q] what
+ *                 dd_exact_select counts
+ *   *found        the distinct k-mers of the universe
+ * A sample that is empty, shorter than k or without a valid k-mer gives a zero row; a sample may be byte-identical to an
+ * input.  The sample's own distinct count is not part of this entry (dd_exact_count gives it).  Nothing is written unless
+ * the call returns DD_OK; two calls on the same inputs return identical bytes.  The device form takes n + ns buffers: the
+ * n universe inputs first, the ns samples behind them.
+ * The sort, the masks, the emission (always the single query (0, 0)) and the ordering are dd_exact_locate's, so are budget
+ * and passes (DD_EXACT_MB), dd_last_sketch_stats' third value and the DD_KERNEL_EXACT timer; the samples are tokenised
+ * with the universe but stay out of the sort and out of the slot count that sizes the record area.  Each sample's walk
+ * marks the records it holds in a bitmap of ns x ceil(found / 32) x 4 bytes of HBM (DD_ENOMEM with a message naming the
+ * bytes when that cannot be had); one tally of the marks gives every count. */
+int dd_exact_screen(dd_ctx *, const char *const *paths, int n, const char *const *samples, int ns, int k,
+                    const uint64_t *all /*[nq]*/, const uint64_t *none /*[nq]*/, int nq, uint64_t *shared /*[ns+1][n]*/,
+                    uint64_t *match /*[ns+1][nq]*/, uint64_t *found);
+int dd_exact_screen_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
+                           const uint64_t *all, const uint64_t *none, int nq, uint64_t *shared, uint64_t *match,
+                           uint64_t *found);
 /* Host only, no context and no device: names, sequence lengths and token starts of the records of one FASTA / FASTQ file,
  * plain or gzip, read by the loaders and record rules the exact calls and dd_sketch_files use.  K0 puts one BREAK token
  * where each header line ends -- IN FRONT of its record's bases -- and one for every ambiguous byte, so
@@ -348,7 +377,7 @@ int dd_exact_greedy_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate */
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen */
 #define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);
