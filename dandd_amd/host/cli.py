@@ -174,14 +174,75 @@ def _deltadelta_groups(tree, args):
     return groups, [title[g[0]] for g in groups]
 
 
+# ---- what the analyses over a loaded tree (deltadelta, abba, greedy, core, screen) share ------------------------------------
+def _open_tree(cmd, args, exact=False, safe=False):
+    """-> (the tree of -d, the prefix of the command's output files).  exact: the command sums over membership masks, so a
+    tree of sketches is an exit; safe: the command has an object path, which --safe asks for through the experiment."""
+    tree = _load_tree(args.delta_tree)
+    tree.speciesinfo.update(tool=tree.experiment["tool"])
+    if exact and tree.experiment["tool"] != "kmc":
+        sys.exit(f"{cmd}: {args.delta_tree} is a tree of sketches: build it with `tree --exact` -- intersections are sums over exact "
+                 "membership masks, and inclusion-exclusion over HyperLogLog union estimates amplifies their error")
+    if not args.tag:
+        args.tag = tree.speciesinfo.tag
+    if safe and args.safety:
+        tree.experiment["safety"] = True
+    return tree, tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
+
+
+def _window_or_exit(cmd, args, tree, why=""):
+    """-> the k window (lo, hi) of --ksweep, else the tree's own; `why` says what a hill-climb would make of the command"""
+    if args.ksweep:
+        return (int(args.mink), int(args.maxk))
+    if tree.experiment.get("ksweep") is not None:
+        return tuple(int(v) for v in tree.experiment["ksweep"])
+    sys.exit(f"{cmd}: a k window is needed: give --ksweep --mink --maxk, or a tree built with --ksweep" + (f" ({why})" if why else ""))
+
+
+def _universe_or_exit(cmd, tree, args, least, most=None, most_why=""):
+    """-> the FASTAs of -f (default: every leaf), in the order `progressive -f` takes them: `least` to `most` of them"""
+    fastas = tree.progressive_fastas(args.flist_loc)
+    n = len(fastas)
+    if n < least:
+        sys.exit(f"{cmd}: {n} genome(s) in the universe: at least 2 are needed" if least == 2 else
+                 f"{cmd}: {n} genomes in the universe: at least {least} is needed")
+    if most is not None and n > most:
+        sys.exit(f"{cmd}: {n} genomes in the universe: at most {most} ({most_why}); choose them with -f/--fastas")
+    return fastas
+
+
+MASK_BITS = "a membership mask has one bit per genome"    # why `core` and `screen` take at most 64 genomes
+
+
+def _groups_in_universe(cmd, args, leaf_of, fastas):
+    """-> (groups, labels) of -g, every member in the universe; ([], []) without -g"""
+    if not args.groups_loc:
+        return [], []
+    groups, labels = _read_groups(cmd, args.groups_loc, leaf_of)
+    for g in groups:
+        for f in g:
+            if f not in fastas:
+                sys.exit(f"{cmd}: {f} (-g) is not in the universe of this run (-f)")
+    return groups, labels
+
+
+def _rank0_after_presketch(tree, window):
+    """A multi-GPU run: every rank sketches its share of the leaves for the window; -> True on the rank that finishes alone"""
+    rank, world = deltatree.dist_ranks()
+    if world > 1:
+        tree.presketch_range(*window)      # (ends at the barrier, which switches sharding off: the rank is asked for before it)
+    return rank == 0
+
+
+def _finish(tree):
+    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
+    tree.speciesinfo.save_references(fast=False)
+
+
 def deltadelta_command(args):
     """How much each genome (or group of genomes) adds to the collection's delta: delta(all) - delta(all but it), the quantity
     of the reference's DeltaTree.find_delta_delta (lib/huffman_dandd.py:559-566), for every group in one command."""
-    tree = _load_tree(args.delta_tree)
-    tree.speciesinfo.update(tool=tree.experiment["tool"])
-    if not args.tag:
-        args.tag = tree.speciesinfo.tag
-    outfile = tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
+    tree, outfile = _open_tree("deltadelta", args)
     groups, labels = _deltadelta_groups(tree, args)
     os.makedirs(args.outdir, exist_ok=True)
     window = (int(args.mink), int(args.maxk)) if args.ksweep else (None, None)
@@ -192,8 +253,7 @@ def deltadelta_command(args):
     write_listdict_to_csv(outfile + ".deltadelta.csv", rows)
     if summary:
         write_listdict_to_csv(outfile + "_deltadeltasummary.csv", summary)
-    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
-    tree.speciesinfo.save_references(fast=False)
+    _finish(tree)
 
 
 def _write_csv(path, cols, rows):
@@ -210,27 +270,11 @@ def abba_command(args):
     each genome's mean / min / max contribution, and "A before B, B before A" -- b's mean increment at each of its
     positions over the orderings with a before it and over those with a after it.  The reference planned this sub-command
     (lib/dandd_cmd.py:248-258, commented out) and sampled orderings with `progressive` in its place."""
-    tree = _load_tree(args.delta_tree)
-    tree.speciesinfo.update(tool=tree.experiment["tool"])
-    if not args.tag:
-        args.tag = tree.speciesinfo.tag
-    outfile = tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
-    if args.ksweep:
-        window = (int(args.mink), int(args.maxk))
-    elif tree.experiment.get("ksweep") is not None:
-        window = tuple(int(v) for v in tree.experiment["ksweep"])
-    else:
-        sys.exit("abba: a k window is needed: give --ksweep --mink --maxk, or a tree built with --ksweep "
-                 "(hill-climb deltas per subset would depend on the order of the climbs)")
-    if args.safety:
-        tree.experiment["safety"] = True
+    tree, outfile = _open_tree("abba", args, safe=True)
+    window = _window_or_exit("abba", args, tree, why="hill-climb deltas per subset would depend on the order of the climbs")
     leaf_of = _leaf_lookup(tree, "abba", args.delta_tree)
-    fastas = tree.progressive_fastas(args.flist_loc)
+    fastas = _universe_or_exit("abba", tree, args, least=2, most=16, most_why="2^n subset unions")
     n = len(fastas)
-    if n < 2:
-        sys.exit(f"abba: {n} genome(s) in the universe: at least 2 are needed")
-    if n > 16:
-        sys.exit(f"abba: {n} genomes in the universe: at most 16 (2^n subset unions); choose them with -f/--fastas")
     if (args.fastaA is None) != (args.fastaB is None):
         sys.exit("abba: -A/--fastaA and -B/--fastaB go together")
     pairs = [(a, b) for a in range(n) for b in range(n) if a != b]
@@ -243,11 +287,8 @@ def abba_command(args):
                 sys.exit(f"abba: {f} is not in the universe of this run (-f)")
         ia, ib = fastas.index(fa), fastas.index(fb)
         pairs = [(ia, ib), (ib, ia)]
-    if deltatree.dist_ranks()[1] > 1:
-        # every rank sketches its share of the leaves for the window; rank 0 finishes alone
-        tree.presketch_range(*window)
-        if deltatree.dist_ranks()[0] != 0:
-            return
+    if not _rank0_after_presketch(tree, window):
+        return
     os.makedirs(args.outdir, exist_ok=True)
     ex = tree.ordering_expectations(fastas, *window)
     delta, kval, growth, contrib = ex["delta"], ex["kval"], ex["growth"], ex["contrib"]
@@ -277,33 +318,18 @@ def abba_command(args):
         rows = [[mask, int(size[mask]), float(delta[mask]), int(kval[mask]),
                  "|".join(fastas[i] for i in range(n) if mask >> i & 1)] for mask in range(1, full + 1)]
         _write_csv(outfile + ".abba_subsets.csv", ["mask", "ngen", "delta", "kval", "fastas"], rows)
-    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
-    tree.speciesinfo.save_references(fast=False)
+    _finish(tree)
 
 
 def greedy_command(args):
     """The steepest and the flattest growth ordering: add at each step the genome that raises delta the most (--mode max) or
     the least (min) -- the envelope `progressive`'s sampled orderings are read against, and the answer to "which genome
     next".  Each step depends on the union so far, so the orderings cannot be listed in advance."""
-    tree = _load_tree(args.delta_tree)
-    tree.speciesinfo.update(tool=tree.experiment["tool"])
-    if not args.tag:
-        args.tag = tree.speciesinfo.tag
-    outfile = tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
-    if args.ksweep:
-        window = (int(args.mink), int(args.maxk))
-    elif tree.experiment.get("ksweep") is not None:
-        window = tuple(int(v) for v in tree.experiment["ksweep"])
-    else:
-        sys.exit("greedy: a k window is needed: give --ksweep --mink --maxk, or a tree built with --ksweep "
-                 "(hill-climb deltas per candidate would depend on the order of the climbs)")
-    if args.safety:
-        tree.experiment["safety"] = True
+    tree, outfile = _open_tree("greedy", args, safe=True)
+    window = _window_or_exit("greedy", args, tree, why="hill-climb deltas per candidate would depend on the order of the climbs")
     leaf_of = _leaf_lookup(tree, "greedy", args.delta_tree)
-    fastas = tree.progressive_fastas(args.flist_loc)
+    fastas = _universe_or_exit("greedy", tree, args, least=2)
     n = len(fastas)
-    if n < 2:
-        sys.exit(f"greedy: {n} genome(s) in the universe: at least 2 are needed")
     base = []
     if args.base_loc:
         with open(args.base_loc) as fh:
@@ -321,11 +347,8 @@ def greedy_command(args):
     if steps < len(base):
         sys.exit(f"greedy: --steps {steps} is fewer than the {len(base)} genomes of -b/--base, which start every ordering")
     modes = ["max", "min"] if args.mode == "both" else [args.mode]
-    if deltatree.dist_ranks()[1] > 1:
-        # every rank sketches its share of the leaves for the window; rank 0 finishes alone
-        tree.presketch_range(*window)
-        if deltatree.dist_ranks()[0] != 0:
-            return
+    if not _rank0_after_presketch(tree, window):
+        return
     os.makedirs(args.outdir, exist_ok=True)
     res = tree.greedy_orderings(fastas, *window, modes, base=base, steps=steps)
     rows, summary = [], []
@@ -342,8 +365,7 @@ def greedy_command(args):
             fh.write("".join(f + "\n" for f in r["order"]))
     _write_csv(outfile + ".greedy.csv", ["mode", "ngen", "fasta", "delta", "kval", "gain", "fastas"], rows)
     _write_csv(outfile + ".greedysummary.csv", ["mode", "ngen", "kval", "card", "delta_pos"], summary)
-    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
-    tree.speciesinfo.save_references(fast=False)
+    _finish(tree)
 
 
 def core_command(args):
@@ -351,29 +373,11 @@ def core_command(args):
     of every prefix of an ordering next to its union (the second curve of a pan/core plot), and per group of genomes its
     core, its private k-mers and its signature (in every member, in nobody else).  All of it sums over the membership
     masks of an exact tree; sketches have no such sums (inclusion-exclusion over 2^n union estimates amplifies their error)."""
-    tree = _load_tree(args.delta_tree)
-    tree.speciesinfo.update(tool=tree.experiment["tool"])
-    if tree.experiment["tool"] != "kmc":
-        sys.exit(f"core: {args.delta_tree} is a tree of sketches: build it with `tree --exact` -- intersections are sums over exact "
-                 "membership masks, and inclusion-exclusion over HyperLogLog union estimates amplifies their error")
-    if not args.tag:
-        args.tag = tree.speciesinfo.tag
-    outfile = tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
-    if args.ksweep:
-        window = (int(args.mink), int(args.maxk))
-    elif tree.experiment.get("ksweep") is not None:
-        window = tuple(int(v) for v in tree.experiment["ksweep"])
-    else:
-        sys.exit("core: a k window is needed: give --ksweep --mink --maxk, or a tree built with --ksweep")
-    if args.safety:
-        tree.experiment["safety"] = True
+    tree, outfile = _open_tree("core", args, exact=True, safe=True)
+    window = _window_or_exit("core", args, tree)
     leaf_of = _leaf_lookup(tree, "core", args.delta_tree)
-    fastas = tree.progressive_fastas(args.flist_loc)
+    fastas = _universe_or_exit("core", tree, args, least=1, most=64, most_why=MASK_BITS)
     n = len(fastas)
-    if n < 1:
-        sys.exit(f"core: {n} genomes in the universe: at least 1 is needed")
-    if n > 64:
-        sys.exit(f"core: {n} genomes in the universe: at most 64 (a membership mask has one bit per genome); choose them with -f/--fastas")
     orderings = [tuple(range(n))]
     if args.ordering_file or args.norderings:
         try:
@@ -383,32 +387,25 @@ def core_command(args):
     for o in orderings:
         if sorted(o) != list(range(n)):
             sys.exit(f"core: an ordering of {len(o)} entries does not order the {n} genomes of the universe")
-    groups, labels = [], []
-    if args.groups_loc:
-        groups, labels = _read_groups("core", args.groups_loc, leaf_of)
-        for g in groups:
-            for f in g:
-                if f not in fastas:
-                    sys.exit(f"core: {f} (-g) is not in the universe of this run (-f)")
+    groups, labels = _groups_in_universe("core", args, leaf_of, fastas)
+
+    def in_window_or_exit(flag, ks):
+        for k in ks or []:
+            if not max(1, window[0]) <= k <= window[1]:
+                sys.exit(f"core: {flag} {k} is outside the k window {max(1, window[0])}..{window[1]}")
     if not args.kmers and (args.kmers_k or args.kmers_max is not None):
         sys.exit("core: --kmers-k and --kmers-max go with --kmers")
     kmers_max = 1_000_000 if args.kmers_max is None else int(args.kmers_max)
     if args.kmers:
-        for k in args.kmers_k or []:
-            if not max(1, window[0]) <= k <= window[1]:
-                sys.exit(f"core: --kmers-k {k} is outside the k window {max(1, window[0])}..{window[1]}")
+        in_window_or_exit("--kmers-k", args.kmers_k)
         if kmers_max < 0:
             sys.exit(f"core: --kmers-max {kmers_max}: a number of k-mers")
-        if not groups:                                               # the whole universe: its core is the core genome
-            groups, labels = [list(fastas)], ["all"]
     if not args.regions and args.regions_k:
         sys.exit("core: --regions-k goes with --regions")
     if args.regions:
-        for k in args.regions_k or []:
-            if not max(1, window[0]) <= k <= window[1]:
-                sys.exit(f"core: --regions-k {k} is outside the k window {max(1, window[0])}..{window[1]}")
-        if not groups:
-            groups, labels = [list(fastas)], ["all"]
+        in_window_or_exit("--regions-k", args.regions_k)
+    if (args.kmers or args.regions) and not groups:                  # the whole universe: its core is the core genome
+        groups, labels = [list(fastas)], ["all"]
     os.makedirs(args.outdir, exist_ok=True)
     try:
         res = tree.core_tables(fastas, *window, orderings, groups)
@@ -472,8 +469,7 @@ def core_command(args):
                     fh.write("".join(f"{name}\t{start}\t{end}\t{base}\n" for name, start, end in rows))
                     index.append([labels[gi], cls, k, base, len(rows), sum(end - start for _, start, end in rows), os.path.basename(path)])
         _write_csv(outfile + ".core_regions.csv", ["group", "class", "k", "fasta", "regions", "bases", "file"], index)
-    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
-    tree.speciesinfo.save_references(fast=False)
+    _finish(tree)
 
 
 def screen_command(args):
@@ -481,14 +477,7 @@ def screen_command(args):
     genome a sample contains and the other way round, which genome it is closest to, how much of it is in the pan-genome and
     the core, and with -g which group's core, private k-mers and signature it carries.  Counts are over distinct k-mers;
     the samples enter no sort and change none of the collection's numbers."""
-    tree = _load_tree(args.delta_tree)
-    tree.speciesinfo.update(tool=tree.experiment["tool"])
-    if tree.experiment["tool"] != "kmc":
-        sys.exit(f"screen: {args.delta_tree} is a tree of sketches: build it with `tree --exact` -- intersections are sums over exact "
-                 "membership masks, and inclusion-exclusion over HyperLogLog union estimates amplifies their error")
-    if not args.tag:
-        args.tag = tree.speciesinfo.tag
-    outfile = tree.make_prefix(tag=args.tag, label=args.label, outdir=args.outdir)
+    tree, outfile = _open_tree("screen", args, exact=True)
     ks = sorted(set(int(k) for k in args.ks)) if args.ks else [int(tree.root_k())]
     for k in ks:
         if not 1 <= k <= 64:
@@ -508,19 +497,9 @@ def screen_command(args):
         if not os.path.isfile(f):
             sys.exit(f"screen: {f} not found")
     leaf_of = _leaf_lookup(tree, "screen", args.delta_tree)
-    fastas = tree.progressive_fastas(args.flist_loc)
-    n, ns = len(fastas), len(samples)
-    if n < 1:
-        sys.exit(f"screen: {n} genomes in the universe: at least 1 is needed")
-    if n > 64:
-        sys.exit(f"screen: {n} genomes in the universe: at most 64 (a membership mask has one bit per genome); choose them with -f/--fastas")
-    groups, labels = [], []
-    if args.groups_loc:
-        groups, labels = _read_groups("screen", args.groups_loc, leaf_of)
-        for g in groups:
-            for f in g:
-                if f not in fastas:
-                    sys.exit(f"screen: {f} (-g) is not in the universe of this run (-f)")
+    fastas = _universe_or_exit("screen", tree, args, least=1, most=64, most_why=MASK_BITS)
+    ns = len(samples)
+    groups, labels = _groups_in_universe("screen", args, leaf_of, fastas)
     try:
         res = tree.screen_tables(fastas, samples, ks, groups)
     except (ValueError, OSError) as e:
@@ -552,8 +531,7 @@ def screen_command(args):
                                                  "best_genome_containment"], summary)
     if groups:
         _write_csv(outfile + ".screen_groups.csv", ["sample", "k", "group", "class", "marker_kmers", "hits", "fraction"], marks)
-    tree.speciesinfo.save_cardkey(tree.experiment["tool"])
-    tree.speciesinfo.save_references(fast=False)
+    _finish(tree)
 
 
 def serve_command(args):

@@ -20,6 +20,7 @@ import weakref
 import pickle
 import sys
 from collections import namedtuple
+from functools import cached_property
 from itertools import permutations
 from math import factorial
 from random import sample, shuffle
@@ -636,6 +637,72 @@ DEFAULT_EXPERIMENT = {"tool": "dashing", "registers": 20, "canonicalize": True, 
                       "lowmem": False}
 
 
+def _batched(experiment):
+    """May an analysis take a backend's whole table in one call?  Not under --safe, not under DD_NO_PREFETCH."""
+    return not experiment.get("safety") and not os.environ.get("DD_NO_PREFETCH")
+
+
+# The k-mer classes of a group of genomes: membership queries (all of, none of) over the masks of a universe, from the
+# group's mask G and the universe's mask `full`.  Their order is the order of every table and CSV column that holds them.
+KMER_QUERIES = {"core": lambda G, full: (G, 0), "private": lambda G, full: (0, full ^ G), "signature": lambda G, full: (G, full ^ G)}
+
+
+def group_queries(gmasks, full):
+    """-> (alls, nones): the KMER_QUERIES of every group mask, group after group, as a backend's select entry points take them"""
+    pairs = [query(G, full) for G in gmasks for query in KMER_QUERIES.values()]
+    return [a for a, _ in pairs], [b for _, b in pairs]
+
+
+class _Universe:
+    """The leaf FASTAs one analysis call works over (bit i of a membership mask is fastas[i]) and its k window
+    [max(1, lo), hi]: the experiment and backend of that window, the leaves' files (made on first use: the object paths
+    never ask), the backend's two ways to fail, and the object path for one union.  A local of the call -- trees are
+    pickled, so it is never stored on one, nor on a node or an experiment."""
+
+    def __init__(self, tree, fastas, lo, hi):
+        by_fasta = {leaf.fastas[0]: leaf for leaf in tree.leaf_nodes()}
+        self.tree, self.fastas = tree, fastas
+        self.nodes = [by_fasta[f] for f in fastas]
+        self.n = len(self.nodes)
+        self.index = {f: i for i, f in enumerate(fastas)}
+        self.full = (1 << self.n) - 1
+        self.lo, self.hi = max(1, int(lo)), int(hi)
+        if self.hi < self.lo:
+            raise ValueError(f"empty k window {self.lo}..{self.hi}")
+        self.ks = list(range(self.lo, self.hi + 1))
+        self.exp = dict(tree.experiment, ksweep=(self.lo, self.hi))
+        self.batched = _batched(self.exp)
+
+    @cached_property
+    def be(self):
+        return backend_for(self.exp)
+
+    @cached_property
+    def paths(self):
+        return self.tree._leaf_files(self.nodes, self.lo, self.hi)
+
+    def masks(self, groups):
+        """groups (lists of FASTAs of the universe) -> their membership masks"""
+        return [sum(1 << self.index[f] for f in set(g)) for g in groups]
+
+    def need(self, *entries, why):
+        for entry in entries:
+            if not hasattr(self.be, entry):
+                raise ValueError(f"the backend {getattr(self.be, 'name', type(self.be).__name__)} has no {entry}: {why} exact membership masks")
+
+    def table(self, got, shape=None):
+        """what a mask entry point gave -- None: no table for these leaves -- as unsigned integers of `shape` (None: as it is)"""
+        if got is None:
+            raise ValueError(f"the backend has no membership masks for {self.n} genomes")
+        return got if shape is None else np.asarray(got).astype(np.uint64).reshape(shape)
+
+    def union_cards(self, node_indices):
+        """The object path for one union: a SubSpider over these genomes of the universe, swept over the window -> cards [K]"""
+        sub = SubSpider([self.nodes[i] for i in node_indices], self.tree.speciesinfo, self.exp)
+        sub.root.node_ksweep(self.lo, self.hi)
+        return [sub.root.ksketches[k].card for k in self.ks]
+
+
 class DeltaTree:
     def __init__(self, fasta_files, speciesinfo, nchildren=2, leafnodes=(), experiment=None, padding=True):
         self.experiment = experiment if experiment is not None else dict(DEFAULT_EXPERIMENT, baseset=set())
@@ -904,7 +971,7 @@ class DeltaTree:
         exp = dict(self.experiment, ksweep=tuple(int(v) for v in window) if window is not None else None)
         be = backend_for(exp)
         sched = None
-        if hasattr(be, "leave_out_cards") and not exp.get("safety") and not os.environ.get("DD_NO_PREFETCH"):
+        if hasattr(be, "leave_out_cards") and _batched(exp):
             lo, hi = self._table_window(exp)
             lo = max(1, lo)
             if hi >= lo:
@@ -966,26 +1033,17 @@ class DeltaTree:
           * Object path (--safe, DD_NO_PREFETCH, a backend without a table for these leaves, the CPU checkers): one SubSpider
             per non-empty subset.
         -> dict: ks, cards [2^n][K], delta [2^n], kval [2^n] and the abba_expectations entries"""
-        by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
-        nodes = [by_fasta[f] for f in fastas]
-        n = len(nodes)
-        lo, hi = max(1, int(lo)), int(hi)
-        if hi < lo:
-            raise ValueError(f"empty k window {lo}..{hi}")
-        ks = np.arange(lo, hi + 1)
-        exp = dict(self.experiment, ksweep=(lo, hi))
-        be = backend_for(exp)
+        u = self._universe(fastas, lo, hi)
+        n, ks = u.n, np.array(u.ks)
         cards = None
-        if hasattr(be, "subset_cards") and not exp.get("safety") and not os.environ.get("DD_NO_PREFETCH"):
-            cards = be.subset_cards(self._leaf_files(nodes, lo, hi))
+        if hasattr(u.be, "subset_cards") and u.batched:
+            cards = u.be.subset_cards(u.paths)
         if cards is not None:
             cards = np.asarray(cards, dtype=np.float64).reshape(1 << n, len(ks))
         else:
             cards = np.zeros((1 << n, len(ks)))
             for mask in range(1, 1 << n):
-                sub = SubSpider([nodes[i] for i in range(n) if mask >> i & 1], self.speciesinfo, exp)
-                sub.root.node_ksweep(lo, hi)
-                cards[mask] = [sub.root.ksketches[k].card for k in ks]
+                cards[mask] = u.union_cards([i for i in range(n) if mask >> i & 1])
         ratio = cards / ks
         last = len(ks) - 1 - np.argmax(ratio[:, ::-1], axis=1)        # (ties: the larger k, as _window_delta)
         delta = ratio[np.arange(1 << n), last]
@@ -1008,34 +1066,27 @@ class DeltaTree:
             genomes or whose masks do not fit their store): one SubSpider per (step, candidate), through the cardinality
             cache.
         -> dict: ks, and per mode dict(order: FASTAs [steps], cards [steps][K], delta [steps], kval [steps])"""
-        by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
         base = list(base)
         given = set(base)
         seq = base + [f for f in fastas if f not in given]          # candidates in tie-break order behind the given start
-        nodes = [by_fasta[f] for f in seq]
-        n, nfixed = len(nodes), len(base)
+        n, nfixed = len(seq), len(base)
         steps = n if steps is None else int(steps)
         if not 1 <= steps <= n or steps < nfixed:
             raise ValueError(f"{steps} steps: between {max(1, nfixed)} and {n}")
-        lo, hi = max(1, int(lo)), int(hi)
-        if hi < lo:
-            raise ValueError(f"empty k window {lo}..{hi}")
-        ks = list(range(lo, hi + 1))
-        exp = dict(self.experiment, ksweep=(lo, hi))
-        be = backend_for(exp)
-        batched = not exp.get("safety") and not os.environ.get("DD_NO_PREFETCH")
+        u = self._universe(seq, lo, hi)
+        be, ks = u.be, u.ks
         out = {"ks": ks}
         table = None
         for mode in modes:
             order = cards = None
-            if batched and hasattr(be, "greedy_cards"):
-                got = be.greedy_cards(self._leaf_files(nodes, lo, hi), mode, nfixed, steps, lo)
+            if u.batched and hasattr(be, "greedy_cards"):
+                got = be.greedy_cards(u.paths, mode, nfixed, steps, u.lo)
                 if got is not None:
                     order = [int(i) for i in got[0]]
                     cards = np.asarray(got[1], dtype=np.float64).reshape(steps, len(ks))
             if order is None:
-                if table is None and batched and n <= 16 and hasattr(be, "subset_cards"):
-                    table = be.subset_cards(self._leaf_files(nodes, lo, hi))
+                if table is None and u.batched and n <= 16 and hasattr(be, "subset_cards"):
+                    table = be.subset_cards(u.paths)
                     if table is not None:
                         table = np.asarray(table, dtype=np.float64).reshape(1 << n, len(ks))
                 if table is not None:
@@ -1043,9 +1094,7 @@ class DeltaTree:
                         return table[sum(1 << i for i in chosen) | 1 << c]
                 else:
                     def card_of(chosen, c):
-                        sub = SubSpider([nodes[i] for i in chosen] + [nodes[c]], self.speciesinfo, exp)
-                        sub.root.node_ksweep(lo, hi)
-                        return [sub.root.ksketches[k].card for k in ks]
+                        return u.union_cards([*chosen, c])
                 order, cards = _greedy_walk(card_of, n, nfixed, steps, mode, ks)
             picked = [_window_delta([float(c) for c in row], ks) for row in cards]
             out[mode] = dict(order=[seq[i] for i in order], cards=np.asarray(cards, dtype=np.float64),
@@ -1060,34 +1109,19 @@ class DeltaTree:
           core [o][n][K]      k-mers held by every one of the first j+1 genomes of each ordering (core_progressive_counts)
           pan [o][n][K]       the union of the same prefixes: progressive_cards where the backend has that table, else one
                               SubSpider per prefix (the object path of `progressive`)
-          groups [g][3][K]    with `groups` (lists of FASTAs): core (G, 0), private (0, full ^ G) and signature
-                              (G, full ^ G) of every group, three queries each in one select_counts call
+          groups [g][3][K]    with `groups` (lists of FASTAs): core, private and signature k-mers (KMER_QUERIES) of
+                              every group, three queries each in one select_counts call
         There is no object path behind the three new tables: a backend without them, or without a table for these leaves,
         is a ValueError.  -> dict: ks and the tables as integer arrays"""
-        by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
-        nodes = [by_fasta[f] for f in fastas]
-        n = len(nodes)
-        lo, hi = max(1, int(lo)), int(hi)
-        if hi < lo:
-            raise ValueError(f"empty k window {lo}..{hi}")
-        ks = list(range(lo, hi + 1))
-        exp = dict(self.experiment, ksweep=(lo, hi))
-        be = backend_for(exp)
-        for entry in ("spectrum_counts", "core_progressive_counts", "select_counts"):
-            if not hasattr(be, entry):
-                raise ValueError(f"the backend {getattr(be, 'name', type(be).__name__)} has no {entry}: intersections need exact membership masks")
-        paths = self._leaf_files(nodes, lo, hi)
+        u = self._universe(fastas, lo, hi)
+        u.need("spectrum_counts", "core_progressive_counts", "select_counts", why="intersections need")
+        be, paths, n, ks = u.be, u.paths, u.n, u.ks
         orderings = [[int(i) for i in o] for o in orderings]
-
-        def table(got, shape):
-            if got is None:
-                raise ValueError(f"the backend has no membership masks for {n} genomes")
-            return np.asarray(got).astype(np.uint64).reshape(shape)
         out = {"ks": ks}
-        out["spectrum"] = table(be.spectrum_counts(paths), (n + 1, len(ks)))
-        out["core"] = table(be.core_progressive_counts(paths, orderings), (len(orderings), n, len(ks)))
+        out["spectrum"] = u.table(be.spectrum_counts(paths), (n + 1, len(ks)))
+        out["core"] = u.table(be.core_progressive_counts(paths, orderings), (len(orderings), n, len(ks)))
         pan = None
-        if hasattr(be, "progressive_cards") and not exp.get("safety") and not os.environ.get("DD_NO_PREFETCH"):
+        if hasattr(be, "progressive_cards") and u.batched:
             pan = be.progressive_cards(paths, orderings)
         if pan is None:
             pan = np.zeros((len(orderings), n, len(ks)))
@@ -1096,78 +1130,54 @@ class DeltaTree:
                 for j in range(n):
                     key = frozenset(order[:j + 1])
                     if key not in seen:
-                        sub = SubSpider([nodes[i] for i in sorted(key)], self.speciesinfo, exp)
-                        sub.root.node_ksweep(lo, hi)
-                        seen[key] = [sub.root.ksketches[k].card for k in ks]
+                        seen[key] = u.union_cards(sorted(key))
                     pan[o, j] = seen[key]
         out["pan"] = np.rint(np.asarray(pan, dtype=np.float64)).astype(np.uint64).reshape(len(orderings), n, len(ks))
         if groups:
-            index = {f: i for i, f in enumerate(fastas)}
-            full = (1 << n) - 1
-            masks = [sum(1 << index[f] for f in set(g)) for g in groups]
-            alls = [m for G in masks for m in (G, 0, G)]
-            nones = [m for G in masks for m in (0, full ^ G, full ^ G)]
-            out["groups"] = table(be.select_counts(paths, alls, nones), (len(groups), 3, len(ks)))
+            out["groups"] = u.table(be.select_counts(paths, *group_queries(u.masks(groups), u.full)), (len(groups), 3, len(ks)))
         return out
 
-    KMER_CLASSES = ("core", "private", "signature")       # the columns of core_tables' groups, in that order
+    KMER_CLASSES = tuple(KMER_QUERIES)                    # the columns of core_tables' groups, in that order
 
     def _core_cells(self, fastas, groups, wanted, ks, window, counts, entry):
-        """What core_kmers and core_regions share: the window, the backend (which must have select_counts and `entry`), the leaf
-        files, and one cell per group, class of `wanted` and k -- the class's argmax of count / k over the window
+        """What core_kmers and core_regions share: the universe over the window, whose backend must have select_counts and
+        `entry`, and one cell per group, class of `wanted` and k -- the class's argmax of count / k over the window
         (_window_delta's rule: the *_k of the group summary), or every k of `ks`.
-        -> (backend, leaf files, n, members [g] (indices into fastas), cells [(group, class, k, all, none, count)])"""
-        by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
-        nodes = [by_fasta[f] for f in fastas]
-        n = len(nodes)
+        -> (universe, members [g] (indices into fastas), cells [(group, class, k, all, none, count)])"""
         wanted = [c for c in self.KMER_CLASSES if c in set(wanted)]
         if window is None:
             window = self.experiment.get("ksweep")
         if window is None:
             raise ValueError("a k window is needed")
-        lo, hi = max(1, int(window[0])), int(window[1])
-        if hi < lo:
-            raise ValueError(f"empty k window {lo}..{hi}")
-        window_ks = list(range(lo, hi + 1))
+        u = self._universe(fastas, *window)
         for k in ks or []:
-            if int(k) not in window_ks:
-                raise ValueError(f"k={k} is outside the window {lo}..{hi}")
-        exp = dict(self.experiment, ksweep=(lo, hi))
-        be = backend_for(exp)
-        for name in ("select_counts", entry):
-            if not hasattr(be, name):
-                raise ValueError(f"the backend {getattr(be, 'name', type(be).__name__)} has no {name}: intersections need exact membership masks")
-        paths = self._leaf_files(nodes, lo, hi)
-        index = {f: i for i, f in enumerate(fastas)}
-        full = (1 << n) - 1
-        members = [sorted({index[f] for f in g}) for g in groups]
-        gmasks = [sum(1 << i for i in m) for m in members]
-        query = {"core": lambda G: (G, 0), "private": lambda G: (0, full ^ G), "signature": lambda G: (G, full ^ G)}
+            if int(k) not in u.ks:
+                raise ValueError(f"k={k} is outside the window {u.lo}..{u.hi}")
+        u.need("select_counts", entry, why="intersections need")
+        paths = u.paths
+        members = [sorted({u.index[f] for f in g}) for g in groups]
+        gmasks = u.masks(groups)
         if counts is None:
-            alls = [m for G in gmasks for m in (G, 0, G)]
-            nones = [m for G in gmasks for m in (0, full ^ G, full ^ G)]
-            counts = be.select_counts(paths, alls, nones)
-            if counts is None:
-                raise ValueError(f"the backend has no membership masks for {n} genomes")
-        counts = np.asarray(counts).astype(np.uint64).reshape(len(groups), 3, len(window_ks))
+            counts = u.be.select_counts(paths, *group_queries(gmasks, u.full))
+        counts = u.table(counts, (len(groups), 3, len(u.ks)))
         cells = []
         for gi, G in enumerate(gmasks):
             for cls in wanted:
                 col = [int(v) for v in counts[gi, self.KMER_CLASSES.index(cls)]]
-                for k in ([int(k) for k in ks] if ks else [_window_delta(col, window_ks)[1]]):
-                    cells.append((gi, cls, k, *query[cls](G), col[k - lo]))
-        return be, paths, n, members, cells
+                for k in ([int(k) for k in ks] if ks else [_window_delta(col, u.ks)[1]]):
+                    cells.append((gi, cls, k, *KMER_QUERIES[cls](G, u.full), col[k - u.lo]))
+        return u, members, cells
 
     def core_kmers(self, fastas, groups, wanted, ks=None, limit=1_000_000, window=None, counts=None):
         """The k-mers behind the cells of core_tables' `groups`: for every group (lists of FASTAs of the universe `fastas`) and
-        every class of `wanted` (core (G, 0), private (0, full ^ G), signature (G, full ^ G)) the k-mers themselves at the k
+        every class of `wanted` (core, private, signature: KMER_QUERIES) the k-mers themselves at the k
         where count / k is largest over the window (_window_delta's rule: the *_k of the group summary), or at every k of
         `ks`.  window: (lo, hi), default the tree's --ksweep; counts: core_tables(...)["groups"] of the same window where the
         caller has it, else one select_counts call.  ONE select_kmers call per distinct k carries every query of that k; the
         records come back once each, ascending, and go to their queries by their masks, here.  A cell of more than `limit`
         k-mers is a ValueError that names it, before any k-mer is asked for.
         -> list of dict(group, cls, k, kmers uint64 [m][2] (lo, hi), masks uint64 [m]) in (group, class as KMER_CLASSES, k) order"""
-        be, paths, n, _, cells = self._core_cells(fastas, groups, wanted, ks, window, counts, "select_kmers")
+        u, _, cells = self._core_cells(fastas, groups, wanted, ks, window, counts, "select_kmers")
         for gi, cls, k, _, _, count in cells:
             if count > limit:
                 raise ValueError(f"group {gi + 1}, {cls}, k={k}: {count} k-mers, more than the limit of {limit}")
@@ -1175,9 +1185,7 @@ class DeltaTree:
         for k in sorted({cell[2] for cell in cells}):
             mine = sorted({(a, b) for _, _, kk, a, b, _ in cells if kk == k})
             room = sum(count for _, _, kk, _, _, count in cells if kk == k)     # (the union of the queries holds no more)
-            res = be.select_kmers(paths, k, [a for a, _ in mine], [b for _, b in mine], room)
-            if res is None:
-                raise ValueError(f"the backend has no membership masks for {n} genomes")
+            res = u.table(u.be.select_kmers(u.paths, k, [a for a, _ in mine], [b for _, b in mine], room))
             got[k] = (np.asarray(res[0], dtype=np.uint64).reshape(-1, 2), np.asarray(res[1], dtype=np.uint64).reshape(-1))
         out = []
         for gi, cls, k, a, b, count in cells:
@@ -1197,15 +1205,12 @@ class DeltaTree:
         -> list of dict(group, cls, k, genomes [(fasta, [(record name, start, end)])]) in (group, class as KMER_CLASSES, k)
         order; a cell's genomes in the universe's order, a genome's rows by record, then start"""
         from ..engine import regions_from_hits
-        be, paths, n, members, cells = self._core_cells(fastas, groups, wanted, ks, window, counts, "locate_hits")
+        u, members, cells = self._core_cells(fastas, groups, wanted, ks, window, counts, "locate_hits")
         got = {}                                                       # (k, all, none, genome) -> intervals per record
         names = {}                                                     # genome -> its records' names
         for k in sorted({cell[2] for cell in cells}):
             jobs = sorted({(a, b, g) for gi, _, kk, a, b, _ in cells if kk == k for g in members[gi]})
-            res = be.locate_hits(paths, k, jobs)
-            if res is None:
-                raise ValueError(f"the backend has no membership masks for {n} genomes")
-            recs, hits = res
+            recs, hits = u.table(u.be.locate_hits(u.paths, k, jobs))
             for (a, b, g), words in zip(jobs, hits):
                 rec_names, seq_len, tok_start, _ = recs[g]
                 names[g] = list(rec_names)
@@ -1223,27 +1228,19 @@ class DeltaTree:
     def screen_tables(self, fastas, samples, ks, groups=None):
         """Exact containment of `samples` (files that are no leaves: FASTA / FASTQ, plain or gzip) in the universe `fastas`
         (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]) at every k of `ks`.  The queries are (0, 0) -- in the
-        pan-genome at all --, (full, 0) -- in the core --, then core (G, 0), private (0, full ^ G) and signature
-        (G, full ^ G) of every group of `groups` (lists of FASTAs), in KMER_CLASSES order.  The samples go to the backend's
+        pan-genome at all --, (full, 0) -- in the core --, then the core, private and signature k-mers
+        (KMER_QUERIES, in that order) of every group of `groups` (lists of FASTAs).  The samples go to the backend's
         screen_counts in batches of at most SCREEN_BATCH_FILES files or SCREEN_BATCH_BYTES bytes, whichever comes first; each
         batch sorts the universe again, which is cheap next to reading the samples.  A sample's own distinct k-mers are a
         leaf database of its own, made in a temporary directory and counted by the backend's card.  There is no object path:
         a backend without screen_counts, or without a table for these leaves, is a ValueError.
         -> dict: ks, shared [K][ns+1][n], match [K][ns+1][nq] (row ns: the universe itself), sample_kmers [K][ns]"""
         import tempfile
-        by_fasta = {leaf.fastas[0]: leaf for leaf in self.leaf_nodes()}
-        nodes = [by_fasta[f] for f in fastas]
-        n, ns = len(nodes), len(samples)
+        n, ns, nq = len(fastas), len(samples), 2 + len(self.KMER_CLASSES) * len(groups or [])
         ks = [int(k) for k in ks]
         for k in ks:
             if not 1 <= k <= 64:
                 raise ValueError(f"k={k} is outside 1..64")
-        index = {f: i for i, f in enumerate(fastas)}
-        full = (1 << n) - 1
-        gmasks = [sum(1 << index[f] for f in set(g)) for g in groups or []]
-        alls = [0, full] + [m for G in gmasks for m in (G, 0, G)]
-        nones = [0, 0] + [m for G in gmasks for m in (0, full ^ G, full ^ G)]
-        nq = len(alls)
         batches, size = [[]], 0
         for j, f in enumerate(samples):
             b = os.path.getsize(f)
@@ -1255,17 +1252,14 @@ class DeltaTree:
         out = {"ks": ks, "shared": np.zeros((len(ks), ns + 1, n), dtype=np.uint64), "match": np.zeros((len(ks), ns + 1, nq), dtype=np.uint64),
                "sample_kmers": np.zeros((len(ks), ns), dtype=np.uint64)}
         for kk, k in enumerate(ks):
-            exp = dict(self.experiment, ksweep=(k, k))
-            be = backend_for(exp)
-            if not hasattr(be, "screen_counts"):
-                raise ValueError(f"the backend {getattr(be, 'name', type(be).__name__)} has no screen_counts: containment needs exact membership masks")
-            paths = self._leaf_files(nodes, k, k)
+            u = self._universe(fastas, k, k)
+            u.need("screen_counts", why="containment needs")
+            be, paths = u.be, u.paths
+            alls, nones = group_queries(u.masks(groups or []), u.full)
+            alls, nones = [0, u.full] + alls, [0, 0] + nones
             for batch in batches:
-                got = be.screen_counts(paths, k, [samples[j] for j in batch], alls, nones)
-                if got is None:
-                    raise ValueError(f"the backend has no membership masks for {n} genomes")
-                shared = np.asarray(got[0]).astype(np.uint64).reshape(len(batch) + 1, n)
-                match = np.asarray(got[1]).astype(np.uint64).reshape(len(batch) + 1, nq)
+                got = u.table(be.screen_counts(paths, k, [samples[j] for j in batch], alls, nones))
+                shared, match = u.table(got[0], (len(batch) + 1, n)), u.table(got[1], (len(batch) + 1, nq))
                 out["shared"][kk, batch] = shared[:-1]
                 out["match"][kk, batch] = match[:-1]
                 out["shared"][kk, ns], out["match"][kk, ns] = shared[-1], match[-1]      # (the same in every batch)
@@ -1291,6 +1285,10 @@ class DeltaTree:
             else:
                 hi = min(hi, 64)      # (exact trees: the engine's k <= 64)
         return int(lo), int(hi)
+
+    def _universe(self, fastas, lo, hi):
+        """What every analysis over a set of this tree's leaf FASTAs and a k window starts from (_Universe)"""
+        return _Universe(self, fastas, lo, hi)
 
     def _leaf_files(self, leaves, lo, hi):
         """Make sure every leaf has its sketch file for k in [lo, hi] (one fused GPU pass per leaf)
@@ -1549,7 +1547,8 @@ def write_phylip(tuples, path, k=0):
 
 
 def _window_delta(cards, ks):
-    """delta over a k window: max of card / k, ties going to the larger k (the hill-climb's `<=`) -> (delta, k)"""
+    """delta over a k window: max of card / k, ties going to the larger k (the hill-climb's `<=`; ordering_expectations
+    states the same rule for all its rows at once) -> (delta, k)"""
     best, bestk = 0, 0
     for c, k in zip(cards, ks):
         if best <= c / k:

@@ -327,6 +327,81 @@ def test_exits(host, tmp_path):
     fails(CoreBackend, ["-d", pk65, *WINDOW], "65 genomes", "at most 64", "-f")
 
 
+def test_group_queries_in_class_order(host):
+    """The one table of the k-mer classes: core (G, 0), private (0, full ^ G), signature (G, full ^ G), group after group"""
+    full = 0b111
+    assert host.group_queries([0b011, 0b100], full) == ([3, 0, 3, 4, 0, 4], [0, 4, 4, 0, 3, 3])
+    assert host.DeltaTree.KMER_CLASSES == tuple(host.KMER_QUERIES) == ("core", "private", "signature")
+    for G in (0b011, 0b100):
+        alls, nones = host.group_queries([G], full)
+        assert list(zip(alls, nones)) == [host.KMER_QUERIES[cls](G, full) for cls in host.DeltaTree.KMER_CLASSES]
+    assert host.group_queries([], full) == ([], [])
+
+
+def test_universe_of_a_call(host, tmp_path, monkeypatch):
+    """DeltaTree._universe on the golden exact tree: the window's checks, leaf files only when asked for, the object path of
+    one union, and the backend's two failures."""
+    from dandd_amd.host.compat import load_tree
+    pk = ex.exact_tree(str(tmp_path), host)                       # (leaves hostcheck.ExactBackend as the backend)
+    data = str(tmp_path / "data")
+    tree = load_tree(pk)
+    fastas = [os.path.join(data, n) for n in NAMES[1:4]]
+    with pytest.raises(ValueError, match=r"^empty k window 9\.\.8$"):
+        tree._universe(fastas, 9, 8)
+    with pytest.raises(ValueError, match=r"^empty k window 1\.\.0$"):
+        tree._universe(fastas, -3, 0)
+    passes = []
+    leaf_files = host.DeltaTree._leaf_files
+    monkeypatch.setattr(host.DeltaTree, "_leaf_files", lambda self, nodes, lo, hi: passes.append((len(nodes), lo, hi)) or leaf_files(self, nodes, lo, hi))
+    u = tree._universe(fastas, 8, 10)
+    assert (u.n, u.full, u.lo, u.hi, u.ks) == (3, 0b111, 8, 10, [8, 9, 10])
+    assert u.index == {f: i for i, f in enumerate(fastas)} and [leaf.fastas[0] for leaf in u.nodes] == fastas
+    assert u.exp["ksweep"] == (8, 10) and tree.experiment["ksweep"] is None and u.batched
+    assert tree._universe(fastas, 0, 2).ks == [1, 2]
+    assert u.masks([[fastas[2]], [fastas[1], fastas[0], fastas[1]]]) == [0b100, 0b011]
+    cards = u.union_cards([0, 2])
+    assert passes == []                                           # the object path never asks for the leaves' files
+    sub = host.SubSpider([u.nodes[0], u.nodes[2]], tree.speciesinfo, u.exp)
+    sub.root.node_ksweep(8, 10)
+    assert cards == [sub.root.ksketches[k].card for k in (8, 9, 10)]
+    texts = [open(fastas[i], "rb").read() for i in (0, 2)]
+    assert cards == [float(pyref.exact_count(texts, k, True)) for k in (8, 9, 10)]
+    paths = u.paths
+    assert u.paths is paths and passes == [(3, 8, 10)]
+    assert [[int(json.load(open(p))["k"]) for p in row] for row in paths] == [[8, 9, 10]] * 3
+    u.need("leaf", "card", why="intersections need")
+    with pytest.raises(ValueError, match="^the backend exact has no spectrum_counts: intersections need exact membership masks$"):
+        u.need("leaf", "spectrum_counts", "select_counts", why="intersections need")
+    with pytest.raises(ValueError, match="^the backend exact has no screen_counts: containment needs exact membership masks$"):
+        u.need("screen_counts", why="containment needs")
+    with pytest.raises(ValueError, match="^the backend has no membership masks for 3 genomes$"):
+        u.table(None, (1, 3))
+    got = u.table([[1.0, 2.0, 3.0]], (3, 1))
+    assert got.dtype == np.uint64 and got.tolist() == [[1], [2], [3]] and u.table((1, 2)) == (1, 2)
+    monkeypatch.setenv("DD_NO_PREFETCH", "1")
+    assert not tree._universe(fastas, 8, 10).batched
+    monkeypatch.delenv("DD_NO_PREFETCH")
+    tree.experiment["safety"] = True
+    assert not tree._universe(fastas, 8, 10).batched
+    # a local of the call: nothing of it stays on the tree, which is pickled
+    assert not any(isinstance(v, host._Universe) for v in vars(tree).values())
+
+
+def test_rank_zero_finishes_alone(host, monkeypatch):
+    """abba and greedy under several ranks: every rank presketches the window, and the rank is read BEFORE the barrier at the
+    end of presketch_range switches the sharding off (after it every rank reads as rank 0 of 1)."""
+    from dandd_amd.host import cli
+
+    class Tree:
+        def presketch_range(self, lo, hi):
+            swept.append((lo, hi))
+            monkeypatch.setattr(host, "dist_ranks", lambda: (0, 1))
+    for ranks, alone, sweeps in (((0, 1), True, []), ((0, 2), True, [(8, 12)]), ((1, 2), False, [(8, 12)])):
+        swept = []
+        monkeypatch.setattr(host, "dist_ranks", lambda ranks=ranks: ranks)
+        assert cli._rank0_after_presketch(Tree(), (8, 12)) is alone and swept == sweeps
+
+
 def test_binding_and_backend_have_the_entry_points():
     from dandd_amd import engine
     from dandd_amd.host.backend import HipExactBackend
