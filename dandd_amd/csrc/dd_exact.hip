@@ -15,6 +15,7 @@
 
 #include "dd_common.h"
 #include "dd_kernels.h"
+#include "dd_exact_walk.h"
 
 namespace dd {
 namespace {
@@ -44,88 +45,31 @@ __global__ __launch_bounds__(256) void kmer_extract_kernel(const ExactGenome* __
         __syncthreads();
     }
     const ExactGenome g = tab[blockIdx.y];
-    const unsigned long long ntok = *g.ntok;
     const unsigned long long seg = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const KeyMasks km = key_masks(k);
     unsigned valid = 0, allt = 0;
-    // (MODE 2 keeps every lane in the token loop: the append is a wave-level operation)
-    const bool live = seg * kSegTokens < ntok;
-    if (MODE == 2 ? __any(live) : live) {
-        const uint4* codes4 = reinterpret_cast<const uint4*>(g.codes);
-        const uint2* bad2 = reinterpret_cast<const uint2*>(g.bad);
-        // 128-bit windows serve every k <= 64; the sort, not this kernel, is the cost
-        uint64_t fh = 0, fl = 0, rh = 0, rl = 0;
-        int run = 0;
-        const uint64_t mlo = (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1ull);
-        const uint64_t mhi = (k <= 32) ? 0ull : ((k == 64) ? ~0ull : ((1ull << (2 * k - 64)) - 1ull));
-        const int s = 128 - 2 * k;  // right shift that aligns the reverse-complement window
-        for (int part = (seg > 0 ? 0 : 1); part < 2; ++part) {
-            const unsigned long long sidx = seg - 1 + part;
-            const uint4 c4 = live ? codes4[sidx] : make_uint4(0, 0, 0, 0);
-            const uint2 b2 = live ? bad2[sidx] : make_uint2(~0u, ~0u);
-            const uint32_t cw[4] = {c4.x, c4.y, c4.z, c4.w};
-            const uint64_t bw = ((uint64_t)b2.y << 32) | b2.x;
-#pragma unroll
-            for (int w = 0; w < 4; ++w)
-#pragma unroll 1
-            for (int i = 0; i < 16; ++i) {
-                const int t = w * 16 + i;
-                const uint32_t c = (cw[w] >> (2 * i)) & 3u;
-                run = ((bw >> t) & 1ull) ? 0 : run + 1;
-                fh = (fh << 2) | (fl >> 62);
-                fl = (fl << 2) | c;
-                rl = (rl >> 2) | (rh << 62);
-                rh = (rh >> 2) | ((uint64_t)(3u - c) << 62);
-                const bool have = part != 0 && run >= k;
-                if (MODE != 2 && !have) continue;
-                uint64_t ah = fh & mhi, al = fl & mlo;
-                if (CANON) {
-                    uint64_t bh, bl;
-                    if (s >= 64) {
-                        bh = 0;
-                        bl = rh >> (s - 64);
-                    } else if (s == 0) {
-                        bh = rh;
-                        bl = rl;
-                    } else {
-                        bh = rh >> s;
-                        bl = (rl >> s) | (rh << (64 - s));
-                    }
-                    if (bh < ah || (bh == ah && bl < al)) {
-                        ah = bh;
-                        al = bl;
-                    }
-                }
-                if (MODE == 0) {
-                    const unsigned long long pos = g.base + sidx * kSegTokens + (unsigned)t;
-                    const uint64_t tag = (TAG == 1) ? (uint64_t)blockIdx.y << 56 : 0ull;
-                    out_lo[pos] = WIDE ? al : (al | tag);
-                    if (WIDE) out_hi[pos] = ah | tag;
-                    if (TAG == 2) out_g[pos] = (uint8_t)blockIdx.y;
-                    ++valid;
-                    if (al == mlo && ah == mhi) allt = 1;
-                } else if (MODE == 1) {
-                    atomicAdd(&lhist[exact_bin(al, WIDE ? ah : 0ull)], 1u);
-                } else {
-                    const uint32_t bin = exact_bin(al, WIDE ? ah : 0ull);
-                    const bool take = have && bin >= bin_lo && bin < bin_hi;
-                    const unsigned long long mask = __ballot(take);
-                    if (mask) {
-                        const uint32_t lane = threadIdx.x & 63u;
-                        unsigned long long basepos = 0;
-                        if (lane == (uint32_t)__builtin_ctzll(mask)) basepos = atomicAdd(&counters[3], (unsigned long long)__builtin_popcountll(mask));
-                        basepos = __shfl(basepos, __builtin_ctzll(mask));
-                        if (take) {
-                            const unsigned long long pos = basepos + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-                            const uint64_t tag = (TAG == 1) ? (uint64_t)blockIdx.y << 56 : 0ull;
-                            out_lo[pos] = WIDE ? al : (al | tag);
-                            if (WIDE) out_hi[pos] = ah | tag;
-                            if (TAG == 2) out_g[pos] = (uint8_t)blockIdx.y;
-                        }
-                    }
-                }
+    // the sort, not this kernel, is the cost.  (MODE 2 keeps every lane in the token loop: the append is a wave-level operation)
+    walk_segment<CANON, MODE == 2>(g.codes, g.bad, *g.ntok, seg, k, [&](unsigned long long sidx, int t, uint64_t ah, uint64_t al, bool have) {
+        unsigned long long pos;
+        if (MODE == 0) {
+            pos = g.base + sidx * kSegTokens + (unsigned)t;
+            ++valid;
+            if (al == km.lo && ah == km.hi) allt = 1;
+        } else {
+            const uint32_t bin = exact_bin(al, WIDE ? ah : 0ull);
+            if (MODE == 1) {
+                atomicAdd(&lhist[bin], 1u);
+                return;
             }
+            const bool take = have && bin >= bin_lo && bin < bin_hi;
+            pos = wave_append(take, &counters[3]);
+            if (!take) return;
         }
-    }
+        const uint64_t tag = (TAG == 1) ? (uint64_t)blockIdx.y << 56 : 0ull;
+        out_lo[pos] = WIDE ? al : (al | tag);
+        if (WIDE) out_hi[pos] = ah | tag;
+        if (TAG == 2) out_g[pos] = (uint8_t)blockIdx.y;
+    });
     if (MODE == 1) {
         __syncthreads();
         for (int i = threadIdx.x; i < (1 << kExactBinBits); i += blockDim.x)
@@ -169,38 +113,70 @@ void launch_kmer_extract(const ExactGenome* tab_dev, int ng, size_t max_segments
                          unsigned long long* hist, uint32_t bin_lo, uint32_t bin_hi, int tag, uint8_t* g) {
     if (ng <= 0 || !max_segments) return;
     const dim3 grid((unsigned)((max_segments + 255) / 256), (unsigned)ng), block(256);
-    const bool wide = k > 32;
-#define DD_EX(CN, WD, MD, TG) \
-    hipLaunchKernelGGL((kmer_extract_kernel<CN, WD, MD, TG>), grid, block, 0, st, tab_dev, k, lo, hi, counters, hist, bin_lo, bin_hi, g)
-#define DD_EX_TAG(CN, WD, MD)            \
-    do {                                 \
-        if (tag == 0) DD_EX(CN, WD, MD, 0); \
-        else if (tag == 1) DD_EX(CN, WD, MD, 1); \
-        else DD_EX(CN, WD, MD, 2);       \
-    } while (0)
-#define DD_EX_MODE(CN, WD)             \
-    do {                               \
-        if (mode == 0) DD_EX_TAG(CN, WD, 0); \
-        else if (mode == 1) DD_EX(CN, WD, 1, 0); \
-        else DD_EX_TAG(CN, WD, 2);     \
-    } while (0)
-    if (canonical) {
-        if (wide) DD_EX_MODE(true, true); else DD_EX_MODE(true, false);
-    } else {
-        if (wide) DD_EX_MODE(false, true); else DD_EX_MODE(false, false);
-    }
-#undef DD_EX_MODE
-#undef DD_EX_TAG
-#undef DD_EX
+    // the (mode, tag) the kernel is built for: mode 1 writes no k-mer and takes no tag
+    const auto mode_tag = [&](const auto& f) {
+        using std::integral_constant;
+        switch (mode == 1 ? 3 : (mode ? 4 : 0) + std::min(std::max(tag, 0), 2)) {
+            case 0: return f(integral_constant<int, 0>{}, integral_constant<int, 0>{});
+            case 1: return f(integral_constant<int, 0>{}, integral_constant<int, 1>{});
+            case 2: return f(integral_constant<int, 0>{}, integral_constant<int, 2>{});
+            case 3: return f(integral_constant<int, 1>{}, integral_constant<int, 0>{});
+            case 4: return f(integral_constant<int, 2>{}, integral_constant<int, 0>{});
+            case 5: return f(integral_constant<int, 2>{}, integral_constant<int, 1>{});
+            default: return f(integral_constant<int, 2>{}, integral_constant<int, 2>{});
+        }
+    };
+    dispatch_bool(canonical != 0, [&](auto cn) {
+        dispatch_bool(k > 32, [&](auto wd) {
+            mode_tag([&](auto md, auto tg) {
+                hipLaunchKernelGGL((kmer_extract_kernel<decltype(cn)::value, decltype(wd)::value, decltype(md)::value, decltype(tg)::value>), grid,
+                                   block, 0, st, tab_dev, k, lo, hi, counters, hist, bin_lo, bin_hi, g);
+            });
+        });
+    });
 }
 
-size_t exact_sort_temp_bytes(size_t n, int k) {
-    size_t a = 0, b = 0;
-    uint64_t* nul = nullptr;
-    (void)rocprim::radix_sort_keys(nullptr, a, nul, nul, n, 0, 64);
-    if (k > 32) (void)rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul, nul, n, 0, 64);
-    return std::max(a, b) + 256;
+// ---- the one ordered sort of the exact path --------------------------------------------------------------------------
+namespace {
+
+template <class F>
+hipError_t sort_keys(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, F* f, F* f_alt, size_t n, int k, void* temp,
+                     size_t tb, hipStream_t st) {
+    hipError_t e;
+    if (k <= 32) {
+        const unsigned bits = (unsigned)(2 * k);
+        return f ? rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, f, f_alt, n, 0, bits, st) : rocprim::radix_sort_keys(temp, tb, lo, lo_alt, n, 0, bits, st);
+    }
+    // stable LSD over the 128-bit key: low word first, then the high word's 2k - 64 bits.  A pair sort carries ONE value
+    // array, so each pass runs once more for the follower, in front: the same keys give the same permutation (the sort is
+    // stable and deterministic).
+    const unsigned bits = (unsigned)(2 * k - 64);
+    if (f && (e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, f, f_alt, n, 0, 64, st)) != hipSuccess) return e;
+    if ((e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, hi, hi_alt, n, 0, 64, st)) != hipSuccess) return e;
+    if (f && (e = rocprim::radix_sort_pairs(temp, tb, hi_alt, hi, f_alt, f, n, 0, bits, st)) != hipSuccess) return e;
+    return rocprim::radix_sort_pairs(temp, tb, hi_alt, hi, lo_alt, lo, n, 0, bits, st);
 }
+
+}  // namespace
+
+size_t exact_sort_keys_temp_bytes(size_t n, int k, size_t follow_bytes) {
+    size_t a = 0, b = 0, c = 0;
+    uint64_t* nul = nullptr;
+    uint8_t* nul8 = nullptr;
+    (void)rocprim::radix_sort_keys(nullptr, a, nul, nul, n, 0, 64);
+    if (follow_bytes == 1) (void)rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul8, nul8, n, 0, 64);
+    if (k > 32 || follow_bytes == 8) (void)rocprim::radix_sort_pairs(nullptr, c, nul, nul, nul, nul, n, 0, 64);
+    return std::max(a, std::max(b, c)) + 256;
+}
+
+hipError_t launch_exact_sort_keys(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, void* follow, void* follow_alt,
+                                  size_t follow_bytes, size_t n, int k, void* temp, size_t temp_bytes, hipStream_t st) {
+    if (follow && follow_bytes == 8)
+        return sort_keys(lo, hi, lo_alt, hi_alt, static_cast<uint64_t*>(follow), static_cast<uint64_t*>(follow_alt), n, k, temp, temp_bytes, st);
+    return sort_keys(lo, hi, lo_alt, hi_alt, static_cast<uint8_t*>(follow), static_cast<uint8_t*>(follow_alt), n, k, temp, temp_bytes, st);
+}
+
+size_t exact_sort_temp_bytes(size_t n, int k) { return exact_sort_keys_temp_bytes(n, k, 0); }
 
 // Sorts (lo[, hi]) using (lo_alt[, hi_alt]) as the other half of the double buffer and adds the
 // number of distinct values (compared on their 2k significant bits) to counters[2].
@@ -208,29 +184,14 @@ hipError_t launch_exact_sort_count(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt,
                                    int k, void* temp, size_t temp_bytes, unsigned long long* counters,
                                    hipStream_t st) {
     if (!n) return hipSuccess;
-    const uint64_t mlo = (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    const uint64_t mhi = (k <= 32) ? 0ull : ((k == 64) ? ~0ull : ((1ull << (2 * k - 64)) - 1ull));
-    hipError_t e;
-    const uint64_t *slo, *shi = nullptr;
-    if (k <= 32) {
-        e = rocprim::radix_sort_keys(temp, temp_bytes, lo, lo_alt, n, 0, (unsigned)(2 * k), st);
-        if (e != hipSuccess) return e;
-        slo = lo_alt;
-    } else {
-        // stable LSD over the 128-bit key: low word first, then the high word's 2k-64 bits
-        e = rocprim::radix_sort_pairs(temp, temp_bytes, lo, lo_alt, hi, hi_alt, n, 0, 64, st);
-        if (e != hipSuccess) return e;
-        e = rocprim::radix_sort_pairs(temp, temp_bytes, hi_alt, hi, lo_alt, lo, n, 0, (unsigned)(2 * k - 64), st);
-        if (e != hipSuccess) return e;
-        slo = lo;
-        shi = hi;
-    }
-    size_t blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (k <= 32)
-        hipLaunchKernelGGL(count_unique_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, slo, shi, n, mlo, mhi, counters);
-    else
-        hipLaunchKernelGGL(count_unique_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, slo, shi, n, mlo, mhi, counters);
+    const hipError_t e = launch_exact_sort_keys(lo, hi, lo_alt, hi_alt, nullptr, nullptr, 0, n, k, temp, temp_bytes, st);
+    if (e != hipSuccess) return e;
+    const KeyMasks km = key_masks(k);
+    const size_t blocks = std::min<size_t>((n + 255) / 256, 4096);
+    dispatch_bool(k > 32, [&](auto wd) {
+        constexpr bool W = decltype(wd)::value;
+        hipLaunchKernelGGL(count_unique_kernel<W>, dim3((unsigned)blocks), dim3(256), 0, st, W ? lo : lo_alt, W ? hi : nullptr, n, km.lo, km.hi, counters);
+    });
     return hipGetLastError();
 }
 

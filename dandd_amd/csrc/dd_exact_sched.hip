@@ -34,12 +34,11 @@
 //                                with one atomicAdd per tile
 //   emit_kernel   (at the end of this file) sched_kernel's sibling for the selected k-mers themselves: no accumulator, the keys
 //                 and masks of the runs that match a query leave for HBM; launch_exact_emit_order then puts them in key order
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include <algorithm>
 
 #include "dd_common.h"
 #include "dd_kernels.h"
+#include "dd_exact_walk.h"
 
 namespace dd {
 namespace {
@@ -135,17 +134,47 @@ DD_D void thread_summary(uint32_t head, const uint64_t (&bit)[kItems], uint32_t&
     }
 }
 
+// The front of a chunk of the sorted array, by a whole workgroup: the calling thread's kItems slots from `first` on, and
+// the segmented OR-scan of the chunk over them.  (ef, ev): what the runs in front of the thread's slots, inside the chunk,
+// have collected; (tf, tv): the chunk's total.  Holds a barrier.
+struct ChunkScan {
+    size_t first;
+    uint32_t head, tail, ef, tf;
+    uint64_t bit[kItems], ev, tv;
+};
+template <bool WIDE>
+DD_D void chunk_scan(const SortedView& s, size_t chunk, ChunkScan& c) {
+    __shared__ uint32_t sf[kThreads / 64];
+    __shared__ uint64_t sv[kThreads / 64];
+    uint32_t f;
+    uint64_t v;
+    c.first = chunk * kChunk + (size_t)threadIdx.x * kItems;
+    load_items<WIDE>(s, c.first, c.head, c.tail, c.bit);
+    thread_summary(c.head, c.bit, f, v);
+    block_seg_scan<kThreads / 64>(f, v, sf, sv, c.ef, c.ev, c.tf, c.tv);
+}
+// ... and the runs of the chunk: f(slot, run, ends) for each of the thread's slots, in order, by whole waves -- `run` the
+// OR of the slot's run so far, the part in the chunks in front (carry) included; `ends`: the slot is the last of its run and
+// the run holds a genome.  The slots the single-pass layout never wrote set no bit: a run of them alone never ends.
+template <bool WIDE, class F>
+DD_D void chunk_runs(const SortedView& s, size_t chunk, const uint64_t* __restrict__ carry, F&& f) {
+    ChunkScan c;
+    chunk_scan<WIDE>(s, chunk, c);
+    uint64_t run = c.ef ? c.ev : (c.ev | carry[chunk]);
+#pragma unroll
+    for (int j = 0; j < kItems; ++j) {
+        if ((c.head >> j) & 1u) run = 0;
+        run |= c.bit[j];
+        f(c.first + j, run, ((c.tail >> j) & 1u) && run != 0);
+    }
+}
+
 template <bool WIDE>
 __global__ __launch_bounds__(kThreads) void sched_summary_kernel(SortedView s, uint32_t* __restrict__ sum_f,
                                                                uint64_t* __restrict__ sum_v) {
-    __shared__ uint32_t sf[kThreads / 64];
-    __shared__ uint64_t sv[kThreads / 64];
-    uint32_t head, tail, f, ef, tf;
-    uint64_t bit[kItems], v, ev, tv;
-    load_items<WIDE>(s, (size_t)blockIdx.x * kChunk + (size_t)threadIdx.x * kItems, head, tail, bit);
-    thread_summary(head, bit, f, v);
-    block_seg_scan<kThreads / 64>(f, v, sf, sv, ef, ev, tf, tv);
-    if (threadIdx.x == 0) sum_f[blockIdx.x] = tf, sum_v[blockIdx.x] = tv;
+    ChunkScan c;
+    chunk_scan<WIDE>(s, blockIdx.x, c);
+    if (threadIdx.x == 0) sum_f[blockIdx.x] = c.tf, sum_v[blockIdx.x] = c.tv;
 }
 
 // one workgroup: carry[c] = the OR the run open at the end of chunk c-1 has collected (chunk c uses it for the slots in
@@ -200,9 +229,12 @@ struct SchedArgs {
 };
 
 // ---- accumulators: init (LDS state), consume (one tile of masks; whole workgroup), flush (once per workgroup) ----
+// and, for the host: lds(n, norder), the dynamic LDS init carves, and words(n, norder, ngroups), the counts behind acc[0]
 struct AccSubsets {
     uint32_t* hist;     // [2^min(n, 15)]: the bins of this workgroup's slice
     int bits;
+    static size_t lds(int n, int) { return (size_t)4 << std::min(n, kExactSubsetsLdsN); }
+    static size_t words(int n, int, int) { return (size_t)1 << n; }
     DD_D void init(const SchedArgs& a, uint64_t* dyn) {
         bits = a.n < kExactSubsetsLdsN ? a.n : kExactSubsetsLdsN;
         hist = reinterpret_cast<uint32_t*>(dyn);
@@ -225,6 +257,8 @@ struct AccLeaveOut {
     uint64_t* gmask;    // [64]
     int32_t* gob;       // [64] group of bit, -1: never left out
     uint32_t* excl;     // [64] k-mers only group g holds
+    static size_t lds(int, int) { return 64 * 8 + 64 * 4 + 64 * 4; }
+    static size_t words(int, int, int ngroups) { return (size_t)ngroups; }
     DD_D void init(const SchedArgs& a, uint64_t* dyn) {
         gmask = dyn;
         gob = reinterpret_cast<int32_t*>(dyn + 64);
@@ -253,6 +287,8 @@ struct AccLeaveOut {
 struct AccProgressive {
     uint64_t* prefix;   // [norder][n]
     uint32_t* hist;     // [norder][n]: k-mers whose first genome in ordering o stands at position j
+    static size_t lds(int n, int norder) { return (size_t)norder * n * 12 + 16; }
+    static size_t words(int n, int norder, int) { return (size_t)norder * n; }
     DD_D void init(const SchedArgs& a, uint64_t* dyn) {
         prefix = dyn;
         hist = reinterpret_cast<uint32_t*>(dyn + (size_t)a.norder * a.n);
@@ -286,6 +322,8 @@ struct AccPairwise {
     uint8_t *pi, *pj;   // pair p = (pi[p], pj[p]), i <= j
     int npairs;
     unsigned long long sum[kPairSlots];
+    static size_t lds(int n, int) { return (size_t)(kChunk / 64) * n * 8 + (size_t)n * (n + 1) + 16; }
+    static size_t words(int n, int, int) { return (size_t)n * (n + 1) / 2; }
     DD_D void init(const SchedArgs& a, uint64_t* dyn) {
         planes = dyn;
         pi = reinterpret_cast<uint8_t*>(dyn + (size_t)(kChunk / 64) * a.n);
@@ -335,6 +373,8 @@ struct AccPairwise {
 struct AccSpectrum {
     uint32_t* bins;     // [65]: k-mers held by exactly j genomes
     uint32_t one, all;  // this thread's masks of 1 and of n bits: the two bins related genomes fill, kept off the LDS atomics
+    static size_t lds(int, int) { return 65 * 4 + 12; }
+    static size_t words(int n, int, int) { return (size_t)n + 1; }
     DD_D void init(const SchedArgs&, uint64_t* dyn) {
         bins = reinterpret_cast<uint32_t*>(dyn);
         if (threadIdx.x <= 64) bins[threadIdx.x] = 0;
@@ -361,6 +401,8 @@ struct AccCoreProgressive {
     uint32_t* hist;     // [norder][n]: k-mers that hold genomes 0..j of ordering o and not genome j+1
     uint32_t* fulls;    // [1]: the workgroup's full masks
     uint32_t full;      // this thread's full masks: position n-1 of every ordering
+    static size_t lds(int n, int norder) { return (size_t)norder * n * 12 + 16; }
+    static size_t words(int n, int norder, int) { return (size_t)norder * n; }
     DD_D void init(const SchedArgs& a, uint64_t* dyn) {
         prefix = dyn;
         hist = reinterpret_cast<uint32_t*>(dyn + (size_t)a.norder * a.n);
@@ -406,6 +448,8 @@ struct AccSelect {
     uint32_t* hits;     // [norder]
     uint32_t width;     // threads that share one stripe of the tile: a power of two >= the queries, kThreads at most
     uint32_t c[kSelectSlots];   // hits of queries (threadIdx.x % width) + r * kThreads among the masks of this thread's stripe
+    static size_t lds(int, int norder) { return (size_t)norder * 20 + 16; }
+    static size_t words(int, int norder, int) { return (size_t)norder; }
     DD_D void init(const SchedArgs& a, uint64_t* dyn) {
         pair = dyn;
         hits = reinterpret_cast<uint32_t*>(dyn + 2 * (size_t)a.norder);
@@ -431,7 +475,7 @@ struct AccSelect {
             const uint64_t m = tile[i];
 #pragma unroll
             for (int r = 0; r < kSelectSlots; ++r)
-                if (r < rounds) c[r] += (m & all[r]) == all[r] && (m & none[r]) == 0;
+                if (r < rounds) c[r] += mask_matches(m, all[r], none[r]);
         }
     }
     DD_D void flush(const SchedArgs& a, uint32_t) {
@@ -449,6 +493,8 @@ struct AccSelect {
 
 struct AccStream {
     unsigned long long* at;   // [1]: where this tile goes, from the thread that reserved it to the others (no state: rewritten per tile)
+    static size_t lds(int, int) { return 16; }
+    static size_t words(int, int, int) { return 0; }
     DD_D void init(const SchedArgs&, uint64_t* dyn) { at = reinterpret_cast<unsigned long long*>(dyn); }
     DD_D void consume(const SchedArgs& a, const uint64_t* tile, uint32_t cnt, uint32_t) {
         if (!cnt) return;   // (cnt is the same in every thread)
@@ -469,36 +515,17 @@ __global__ __launch_bounds__(kThreads) void sched_kernel(SortedView s, const uin
                                                        SchedArgs a) {
     extern __shared__ uint64_t dyn[];
     __shared__ uint64_t tile[kChunk];
-    __shared__ uint32_t sf[kThreads / 64];
-    __shared__ uint64_t sv[kThreads / 64];
     __shared__ uint32_t cnt;
     Acc acc;
     acc.init(a, dyn);
     unsigned long long seen = 0;   // (thread 0: masks of this workgroup)
-    const uint32_t lane = threadIdx.x & 63;
     const uint32_t slice = blockIdx.x % (uint32_t)a.slices;   // (the grid is a multiple of the slices)
     for (size_t chunk = blockIdx.x / (uint32_t)a.slices; chunk < nchunks; chunk += gridDim.x / (uint32_t)a.slices) {
-        if (threadIdx.x == 0) cnt = 0;
-        uint32_t head, tail, f, ef, tf;
-        uint64_t bit[kItems], v, ev, tv;
-        load_items<WIDE>(s, chunk * kChunk + (size_t)threadIdx.x * kItems, head, tail, bit);
-        thread_summary(head, bit, f, v);
-        block_seg_scan<kThreads / 64>(f, v, sf, sv, ef, ev, tf, tv);   // (its barrier also publishes cnt = 0 and the init)
-        uint64_t run = ef ? ev : (ev | carry[chunk]);
-#pragma unroll
-        for (int j = 0; j < kItems; ++j) {
-            if ((head >> j) & 1u) run = 0;
-            run |= bit[j];
-            const bool emit = ((tail >> j) & 1u) && run != 0;
-            const unsigned long long em = __ballot(emit);
-            if (em) {
-                const int leader = __builtin_ctzll(em);
-                uint32_t at = 0;
-                if ((int)lane == leader) at = atomicAdd(&cnt, (uint32_t)__builtin_popcountll(em));
-                at = __shfl(at, leader);
-                if (emit) tile[at + __builtin_popcountll(em & ((1ull << lane) - 1ull))] = run;
-            }
-        }
+        if (threadIdx.x == 0) cnt = 0;   // (the scan's barrier publishes it, and the init)
+        chunk_runs<WIDE>(s, chunk, carry, [&](size_t, uint64_t run, bool ends) {
+            const uint32_t at = wave_append(ends, &cnt);
+            if (ends) tile[at] = run;
+        });
         __syncthreads();
         const uint32_t have = cnt;
         if (threadIdx.x == 0 && slice == 0) seen += have;
@@ -513,22 +540,29 @@ __global__ __launch_bounds__(kThreads) void sched_kernel(SortedView s, const uin
 // orderings one progressive or core-progressive launch takes: prefix masks + histogram within 40 KiB of LDS
 int max_orderings(int n) { return std::max(1, (40 << 10) / (12 * n)); }
 
-size_t sched_dyn_lds(int kind, int n, int norder) {
+// the one place that maps a kSched* to its accumulator: f(AccTag<Acc>)
+template <class Acc>
+struct AccTag {
+    using type = Acc;
+};
+template <class F>
+auto with_acc(int kind, const F& f) {
     switch (kind) {
-        case kSchedPairwise: return (size_t)(kChunk / 64) * n * 8 + (size_t)n * (n + 1) + 16;
-        case kSchedProgressive: return (size_t)norder * n * 12 + 16;
-        case kSchedLeaveOut: return 64 * 8 + 64 * 4 + 64 * 4;
-        case kSchedSpectrum: return 65 * 4 + 12;
-        case kSchedCoreProgressive: return (size_t)norder * n * 12 + 16;
-        case kSchedSelect: return (size_t)norder * 20 + 16;
-        case kSchedStream: return 16;
-        default: return (size_t)4 << std::min(n, kExactSubsetsLdsN);
+        case kSchedPairwise: return f(AccTag<AccPairwise>{});
+        case kSchedProgressive: return f(AccTag<AccProgressive>{});
+        case kSchedLeaveOut: return f(AccTag<AccLeaveOut>{});
+        case kSchedSpectrum: return f(AccTag<AccSpectrum>{});
+        case kSchedCoreProgressive: return f(AccTag<AccCoreProgressive>{});
+        case kSchedSelect: return f(AccTag<AccSelect>{});
+        case kSchedStream: return f(AccTag<AccStream>{});
+        default: return f(AccTag<AccSubsets>{});
     }
 }
 
-// the masks of a k's key words: the low 2k bits of lo, the low 2k - 64 of hi
-uint64_t key_mask_lo(int k) { return (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1ull); }
-uint64_t key_mask_hi(int k) { return (k <= 32) ? 0ull : ((k == 64) ? ~0ull : ((1ull << (2 * k - 64)) - 1ull)); }
+size_t sched_dyn_lds(int kind, int n, int norder) {
+    return with_acc(kind, [&](auto t) { return decltype(t)::type::lds(n, norder); });
+}
+
 size_t exact_sched_chunks(size_t count) { return (count + kChunk - 1) / kChunk; }
 
 // What sched_kernel and emit_kernel both stand on: the scratch carved (open-run ORs | carries | flags, one per chunk), the
@@ -544,68 +578,36 @@ SortedHead sorted_head(const ExactSorted& sorted, size_t count, int k, int n, vo
     uint64_t* sum_v = static_cast<uint64_t*>(scratch);
     uint64_t* carry = sum_v + nchunks;
     uint32_t* sum_f = reinterpret_cast<uint32_t*>(carry + nchunks);
-    const SortedView v{sorted.lo, sorted.hi, sorted.g, key_mask_lo(k), key_mask_hi(k), count, n};
-    if (k > 32) hipLaunchKernelGGL(sched_summary_kernel<true>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
-    else hipLaunchKernelGGL(sched_summary_kernel<false>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
+    const KeyMasks km = key_masks(k);
+    const SortedView v{sorted.lo, sorted.hi, sorted.g, km.lo, km.hi, count, n};
+    dispatch_bool(k > 32, [&](auto w) {
+        hipLaunchKernelGGL(sched_summary_kernel<decltype(w)::value>, dim3((unsigned)nchunks), dim3(kThreads), 0, st, v, sum_f, sum_v);
+    });
     hipLaunchKernelGGL(sched_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, sum_f, sum_v, nchunks, carry);
     return SortedHead{v, carry, nchunks};
 }
 
-size_t order_temp_bytes(size_t found) {   // of launch_exact_emit_order's sort
-    size_t b = 0;
-    uint64_t* nul = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul, nul, found, 0, 64);
-    return b + 256;
-}
+size_t order_temp_bytes(size_t found, int k) { return exact_sort_keys_temp_bytes(found, k, sizeof(uint64_t)); }   // of launch_exact_emit_order's sort
 
 }  // namespace
 
 size_t exact_sched_acc_words(const ExactSched& s) {
-    switch (s.kind) {
-        case kSchedPairwise: return 1 + (size_t)s.n * (s.n + 1) / 2;
-        case kSchedProgressive: return 1 + (size_t)s.norder * s.n;
-        case kSchedLeaveOut: return 1 + (size_t)s.ngroups;
-        case kSchedSpectrum: return 1 + (size_t)s.n + 1;
-        case kSchedCoreProgressive: return 1 + (size_t)s.norder * s.n;
-        case kSchedSelect: return 1 + (size_t)s.norder;
-        case kSchedStream: return 1;
-        default: return 1 + ((size_t)1 << s.n);
-    }
+    return 1 + with_acc(s.kind, [&](auto t) { return decltype(t)::type::words(s.n, s.norder, s.ngroups); });
 }
 
 // per chunk: flag (u32), open-run OR (u64), carry (u64)
 size_t exact_sched_scratch_bytes(size_t count) { return exact_sched_chunks(count) * 24 + 512; }
 
-size_t exact_sched_temp_bytes(size_t n, int k) {
-    size_t a = 0, b = 0, c = 0;
-    uint64_t* nul = nullptr;
-    uint8_t* nul8 = nullptr;
-    (void)rocprim::radix_sort_keys(nullptr, a, nul, nul, n, 0, 64);
-    (void)rocprim::radix_sort_pairs(nullptr, b, nul, nul, nul8, nul8, n, 0, 64);
-    if (k > 32) (void)rocprim::radix_sort_pairs(nullptr, c, nul, nul, nul, nul, n, 0, 64);
-    return std::max(a, std::max(b, c)) + 256;
-}
+size_t exact_sched_temp_bytes(size_t n, int k) { return exact_sort_keys_temp_bytes(n, k, sizeof(uint8_t)); }
 
+// launch_exact_sort_keys with the genome of tag mode 2 following; only k = 61..64 pay for its second run of each pass.
 hipError_t launch_exact_sort_tagged(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, uint8_t* g, uint8_t* g_alt,
                                     size_t n, int k, void* temp, size_t temp_bytes, hipStream_t st, ExactSorted* out) {
     const bool sep = exact_tag_mode(k) == 2;
-    hipError_t e;
-    if (k <= 32) {
-        const unsigned bits = (unsigned)(2 * k);
-        if (sep) e = rocprim::radix_sort_pairs(temp, temp_bytes, lo, lo_alt, g, g_alt, n, 0, bits, st);
-        else e = rocprim::radix_sort_keys(temp, temp_bytes, lo, lo_alt, n, 0, bits, st);
-        *out = ExactSorted{lo_alt, nullptr, sep ? g_alt : nullptr};
-        return e;
-    }
-    // stable LSD over the 128-bit key, as in launch_exact_sort_count.  A tag of its own follows through a second sort by
-    // the same keys (the sort is stable and deterministic: the same permutation); only k = 61..64 pay for that.
-    const unsigned bits = (unsigned)(2 * k - 64);
-    if (sep && (e = rocprim::radix_sort_pairs(temp, temp_bytes, lo, lo_alt, g, g_alt, n, 0, 64, st)) != hipSuccess) return e;
-    if ((e = rocprim::radix_sort_pairs(temp, temp_bytes, lo, lo_alt, hi, hi_alt, n, 0, 64, st)) != hipSuccess) return e;
-    if (sep && (e = rocprim::radix_sort_pairs(temp, temp_bytes, hi_alt, hi, g_alt, g, n, 0, bits, st)) != hipSuccess) return e;
-    if ((e = rocprim::radix_sort_pairs(temp, temp_bytes, hi_alt, hi, lo_alt, lo, n, 0, bits, st)) != hipSuccess) return e;
-    *out = ExactSorted{lo, hi, sep ? g : nullptr};
-    return hipSuccess;
+    const hipError_t e = launch_exact_sort_keys(lo, hi, lo_alt, hi_alt, sep ? g : nullptr, g_alt, sizeof(uint8_t), n, k, temp, temp_bytes, st);
+    if (k <= 32) *out = ExactSorted{lo_alt, nullptr, sep ? g_alt : nullptr};
+    else if (e == hipSuccess) *out = ExactSorted{lo, hi, sep ? g : nullptr};
+    return e;
 }
 
 hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, const ExactSched& s, void* scratch, hipStream_t st) {
@@ -630,18 +632,10 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
         const unsigned grid = (unsigned)(std::min<size_t>(h.nchunks, 256 * per_cu) * a.slices);
         // (every sched_kernel may take the dynamic LDS a CU has left beside the kernel's own: subsets asks for 128 KiB)
         dispatch_bool(wide, [&](auto w) {
-            constexpr bool W = decltype(w)::value;
-            const dim3 g(grid), t(kThreads);
-            switch (s.kind) {
-                case kSchedPairwise: launch_full_lds<sched_kernel<W, AccPairwise>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
-                case kSchedProgressive: launch_full_lds<sched_kernel<W, AccProgressive>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
-                case kSchedLeaveOut: launch_full_lds<sched_kernel<W, AccLeaveOut>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
-                case kSchedSpectrum: launch_full_lds<sched_kernel<W, AccSpectrum>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
-                case kSchedCoreProgressive: launch_full_lds<sched_kernel<W, AccCoreProgressive>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
-                case kSchedSelect: launch_full_lds<sched_kernel<W, AccSelect>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
-                case kSchedStream: launch_full_lds<sched_kernel<W, AccStream>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
-                default: launch_full_lds<sched_kernel<W, AccSubsets>, kStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, a); break;
-            }
+            with_acc(s.kind, [&](auto t) {
+                launch_full_lds<sched_kernel<decltype(w)::value, typename decltype(t)::type>, kStaticLds>(dim3(grid), dim3(kThreads), dyn, st, h.v, h.carry,
+                                                                                                  h.nchunks, a);
+            });
         });
     }
     return hipGetLastError();
@@ -663,8 +657,6 @@ constexpr size_t kEmitStaticLds = 128;   // emit_kernel's own LDS: the scan's wa
 template <bool WIDE>
 __global__ __launch_bounds__(kThreads) void emit_kernel(SortedView s, const uint64_t* __restrict__ carry, size_t nchunks, ExactEmit a) {
     extern __shared__ uint64_t dyn[];
-    __shared__ uint32_t sf[kThreads / 64];
-    __shared__ uint64_t sv[kThreads / 64];
     __shared__ uint32_t cnt;
     __shared__ unsigned long long at;
     uint64_t* pair = dyn;                          // [nq][2]: (all, none)
@@ -672,37 +664,19 @@ __global__ __launch_bounds__(kThreads) void emit_kernel(SortedView s, const uint
     uint64_t* st_lo = st_mask + kChunk;
     uint64_t* st_hi = st_lo + kChunk;              // WIDE only
     for (int i = threadIdx.x; i < 2 * a.nq; i += kThreads) pair[i] = a.table[i];
-    const uint32_t lane = threadIdx.x & 63;
     for (size_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        if (threadIdx.x == 0) cnt = 0;
-        uint32_t head, tail, f, ef, tf;
-        uint64_t bit[kItems], v, ev, tv;
-        const size_t first = chunk * kChunk + (size_t)threadIdx.x * kItems;
-        load_items<WIDE>(s, first, head, tail, bit);
-        thread_summary(head, bit, f, v);
-        block_seg_scan<kThreads / 64>(f, v, sf, sv, ef, ev, tf, tv);   // (its barrier also publishes cnt = 0 and the pairs)
-        uint64_t run = ef ? ev : (ev | carry[chunk]);
-#pragma unroll
-        for (int j = 0; j < kItems; ++j) {
-            if ((head >> j) & 1u) run = 0;
-            run |= bit[j];
+        if (threadIdx.x == 0) cnt = 0;   // (the scan's barrier publishes it, and the pairs)
+        chunk_runs<WIDE>(s, chunk, carry, [&](size_t slot, uint64_t run, bool ends) {
             bool hit = false;
-            if (((tail >> j) & 1u) && run != 0)
-                for (int q = 0; q < a.nq && !hit; ++q) hit = (run & pair[2 * q]) == pair[2 * q] && (run & pair[2 * q + 1]) == 0;
-            const unsigned long long em = __ballot(hit);
-            if (em) {
-                const int leader = __builtin_ctzll(em);
-                uint32_t p = 0;
-                if ((int)lane == leader) p = atomicAdd(&cnt, (uint32_t)__builtin_popcountll(em));
-                p = __shfl(p, leader);
-                if (hit) {   // (a tail's slot is inside the array: load_items sets the bit only behind a valid slot)
-                    p += __builtin_popcountll(em & ((1ull << lane) - 1ull));
-                    st_mask[p] = run;
-                    st_lo[p] = s.lo[first + j] & s.mlo;
-                    if (WIDE) st_hi[p] = s.hi[first + j] & s.mhi;
-                }
+            if (ends)
+                for (int q = 0; q < a.nq && !hit; ++q) hit = mask_matches(run, pair[2 * q], pair[2 * q + 1]);
+            const uint32_t p = wave_append(hit, &cnt);
+            if (hit) {   // (a run ends inside the array: load_items sets the bit only behind a valid slot)
+                st_mask[p] = run;
+                st_lo[p] = s.lo[slot] & s.mlo;
+                if (WIDE) st_hi[p] = s.hi[slot] & s.mhi;
             }
-        }
+        });
         __syncthreads();
         const uint32_t have = cnt;   // (the same in every thread)
         if (have) {
@@ -730,43 +704,29 @@ hipError_t launch_exact_emit(const ExactSorted& sorted, size_t count, int k, con
     const size_t dyn = ((size_t)2 * e.nq + (size_t)(wide ? 3 : 2) * kChunk) * sizeof(uint64_t);
     const size_t per_cu = std::min<size_t>(4, std::max<size_t>(1, ((size_t)160 << 10) / (dyn + kEmitStaticLds)));
     const dim3 g((unsigned)std::min<size_t>(h.nchunks, 256 * per_cu)), t(kThreads);   // persistent workgroups, as launch_exact_sched sizes them
-    if (wide) launch_full_lds<emit_kernel<true>, (int)kEmitStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, e);
-    else launch_full_lds<emit_kernel<false>, (int)kEmitStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, e);
+    dispatch_bool(wide, [&](auto w) { launch_full_lds<emit_kernel<decltype(w)::value>, (int)kEmitStaticLds>(g, t, dyn, st, h.v, h.carry, h.nchunks, e); });
     return hipGetLastError();
 }
 
 // ---- the emitted records in ascending key order ------------------------------------------------------------------------
-// The records radix-sorted by their 2k-bit key, the mask riding as the value; k > 32: the two stable passes of
-// launch_exact_sort_tagged, low word first, and -- a pair sort carries ONE value array -- each pass run once per array that
-// has to follow, the same keys giving the same permutation.  `work`: the other halves of the double buffers (lo, mask[, hi]),
+// launch_exact_sort_keys over the records, the mask following.  `work`: the other halves of the double buffers (lo, mask[, hi]),
 // then the sort's temp.
 size_t exact_emit_order_bytes(size_t found, int k) {
-    return (size_t)(k > 32 ? 3 : 2) * ((found * sizeof(uint64_t) + 255) / 256 * 256) + order_temp_bytes(found);
+    return (size_t)(k > 32 ? 3 : 2) * ((found * sizeof(uint64_t) + 255) / 256 * 256) + order_temp_bytes(found, k);
 }
 
 hipError_t launch_exact_emit_order(uint64_t* lo, uint64_t* hi, uint64_t* mask, size_t found, int k, void* work, hipStream_t st,
                                    LocateSet* out) {
     const size_t stride = (found * sizeof(uint64_t) + 255) / 256 * 256;
-    size_t tb = order_temp_bytes(found);
     char* wb = static_cast<char*>(work);
     uint64_t* lo_alt = reinterpret_cast<uint64_t*>(wb);
     uint64_t* mask_alt = reinterpret_cast<uint64_t*>(wb + stride);
-    hipError_t e;
-    if (k <= 32) {
-        void* temp = wb + 2 * stride;
-        e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, mask, mask_alt, found, 0, (unsigned)(2 * k), st);
-        *out = LocateSet{lo_alt, nullptr, mask_alt, found};
-        return e;
-    }
-    uint64_t* hi_alt = reinterpret_cast<uint64_t*>(wb + 2 * stride);
-    void* temp = wb + 3 * stride;
-    const unsigned bits = (unsigned)(2 * k - 64);
-    if ((e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, mask, mask_alt, found, 0, 64, st)) != hipSuccess) return e;
-    if ((e = rocprim::radix_sort_pairs(temp, tb, lo, lo_alt, hi, hi_alt, found, 0, 64, st)) != hipSuccess) return e;
-    if ((e = rocprim::radix_sort_pairs(temp, tb, hi_alt, hi, mask_alt, mask, found, 0, bits, st)) != hipSuccess) return e;
-    if ((e = rocprim::radix_sort_pairs(temp, tb, hi_alt, hi, lo_alt, lo, found, 0, bits, st)) != hipSuccess) return e;
-    *out = LocateSet{lo, hi, mask, found};
-    return hipSuccess;
+    uint64_t* hi_alt = reinterpret_cast<uint64_t*>(wb + 2 * stride);   // k > 32 only: the temp stands there otherwise
+    void* temp = wb + (k > 32 ? 3 : 2) * stride;
+    const hipError_t e = launch_exact_sort_keys(lo, hi, lo_alt, hi_alt, mask, mask_alt, sizeof(uint64_t), found, k, temp, order_temp_bytes(found, k), st);
+    if (k <= 32) *out = LocateSet{lo_alt, nullptr, mask_alt, found};
+    else if (e == hipSuccess) *out = LocateSet{lo, hi, mask, found};
+    return e;
 }
 
 }  // namespace dd

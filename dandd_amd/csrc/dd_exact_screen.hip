@@ -5,12 +5,11 @@
 // but the counts leaves the device:
 //
 //   screen   screen_kernel: one thread per 64-token segment of a sample's token stream, one launch unit (gridDim.y) per
-//            sample.  The token walk and the lower_bound on (hi, lo) are locate_kernel's (dd_exact_locate.hip: the segment
-//            in front warms the windows up, run >= k, canonical per the context, keys under mlo / mhi).  An exact hit at
-//            record r sets bit r of the sample's SEEN bitmap (`found` bits in 32-bit words, zeroed by the caller): the word
-//            is read with a plain load first and a no-return atomicOr is issued only while the bit is still clear -- a read
-//            set at 30x coverage sets each bit once and then only reads; a stale read costs one redundant atomic, never a
-//            wrong bit.  A miss is the normal case (a read set of another species).
+//            sample.  The token walk and the lookup in the ordered records are locate_kernel's (walk_segment and find_record
+//            of dd_exact_walk.h).  An exact hit at record r sets bit r of the sample's SEEN bitmap (`found` bits in 32-bit
+//            words, zeroed by the caller): the word is read with a plain load first and a no-return atomicOr is issued only
+//            while the bit is still clear -- a read set at 30x coverage sets each bit once and then only reads; a stale read
+//            costs one redundant atomic, never a wrong bit.  A miss is the normal case (a read set of another species).
 //   tally    tally_kernel: the grid runs over (row, range of the records).  Row s < ns takes the records whose bit in
 //            sample s's bitmap is set, row ns has no bitmap and takes every record: |G_i| and the size of every query class
 //            come out of the same code.  A wave takes 64 consecutive records at a time, lane l the record 64 g + l (the
@@ -32,6 +31,7 @@
 #include <algorithm>
 #include "dd_common.h"
 #include "dd_kernels.h"
+#include "dd_exact_walk.h"
 
 namespace dd {
 namespace {
@@ -42,71 +42,14 @@ __global__ __launch_bounds__(256) void screen_kernel(const ExactGenome* __restri
     const ExactGenome* u = samples + blockIdx.y;
     const unsigned long long ntok = *u->ntok;
     const unsigned long long seg = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (seg * kSegTokens >= ntok) return;
     uint32_t* mine = seen + (unsigned long long)blockIdx.y * words;
-    const uint4* codes4 = reinterpret_cast<const uint4*>(u->codes);
-    const uint2* bad2 = reinterpret_cast<const uint2*>(u->bad);
-    uint64_t fh = 0, fl = 0, rh = 0, rl = 0;
-    int run = 0;
-    const uint64_t mlo = (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    const uint64_t mhi = (k <= 32) ? 0ull : ((k == 64) ? ~0ull : ((1ull << (2 * k - 64)) - 1ull));
-    const int s = 128 - 2 * k;  // right shift that aligns the reverse-complement window
-    for (int part = (seg > 0 ? 0 : 1); part < 2; ++part) {
-        const unsigned long long sidx = seg - 1 + part;
-        const uint4 c4 = codes4[sidx];
-        const uint2 b2 = bad2[sidx];
-        const uint32_t cw[4] = {c4.x, c4.y, c4.z, c4.w};
-        const uint64_t bw = ((uint64_t)b2.y << 32) | b2.x;
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-#pragma unroll 1
-        for (int i = 0; i < 16; ++i) {
-            const int t = w * 16 + i;
-            const uint32_t c = (cw[w] >> (2 * i)) & 3u;
-            run = ((bw >> t) & 1ull) ? 0 : run + 1;
-            fh = (fh << 2) | (fl >> 62);
-            fl = (fl << 2) | c;
-            rl = (rl >> 2) | (rh << 62);
-            rh = (rh >> 2) | ((uint64_t)(3u - c) << 62);
-            if (part == 0 || run < k) continue;
-            uint64_t ah = fh & mhi, al = fl & mlo;
-            if (CANON) {
-                uint64_t bh, bl;
-                if (s >= 64) {
-                    bh = 0;
-                    bl = rh >> (s - 64);
-                } else if (s == 0) {
-                    bh = rh;
-                    bl = rl;
-                } else {
-                    bh = rh >> s;
-                    bl = (rl >> s) | (rh << (64 - s));
-                }
-                if (bh < ah || (bh == ah && bl < al)) {
-                    ah = bh;
-                    al = bl;
-                }
-            }
-            // lower_bound on (hi, lo) over the ordered records
-            unsigned long long first = 0, len = set.found;
-            while (len) {
-                const unsigned long long half = len >> 1, mid = first + half;
-                const uint64_t l = set.lo[mid];
-                bool less = l < al;
-                if (WIDE) {
-                    const uint64_t h = set.hi[mid];
-                    less = h < ah || (h == ah && less);
-                }
-                if (less) first = mid + 1, len -= half + 1;
-                else len = half;
-            }
-            if (first >= set.found || set.lo[first] != al) continue;
-            if (WIDE && set.hi[first] != ah) continue;
-            uint32_t* word = mine + (first >> 5);   // (first < found: inside the row's ceil(found / 32) words)
-            const uint32_t bit = 1u << (first & 31);
-            if (!(*word & bit)) atomicOr(word, bit);
-        }
-    }
+    walk_segment<CANON, false>(u->codes, u->bad, ntok, seg, k, [&](unsigned long long, int, uint64_t ah, uint64_t al, bool) {
+        unsigned long long r;
+        if (!find_record<WIDE>(set, ah, al, r)) return;
+        uint32_t* word = mine + (r >> 5);   // (r < found: inside the row's ceil(found / 32) words)
+        const uint32_t bit = 1u << (r & 31);
+        if (!(*word & bit)) atomicOr(word, bit);
+    });
 }
 
 constexpr int kTallyThreads = 256, kTallyQSlots = kScreenMaxQueries / 64;
@@ -145,7 +88,7 @@ __global__ __launch_bounds__(kTallyThreads) void tally_kernel(const uint64_t* __
             const int top = nq - slot * 64 < 64 ? nq - slot * 64 : 64;
             for (int l = 0; l < top; ++l) {
                 const uint64_t al = pair[2 * (slot * 64 + l)], no = pair[2 * (slot * 64 + l) + 1];
-                const unsigned long long col = __ballot(has && (m & al) == al && (m & no) == 0);
+                const unsigned long long col = __ballot(has && mask_matches(m, al, no));
                 if (lane == l) qsum[slot] += (unsigned long long)__builtin_popcountll(col);
             }
         }

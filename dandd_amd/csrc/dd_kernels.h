@@ -263,6 +263,13 @@ void launch_kmer_extract(const ExactGenome* tab_dev, int ng, size_t max_segments
                          uint64_t* lo, uint64_t* hi, unsigned long long* counters, hipStream_t st, int mode = 0,
                          unsigned long long* hist = nullptr, uint32_t bin_lo = 0, uint32_t bin_hi = 0, int tag = 0,
                          uint8_t* g = nullptr);
+// The one ordered sort of the exact path (dd_exact.hip): n keys radix-sorted by their 2k significant bits -- lo alone for
+// k <= 32, (hi, lo) by two stable passes for k > 32 -- with `follow`, an array of follow_bytes (1 or 8) per key, taking the
+// same permutation (null: keys only).  Every array has its other half of a double buffer; the result is in the _alt halves
+// for k <= 32 (hi is not touched) and back in lo / hi / follow for k > 32.
+size_t exact_sort_keys_temp_bytes(size_t n, int k, size_t follow_bytes);
+hipError_t launch_exact_sort_keys(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, void* follow, void* follow_alt,
+                                  size_t follow_bytes, size_t n, int k, void* temp, size_t temp_bytes, hipStream_t st);
 size_t exact_sort_temp_bytes(size_t n, int k);
 // counters[2] += number of distinct values among the n slots (unwritten slots hold all-ones)
 hipError_t launch_exact_sort_count(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, size_t n,

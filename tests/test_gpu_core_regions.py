@@ -84,6 +84,47 @@ def test_every_position_is_where_the_index_says(engine_factory, fixture_paths, k
         assert not bits[nt:].any()                                         # bits at or beyond ntok are 0
 
 
+@pytest.mark.parametrize("canonical", [True, False])
+@pytest.mark.parametrize("k", [63, 64])
+def test_window_warm_up_at_segment_borders(engine_factory, tmp_path, canonical, k):
+    """The tightest warm-up of the token walk, in all three kernels that walk (extract, locate, screen): a k-mer that ends on
+    the first token of a thread's 64-token segment and needs every other token of the segment in front.  Three records of 197
+    bases (tokens 1..197 behind the BREAK at token 0) with one N at token 63, 64 and 65."""
+    rng = np.random.default_rng(6364)
+    fas = []
+    for n_at in (63, 64, 65):
+        seq = bytearray(b"ACGT"[c] for c in rng.integers(0, 4, 197))
+        seq[n_at - 1] = ord("N")                                           # base j is token j + 1
+        fas.append(b">r\n" + bytes(seq) + b"\n")
+    paths = greedy.write(tmp_path, fas)
+    eng = engine_factory(canonical=canonical)
+    want = []
+    for fa in fas:
+        (seq,) = pyref.records(fa)
+        run, ends = 0, []
+        for j, c in enumerate(seq):
+            run = run + 1 if c in pyref.CODE else 0
+            if run >= k:
+                ends.append(1 + j)
+        want.append(ends)
+    # N at token 64: k = 64 leaves one k-mer behind it that ends at token 128, tokens 65..128; k = 63 one in front, at token 63
+    assert 128 in want[1] and min(want[1][1:] if k == 63 else want[1]) == 64 + k and (63 in want[1]) == (k == 63)
+    got = eng.exact_locate(paths, k, [(0, 0, g) for g in range(3)])
+    for g in range(3):
+        bits = np.unpackbits(got[g].view(np.uint8), bitorder="little")
+        assert len(got[g]) == 4 and np.flatnonzero(bits).tolist() == want[g], (k, canonical, g)
+    keys = [set(pyref.kmers(fa, k, canonical)) for fa in fas]
+    assert all(len(ks) > 0 for ks in keys)
+    for g in range(3):
+        assert eng.exact_count([paths[g]], k) == len(keys[g]), (k, canonical, g)
+    assert eng.exact_count(paths, k) == len(keys[0] | keys[1] | keys[2])
+    shared, match = eng.exact_screen(paths, paths, k, [0], [0])
+    for s in range(3):
+        assert [int(x) for x in shared[s]] == [len(keys[s] & keys[i]) for i in range(3)], (k, canonical, s)
+        assert int(match[s, 0]) == len(keys[s])
+    assert [int(x) for x in shared[3]] == [len(ks) for ks in keys]
+
+
 # ---- G3. ties to the counting and the emitting paths -----------------------------------------------------------------------------
 @pytest.mark.parametrize("k", [21, 33])
 def test_ties_to_select_and_select_kmers(engine_factory, fixture_paths, k):
