@@ -255,16 +255,49 @@ DD_D void sweep_update2(RaiseQueue& s, uint32_t slot0, uint64_t h0, unsigned lon
 
 // Reverse the order of the 16 2-bit fields of a code word: the token stream stores token j at bits
 // [2j, 2j+1] (oldest lowest), the forward window wants the newest token lowest.
-DD_D uint32_t pairrev32(uint32_t x) {
+DD_HD uint32_t pairrev32(uint32_t x) {
     x = __builtin_bitreverse32(x);  // v_bfrev_b32: fields reversed, but so are the two bits inside each
     return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
 }
-DD_D uint64_t pack64(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | lo; }
+DD_HD uint64_t pack64(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | lo; }
+// bits [s, s + 32) of hi:lo.  The count is taken modulo 32, as v_alignbit_b32 takes it: 32 gives lo, not hi.
+DD_HD uint32_t funnel32(uint32_t hi, uint32_t lo, uint32_t s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(hi, lo, s);
+#else
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (s & 31));
+#endif
+}
 
-// ---- rolling windows, one set per thread, shared by every k of the group ------------------------
-// prime(hc): the state after pushing the 64 tokens of the previous segment (hc = its four code
-// words), computed with a handful of bit operations instead of 64 pushes.  The reverse-complement
-// window holds tokens in stream order, newest on top, so it is simply the complement of the words.
+// ---- a segment's token words, prepared once for the slices of its 64 tokens -----------------------------------------------
+// Words 0..3 are the halo (the previous segment), 4..7 the segment.  A window is a slice of the token stream: behind token i
+// of segment word w
+//   the forward window's low word (newest token lowest) is  r[3+w]:r[4+w] >> (30 - 2 i),  r = the pair-reversed words;
+//   the reverse-complement window's top word (stream order, newest on top) is  ~t[4+w]:~t[3+w] >> 2 (i + 1).
+// The second count runs 2..32, and a funnel shift by 32 gives the older word: so d holds the complemented stream moved down
+// by ONE token, d[n] = ~t[n+1]:~t[n] >> 2, and the slice is  d[4+w]:d[3+w] >> 2 i,  0..30 like the forward one.  (The two top
+// bits of d[7] belong to the next segment: no slice reaches them.)  Every further word of a window is the same slice one
+// word down.  A class that looks n words back uses the last n halo words only: the others are never computed.
+struct SegWords {
+    uint32_t r[8], d[8];
+    DD_HD void fill(const uint4& hc, const uint4& sc) {
+        const uint32_t t[8] = {hc.x, hc.y, hc.z, hc.w, sc.x, sc.y, sc.z, sc.w};
+#pragma unroll
+        for (int n = 0; n < 8; ++n) r[n] = pairrev32(t[n]);
+#pragma unroll
+        for (int n = 0; n < 7; ++n) d[n] = funnel32(~t[n + 1], ~t[n], 2);
+        d[7] = ~t[7] >> 2;
+    }
+    // word j (0 = lowest) of the forward window, word j from the top of the reverse-complement window
+    DD_HD uint32_t fwd(int w, int i, int j) const { return funnel32(r[3 + w - j], r[4 + w - j], 30u - 2u * (uint32_t)i); }
+    DD_HD uint32_t rev(int w, int i, int j) const { return funnel32(d[4 + w - j], d[3 + w - j], 2u * (uint32_t)i); }
+};
+
+// ---- k-mer windows, one set per thread, shared by every k of the group --------------------------
+// slice(sw, w, i): the windows behind token i of segment word w -- what 16 w + i + 1 pushes of (fw << 2) | c and
+// (rc >> 2) | (3 - c) << top on the halo would leave -- cut from the prepared words, one funnel shift per 32-bit word
+// (the count is wave-uniform: the walk's token loop is not unrolled).  tests/native/k1_windows.hip checks every form
+// against those pushes on the host.
 //   KC 0: k <= 16 (32-bit windows)   KC 1: 16 <= k <= 32 (64-bit)   KC 3: 33 <= k <= 48 (96-bit: 64 + 32)
 //   KC 2: 49 <= k <= 64 (128-bit: Windows<7>, four 32-bit words)
 template <int KC>
@@ -273,13 +306,9 @@ struct Windows;
 template <>
 struct Windows<0> {
     uint32_t fw = 0, rc = 0;
-    DD_D void prime(const uint4& hc) {
-        fw = pairrev32(hc.w);
-        rc = ~hc.w;
-    }
-    DD_D void push(uint32_t c) {
-        fw = (fw << 2) | c;
-        rc = (rc >> 2) | ((3u - c) << 30);
+    DD_HD void slice(const SegWords& sw, int w, int i) {
+        fw = sw.fwd(w, i, 0);
+        rc = sw.rev(w, i, 0);
     }
     template <bool CANON>
     DD_D uint64_t hash(int k) const {
@@ -293,13 +322,9 @@ struct Windows<0> {
 template <>
 struct Windows<1> {
     uint64_t fw = 0, rc = 0;
-    DD_D void prime(const uint4& hc) {
-        fw = pack64(pairrev32(hc.z), pairrev32(hc.w));
-        rc = ~pack64(hc.w, hc.z);
-    }
-    DD_D void push(uint32_t c) {
-        fw = (fw << 2) | c;
-        rc = (rc >> 2) | ((uint64_t)(3u - c) << 62);
+    DD_HD void slice(const SegWords& sw, int w, int i) {
+        fw = pack64(sw.fwd(w, i, 1), sw.fwd(w, i, 0));
+        rc = pack64(sw.rev(w, i, 0), sw.rev(w, i, 1));
     }
     template <bool CANON>
     DD_D uint64_t hash(int k) const {
@@ -312,24 +337,17 @@ struct Windows<1> {
     }
 };
 
-// The 64-bit class again, as 32-bit halves: a push is two funnel shifts and two shift-or instructions, and the
-// compiler has no 64-bit value to keep a copy of (with u64 members it spent three more instructions per push).
-// Used by the scatter kernels, where the push is paid per (token, k); sweep_kernel shares one push between the
-// ks of a group and keeps Windows<1> (measured equal there).
+// The 64-bit class again, as 32-bit halves: each is one slice, and the compiler has no 64-bit value to put together and
+// take apart again.  Used by the scatter kernels, where the windows are cut per (token, k); sweep_kernel shares them between
+// the ks of a group and keeps Windows<1> (measured equal there).
 template <>
 struct Windows<5> {
     uint32_t fl = 0, fh = 0, rl = 0, rh = 0;
-    DD_D void prime(const uint4& hc) {
-        fh = pairrev32(hc.z);
-        fl = pairrev32(hc.w);
-        rh = ~hc.w;
-        rl = ~hc.z;
-    }
-    DD_D void push(uint32_t c) {
-        fh = __builtin_amdgcn_alignbit(fh, fl, 30);  // (fw << 2) high word
-        fl = (fl << 2) | c;
-        rl = __builtin_amdgcn_alignbit(rh, rl, 2);   // (rc >> 2) low word
-        rh = (rh >> 2) | ((3u - c) << 30);
+    DD_HD void slice(const SegWords& sw, int w, int i) {
+        fl = sw.fwd(w, i, 0);
+        fh = sw.fwd(w, i, 1);
+        rh = sw.rev(w, i, 0);
+        rl = sw.rev(w, i, 1);
     }
     template <bool CANON>
     DD_D uint64_t hash(int k) const {
@@ -360,17 +378,11 @@ template <>
 struct Windows<3> {
     uint64_t fl = 0, rt = 0;  // forward: low 64 bits;  reverse complement, top-aligned: bits 95..32
     uint32_t fh = 0, rb = 0;  // forward: bits 95..64;  reverse complement: bits 31..0
-    DD_D void prime(const uint4& hc) {
-        fl = pack64(pairrev32(hc.z), pairrev32(hc.w));
-        fh = pairrev32(hc.y);
-        rt = ~pack64(hc.w, hc.z);
-        rb = ~hc.y;
-    }
-    DD_D void push(uint32_t c) {
-        fh = __builtin_amdgcn_alignbit(fh, (uint32_t)(fl >> 32), 30);  // (fh << 2) | (fl >> 62)
-        fl = (fl << 2) | c;
-        rb = __builtin_amdgcn_alignbit((uint32_t)rt, rb, 2);           // (rb >> 2) | (rt << 30)
-        rt = (rt >> 2) | ((uint64_t)(3u - c) << 62);
+    DD_HD void slice(const SegWords& sw, int w, int i) {
+        fl = pack64(sw.fwd(w, i, 1), sw.fwd(w, i, 0));
+        fh = sw.fwd(w, i, 2);
+        rt = pack64(sw.rev(w, i, 0), sw.rev(w, i, 1));
+        rb = sw.rev(w, i, 2);
     }
     template <bool CANON>
     DD_D uint64_t hash(int k) const {
@@ -388,21 +400,13 @@ template <>
 struct Windows<6> {
     uint32_t f0 = 0, f1 = 0, f2 = 0;  // forward window, low .. high word
     uint32_t r0 = 0, r1 = 0, r2 = 0;  // reverse complement, top-aligned in 96 bits: r2 holds bits 95..64
-    DD_D void prime(const uint4& hc) {
-        f0 = pairrev32(hc.w);
-        f1 = pairrev32(hc.z);
-        f2 = pairrev32(hc.y);
-        r2 = ~hc.w;
-        r1 = ~hc.z;
-        r0 = ~hc.y;
-    }
-    DD_D void push(uint32_t c) {
-        f2 = __builtin_amdgcn_alignbit(f2, f1, 30);
-        f1 = __builtin_amdgcn_alignbit(f1, f0, 30);
-        f0 = (f0 << 2) | c;
-        r0 = __builtin_amdgcn_alignbit(r1, r0, 2);
-        r1 = __builtin_amdgcn_alignbit(r2, r1, 2);
-        r2 = (r2 >> 2) | ((3u - c) << 30);
+    DD_HD void slice(const SegWords& sw, int w, int i) {
+        f0 = sw.fwd(w, i, 0);
+        f1 = sw.fwd(w, i, 1);
+        f2 = sw.fwd(w, i, 2);
+        r2 = sw.rev(w, i, 0);
+        r1 = sw.rev(w, i, 1);
+        r0 = sw.rev(w, i, 2);
     }
     template <bool CANON>
     DD_D uint64_t hash(int k) const {
@@ -415,32 +419,20 @@ struct Windows<6> {
     }
 };
 
-// The 128-bit class as four 32-bit words per window (see Windows<5>): used by the scatter kernels, whose push is paid per
-// (token, k) -- with u64 members the compiler spent 16 instructions on a push (two 64-bit copies, shift / or pairs,
-// and the funnel shifts that take the words apart again at the hash), this form 12.
+// The 128-bit class as four 32-bit words per window (see Windows<5>): the one form of the class, for every kernel.
 template <>
 struct Windows<7> {
     uint32_t f0 = 0, f1 = 0, f2 = 0, f3 = 0;  // forward window, low .. high word
     uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;  // reverse complement, top-aligned in 128 bits
-    DD_D void prime(const uint4& hc) {
-        f0 = pairrev32(hc.w);
-        f1 = pairrev32(hc.z);
-        f2 = pairrev32(hc.y);
-        f3 = pairrev32(hc.x);
-        r3 = ~hc.w;
-        r2 = ~hc.z;
-        r1 = ~hc.y;
-        r0 = ~hc.x;
-    }
-    DD_D void push(uint32_t c) {
-        f3 = __builtin_amdgcn_alignbit(f3, f2, 30);
-        f2 = __builtin_amdgcn_alignbit(f2, f1, 30);
-        f1 = __builtin_amdgcn_alignbit(f1, f0, 30);
-        f0 = (f0 << 2) | c;
-        r0 = __builtin_amdgcn_alignbit(r1, r0, 2);
-        r1 = __builtin_amdgcn_alignbit(r2, r1, 2);
-        r2 = __builtin_amdgcn_alignbit(r3, r2, 2);
-        r3 = (r3 >> 2) | ((3u - c) << 30);
+    DD_HD void slice(const SegWords& sw, int w, int i) {
+        f0 = sw.fwd(w, i, 0);
+        f1 = sw.fwd(w, i, 1);
+        f2 = sw.fwd(w, i, 2);
+        f3 = sw.fwd(w, i, 3);
+        r3 = sw.rev(w, i, 0);
+        r2 = sw.rev(w, i, 1);
+        r1 = sw.rev(w, i, 2);
+        r0 = sw.rev(w, i, 3);
     }
     template <bool CANON>
     DD_D uint64_t hash(int k) const {  // 49 <= k <= 64
@@ -475,7 +467,7 @@ template <typename T>
 DD_D T* uniform_ptr(T* q) { return reinterpret_cast<T*>(uniform64(reinterpret_cast<uint64_t>(q))); }
 
 // ---- a tile's input and the walk over a segment (the hashed kernels) ---------------------------------------------------
-// A thread's input for one tile: its segment (sc, sb) and the previous one (hc, hb: the halo that primes the windows;
+// A thread's input for one tile: its segment (sc, sb) and the previous one (hc, hb: the halo the first windows reach into;
 // segment 0 starts behind a BREAK).  A kernel issues the loads of tile t+1 before it processes tile t.  (fetch_tile fills
 // the caller's TileIn: returning one by value changed the code around the loads, profiles/k1_shared_walk.txt.)
 struct TileIn {
@@ -499,24 +491,24 @@ DD_D void fetch_tile(const SweepGenome& g, const SweepJob& job, unsigned long lo
     t.sb = gload8(g.bad + seg * 2);
 }
 
-// The 64 tokens of a segment through the caller's windows `win` (primed here from the halo), reached by whole waves:
-// token(clean, run) is called behind every push.  clean is std::true_type on the path where no lane of the wave has a
-// BREAK within its halo or its segment (the common case away from record boundaries and N runs: every window of every
-// k <= 64 is valid; run is not kept there and passed as 0), else std::false_type with run = the clean tokens that end at
-// the current one.  (win is the caller's, and the token is taken from its word before run is updated: in both the compiler's
-// schedule of the token loops follows the order of the source, profiles/k1_shared_walk.txt.)
+// The 64 tokens of a segment through the caller's windows `win` (cut here from the words of halo and segment, prepared once),
+// reached by whole waves -- a segment outside the stream, or segment 0's halo, is zero codes behind BREAKs: its windows are cut
+// like any other and never hashed into a register.  token(clean, run) is called behind every slice.  clean is std::true_type
+// on the path where no lane of the wave has a BREAK within its halo or its segment (the common case away from record
+// boundaries and N runs: every window of every k <= 64 is valid; run is not kept there and passed as 0), else std::false_type
+// with run = the clean tokens that end at the current one.  (win is the caller's: the compiler's schedule of the token loops
+// follows where it is declared, profiles/k1_shared_walk.txt.)
 template <typename Win, typename Token>
 DD_D void walk_segment(const TileIn& in, Win& win, const Token& token) {
-    const uint4 hc = in.hc, sc = in.sc;
     const uint2 hb = in.hb, sb = in.sb;
-    const uint32_t cw[4] = {sc.x, sc.y, sc.z, sc.w};
-    win.prime(hc);
+    SegWords sw;
+    sw.fill(in.hc, in.sc);
     if (__all((hb.x | hb.y | sb.x | sb.y) == 0u)) {
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
 #pragma unroll 1
             for (int i = 0; i < 16; ++i) {
-                win.push((cw[w] >> (2 * i)) & 3u);
+                win.slice(sw, w, i);
                 token(std::true_type{}, 0);
             }
         }
@@ -529,9 +521,8 @@ DD_D void walk_segment(const TileIn& in, Win& win, const Token& token) {
         const uint32_t bw = ((w & 2) ? sb.y : sb.x) >> ((w & 1) * 16);
 #pragma unroll 1
         for (int i = 0; i < 16; ++i) {
-            const uint32_t c = (cw[w] >> (2 * i)) & 3u;
             run = ((bw >> i) & 1u) ? 0 : run + 1;
-            win.push(c);
+            win.slice(sw, w, i);
             token(std::false_type{}, run);
         }
     }

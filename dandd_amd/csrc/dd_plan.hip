@@ -213,8 +213,8 @@ std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbyte
             sc.plan.nb_log2 = nb_log2;
             sc.plan.nepochs = (int)nepochs;
         } else {
-            // The 32-bit class needs few enough VGPRs for 12 waves per SIMD, and measures ~7 % faster with
-            // three 48 KiB workgroups per CU than with two of 80 KiB; the wider classes do not.
+            // The 32-bit class measures ~7 % faster with 48 KiB groups than with 80 KiB ones; the wider classes do not.
+            // (Two 1024-thread workgroups per CU either way: a CU holds 32 waves, 8 per SIMD.)
             int slots_c = slots;
             if (kc == 0) slots_c = (int)std::max<size_t>(1, std::min<size_t>(slots, (48 * 1024) / m));
             const int ngroups = kc == kBitmapClass ? 1 : (nks + slots_c - 1) / slots_c;

@@ -56,12 +56,12 @@ __global__ __launch_bounds__(1024) void trace_kernel(const uint4* __restrict__ c
         for (int t = 0; t + 1 < tiles_per_job; t += 2) {
             const uint4 sa = codes[((size_t)blockIdx.x * tiles_per_job + t) * 1024 + threadIdx.x];
             const uint4 sb = codes[((size_t)blockIdx.x * tiles_per_job + t + 1) * 1024 + threadIdx.x];
-            const uint32_t ca[4] = {sa.x, sa.y, sa.z, sa.w}, cb[4] = {sb.x, sb.y, sb.z, sb.w};
             uint8_t* const chunk_a = reinterpret_cast<uint8_t*>(job_area + (size_t)t * kBinChunkRecords);
             uint8_t* const chunk_b = chunk_a + (size_t)kBinChunkRecords * 4u;
             Windows<5> wa, wb;
-            wa.prime(make_uint4(sa.w, sa.z, sa.y, sa.x));
-            wb.prime(make_uint4(sb.w, sb.z, sb.y, sb.x));
+            SegWords swa, swb;   // (the tile's own words stand in for the halo: timing only)
+            swa.fill(sa, sa);
+            swb.fill(sb, sb);
             auto update = [&](const Probe& q, uint32_t ctr, uint8_t* chunk) {
                 const uint32_t rho = rho_of(q, p);
                 if (rho == 1u) {
@@ -77,8 +77,8 @@ __global__ __launch_bounds__(1024) void trace_kernel(const uint4* __restrict__ c
             for (int w = 0; w < 4; ++w) {
 #pragma unroll 1
                 for (int i = 0; i < 16; ++i) {
-                    wa.push((ca[w] >> (2 * i)) & 3u);
-                    wb.push((cb[w] >> (2 * i)) & 3u);
+                    wa.slice(swa, w, i);
+                    wb.slice(swb, w, i);
                     const Probe qa = probe(wa.template hash<true>(k), p), qb = probe(wb.template hash<true>(k), p);
                     update(qa, 0u, chunk_a);
                     update(qb, 64u, chunk_b);
@@ -95,19 +95,19 @@ __global__ __launch_bounds__(1024) void trace_kernel(const uint4* __restrict__ c
     for (int t = 0; t < tiles_per_job; ++t) {
         const uint4 sc = next;
         if (t + 1 < tiles_per_job) next = codes[((size_t)blockIdx.x * tiles_per_job + t + 1) * 1024 + threadIdx.x];
-        const uint32_t cw[4] = {sc.x, sc.y, sc.z, sc.w};
         const uint32_t ctr = (V == 6) ? 0u : ((uint32_t)t & 1u) * (4u << kBinsLog2);
         uint8_t* const chunk = reinterpret_cast<uint8_t*>(V == 6 ? job_area : job_area + (size_t)t * kBinChunkRecords);
         const uint32_t cap = V == 6 ? (uint32_t)tiles_per_job * kBinCap : (kBinCap >> (kBinsLog2 - 4));
         Windows<5> win;
-        win.prime(make_uint4(sc.w, sc.z, sc.y, sc.x));
+        SegWords sw;   // (the tile's own words stand in for the halo: timing only)
+        sw.fill(sc, sc);
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
 #pragma unroll 1
             for (int i = 0; i < 16; ++i) {
                 unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
                 if (V == 5) t0 = __builtin_readcyclecounter();
-                win.push((cw[w] >> (2 * i)) & 3u);
+                win.slice(sw, w, i);
                 const Probe q = probe(win.template hash<true>(k), p);
                 if (V == 0) {
                     acc ^= q.hi ^ q.lz;
@@ -198,10 +198,10 @@ __global__ __launch_bounds__(1024) void multik_kernel(const uint4* __restrict__ 
     for (int t = 0; t < tiles_per_job; ++t) {
         const uint4 sc = next;
         if (t + 1 < tiles_per_job) next = codes[((size_t)blockIdx.x * tiles_per_job + t + 1) * 1024 + threadIdx.x];
-        const uint32_t cw[4] = {sc.x, sc.y, sc.z, sc.w};
         const uint32_t par = ((uint32_t)t & 1u) * (NK * 64u);
         Windows<5> win;
-        win.prime(make_uint4(sc.w, sc.z, sc.y, sc.x));
+        SegWords sw;   // (the tile's own words stand in for the halo: timing only)
+        sw.fill(sc, sc);
         auto emit = [&](const Probe& q, int j) {
             const uint32_t rho = rho_of(q, p);
             if (ONES_LOG2 && rho == 1u && (q.hi >> (32 - p)) < ones_regs) {
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(1024) void multik_kernel(const uint4* __restrict__ 
         for (int w = 0; w < 4; ++w) {
 #pragma unroll 1
             for (int i = 0; i < 16; ++i) {
-                win.push((cw[w] >> (2 * i)) & 3u);
+                win.slice(sw, w, i);
                 if (PAIR) {
 #pragma unroll
                     for (int j = 0; j < NK; j += 2) {

@@ -23,15 +23,24 @@ __global__ __launch_bounds__(1024) void k1_model(uint32_t* out, int nk, int kfir
     uint32_t s = seed ^ ((blockIdx.x * blockDim.x + threadIdx.x) * 2654435761u);
     uint64_t acc = 0;
     auto lds_slot = [](int j) { return RegsLds{(uint32_t)j}; };
+    RaiseQueue rq{0u, 0u, 0u};  // no queue: a raise is applied at once
     for (int it = 0; it < iters; ++it) {
-        s = s * 1664525u + 1013904223u;
-        const uint32_t cw = s ^ (s >> 15);
+        // eight pseudo-random code words: halo and segment of one walk (dd_k1.h: SegWords)
+        uint32_t t[8];
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+            s = s * 1664525u + 1013904223u;
+            t[n] = s ^ (s >> 15);
+        }
+        SegWords sw;
+        sw.fill(make_uint4(t[0], t[1], t[2], t[3]), make_uint4(t[4], t[5], t[6], t[7]));
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
 #pragma unroll 1
         for (int i = 0; i < 16; ++i) {
-            const uint32_t c = (cw >> (2 * i)) & 3u;
-            win.push(c);
+            win.slice(sw, w, i);
             if (MODE == 0) {
-                sweep_token<KC, true, false>(win, 64, kfirst, nk, p, lds_slot);
+                sweep_token<KC, true, false>(win, 64, kfirst, nk, p, rq);
             } else if (MODE == 5) {
                 // experiment: wave-level pre-filter on the hash alone -- skip the LDS probe of a pair when no
                 // lane's rho can exceed the smallest register of its array (here: smallest = 8)
@@ -76,23 +85,23 @@ static double run(uint32_t* out, int nk, int kfirst, int p, int iters, uint32_t 
     const int wgs_per_cu = (160 / lds_kb);
     const int grid = 256 * wgs_per_cu;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), (size_t)lds_kb * 1024, 0, out, nk, kfirst, p, iters / 8 + 1, 1u, fill);
-    hipDeviceSynchronize();
+    (void)hipDeviceSynchronize();
     hipEventRecord(e0);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), (size_t)lds_kb * 1024, 0, out, nk, kfirst, p, iters, 1u, fill);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms;
     hipEventElapsedTime(&ms, e0, e1);
-    // per SIMD: (16 * wgs_per_cu / 4) waves, each iters*16*nk updates
+    // per SIMD: (16 * wgs_per_cu / 4) waves, each iters*64*nk updates
     const double waves_per_simd = 16.0 * wgs_per_cu / 4.0;
-    const double upd = waves_per_simd * (double)iters * 16.0 * nk;
+    const double upd = waves_per_simd * (double)iters * 64.0 * nk;
     return (double)ms * 1e-3 * ghz * 1e9 / upd;
 }
 
 int main(int argc, char** argv) {
     const double ghz = 2.34;
     const int p = 14;
-    int iters = argc > 1 ? atoi(argv[1]) : 2000;
+    int iters = argc > 1 ? atoi(argv[1]) : 500;
     uint32_t* out;
     if (hipMalloc(&out, 1024 * 1024 * sizeof(uint32_t)) != hipSuccess) return 1;
     printf("K1 inner-loop model, p=%d, cycles per wave-update per SIMD (2.34 GHz), canonical\n", p);
