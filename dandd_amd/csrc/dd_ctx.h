@@ -1,6 +1,6 @@
 // dd_ctx.h -- the context behind the C ABI's opaque dd_ctx, and the host-side helpers the ABI's sources share
 // (dd_api.hip: context, timing and stats, synth, dd_plan_sweep; dd_sketch_api.hip: sketch; dd_k2_api.hip: union, card and the
-// HLL schedules; dd_exact_api.hip: exact count, schedules and greedy; dd_exact_emit_api.hip: the selected k-mers, where they lie and the samples screened against them, all
+// HLL schedules; dd_exact_api.hip: exact count, schedules and greedy; dd_exact_emit_api.hip: the selected k-mers, where they lie, the samples screened against them and the pattern table, all
 // over dd_exact_host.h / dd_exact_passes.hip: call frame, pass driver, emission; dd_ingest.hip: the file-ingestion pipeline; dd_comm.hip: RCCL).
 // Callers see dandd_hip.h only.
 #pragma once
@@ -120,6 +120,7 @@ struct dd_ctx {
     DevBuf masks;  // dd_exact_greedy: cursor and overflow word | gains [64][64] | the mask streams of every k of the call
     DevBuf emit;   // dd_exact_select_kmers, dd_exact_locate (exact_emit_records): cursor (256 B) | lo | hi | mask, `cap` records each
     DevBuf hits;   // dd_exact_locate: the jobs' hit bitmaps, off[njobs] words; dd_exact_screen: counters [ns + 1][n + nq] | the samples' seen bitmaps
+    DevBuf pat[2]; // dd_exact_patterns: the running table in mask order (masks | counts) and where the next merge puts it, in turns
     StageSet stage[2];
     int stage_cur = 0;  // the set of the running (or last) sketch call
     // the job tables of the last few sketch calls: a call over genomes of the same sizes and the same k range (a

@@ -1,9 +1,11 @@
 // dd_exact_emit_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h) that hand k-mers out instead of counting
 // them: the selected k-mers themselves (dd_exact_select_kmers), where they lie in each genome (dd_exact_locate), the
 // record index of a file that turns those places into names (dd_fasta_index), and what samples that are no inputs hold of
-// them (dd_exact_screen).  The three exact entries are one emission (exact_emit_records, dd_exact_host.h) and one ordering
-// of its records on the device (launch_exact_emit_order).  Host-side orchestration only; the kernels are in
-// dd_exact_sched.hip (emit_kernel), dd_exact_locate.hip and dd_exact_screen.hip.
+// them (dd_exact_screen).  Those three exact entries are one emission (exact_emit_records, dd_exact_host.h) and one ordering
+// of its records on the device (launch_exact_emit_order).  And the table of the distinct masks with their multiplicities
+// (dd_exact_patterns), which hands out no k-mer but is ragged like the others: one k per call, a cap and a count.
+// Host-side orchestration only; the kernels are in dd_exact_sched.hip (emit_kernel, AccPatterns), dd_exact_locate.hip,
+// dd_exact_screen.hip and dd_exact_patterns.hip.
 #include "dd_exact_host.h"
 
 extern "C" {
@@ -285,6 +287,117 @@ int dd_exact_screen(dd_ctx* c, const char* const* paths, int n, const char* cons
     return exact_upload_files(c, files.data(), n + ns, [&](auto p, auto s) {
         return dd_exact_screen_device(c, p, s, n, ns, k, all, none, nq, shared, match, found);
     });
+}
+
+// ------------------------------------------------------------------- the membership-pattern table
+// dd_exact_sched.hip's patterns accumulator behind the sort of the schedules for ONE k: a pass leaves (mask, count) pairs in
+// the pair area of the workspace (sized for one pair per slot of the pass, which no pass can exceed), dd_exact_patterns.hip
+// sorts and reduces them in the k-mer arrays the schedule has consumed and merges the rows into the running table, which
+// lives in c->pat[cur] and moves to the other buffer with every merge.  Behind the last pass the table is put in answer
+// order in the workspace and its first min(found, cap) rows come back.
+namespace {
+
+int pattern_slots(int* slots) {
+    *slots = dd::kPatternSlotsDefault;
+    if (const char* e = getenv("DD_PATTERNS_SLOTS")) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end == e || *end || v < dd::kPatternSlotsMin || v > dd::kPatternSlotsMax || (v & (v - 1)))
+            return fail(DD_EINVAL, "DD_PATTERNS_SLOTS=%s: a power of two in %d..%d (the slots of a workgroup's table in LDS)", e,
+                        dd::kPatternSlotsMin, dd::kPatternSlotsMax);
+        *slots = (int)v;
+    }
+    return DD_OK;
+}
+
+}  // namespace
+
+int dd_exact_patterns_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int k, uint64_t* masks,
+                             uint64_t* counts, size_t cap, uint64_t* found, uint64_t* stats) {
+    if (exact_frame(c, fasta_dev, nbytes, n, 64, k, k, found, cap && (!masks || !counts))) return DD_EINVAL;
+    int slots = 0;
+    if (pattern_slots(&slots)) return DD_EINVAL;
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    *found = 0;
+    unsigned long long tally[4] = {0, 0, 0, 0};   // the stats of the ABI
+    const auto done = [&] {
+        for (int i = 0; stats && i < 4; ++i) stats[i] = tally[i];
+        return DD_OK;
+    };
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n, in))) return rc;
+    c->st_blocks = 0;
+    if (!in.slots) return done();
+    if ((rc = c->hist.reserve(sizeof(unsigned long long)))) return rc;
+    unsigned long long* seen_dev = static_cast<unsigned long long*>(c->hist.p);   // M, over all passes
+    DD_HIP(hipMemsetAsync(seen_dev, 0, sizeof(unsigned long long), st));
+    // the running table: rows in mask order, in c->pat[cur]
+    int cur = 0;
+    size_t rows = 0;
+    const uint64_t* tab_mask = nullptr;
+    const unsigned long long* tab_count = nullptr;
+    const ExactLayout layout{"exact patterns", dd::exact_tag_mode(k), dd::exact_patterns_temp_bytes, dd::exact_patterns_scratch_bytes};
+    rc = exact_passes(c, in, n, k, layout, [&](const ExactArrays& a, size_t count) -> int {
+        dd::ExactSorted sorted{};
+        DD_HIP(dd::launch_exact_sort_tagged(a.lo, a.hi, a.lo_alt, a.hi_alt, a.g, a.g_alt, count, k, a.temp, a.temp_bytes, st, &sorted));
+        // (the workspace was carved for at least `count` slots, and every part of the scratch grows with them)
+        const dd::PatternPairs pp = dd::exact_patterns_pairs(a.scratch, count);
+        DD_HIP(hipMemsetAsync(pp.head, 0, 256, st));
+        dd::ExactSched s{dd::kSchedPatterns, n, slots, 0, nullptr, seen_dev};
+        s.store = pp.mask, s.counts = pp.count, s.cursor = pp.head, s.overflow = pp.head + 1, s.pstats = pp.head + 2, s.cap = pp.cap;
+        DD_HIP(dd::launch_exact_sched(sorted, count, k, s, pp.sched_scratch, st));
+        unsigned long long h[5] = {0, 0, 0, 0, 0};   // cursor, overflow, forced flushes, single masks, rows of the reduce
+        DD_HIP(hipMemcpyAsync(h, pp.head, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+        if (h[1] || h[0] > pp.cap)
+            return fail(DD_EHIP, "exact patterns: a pass of %zu k-mer slots wrote %llu pairs, one per distinct k-mer at the most was expected", count, h[0]);
+        tally[1] += h[0], tally[2] += h[2], tally[3] += h[3];
+        if (!h[0]) return DD_OK;
+        // the k-mers are consumed: their arrays are the sort's other half
+        DD_HIP(dd::launch_patterns_reduce(pp, (size_t)h[0], n, a.lo, reinterpret_cast<unsigned long long*>(a.lo_alt), a.temp, a.temp_bytes, st));
+        DD_HIP(hipMemcpyAsync(h + 4, pp.head + 4, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+        const size_t fresh = (size_t)h[4], bytes = dd::exact_patterns_merge_bytes(rows + fresh);
+        DevBuf& dst = c->pat[cur ^ 1];
+        if (dst.reserve(bytes))
+            return fail(DD_ENOMEM, "exact patterns: no device memory for the %zu bytes that merge %zu rows into a table of %zu", bytes, fresh, rows);
+        unsigned long long* rows_dev = nullptr;
+        DD_HIP(dd::launch_patterns_merge(tab_mask, tab_count, rows, pp.mask, pp.count, fresh, dst.p, &rows_dev, st));
+        DD_HIP(hipMemcpyAsync(h + 4, rows_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+        tab_mask = static_cast<const uint64_t*>(dst.p);
+        tab_count = reinterpret_cast<const unsigned long long*>(static_cast<const char*>(dst.p) + dd::exact_patterns_stride(rows + fresh));
+        rows = (size_t)h[4], cur ^= 1;
+        return DD_OK;
+    });
+    if (rc) return rc;
+    DD_HIP(hipMemcpyAsync(&tally[0], seen_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    DD_HIP(hipStreamSynchronize(st));
+    const size_t take = std::min(rows, cap);
+    if (take) {
+        const size_t bytes = dd::exact_patterns_order_bytes(rows);
+        if (c->exact.reserve(bytes)) return fail(DD_ENOMEM, "exact patterns: no device memory for the %zu bytes that put %zu rows in order", bytes, rows);
+        {
+            Span sp(c, DD_KERNEL_EXACT);
+            DD_HIP(dd::launch_patterns_order(tab_mask, tab_count, rows, c->exact.p, st));
+        }
+        std::vector<uint64_t> mk(take), inv(take);
+        DD_HIP(hipMemcpyAsync(mk.data(), c->exact.p, take * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        DD_HIP(hipMemcpyAsync(inv.data(), static_cast<const char*>(c->exact.p) + dd::exact_patterns_stride(rows), take * sizeof(uint64_t),
+                              hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+        for (size_t i = 0; i < take; ++i) masks[i] = mk[i], counts[i] = ~inv[i];   // (nothing is written before everything is known)
+    }
+    *found = rows;
+    return done();
+}
+
+int dd_exact_patterns(dd_ctx* c, const char* const* paths, int n, int k, uint64_t* masks, uint64_t* counts, size_t cap, uint64_t* found,
+                      uint64_t* stats) {
+    return exact_path_form(c, paths, n, 64, k, k, found,
+                           [&](auto p, auto s) { return dd_exact_patterns_device(c, p, s, n, k, masks, counts, cap, found, stats); });
 }
 
 // host only: dd_io.h's record index of one file, in the caller's arrays

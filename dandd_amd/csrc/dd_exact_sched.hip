@@ -32,6 +32,10 @@
 //                 needs them to outlive their sort
 //                   stream       the tile appended to a store in HBM, 8 bytes per distinct k-mer, at a position reserved
 //                                with one atomicAdd per tile
+//                 and the one that asks nothing in advance:
+//                   patterns     the distinct masks with their multiplicities: a hash table of the workgroup in LDS that
+//                                leaves for HBM as (mask, count) pairs when it is full and at the end; the pairs of a pass are
+//                                sorted, reduced and merged into a running table by dd_exact_patterns.hip
 //   emit_kernel   (at the end of this file) sched_kernel's sibling for the selected k-mers themselves: no accumulator, the keys
 //                 and masks of the runs that match a query leave for HBM; launch_exact_emit_order then puts them in key order
 #include <algorithm>
@@ -226,6 +230,8 @@ struct SchedArgs {
     unsigned long long* cursor;       //   that would pass `cap` masks sets
     unsigned long long* overflow;
     unsigned long long cap;
+    unsigned long long* counts;       // patterns: the counts beside the masks in `store` (norder: the slots of the LDS table)
+    unsigned long long* pstats;       // patterns: [0] += flushes a full table forced, [1] += masks that left on their own
 };
 
 // ---- accumulators: init (LDS state), consume (one tile of masks; whole workgroup), flush (once per workgroup) ----
@@ -510,6 +516,145 @@ struct AccStream {
     DD_D void flush(const SchedArgs&, uint32_t) {}
 };
 
+// The masks themselves with their multiplicities: an open-addressing table of the workgroup in LDS -- keys the 64-bit masks
+// (0 is the empty slot: a zero mask never leaves chunk_runs), counts u32 -- that leaves for HBM as (mask, count) pairs at a
+// position reserved with one atomicAdd per flush, as the stream reserves its tiles.  A thread places its masks of a tile by
+// linear probing over at most kPatternProbe slots (64-bit LDS compare-and-swap on the key, LDS add on the count).  When some
+// thread of the workgroup could not place a mask, the whole workgroup writes the table out and clears it, the masks left over
+// are tried once more on the empty table, and one that still finds no slot (more than kPatternProbe of the left-over masks
+// share its probe sequence) leaves on its own as (mask, weight): every tile costs one such round at the most, whatever the
+// masks are.  The full mask -- where related genomes put most k-mers -- is counted in a register and leaves as one pair per
+// workgroup at the flush; of the others, the first live mask of each wave is added once for all the lanes that hold it (one
+// round, as agg_add).  A pair stands for at least one mask seen, so a pass writes no more pairs than it has slots.
+constexpr int kPatternProbe = 16;
+DD_D uint32_t pattern_hash(uint64_t m, int shift) {   // shift = 64 - log2(slots): the product's top bits, which depend on every bit of m
+    return (uint32_t)((m * 0x9E3779B97F4A7C15ull) >> shift);
+}
+
+struct AccPatterns {
+    unsigned long long* keys;   // [slots]
+    uint32_t* cnts;             // [slots]
+    unsigned long long* fulls;  // [1]: the workgroup's full masks
+    unsigned long long* at;     // [1]: where a flush goes
+    uint32_t* used;             // [2]: non-empty slots of a flush; the position its writers count on
+    uint32_t slots;
+    int shift;                  // 64 - log2(slots)
+    unsigned long long full;    // this thread's full masks
+    static size_t lds(int, int slots) { return (size_t)slots * 12 + 32; }
+    static size_t words(int, int, int) { return 0; }
+    DD_D void init(const SchedArgs& a, uint64_t* dyn) {
+        slots = (uint32_t)a.norder;   // a power of two, 64 at least
+        shift = 64 - __builtin_ctz(slots);
+        keys = reinterpret_cast<unsigned long long*>(dyn);
+        cnts = reinterpret_cast<uint32_t*>(keys + slots);
+        fulls = reinterpret_cast<unsigned long long*>(cnts + slots);   // (slots is even: 8-byte aligned)
+        at = fulls + 1;
+        used = reinterpret_cast<uint32_t*>(at + 1);
+        for (uint32_t s = threadIdx.x; s < slots; s += kThreads) keys[s] = 0ull, cnts[s] = 0u;
+        if (threadIdx.x == 0) *fulls = 0ull, *at = 0ull, used[0] = used[1] = 0u;
+        full = 0;
+    }
+    DD_D bool insert(uint64_t m, uint32_t weight) {
+        const uint32_t h = pattern_hash(m, shift);
+        for (int p = 0; p < kPatternProbe; ++p) {
+            const uint32_t s = (h + (uint32_t)p) & (slots - 1u);
+            unsigned long long was = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (was == 0ull) was = atomicCAS(&keys[s], 0ull, (unsigned long long)m);
+            if (was == 0ull || was == m) {
+                atomicAdd(&cnts[s], weight);
+                return true;
+            }
+        }
+        return false;
+    }
+    // (mask, count) pairs for HBM at a reserved position; a range that would pass the capacity is not written and says so
+    DD_D void put(const SchedArgs& a, unsigned long long pos, uint64_t m, unsigned long long count) {
+        a.store[pos] = m, a.counts[pos] = count;
+    }
+    // the table written out and cleared, by the whole workgroup; holds barriers
+    DD_D void spill(const SchedArgs& a) {
+        uint32_t mine = 0;
+        for (uint32_t s = threadIdx.x; s < slots; s += kThreads) mine += keys[s] != 0ull;
+        if (mine) atomicAdd(&used[0], mine);
+        __syncthreads();
+        const uint32_t total = used[0];
+        if (threadIdx.x == 0 && total) *at = atomicAdd(a.cursor, (unsigned long long)total);
+        __syncthreads();
+        const unsigned long long base = *at;
+        const bool room = base + total <= a.cap;
+        if (total && !room && threadIdx.x == 0) *a.overflow = 1ull;
+        for (uint32_t s0 = 0; s0 < slots; s0 += kThreads) {   // (slots is a multiple of 64: whole waves)
+            const uint32_t s = s0 + threadIdx.x;
+            const bool live = s < slots && keys[s] != 0ull;
+            const uint32_t p = wave_append(live, &used[1]);
+            if (live) {
+                if (room) put(a, base + p, keys[s], (unsigned long long)cnts[s]);
+                keys[s] = 0ull, cnts[s] = 0u;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) used[0] = used[1] = 0u;
+        __syncthreads();
+    }
+    DD_D void consume(const SchedArgs& a, const uint64_t* tile, uint32_t cnt, uint32_t) {
+        if (!cnt) return;   // (cnt is the same in every thread)
+        const uint64_t every = a.n == 64 ? ~0ull : ((1ull << a.n) - 1ull);
+        const int lane = threadIdx.x & 63;
+        uint32_t left = 0, weight[kItems];   // bit j: mask j * kThreads + threadIdx.x of the tile found no slot
+#pragma unroll
+        for (int j = 0; j < kItems; ++j) {
+            const uint32_t i = (uint32_t)j * kThreads + threadIdx.x;
+            uint64_t m = i < cnt ? tile[i] : 0ull;
+            if (m == every) ++full, m = 0ull;
+            // one round of wave aggregation: the first live lane's mask is added once for every lane that holds it
+            bool live = m != 0ull;
+            weight[j] = 1u;
+            const unsigned long long act = __ballot(live);
+            if (act) {
+                const int leader = __builtin_ctzll(act);
+                const uint64_t v = __shfl((unsigned long long)m, leader);
+                const unsigned long long same = __ballot(live && m == v);
+                if (lane == leader) weight[j] = (uint32_t)__builtin_popcountll(same);
+                else if (m == v) live = false;
+            }
+            if (live && !insert(m, weight[j])) left |= 1u << j;
+        }
+        if (!__syncthreads_or(left != 0u)) return;
+        // a full table: written out, and the masks left over placed in the empty one, or sent on their own
+        if (threadIdx.x == 0) atomicAdd(&a.pstats[0], 1ull);
+        spill(a);
+#pragma unroll
+        for (int j = 0; j < kItems; ++j) {
+            const bool pending = (left >> j) & 1u;
+            const uint64_t m = pending ? tile[(uint32_t)j * kThreads + threadIdx.x] : 0ull;
+            const bool single = pending && !insert(m, weight[j]);
+            const unsigned long long singles = __ballot(single);
+            if (singles) {   // (wave_append on the device cursor, with the capacity checked for the wave's range)
+                const int leader = __builtin_ctzll(singles);
+                const uint32_t nw = (uint32_t)__builtin_popcountll(singles);
+                unsigned long long base = 0;
+                if (lane == leader) base = atomicAdd(a.cursor, (unsigned long long)nw), atomicAdd(&a.pstats[1], (unsigned long long)nw);
+                base = __shfl(base, leader);
+                if (base + nw <= a.cap) {
+                    if (single) put(a, base + (unsigned long long)__builtin_popcountll(singles & ((1ull << lane) - 1ull)), m, weight[j]);
+                } else if (lane == leader) {
+                    *a.overflow = 1ull;
+                }
+            }
+        }
+    }
+    DD_D void flush(const SchedArgs& a, uint32_t) {
+        if (full) atomicAdd(fulls, full);
+        __syncthreads();
+        if (threadIdx.x == 0 && *fulls) {   // the full mask never entered the table: one pair of the workgroup's own
+            const unsigned long long pos = atomicAdd(a.cursor, 1ull);
+            if (pos < a.cap) put(a, pos, a.n == 64 ? ~0ull : ((1ull << a.n) - 1ull), *fulls);
+            else *a.overflow = 1ull;
+        }
+        spill(a);
+    }
+};
+
 template <bool WIDE, class Acc>
 __global__ __launch_bounds__(kThreads) void sched_kernel(SortedView s, const uint64_t* __restrict__ carry, size_t nchunks,
                                                        SchedArgs a) {
@@ -555,6 +700,7 @@ auto with_acc(int kind, const F& f) {
         case kSchedCoreProgressive: return f(AccTag<AccCoreProgressive>{});
         case kSchedSelect: return f(AccTag<AccSelect>{});
         case kSchedStream: return f(AccTag<AccStream>{});
+        case kSchedPatterns: return f(AccTag<AccPatterns>{});
         default: return f(AccTag<AccSubsets>{});
     }
 }
@@ -619,7 +765,8 @@ hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, co
     const int items = (by_order || by_query) ? s.norder : 1, per = by_order ? max_orderings(s.n) : (by_query ? kSelectBatch : 1);
     const size_t tstride = by_order ? (size_t)s.n : 2, astride = by_order ? (size_t)s.n : 1;
     for (int o0 = 0; o0 < items; o0 += per) {
-        SchedArgs a{s.n, 0, s.ngroups, s.table, s.acc, o0 == 0, 1, s.store, s.cursor, s.overflow, s.cap};
+        SchedArgs a{s.n, 0, s.ngroups, s.table, s.acc, o0 == 0, 1, s.store, s.cursor, s.overflow, s.cap, s.counts, s.pstats};
+        if (s.kind == kSchedPatterns) a.norder = s.norder;
         if (s.kind == kSchedSubsets && s.n > kExactSubsetsLdsN) a.slices = 1 << (s.n - kExactSubsetsLdsN);
         if (by_order || by_query) {
             a.norder = std::min(per, items - o0);

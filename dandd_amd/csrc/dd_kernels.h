@@ -286,7 +286,8 @@ inline constexpr int exact_tag_mode(int k) { return (k <= 32 ? 2 * k : 2 * k - 6
 constexpr int kExactSubsetsLdsN = 15;   // subsets: 2^n histogram bins in LDS (u32, 128 KiB at 15); n = 16 as two halves by the top bit
 enum { kSchedPairwise = 0, kSchedProgressive = 1, kSchedLeaveOut = 2, kSchedSubsets = 3,
        kSchedSpectrum = 4, kSchedCoreProgressive = 5, kSchedSelect = 6,    // 4..6: the intersection schedules
-       kSchedStream = 7 };   // the masks themselves, kept in HBM for a walk that needs every k's masks at once (dd_exact_greedy.hip)
+       kSchedStream = 7,     // the masks themselves, kept in HBM for a walk that needs every k's masks at once (dd_exact_greedy.hip)
+       kSchedPatterns = 8 }; // the distinct masks with their multiplicities, as (mask, count) pairs for dd_exact_patterns.hip
 struct ExactSorted {            // where launch_exact_sort_tagged left the sorted k-mers
     const uint64_t* lo;
     const uint64_t* hi;         // k > 32
@@ -294,7 +295,8 @@ struct ExactSorted {            // where launch_exact_sort_tagged left the sorte
 };
 struct ExactSched {
     int kind, n;
-    int norder;                 // progressive, core-progressive: orderings; select: queries (any number >= 1)
+    int norder;                 // progressive, core-progressive: orderings; select: queries (any number >= 1);
+                                // patterns: slots of a workgroup's LDS table, a power of two in kPatternSlotsMin..kPatternSlotsMax
     int ngroups;                // leave-out
     const uint64_t* table;      // device; progressive: prefix masks [norder][n]; leave-out: group of bit i [64] (~0: never left out),
                                 //         then the groups' masks [ngroups]; core-progressive: the prefix masks of progressive;
@@ -307,7 +309,7 @@ struct ExactSched {
                                 //   spectrum: then [n+1] k-mers held by exactly j genomes
                                 //   core-progressive: then [norder][n] k-mers that hold genomes 0..j of ordering o and not genome j+1
                                 //   select: then [norder] k-mers whose mask contains all[q] and meets none[q] nowhere
-                                //   stream: nothing more
+                                //   stream, patterns: nothing more
     // stream: every mask is appended to store[] at a position reserved on *cursor (one reservation per tile of masks, so their
     // order is whatever the reservations give); a tile that would pass `cap` sets *overflow and is not written, the cursor
     // still advances: it says how many masks the store would have had to hold
@@ -315,6 +317,11 @@ struct ExactSched {
     unsigned long long* cursor = nullptr;
     unsigned long long* overflow = nullptr;
     unsigned long long cap = 0;
+    // patterns: (mask, count) pairs go to store[] / counts[] at positions reserved on *cursor, one reservation per flush of a
+    // workgroup's table; the same capacity rule.  A pair stands for at least one distinct k-mer of the pass, so cap = the
+    // slots of the pass is never passed.  pstats[0] += flushes a full table forced, pstats[1] += masks that left singly.
+    unsigned long long* counts = nullptr;
+    unsigned long long* pstats = nullptr;
 };
 size_t exact_sched_acc_words(const ExactSched& s);
 size_t exact_sched_temp_bytes(size_t n, int k);
@@ -349,6 +356,38 @@ struct LocateSet {                  // where launch_exact_emit_order left the re
 size_t exact_emit_order_bytes(size_t found, int k);
 hipError_t launch_exact_emit_order(uint64_t* lo, uint64_t* hi, uint64_t* mask, size_t found, int k, void* work, hipStream_t st,
                                    LocateSet* out);
+
+// ---------------------------------------------------------------------------------------
+// the membership-pattern table (dd_exact_patterns.hip) behind kSchedPatterns: the pairs of a pass sorted by mask and reduced,
+// the result merged into a running table in mask order, the table put in answer order behind the last pass.  rocPRIM on the
+// caller's stream; every count is a u64.
+// ---------------------------------------------------------------------------------------
+constexpr int kPatternSlotsMin = 64, kPatternSlotsMax = 8192, kPatternSlotsDefault = 4096;   // 12 B of LDS per slot
+struct PatternPairs {               // the pair area of a pass, carved from the scratch behind the sort's temp
+    unsigned long long* head;       // [32]: cursor, overflow word, forced flushes, single masks; [4]: where a reduce leaves its row count
+    uint64_t* mask;                 // [cap]
+    unsigned long long* count;      // [cap]
+    size_t cap;
+    void* sched_scratch;            // exact_sched_scratch_bytes(keys) for launch_exact_sched
+};
+size_t exact_patterns_scratch_bytes(size_t keys);
+size_t exact_patterns_temp_bytes(size_t keys, int k);   // the larger of the tagged sort's temp and the reduce's
+PatternPairs exact_patterns_pairs(void* scratch, size_t keys);
+// pairs [0, npairs) of `p`, masks of n bits -> rows in mask order, each mask once, back in p.mask / p.count; their number to p.head[4].
+// alt_mask / alt_count: npairs words each (the k-mer arrays of the pass, which the schedule has consumed).
+hipError_t launch_patterns_reduce(const PatternPairs& p, size_t npairs, int n, uint64_t* alt_mask, unsigned long long* alt_count, void* temp,
+                                  size_t temp_bytes, hipStream_t st);
+// table (rows_a, mask order) + rows of a pass (rows_b, mask order) -> a table in mask order at the front of `dst`
+// (exact_patterns_merge_bytes(rows_a + rows_b) of device memory): masks at dst, counts at dst + patterns_stride(rows_a + rows_b);
+// its row count to *rows_out (device, inside dst)
+size_t exact_patterns_stride(size_t rows);
+size_t exact_patterns_merge_bytes(size_t rows);
+hipError_t launch_patterns_merge(const uint64_t* mask_a, const unsigned long long* count_a, size_t rows_a, const uint64_t* mask_b,
+                                 const unsigned long long* count_b, size_t rows_b, void* dst, unsigned long long** rows_out, hipStream_t st);
+// the table in answer order -- count descending, ties by mask ascending -- in `work` (exact_patterns_order_bytes(rows)):
+// masks at work, INVERTED counts (~count) at work + exact_patterns_stride(rows)
+size_t exact_patterns_order_bytes(size_t rows);
+hipError_t launch_patterns_order(const uint64_t* mask, const unsigned long long* count, size_t rows, void* work, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // the positions of the selected k-mers (dd_exact_locate.hip), behind launch_exact_emit_order: every token of a painted

@@ -37,6 +37,7 @@ EXPORTS = [
     "dd_exact_select_kmers", "dd_exact_select_kmers_device",
     "dd_exact_locate", "dd_exact_locate_device", "dd_fasta_index",
     "dd_exact_screen", "dd_exact_screen_device",
+    "dd_exact_patterns", "dd_exact_patterns_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
     "dd_comm_unique_id", "dd_comm_init", "dd_comm_destroy", "dd_comm_info", "dd_allreduce_max_u8", "dd_allgather_u8",
@@ -191,6 +192,10 @@ def load_library(path=None):
     lib.dd_exact_screen.argtypes = [vp, paths_t, i32, paths_t, i32, i32, vp, vp, i32, vp, vp, C.POINTER(u64)]
     lib.dd_exact_screen_device.restype = i32
     lib.dd_exact_screen_device.argtypes = [vp, ptrs_t, sizes_t, i32, i32, i32, vp, vp, i32, vp, vp, C.POINTER(u64)]
+    for name, src in (("dd_exact_patterns", [paths_t]), ("dd_exact_patterns_device", [ptrs_t, sizes_t])):
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = [vp] + src + [i32, i32, vp, vp, sz, C.POINTER(u64), vp]
     lib.dd_fasta_index.restype = i32
     lib.dd_fasta_index.argtypes = [C.c_char_p, vp, vp, sz, C.POINTER(u64), vp, sz, C.POINTER(sz), C.POINTER(u64)]
     lib.dd_timing_enable.restype = i32
@@ -870,6 +875,36 @@ class Engine:
         ns = total - int(n)
         return self._exact_screen(lambda *rest: self._lib.dd_exact_screen_device(self._ctx, *args, int(n), ns, *rest),
                                   int(n), ns, k, all_masks, none_masks)
+
+    # -- the membership-pattern table: the distinct masks and how many k-mers carry each (dd_exact_patterns.hip) ------------
+    last_patterns_stats = None   # of the last exact_patterns call: (distinct k-mers, pairs written to HBM, forced flushes, single masks)
+
+    def _exact_patterns(self, src, k, cap):
+        args, n, suffix = src
+        fn = getattr(self._lib, f"dd_exact_patterns{suffix}")
+
+        def call(room):
+            masks, counts = np.zeros(room, dtype=np.uint64), np.zeros(room, dtype=np.uint64)
+            found, stats = C.c_uint64(), np.zeros(4, dtype=np.uint64)
+            self._check(fn(self._ctx, *args, n, int(k), masks.ctypes.data if room else None, counts.ctypes.data if room else None, room,
+                           C.byref(found), stats.ctypes.data))
+            self.last_patterns_stats = tuple(int(v) for v in stats)
+            m = min(int(found.value), room)
+            return masks[:m], counts[:m], int(found.value)
+        if cap is not None:
+            return call(max(int(cap), 0))
+        got = call(0)                     # a pure count, then room for every row
+        return call(got[2]) if got[2] else got
+
+    def exact_patterns(self, paths, k, cap=None):
+        """FASTA files (n <= 64), one k -> (masks uint64 [m], counts uint64 [m], found): the distinct membership masks (bit i:
+        file i) and the distinct k-mers that carry exactly each, count descending, ties by mask ascending; found: the number
+        of distinct masks, m = min(found, cap) -- a cap below found gives the top cap rows.  cap=None: two calls, one that
+        counts and one with room for every row.  last_patterns_stats: the stats of the last call (include/dandd_hip.h)."""
+        return self._exact_patterns(self._exact_src(paths=paths), k, cap)
+
+    def exact_patterns_device(self, fasta_ptrs, nbytes, k, cap=None):
+        return self._exact_patterns(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), k, cap)
 
     # -- exact greedy: the masks of every k kept on the device, one read of them per step (dd_exact_greedy.hip) ---------
     def _exact_greedy(self, src, kmin, kmax, mode, cand, nfixed, nsteps):

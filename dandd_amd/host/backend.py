@@ -375,6 +375,20 @@ class HipExactBackend:
             raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
         return self.engine.exact_screen(files, [str(f) for f in sample_files], int(k), all_masks, none_masks)
 
+    def pattern_counts(self, leaf_paths, k, limit):
+        """the distinct membership masks of the leaves at one k of the window and how many k-mers carry each
+        (dd_exact_patterns): -> (masks uint64 [m], counts uint64 [m], found, distinct), count descending, ties by mask
+        ascending; found: the number of distinct masks, m = min(found, limit) (limit None: every row), distinct: the
+        distinct k-mers of the leaves together, in the rows or not."""
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, kmin, kmax = win
+        if not kmin <= int(k) <= kmax:
+            raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
+        masks, counts, found = self.engine.exact_patterns(files, int(k), cap=None if limit is None else int(limit))
+        return masks, counts, found, int(self.engine.last_patterns_stats[0])
+
     def greedy_cards(self, leaf_paths, mode, nfixed, nsteps, kmin):
         """HipBackend.greedy_cards on exact counts (dd_exact_greedy): -> (order [nsteps] as indices into leaf_paths, cards
         float64 [nsteps][K]), ties going to the leaf the caller lists first.  None -- the caller goes on as without this

@@ -1,6 +1,6 @@
-"""`dandd tree | progressive | kij | deltadelta | abba | greedy | core | screen` on the MI355X engine: same sub-commands, flags, defaults and
-output files as /root/reference/lib/dandd_cmd.py (flags :141-286, handlers :43-132); only the
-sketching backend differs.  Run as  python -m dandd_amd.host.cli <subcommand> ...
+"""`dandd tree | progressive | kij | deltadelta | abba | greedy | core | screen | patterns` on the MI355X engine: same sub-commands, flags,
+defaults and output files as /root/reference/lib/dandd_cmd.py (flags :141-286, handlers :43-132); only the
+sketching backend differs.  (deltadelta, abba, greedy, core, screen and patterns are this package's own: the reference has none of them.)  Run as  python -m dandd_amd.host.cli <subcommand> ...
 """
 import argparse
 import os
@@ -174,7 +174,7 @@ def _deltadelta_groups(tree, args):
     return groups, [title[g[0]] for g in groups]
 
 
-# ---- what the analyses over a loaded tree (deltadelta, abba, greedy, core, screen) share ------------------------------------
+# ---- what the analyses over a loaded tree (deltadelta, abba, greedy, core, screen, patterns) share ------------------------------------
 def _open_tree(cmd, args, exact=False, safe=False):
     """-> (the tree of -d, the prefix of the command's output files).  exact: the command sums over membership masks, so a
     tree of sketches is an exit; safe: the command has an object path, which --safe asks for through the experiment."""
@@ -211,7 +211,7 @@ def _universe_or_exit(cmd, tree, args, least, most=None, most_why=""):
     return fastas
 
 
-MASK_BITS = "a membership mask has one bit per genome"    # why `core` and `screen` take at most 64 genomes
+MASK_BITS = "a membership mask has one bit per genome"    # why `core`, `screen` and `patterns` take at most 64 genomes
 
 
 def _groups_in_universe(cmd, args, leaf_of, fastas):
@@ -534,6 +534,63 @@ def screen_command(args):
     _finish(tree)
 
 
+def patterns_command(args):
+    """Which sets of genomes share k-mers, and how many: the distinct membership masks of the universe with the distinct
+    k-mers that carry exactly each -- the table behind an UpSet plot, and what tells which groups `core -g` and `screen -g`
+    are worth asking about.  --splits reads the table as bipartitions of the universe and gives each its support."""
+    tree, outfile = _open_tree("patterns", args, exact=True)
+    ks = sorted(set(int(k) for k in args.ks)) if args.ks else [int(tree.root_k())]
+    window = tree.experiment.get("ksweep")
+    for k in ks:
+        if not 1 <= k <= 64:
+            sys.exit(f"patterns: -k {k} is outside 1..64")
+        if window is not None and not max(1, int(window[0])) <= k <= int(window[1]):
+            sys.exit(f"patterns: -k {k} is outside the k window {max(1, int(window[0]))}..{int(window[1])} of the tree")
+    top, most = int(args.top), int(args.max_patterns)
+    if top < 0 or most < 0:
+        sys.exit("patterns: --top and --max-patterns are numbers of rows")
+    fastas = _universe_or_exit("patterns", tree, args, least=1, most=64, most_why=MASK_BITS)
+    n = len(fastas)
+    full = (1 << n) - 1
+    whole = args.splits or top == 0 or top > most        # (--splits needs every row)
+    try:
+        res = tree.pattern_tables(fastas, ks, top=most + 1)               # (one row more than allowed: too many shows)
+    except (ValueError, OSError) as e:
+        sys.exit("patterns: " + " ".join(str(e).split()))
+    for k in ks:
+        if whole and res[k]["found"] > most:
+            sys.exit(f"patterns: {res[k]['found']} patterns at k={k}, more than --max-patterns {most}; give --top N for the largest N, "
+                     "or raise --max-patterns")
+
+    def members(mask):
+        return ";".join(f for i, f in enumerate(fastas) if mask >> i & 1)
+    rows, summary, splits = [], [], []
+    for k in ks:                                                          # (nothing is written before every table is there)
+        t = res[k]
+        table = list(zip(t["masks"], t["counts"]))
+        shown = table if top == 0 else table[:top]
+        for rank, (mask, count) in enumerate(shown, 1):
+            rows.append([k, rank, count, count / t["distinct"] if t["distinct"] else None, bin(mask).count("1"), f"{mask:x}", members(mask)])
+        # core and singletons are sums over the whole table: empty cells when it has more than --max-patterns rows
+        known = t["found"] <= most
+        summary.append([k, t["distinct"], t["found"], len(shown), sum(c for _, c in shown),
+                        sum(c for m, c in table if m == full) if known else None,
+                        sum(c for m, c in table if m & (m - 1) == 0) if known else None, members(shown[0][0]) if shown else None])
+        if args.splits:
+            count_of = dict(table)
+            sides = sorted({min(m, full ^ m) for m in count_of if 2 <= bin(m).count("1") <= n - 2})
+            found = [(count_of.get(a, 0) + count_of.get(full ^ a, 0), a) for a in sides]
+            for support, a in sorted(found, key=lambda r: (-r[0], r[1])):
+                splits.append([k, members(a), members(full ^ a), support])
+    os.makedirs(args.outdir, exist_ok=True)
+    _write_csv(outfile + ".patterns.csv", ["k", "rank", "kmers", "fraction", "ngenomes", "mask", "members"], rows)
+    _write_csv(outfile + ".patterns_summary.csv", ["k", "distinct_kmers", "patterns", "rows_written", "kmers_in_rows", "core", "singletons",
+                                                   "top_members"], summary)
+    if args.splits:
+        _write_csv(outfile + ".splits.csv", ["k", "side_a", "side_b", "support"], splits)
+    _finish(tree)
+
+
 def serve_command(args):
     """A resident `dandd`: commands arrive over a unix socket (dandd_amd.host.client), run one at a time in THIS process --
     whose backends (deltatree._backends: GPU context, kernel modules, pinned buffers, job-table cache) outlive them -- with the
@@ -772,6 +829,26 @@ def build_parser():
     sc.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     sc.add_argument("-l", "--label", dest="label", default="")
     sc.set_defaults(func=screen_command)
+
+    pa = subs.add_parser("patterns", parents=[common],
+                         description="which sets of up to 64 genomes of a `tree --exact` share k-mers, and how many: the distinct membership "
+                                     "patterns with their k-mer counts")
+    pa.add_argument("-d", "--dtree", dest="delta_tree", required=True)
+    pa.add_argument("-s", "--tag", dest="tag", type=str)
+    pa.add_argument("-f", "--fastas", dest="flist_loc", default=None, type=str,
+                    help="the genomes of the universe (default: every leaf), in the order `progressive -f` takes them")
+    pa.add_argument("-k", dest="ks", action="append", type=int, default=None, metavar="K",
+                    help="the patterns at this k (1..64, repeatable; default: the k of the tree's root)")
+    pa.add_argument("--top", dest="top", type=int, default=1000, metavar="N", help="write the N largest patterns (default 1000; 0: all)")
+    pa.add_argument("--max-patterns", dest="max_patterns", type=int, default=1_000_000, metavar="N",
+                    help="most patterns of one k a whole table may have (--top 0, --splits; default 1000000): more ends the command "
+                         "before anything is written")
+    pa.add_argument("--splits", dest="splits", default=False, action="store_true",
+                    help="also write every bipartition {mask, rest} with 2 <= genomes <= n - 2 on a side and its support "
+                         "(<prefix>.splits.csv)")
+    pa.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
+    pa.add_argument("-l", "--label", dest="label", default="")
+    pa.set_defaults(func=patterns_command)
 
     # (not in the reference: its every command is a fresh process that shells out to fresh `dashing` processes)
     sv = subs.add_parser("serve", description="keep the GPU context alive and run the commands dandd_amd.host.client forwards")

@@ -1270,6 +1270,26 @@ class DeltaTree:
                     out["sample_kmers"][kk, j] = int(be.card(db))
         return out
 
+    # ---- which sets of genomes share k-mers (`dandd patterns`) --------------------------------------------------------------
+    def pattern_tables(self, fastas, ks, top=None):
+        """The membership patterns of the universe `fastas` (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]) at every
+        k of `ks`: the distinct masks and the distinct k-mers that carry exactly each, count descending, ties by mask
+        ascending -- the first `top` of them (None: all).  One pattern_counts call of the backend per k.  There is no object
+        path: a backend without pattern_counts, or without a table for these leaves, is a ValueError.
+        -> dict: ks, and per k of it dict(masks [int], counts [int], found: the number of distinct masks, distinct: the distinct
+        k-mers of the universe)"""
+        ks = [int(k) for k in ks]
+        for k in ks:
+            if not 1 <= k <= 64:
+                raise ValueError(f"k={k} is outside 1..64")
+        out = {"ks": ks}
+        for k in ks:
+            u = self._universe(fastas, k, k)
+            u.need("pattern_counts", why="the pattern table is a count over")
+            masks, counts, found, distinct = u.table(u.be.pattern_counts(u.paths, k, None if top is None else int(top)))
+            out[k] = dict(masks=[int(m) for m in masks], counts=[int(v) for v in counts], found=int(found), distinct=int(distinct))
+        return out
+
     # ---- batched GPU union schedules ------------------------------------------------------------------
     def _table_window(self, experiment):
         """[lo, hi] of a union table for climbs over this tree's leaves: the --ksweep window, or a hill-climb's guess -- the

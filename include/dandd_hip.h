@@ -334,6 +334,31 @@ int dd_exact_screen(dd_ctx *, const char *const *paths, int n, const char *const
 int dd_exact_screen_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
                            const uint64_t *all, const uint64_t *none, int nq, uint64_t *shared, uint64_t *match,
                            uint64_t *found);
+/* ---- the membership-pattern table ------------------------------------------------------------------------------
+ * Which sets of inputs share k-mers, and how many: the DISTINCT membership masks of the universe with their multiplicities
+ * (the table behind an UpSet plot; every other mask statistic above -- spectrum, select, a subset union -- is a sum over
+ * it).  ONE k per call (the outputs are ragged), 1 <= n <= 64, 1 <= k <= 64; the sort and the masks of the schedules above,
+ * a hash table per workgroup in LDS as the accumulator (dd_exact_sched.hip), and the (mask, count) pairs it leaves sorted,
+ * reduced and merged on the device (dd_exact_patterns.hip).  `found` must not be null; masks and counts may be null only when
+ * cap == 0, which makes the call a pure count.
+ *   *found    the number of distinct non-zero masks
+ *   rows 0 .. min(found, cap) - 1:  masks[i] (bit j: input j holds the k-mers of this row) and counts[i], the distinct
+ *             k-mers with exactly that mask, in the order COUNT DESCENDING, ties by MASK ASCENDING (unsigned).
+ *   found > cap:  UNLIKE dd_exact_select_kmers the call returns DD_OK WITH A VALID PREFIX: the whole table is on the device
+ *             anyway, and the cap rows written are the first cap rows of the full answer (the top-cap patterns).
+ *   stats     null, or 4 words: [0] the distinct k-mers seen (the sum of every count of the table), [1] the pairs the
+ *             workgroups wrote to HBM, [2] the flushes a full LDS table forced, [3] the masks written through singly.
+ * Two calls on the same inputs return identical bytes.  An empty input, or one without a k-mer of length k, sets no bit;
+ * when no input holds a k-mer, *found = 0.  Budget and passes are those of dd_exact_count (DD_EXACT_MB): the pairs of a
+ * pass wait in 16 bytes per k-mer slot of the pass inside the exact workspace -- a pass writes at most one pair per distinct
+ * k-mer, so that never overflows -- and the running table is kept beside the workspace, 16 bytes per row (DD_ENOMEM with a
+ * message naming the bytes when it cannot be had).  dd_last_sketch_stats' third value is the number of passes, kernel time
+ * is DD_KERNEL_EXACT's.  DD_PATTERNS_SLOTS (read on every call): the slots of a workgroup's table, a power of two in
+ * 64..8192, 4096 when unset; anything else is DD_EINVAL. */
+int dd_exact_patterns(dd_ctx *, const char *const *paths, int n, int k, uint64_t *masks /*[cap]*/,
+                      uint64_t *counts /*[cap]*/, size_t cap, uint64_t *found, uint64_t *stats /*[4] or null*/);
+int dd_exact_patterns_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int k,
+                             uint64_t *masks, uint64_t *counts, size_t cap, uint64_t *found, uint64_t *stats);
 /* Host only, no context and no device: names, sequence lengths and token starts of the records of one FASTA / FASTQ file,
  * plain or gzip, read by the loaders and record rules the exact calls and dd_sketch_files use.  K0 puts one BREAK token
  * where each header line ends -- IN FRONT of its record's bases -- and one for every ambiguous byte, so
@@ -377,7 +402,7 @@ int dd_exact_greedy_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen */
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen; the accumulation, merges and ordering of dd_exact_patterns */
 #define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);
