@@ -133,7 +133,9 @@ __device__ __noinline__ bool build_table(uint32_t first, int n, int kind, uint32
         o += cl;
     }
     if (nonzero == 0) return kind == 1;   // (a block of literals only may come with no distance code at all: RFC 1951, 3.2.7)
-    if (left > 0 && !(kind == 1 && nonzero == 1)) return false;   // incomplete: only a one-code distance tree may be
+    // incomplete: only ONE code of ONE bit may be, as in zlib's inflate_table (a used distance code of two bits and more with no
+    // sibling is refused there, and was sketched here); the literal/length tree of an empty block may be the end-of-block code alone
+    if (left > 0 && !(nonzero == 1 && uni(l16(cnt_off + 2u)) == 1u)) return false;
     // every symbol in turn (uniform), its table replicas spread over the lanes
     for (int i = 0; i < n; ++i) {
         const uint32_t l = uni((uint32_t)g_lds[kLens + first + i]);

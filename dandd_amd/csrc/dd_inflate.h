@@ -117,20 +117,25 @@ struct Huff {
             pair[idx] = v;
         }
     }
-    // returns false when the lengths do not form a usable code (over-subscribed; incomplete unless `allow_incomplete`)
+    // returns false when the lengths do not form a usable code: over-subscribed, or incomplete -- except, with `allow_incomplete`,
+    // ONE code of ONE bit, the only incomplete code zlib's inflate_table takes (its other bit pattern then decodes to nothing)
     bool build(const uint8_t* len, int n, bool allow_incomplete) {
         memset(count, 0, sizeof count);
         for (int i = 0; i < n; ++i) ++count[len[i]];
-        if (count[0] == n) return false;
-        int left = 1;
         maxlen = 0;
+        if (count[0] == n) {   // no code at all: a distance tree may be that under a block of literals only (RFC 1951, 3.2.7; zlib takes it)
+            if (!allow_incomplete) return false;
+            memset(fast, 0, sizeof fast);
+            return true;       // (count[1..15] are zero: decode() finds no code, a match is refused)
+        }
+        int left = 1;
         for (int l = 1; l <= 15; ++l) {
             left <<= 1;
             left -= count[l];
             if (left < 0) return false;
             if (count[l]) maxlen = l;
         }
-        if (left > 0 && !(allow_incomplete && n - count[0] == 1)) return false;
+        if (left > 0 && !(allow_incomplete && n - count[0] == 1 && count[1] == 1)) return false;
         uint16_t offs[16];
         offs[1] = 0;
         for (int l = 1; l < 15; ++l) offs[l + 1] = (uint16_t)(offs[l] + count[l]);
@@ -215,18 +220,21 @@ struct BlockCodes {
             }
         }
         if (!lens[256]) return false;   // no end-of-block code
-        return lit.build(lens, hlit, false) && dist.build(lens + hlit, hdist, true);
+        // (zlib takes the one-code exception for both trees: a literal/length tree of the end-of-block code alone heads an empty block)
+        return lit.build(lens, hlit, true) && dist.build(lens + hlit, hdist, true);
     }
-    void set_fixed() {
+    bool set_fixed() {
         uint8_t l[288];
         for (int i = 0; i < 144; ++i) l[i] = 8;
         for (int i = 144; i < 256; ++i) l[i] = 9;
         for (int i = 256; i < 280; ++i) l[i] = 7;
         for (int i = 280; i < 288; ++i) l[i] = 8;
-        lit.build(l, 288, false);
-        uint8_t d[30];
-        for (int i = 0; i < 30; ++i) d[i] = 5;
-        dist.build(d, 30, true);
+        // (the fixed distance code has 32 codes of 5 bits: 30 and 31 may not occur -- the decoder refuses them --, but they
+        // belong to the code; 30 codes of 5 bits are incomplete, build() refused them and every match of a fixed block was
+        // decoded with whatever the distance table held before)
+        uint8_t d[32];
+        for (int i = 0; i < 32; ++i) d[i] = 5;
+        return lit.build(l, 288, false) && dist.build(d, 32, false);
     }
 };
 
@@ -298,7 +306,7 @@ inline int decode_piece(const uint8_t* in, size_t n, uint64_t start, uint64_t st
         } else {
             if (btype == 1) {
                 if (trial_blocks) return -1;   // (fixed codes validate nothing: never a starting point)
-                codes.set_fixed();
+                if (!codes.set_fixed()) return -1;
             } else if (!codes.read_dynamic(b)) {
                 return -1;
             }
