@@ -1,11 +1,11 @@
 // dd_exact_emit_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h) that hand k-mers out instead of counting
 // them: the selected k-mers themselves (dd_exact_select_kmers), where they lie in each genome (dd_exact_locate), the
 // record index of a file that turns those places into names (dd_fasta_index), and what samples that are no inputs hold of
-// them (dd_exact_screen).  Those three exact entries are one emission (exact_emit_records, dd_exact_host.h) and one ordering
-// of its records on the device (launch_exact_emit_order).  And the table of the distinct masks with their multiplicities
+// them (dd_exact_screen) and where along themselves (dd_exact_paint).  Those four exact entries are one emission
+// (exact_emit_records, dd_exact_host.h) and one ordering of its records on the device (launch_exact_emit_order).  And the table of the distinct masks with their multiplicities
 // (dd_exact_patterns), which hands out no k-mer but is ragged like the others: one k per call, a cap and a count.
 // Host-side orchestration only; the kernels are in dd_exact_sched.hip (emit_kernel, AccPatterns), dd_exact_locate.hip,
-// dd_exact_screen.hip and dd_exact_patterns.hip.
+// dd_exact_screen.hip, dd_exact_paint.hip and dd_exact_patterns.hip.
 #include "dd_exact_host.h"
 
 extern "C" {
@@ -286,6 +286,116 @@ int dd_exact_screen(dd_ctx* c, const char* const* paths, int n, const char* cons
         if (!(files[(size_t)i] = i < n ? paths[i] : samples[i - n])) return fail(DD_EINVAL, "null argument");
     return exact_upload_files(c, files.data(), n + ns, [&](auto p, auto s) {
         return dd_exact_screen_device(c, p, s, n, ns, k, all, none, nq, shared, match, found);
+    });
+}
+
+// ------------------------------------------------------------------- samples painted window by window
+// dd_exact_paint.hip: everything of dd_exact_screen up to the ordered records -- K0 over the universe's inputs and the samples,
+// the sort and the emission over the universe alone with the single query (0, 0), the records put in key order --, then one
+// walk of every sample that keeps the position: a row of n + 2 counters per window of the sample's token stream, in c->hits.
+// The shape of the answer is checked like dd_exact_locate's: each sample's share of off[] against its token count.
+namespace {
+
+int paint_args(dd_ctx* c, const void* inputs, int n, int ns, int k, uint64_t window, const uint64_t* off, const uint64_t* found) {
+    if (exact_args(c, inputs, n, 64, k, k, found)) return DD_EINVAL;
+    if (ns < 1 || ns > 1024) return fail(DD_EINVAL, "ns=%d outside 1..1024 samples in one call; split them over calls", ns);
+    if (window < dd::kSegTokens || window > dd::kPaintMaxWindow || window % dd::kSegTokens)
+        return fail(DD_EINVAL, "window=%llu: a multiple of %d in %d..%zu tokens (a window is whole 64-token segments)", (unsigned long long)window,
+                    (int)dd::kSegTokens, (int)dd::kSegTokens, dd::kPaintMaxWindow);
+    if (!off) return fail(DD_EINVAL, "null argument");
+    return DD_OK;
+}
+
+}  // namespace
+
+int dd_exact_paint_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns, int k, uint64_t window,
+                          const uint64_t* off, uint32_t* counts, uint64_t* found) {
+    if (paint_args(c, fasta_dev, n, ns, k, window, off, found)) return DD_EINVAL;
+    if (!nbytes) return fail(DD_EINVAL, "null argument");
+    if (exact_check_inputs(fasta_dev, nbytes, n + ns)) return DD_EINVAL;
+    if (off[ns] < off[0]) return fail(DD_EINVAL, "off[] must ascend");
+    const uint64_t rows = off[ns] - off[0];   // (each sample's own share is checked once the samples' token counts are known)
+    if (rows && !counts) return fail(DD_EINVAL, "null argument");
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    ExactInputs in;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n + ns, in))) return rc;   // K0 over everything, once
+    c->st_blocks = 0;
+    const bool tokens = in.slots != 0;
+    // the shape of the answer: every sample's ntok
+    std::vector<unsigned long long> ntok((size_t)ns, 0ull);
+    if (tokens) {
+        for (int s = 0; s < ns; ++s)
+            DD_HIP(hipMemcpyAsync(&ntok[(size_t)s], in.etab[(size_t)(n + s)].ntok, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+    }
+    // one image for both tables: the emission's single query (0, 0) | the first row of every sample [ns]
+    const size_t pbytes = 256;
+    std::vector<char> image(pbytes + sizeof(unsigned long long) * (size_t)ns, 0);
+    unsigned long long* row0 = reinterpret_cast<unsigned long long*>(image.data() + pbytes);
+    size_t sample_segments = 0;
+    for (int s = 0; s < ns; ++s) {
+        const uint64_t want = (ntok[(size_t)s] + window - 1) / window;
+        if (off[s + 1] - off[s] != want)
+            return fail(DD_EINVAL, "sample %d: off[%d] - off[%d] = %llu rows, %llu expected (it holds %llu tokens, %llu to a window)", s, s + 1, s,
+                        (unsigned long long)(off[s + 1] - off[s]), (unsigned long long)want, ntok[(size_t)s], (unsigned long long)window);
+        row0[s] = off[s] - off[0];
+        sample_segments = std::max(sample_segments, (size_t)((ntok[(size_t)s] + dd::kSegTokens - 1) / dd::kSegTokens));
+    }
+    // the sort sees the universe only
+    in.slots = 0, in.max_segments = 0;
+    for (int g = 0; g < n; ++g) {
+        const size_t segs = (nbytes[g] + dd::kSegTokens - 1) / dd::kSegTokens;
+        in.slots += segs * dd::kSegTokens, in.max_segments = std::max(in.max_segments, segs);
+    }
+    const size_t ncol = (size_t)n + 2, cbytes = (size_t)rows * ncol * sizeof(uint32_t);
+    unsigned long long total = 0;
+    dd::ExactEmit e{};
+    if (tokens && in.slots) {
+        const size_t dcap = in.slots;
+        if (c->emit.reserve(exact_emit_bytes(dcap)))
+            return fail(DD_ENOMEM, "exact paint: no device memory for the %zu bytes of the record area (24 bytes per k-mer slot of the universe)",
+                        exact_emit_bytes(dcap));
+        if ((rc = exact_emit_records(c, in, n, k, "exact paint", 1, image.data(), image.size(), dcap, e, &total))) return rc;
+        if (total > dcap) return fail(DD_EHIP, "exact paint: %llu records emitted, the universe has %zu k-mer slots", total, dcap);
+    } else if (rows) {
+        if ((rc = stage_table(c, c->ord, image.data(), image.size()))) return rc;   // (no emission has staged it)
+    }
+    std::vector<uint32_t> host((size_t)rows * ncol);
+    if (rows) {
+        if (c->hits.reserve(cbytes))
+            return fail(DD_ENOMEM, "exact paint: no device memory for the %zu bytes of the windows' counters (%llu rows x %zu columns of 4 bytes)",
+                        cbytes, (unsigned long long)rows, ncol);
+        if (total && (rc = exact_emit_order_room(c, "exact paint", total, k))) return rc;
+        uint32_t* counts_dev = static_cast<uint32_t*>(c->hits.p);
+        DD_HIP(hipMemsetAsync(counts_dev, 0, cbytes, st));
+        {
+            Span sp(c, DD_KERNEL_EXACT);
+            dd::LocateSet set{};   // (an empty universe: no record, column 0 alone)
+            if (total) DD_HIP(dd::launch_exact_emit_order(e.lo, e.hi, e.mask, (size_t)total, k, c->exact.p, st, &set));
+            const unsigned long long* row0_dev = reinterpret_cast<const unsigned long long*>(static_cast<const char*>(c->ord.p) + pbytes);
+            dd::launch_exact_paint(in.etab_dev + n, ns, sample_segments, k, c->canonical, set, n, (size_t)(window / dd::kSegTokens), row0_dev,
+                                   counts_dev, st);
+            DD_HIP(hipGetLastError());
+        }
+        DD_HIP(hipMemcpyAsync(host.data(), counts_dev, cbytes, hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+        memcpy(counts + off[0] * ncol, host.data(), cbytes);   // (nothing is written before everything is known)
+    }
+    *found = total;
+    return DD_OK;
+}
+
+int dd_exact_paint(dd_ctx* c, const char* const* paths, int n, const char* const* samples, int ns, int k, uint64_t window,
+                   const uint64_t* off, uint32_t* counts, uint64_t* found) {
+    if (paint_args(c, paths, n, ns, k, window, off, found)) return DD_EINVAL;
+    if (!samples) return fail(DD_EINVAL, "null argument");
+    std::vector<const char*> files((size_t)(n + ns));
+    for (int i = 0; i < n + ns; ++i)
+        if (!(files[(size_t)i] = i < n ? paths[i] : samples[i - n])) return fail(DD_EINVAL, "null argument");
+    return exact_upload_files(c, files.data(), n + ns, [&](auto p, auto s) {
+        return dd_exact_paint_device(c, p, s, n, ns, k, window, off, counts, found);
     });
 }
 

@@ -421,6 +421,18 @@ void launch_exact_tally(const LocateSet& set, const uint32_t* seen_dev, size_t w
                         unsigned long long* shared_dev, unsigned long long* match_dev, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// samples that are no leaves, painted window by window (dd_exact_paint.hip), behind launch_exact_emit_order.
+// ---------------------------------------------------------------------------------------
+constexpr int kPaintPlanes = 7;           // bit planes of a thread's per-genome counters: a segment ends at most 64 = 1000000b k-mers
+constexpr size_t kPaintMaxWindow = (size_t)1 << 22;   // tokens of a window at the most (a multiple of kSegTokens, from kSegTokens on)
+// samples_dev[ns]: the samples' token streams (`base` is not read).  counts_dev [rows][n + 2] u32, zeroed by the caller:
+// sample s owns ceil(ntok_s / (64 window_segments)) rows from row0_dev[s] on, one per window of its token stream; row w,
+// column 0 += the tokens of the window at which a valid k-mer ends, column 1 += those whose k-mer is a record of `set`,
+// column 2 + i += those whose record's mask has bit i.  An empty set (found = 0, no array read) gives column 0 alone.
+void launch_exact_paint(const ExactGenome* samples_dev, int ns, size_t max_segments, int k, int canonical, const LocateSet& set, int n,
+                        size_t window_segments, const unsigned long long* row0_dev, uint32_t* counts_dev, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // exact greedy walk (dd_exact_greedy.hip) over the mask streams of kSchedStream: one launch per step of the walk reads
 // every stream once.  gain[kk][b] += masks of stream kk (store[seg.off[kk] .. seg.off[kk + 1])) that meet `chosen` nowhere
 // and hold bit b, for every b < 64 (a bit of `chosen` gains 0).  gain_dev [K][64], zeroed by the caller.

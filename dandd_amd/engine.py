@@ -37,6 +37,7 @@ EXPORTS = [
     "dd_exact_select_kmers", "dd_exact_select_kmers_device",
     "dd_exact_locate", "dd_exact_locate_device", "dd_fasta_index",
     "dd_exact_screen", "dd_exact_screen_device",
+    "dd_exact_paint", "dd_exact_paint_device",
     "dd_exact_patterns", "dd_exact_patterns_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
@@ -192,6 +193,10 @@ def load_library(path=None):
     lib.dd_exact_screen.argtypes = [vp, paths_t, i32, paths_t, i32, i32, vp, vp, i32, vp, vp, C.POINTER(u64)]
     lib.dd_exact_screen_device.restype = i32
     lib.dd_exact_screen_device.argtypes = [vp, ptrs_t, sizes_t, i32, i32, i32, vp, vp, i32, vp, vp, C.POINTER(u64)]
+    lib.dd_exact_paint.restype = i32
+    lib.dd_exact_paint.argtypes = [vp, paths_t, i32, paths_t, i32, i32, u64, vp, vp, C.POINTER(u64)]
+    lib.dd_exact_paint_device.restype = i32
+    lib.dd_exact_paint_device.argtypes = [vp, ptrs_t, sizes_t, i32, i32, i32, u64, vp, vp, C.POINTER(u64)]
     for name, src in (("dd_exact_patterns", [paths_t]), ("dd_exact_patterns_device", [ptrs_t, sizes_t])):
         fn = getattr(lib, name)
         fn.restype = i32
@@ -292,6 +297,31 @@ def regions_from_hits(words, k, tok_start, seq_len):
         last = np.append(first[1:], e.size) - 1
         out.append(np.stack([e[first] - k, e[last]], axis=1) if e.size else np.zeros((0, 2), dtype=np.int64))
     return out
+
+
+def paint_windows(nwin, window, tok_start, seq_len):
+    """Host-side, pure numpy: the windows of exact_paint (window w covers the tokens w * window .. (w + 1) * window - 1 of a
+    file's token stream) and the file's record index (fasta_index) -> (record int64 [nwin], start int64 [nwin], end int64
+    [nwin], records int64 [nwin]): the record that holds the window's first base, the 0-based half-open interval of that
+    record's bases the window covers, and the number of records the window touches (holds a base of).  A window without a
+    base -- nothing but BREAKs of empty records -- has record -1, the interval (0, 0) and 0 records."""
+    nwin, window = int(nwin), int(window)
+    starts, lens = np.asarray(tok_start, dtype=np.int64).reshape(-1), np.asarray(seq_len, dtype=np.int64).reshape(-1)
+    lo = np.arange(nwin, dtype=np.int64) * window
+    hi = lo + window                                                   # tokens [lo, hi)
+    full = np.flatnonzero(lens > 0)                                    # the records that hold a base, by token: ascending, disjoint
+    fs, fe = starts[full], starts[full] + lens[full]
+    first = np.searchsorted(fe, lo, side="right")                      # the first of them that ends behind the window's start
+    behind = np.searchsorted(fs, hi, side="left")                      # ... and the first that starts at or behind its end
+    count = np.maximum(behind - first, 0)
+    has = count > 0
+    at = np.where(has, first, 0)
+    record, start, end = np.full(nwin, -1, dtype=np.int64), np.zeros(nwin, dtype=np.int64), np.zeros(nwin, dtype=np.int64)
+    if full.size:
+        record[has] = full[at[has]]
+        start[has] = np.maximum(lo[has] - fs[at[has]], 0)
+        end[has] = np.minimum(hi[has], fe[at[has]]) - fs[at[has]]
+    return record, start, end, count.astype(np.int64)
 
 
 def kmer_text(kmers, k):
@@ -875,6 +905,42 @@ class Engine:
         ns = total - int(n)
         return self._exact_screen(lambda *rest: self._lib.dd_exact_screen_device(self._ctx, *args, int(n), ns, *rest),
                                   int(n), ns, k, all_masks, none_masks)
+
+    # -- samples painted window by window: the same records, then a walk that keeps the position (dd_exact_paint.hip) ------
+    last_paint_found = None   # of the last exact_paint call: the distinct k-mers of the universe
+    def _exact_paint(self, call, n, ns, k, window, ntok):
+        window = int(window)
+        off = np.zeros(max(ns, 0) + 1, dtype=np.uint64)
+        for s in range(ns):
+            off[s + 1] = off[s] + np.uint64(-(-int(ntok[s]) // window) if window > 0 and s < len(ntok) else 0)
+        rows = int(off[max(ns, 0)])
+        counts = np.zeros((max(rows, 1), max(n, 0) + 2), dtype=np.uint32)
+        found = C.c_uint64()
+        self._check(call(int(k), window, off.ctypes.data, counts.ctypes.data, C.byref(found)))
+        self.last_paint_found = int(found.value)
+        return [counts[int(off[s]):int(off[s + 1])].copy() for s in range(ns)]
+
+    def exact_paint(self, paths, samples, k, window, ntok=None):
+        """FASTA files (n <= 64: the universe), sample files (FASTA / FASTQ, plain or gzip, ns <= 1024), one k, a window of
+        `window` tokens (a multiple of 64 in 64 .. 2^22) -> list of uint32 [nwin_s][n+2] arrays, one per sample, a row per
+        window of the sample's token stream (paint_windows gives the windows' places in the records): column 0 the tokens of
+        the window at which a valid k-mer ends, column 1 those whose k-mer the universe holds, column 2 + i those whose k-mer
+        file i holds.  Counts are over positions.  ntok: the samples' token counts where the caller has them, else one
+        fasta_index per sample.  last_paint_found: the universe's distinct k-mers."""
+        if ntok is None:                                              # the shape of the answer: the samples' token counts
+            ntok = [fasta_index(p)[3] for p in samples]
+        pa = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        sa = (C.c_char_p * max(len(samples), 1))(*[os.fsencode(p) for p in samples])
+        return self._exact_paint(lambda *rest: self._lib.dd_exact_paint(self._ctx, pa, len(paths), sa, len(samples), *rest),
+                                 len(paths), len(samples), k, window, ntok)
+
+    def exact_paint_device(self, fasta_ptrs, nbytes, n, k, window, ntok):
+        """exact_paint over FASTA bytes on the device: the n universe inputs first, the samples behind them; ntok: every
+        sample's token count (the library checks them)."""
+        args, total, _ = self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes)
+        ns = total - int(n)
+        return self._exact_paint(lambda *rest: self._lib.dd_exact_paint_device(self._ctx, *args, int(n), ns, *rest),
+                                 int(n), ns, k, window, ntok)
 
     # -- the membership-pattern table: the distinct masks and how many k-mers carry each (dd_exact_patterns.hip) ------------
     last_patterns_stats = None   # of the last exact_patterns call: (distinct k-mers, pairs written to HBM, forced flushes, single masks)

@@ -375,6 +375,21 @@ class HipExactBackend:
             raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
         return self.engine.exact_screen(files, [str(f) for f in sample_files], int(k), all_masks, none_masks)
 
+    def paint_counts(self, leaf_paths, k, sample_files, window):
+        """files that are no leaves painted window by window with the leaves' k-mers at one k of the window (dd_exact_paint):
+        -> ([(names, seq_len, tok_start, ntok)] per sample, [uint32 [nwin][n+2]] per sample); a row per `window` tokens of
+        the sample's token stream: the positions where a valid k-mer ends, where the leaves hold it at all, and where leaf i
+        holds it (engine.paint_windows places the windows in the records)."""
+        from ..engine import fasta_index
+        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
+        if win is None:
+            return None
+        _, files, kmin, kmax = win
+        if not kmin <= int(k) <= kmax:
+            raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
+        index = [fasta_index(str(f)) for f in sample_files]
+        return index, self.engine.exact_paint(files, [str(f) for f in sample_files], int(k), int(window), ntok=[ix[3] for ix in index])
+
     def pattern_counts(self, leaf_paths, k, limit):
         """the distinct membership masks of the leaves at one k of the window and how many k-mers carry each
         (dd_exact_patterns): -> (masks uint64 [m], counts uint64 [m], found, distinct), count descending, ties by mask

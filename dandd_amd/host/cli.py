@@ -1,6 +1,7 @@
 """`dandd tree | progressive | kij | deltadelta | abba | greedy | core | screen | patterns` on the MI355X engine: same sub-commands, flags,
 defaults and output files as /root/reference/lib/dandd_cmd.py (flags :141-286, handlers :43-132); only the
 sketching backend differs.  (deltadelta, abba, greedy, core, screen and patterns are this package's own: the reference has none of them.)  Run as  python -m dandd_amd.host.cli <subcommand> ...
+`screen --paint W` adds where along each sample the collection's k-mers lie: one row per window of W bases.
 """
 import argparse
 import os
@@ -476,12 +477,17 @@ def screen_command(args):
     """New samples -- assemblies or read sets that are no leaves -- against the genomes of an exact tree: how much of each
     genome a sample contains and the other way round, which genome it is closest to, how much of it is in the pan-genome and
     the core, and with -g which group's core, private k-mers and signature it carries.  Counts are over distinct k-mers;
-    the samples enter no sort and change none of the collection's numbers."""
+    the samples enter no sort and change none of the collection's numbers.  --paint W adds the positional answer: every
+    sample in windows of W bases, counted over positions (_paint_rows)."""
     tree, outfile = _open_tree("screen", args, exact=True)
     ks = sorted(set(int(k) for k in args.ks)) if args.ks else [int(tree.root_k())]
     for k in ks:
         if not 1 <= k <= 64:
             sys.exit(f"screen: -k {k} is outside 1..64")
+    if args.paint is not None and (args.paint < 64 or args.paint % 64 or args.paint > 1 << 22):
+        sys.exit(f"screen: --paint {args.paint}: a window is a multiple of 64 bases in 64..{1 << 22}")
+    if args.paint_matrix and args.paint is None:
+        sys.exit("screen: --paint-matrix goes with --paint")
     names = list(args.samples)
     if args.query_loc:
         if not os.path.isfile(args.query_loc):
@@ -502,6 +508,7 @@ def screen_command(args):
     groups, labels = _groups_in_universe("screen", args, leaf_of, fastas)
     try:
         res = tree.screen_tables(fastas, samples, ks, groups)
+        painted = tree.paint_tables(fastas, samples, ks, args.paint) if args.paint is not None else None
     except (ValueError, OSError) as e:
         sys.exit("screen: " + " ".join(str(e).split()))
 
@@ -531,7 +538,49 @@ def screen_command(args):
                                                  "best_genome_containment"], summary)
     if groups:
         _write_csv(outfile + ".screen_groups.csv", ["sample", "k", "group", "class", "marker_kmers", "hits", "fraction"], marks)
+    if painted is not None:
+        windows, segments, matrix = _paint_rows(samples, fastas, painted)
+        _write_csv(outfile + ".paint.csv", ["sample", "k", "window", "tok_start", "tok_end", "record", "start", "end", "records", "valid", "in_pan",
+                                            "novel", "best_fasta", "best_shared", "second_fasta", "second_shared"], windows)
+        _write_csv(outfile + ".paint_segments.csv", ["sample", "k", "first_window", "last_window", "tok_start", "tok_end", "best_fasta", "valid",
+                                                     "in_pan", "best_shared"], segments)
+        if args.paint_matrix:
+            _write_csv(outfile + ".paint_matrix.csv", ["sample", "k", "window", *fastas], matrix)
     _finish(tree)
+
+
+def _paint_rows(samples, fastas, painted):
+    """paint_tables' counters -> the rows of <prefix>.paint.csv (one per sample, k and window: where the window lies, and
+    the two genomes that share most positions with it -- ties: the earlier genome of the universe; empty cells where nothing
+    is shared), of .paint_segments.csv (runs of consecutive windows of a sample and k with the same best genome; the windows
+    the universe holds nothing of form runs of their own, with an empty best_fasta: the novel stretches) and of
+    .paint_matrix.csv (the genomes' columns as they are)."""
+    from ..engine import paint_windows
+    W = painted["window"]
+    windows, segments, matrix = [], [], []
+    for s, sample in enumerate(samples):
+        names, seq_len, tok_start, ntok = painted["index"][s]
+        for kk, k in enumerate(painted["ks"]):
+            rows = painted["counts"][kk][s]
+            record, start, end, records = paint_windows(len(rows), W, tok_start, seq_len)
+            seg = seg_best = None                                        # the row of the segments in the making, and its best genome
+            for w, row in enumerate(rows):
+                valid, in_pan, cols = int(row[0]), int(row[1]), [int(v) for v in row[2:]]
+                order = sorted(range(len(cols)), key=lambda i: (-cols[i], i))
+                best = order[0] if in_pan else None
+                second = order[1] if in_pan and len(order) > 1 and cols[order[1]] else None
+                windows.append([sample, k, w, w * W, min((w + 1) * W, int(ntok)), names[record[w]] if record[w] >= 0 else None,
+                                int(start[w]), int(end[w]), int(records[w]), valid, in_pan, valid - in_pan,
+                                None if best is None else fastas[best], None if best is None else cols[best],
+                                None if second is None else fastas[second], None if second is None else cols[second]])
+                matrix.append([sample, k, w, *cols])
+                if seg is None or seg_best != best:
+                    seg, seg_best = [sample, k, w, w, w * W, 0, None if best is None else fastas[best], 0, 0, None if best is None else 0], best
+                    segments.append(seg)
+                seg[3], seg[5], seg[7], seg[8] = w, windows[-1][4], seg[7] + valid, seg[8] + in_pan
+                if best is not None:
+                    seg[9] += cols[best]
+    return windows, segments, matrix
 
 
 def patterns_command(args):
@@ -825,6 +874,12 @@ def build_parser():
     sc.add_argument("-q", "--queries", dest="query_loc", default=None, type=str, help="a file of sample paths, one per line")
     sc.add_argument("-k", dest="ks", action="append", type=int, default=None, metavar="K",
                     help="screen at this k (1..64, repeatable; default: the k of the tree's root)")
+    sc.add_argument("--paint", dest="paint", type=int, default=None, metavar="W",
+                    help="also paint every sample in windows of W bases (a multiple of 64): per window the positions whose k-mer the "
+                         "collection holds, the two genomes that share most of them (<prefix>.paint.csv) and the runs of windows with "
+                         "the same best genome, novel stretches among them (<prefix>.paint_segments.csv)")
+    sc.add_argument("--paint-matrix", dest="paint_matrix", default=False, action="store_true",
+                    help="with --paint: also write every genome's shared positions per window (<prefix>.paint_matrix.csv)")
     sc.add_argument("samples", nargs="*", metavar="SAMPLE", help="FASTA / FASTQ files, plain or gzip, that are no leaves of the tree")
     sc.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     sc.add_argument("-l", "--label", dest="label", default="")

@@ -1241,14 +1241,7 @@ class DeltaTree:
         for k in ks:
             if not 1 <= k <= 64:
                 raise ValueError(f"k={k} is outside 1..64")
-        batches, size = [[]], 0
-        for j, f in enumerate(samples):
-            b = os.path.getsize(f)
-            if batches[-1] and (len(batches[-1]) >= self.SCREEN_BATCH_FILES or size + b > self.SCREEN_BATCH_BYTES):
-                batches.append([])
-                size = 0
-            batches[-1].append(j)
-            size += b
+        batches = self._sample_batches(samples)
         out = {"ks": ks, "shared": np.zeros((len(ks), ns + 1, n), dtype=np.uint64), "match": np.zeros((len(ks), ns + 1, nq), dtype=np.uint64),
                "sample_kmers": np.zeros((len(ks), ns), dtype=np.uint64)}
         for kk, k in enumerate(ks):
@@ -1268,6 +1261,46 @@ class DeltaTree:
                     db = os.path.join(tmp, f"s{j}.k{k}")
                     be.leaf(f, [k], [db])
                     out["sample_kmers"][kk, j] = int(be.card(db))
+        return out
+
+    def _sample_batches(self, samples):
+        """indices of `samples` in batches of at most SCREEN_BATCH_FILES files or SCREEN_BATCH_BYTES bytes, whichever comes first"""
+        batches, size = [[]], 0
+        for j, f in enumerate(samples):
+            b = os.path.getsize(f)
+            if batches[-1] and (len(batches[-1]) >= self.SCREEN_BATCH_FILES or size + b > self.SCREEN_BATCH_BYTES):
+                batches.append([])
+                size = 0
+            batches[-1].append(j)
+            size += b
+        return batches
+
+    def paint_tables(self, fastas, samples, ks, window):
+        """Where along each of `samples` (files that are no leaves: FASTA / FASTQ, plain or gzip) the k-mers of the universe
+        `fastas` (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]) lie, at every k of `ks`: the sample's token stream
+        (one BREAK in front of every record's bases) in windows of `window` tokens, a multiple of 64, and per window the
+        positions where a valid k-mer ends, where the universe holds it, and where fastas[i] holds it -- positions, not
+        distinct k-mers.  The samples go to the backend's paint_counts in screen_tables' batches.  There is no object path:
+        a backend without paint_counts, or without a table for these leaves, is a ValueError.
+        -> dict: ks, window, index [ns] of (names, seq_len, tok_start, ntok), counts [K][ns] of uint32 [nwin_s][n+2]"""
+        n, ns, window = len(fastas), len(samples), int(window)
+        ks = [int(k) for k in ks]
+        for k in ks:
+            if not 1 <= k <= 64:
+                raise ValueError(f"k={k} is outside 1..64")
+        if window < 64 or window % 64 or window > 1 << 22:
+            raise ValueError(f"a window of {window} tokens: a multiple of 64 in 64..{1 << 22} is needed")
+        batches = self._sample_batches(samples)
+        out = {"ks": ks, "window": window, "index": [None] * ns, "counts": [[None] * ns for _ in ks]}
+        for kk, k in enumerate(ks):
+            u = self._universe(fastas, k, k)
+            u.need("paint_counts", why="painting needs")
+            for batch in batches:
+                index, counts = u.table(u.be.paint_counts(u.paths, k, [samples[j] for j in batch], window))
+                for j, ix, rows in zip(batch, index, counts):
+                    nwin = -(-int(ix[3]) // window)
+                    out["index"][j] = ix
+                    out["counts"][kk][j] = u.table(rows, (nwin, n + 2)).astype(np.uint32)
         return out
 
     # ---- which sets of genomes share k-mers (`dandd patterns`) --------------------------------------------------------------

@@ -334,6 +334,34 @@ int dd_exact_screen(dd_ctx *, const char *const *paths, int n, const char *const
 int dd_exact_screen_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
                            const uint64_t *all, const uint64_t *none, int nq, uint64_t *shared, uint64_t *match,
                            uint64_t *found);
+/* ---- samples painted window by window ---------------------------------------------------------------------------
+ * dd_exact_screen says how much of a sample each input holds; this says WHERE along the sample (dd_exact_paint.hip): the
+ * token stream of every sample as K0 lays it out (dd_fasta_index below) is cut into windows of `window` tokens, window w
+ * covering the tokens w * window .. (w + 1) * window - 1, and every window gets a row of n + 2 counters.  A k-mer belongs to
+ * the window that holds its END token (dd_exact_locate's convention).  ONE k per call, 1 <= k <= 64, 1 <= n <= 64 universe
+ * inputs, 1 <= ns <= 1024 samples; `window` a multiple of 64 in 64 .. 1 << 22, anything else is DD_EINVAL with a message.
+ *   counts    sample s owns the rows off[s] .. off[s+1]-1, n + 2 columns of 32 bits each, counting the tokens of the window
+ *             at which
+ *               column 0      a valid k-mer ends (no BREAK among its k tokens; canonical per the context)
+ *               column 1      that k-mer is a k-mer of the universe
+ *               column 2 + i  that k-mer's membership mask has bit i: input i holds it
+ *             Counts are over POSITIONS, not distinct k-mers: a k-mer that stands three times in a window counts three
+ *             times (dd_exact_screen is the distinct count).  off[s+1] - off[s] must be ceil(ntok / window) of sample s, else
+ *             DD_EINVAL with a message naming the sample and the number expected; counts may be null only when no row is
+ *             asked for.  Nothing is written to counts unless the call returns DD_OK.
+ *   *found    the distinct k-mers of the universe
+ * An empty sample has no rows, one shorter than k has all-zero rows, an empty universe gives column 0 only; a sample may be
+ * byte-identical to an input.  Two calls on the same inputs return identical bytes (integer sums).  The device form takes
+ * n + ns buffers: the n universe inputs first, the ns samples behind them.
+ * The sort, the masks, the emission (the single query (0, 0)) and the ordering are dd_exact_screen's, so are budget and
+ * passes (DD_EXACT_MB), dd_last_sketch_stats' third value and the DD_KERNEL_EXACT timer; the samples are tokenised with the
+ * universe but stay out of the sort and out of the slot count that sizes the record area.  The rows wait in
+ * off[ns] - off[0] rows x (n + 2) x 4 bytes of HBM (DD_ENOMEM with a message naming the bytes when that cannot be had). */
+int dd_exact_paint(dd_ctx *, const char *const *paths, int n, const char *const *samples, int ns, int k,
+                   uint64_t window, const uint64_t *off /*[ns+1], in windows*/,
+                   uint32_t *counts /*[off[ns]][n+2]*/, uint64_t *found);
+int dd_exact_paint_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
+                          uint64_t window, const uint64_t *off, uint32_t *counts, uint64_t *found);
 /* ---- the membership-pattern table ------------------------------------------------------------------------------
  * Which sets of inputs share k-mers, and how many: the DISTINCT membership masks of the universe with their multiplicities
  * (the table behind an UpSet plot; every other mask statistic above -- spectrum, select, a subset union -- is a sum over
@@ -402,7 +430,7 @@ int dd_exact_greedy_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen; the accumulation, merges and ordering of dd_exact_patterns */
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen; the emission, ordering and window walk of dd_exact_paint; the accumulation, merges and ordering of dd_exact_patterns */
 #define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);
