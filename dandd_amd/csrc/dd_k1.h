@@ -13,39 +13,69 @@ namespace dd {
 
 extern __shared__ __attribute__((aligned(16))) uint8_t g_lds[];
 
-DD_D uint32_t ffbh(uint32_t x) {  // leading zeros; 0xFFFFFFFF for x == 0
+// The arithmetic of hash and probe is host-visible: the instruction forms are the device's, plain C the host's, so that
+// tests/native/k1_hash.hip can run it against dd::wang64 and the definitions without a GPU.
+DD_HD uint32_t ffbh(uint32_t x) {  // leading zeros; 0xFFFFFFFF for x == 0
+#if defined(__HIP_DEVICE_COMPILE__)
     uint32_t r;
     asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(x));
     return r;
+#else
+    return x ? (uint32_t)__builtin_clz(x) : ~0u;
+#endif
 }
-DD_D uint32_t mul_lo(uint32_t a, uint32_t c) {  // opaque to the optimiser: stays one v_mul_lo_u32
+DD_HD uint32_t mul_lo(uint32_t a, uint32_t c) {  // opaque to the optimiser: stays one v_mul_lo_u32
+#if defined(__HIP_DEVICE_COMPILE__)
     uint32_t r;
     asm("v_mul_lo_u32 %0, %1, %2" : "=v"(r) : "v"(a), "s"(c));
     return r;
+#else
+    return a * c;
+#endif
+}
+// bits [s, s + 32) of hi:lo.  The count is taken modulo 32, as v_alignbit_b32 takes it: 32 gives lo, not hi.
+DD_HD uint32_t funnel32(uint32_t hi, uint32_t lo, uint32_t s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(hi, lo, s);
+#else
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (s & 31));
+#endif
 }
 template <int SH>
-DD_D uint64_t lshl_add64(uint64_t a, uint64_t b) {  // (a << SH) + b, SH in 0..4, one instruction
+DD_HD uint64_t lshl_add64(uint64_t a, uint64_t b) {  // (a << SH) + b, SH in 0..4, one instruction
+#if defined(__HIP_DEVICE_COMPILE__)
     uint64_t r;
     asm("v_lshl_add_u64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "n"(SH), "v"(b));
     return r;
+#else
+    return (a << SH) + b;
+#endif
 }
-// x * C + addend (mod 2^64), C a 32-bit constant: v_mad_u64_u32 + v_mul_lo_u32 + v_add_u32
+// x * C + addend (mod 2^64), C a 32-bit constant: v_mad_u64_u32 + v_mul_lo_u32 + v_add_u32 (HI_ZERO, x < 2^32: the mad alone)
 template <bool HI_ZERO>
-DD_D uint64_t mul64_c32(uint64_t x, uint32_t C, uint64_t addend) {
+DD_HD uint64_t mul64_c32(uint64_t x, uint32_t C, uint64_t addend) {
     const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
     const uint64_t pr = (uint64_t)lo * C + addend;
     if (HI_ZERO) return pr;
     const uint32_t ph = (uint32_t)(pr >> 32) + mul_lo(hi, C);
     return ((uint64_t)ph << 32) | (uint32_t)pr;
 }
+// x * C (mod 2^64) with nothing to add: the high product goes in as the mad's addend, lo * C + (mul_lo(hi, C) << 32) --
+// v_mul_lo_u32 writes the odd half of a register pair whose even half stays zero, v_mad_u64_u32 takes the pair as src2, and
+// the v_add_u32 of mul64_c32 is gone.  (Not for x * (2^21 - 1) - 1: the high word of that addend would be hi * C - 1, and
+// every way to it -- (hi << 21) + ~hi, the modular inverse, a 64-bit -1 behind -- costs the instruction back.)
+DD_HD uint64_t mul64_c32_fold(uint64_t x, uint32_t C) {
+    const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+    return (uint64_t)lo * C + ((uint64_t)mul_lo(hi, C) << 32);
+}
 
-// Thomas Wang 64-bit mix, identical to dd::wang64 (asserted on every lane by the GPU parity tests),
-// arranged for the gfx950 issue costs (dd_sweep.hip, head): 18 instructions.
+// Thomas Wang 64-bit mix, identical to dd::wang64 (tests/native/k1_hash.hip on the host; asserted on every lane by the
+// GPU parity tests), arranged for the gfx950 issue costs (dd_sweep.hip, head): 18 instructions, 16 for HI_ZERO.
 template <bool HI_ZERO>
-DD_D uint64_t wang64_fast(uint64_t x) {
+DD_HD uint64_t wang64_fast(uint64_t x) {
     x = mul64_c32<HI_ZERO>(x, 0x1FFFFFu, ~0ull);  // ~x + (x << 21) = x * (2^21 - 1) - 1
     x ^= x >> 24;
-    x = mul64_c32<false>(x, 265u, 0ull);          // x + (x << 3) + (x << 8)
+    x = mul64_c32_fold(x, 265u);                  // x + (x << 3) + (x << 8)
     x ^= x >> 14;
     x = lshl_add64<2>(lshl_add64<2>(x, x), x);    // x + (x << 2) + (x << 4) = ((5x) << 2) + x
     x ^= x >> 28;
@@ -63,7 +93,7 @@ struct RegsLds {
     uint32_t slot;  // the slot's registers start at byte slot << p of g_lds
     using Addr = uint32_t;
     // address of register  hi >> (32-p)  (the top p bits of the hash): one v_alignbit of slot:hi
-    DD_D Addr at(uint32_t hi, int p) const { return __builtin_amdgcn_alignbit(slot, hi, 32 - p); }
+    DD_HD Addr at(uint32_t hi, int p) const { return funnel32(slot, hi, 32u - (uint32_t)p); }
     DD_D static uint32_t shift(Addr a) { return (a & 3u) * 8u; }
     // Registers are read at their ABSOLUTE LDS address: every kernel that uses this struct has no static LDS, so the
     // dynamic array g_lds starts at 0 (lds_starts_at_zero() at the top of each checks it), and indexing through the
@@ -103,11 +133,11 @@ DD_D uint32_t load4_fresh(const uint32_t* p) { return gload4_fresh(p); }
 struct Probe {
     uint32_t hi, lz, hiw, lo;
 };
-DD_D Probe probe(uint64_t h, int p) {
+DD_HD Probe probe(uint64_t h, int p) {
     const uint32_t hi = (uint32_t)(h >> 32), lo = (uint32_t)h;
     Probe r;
     r.hi = hi;
-    r.hiw = __builtin_amdgcn_alignbit(hi, lo, 32 - p);  // bits 63..32 of (h << p)
+    r.hiw = funnel32(hi, lo, 32u - (uint32_t)p);  // bits 63..32 of (h << p)
     r.lz = ffbh(r.hiw);
     r.lo = lo;
     return r;
@@ -260,14 +290,6 @@ DD_HD uint32_t pairrev32(uint32_t x) {
     return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
 }
 DD_HD uint64_t pack64(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | lo; }
-// bits [s, s + 32) of hi:lo.  The count is taken modulo 32, as v_alignbit_b32 takes it: 32 gives lo, not hi.
-DD_HD uint32_t funnel32(uint32_t hi, uint32_t lo, uint32_t s) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_alignbit(hi, lo, s);
-#else
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (s & 31));
-#endif
-}
 
 // ---- a segment's token words, prepared once for the slices of its 64 tokens -----------------------------------------------
 // Words 0..3 are the halo (the previous segment), 4..7 the segment.  A window is a slice of the token stream: behind token i

@@ -19,8 +19,10 @@
 // everything else used here (v_lshlrev_b32, v_alignbit, v_mul_lo_u32, v_ffbh, v_cmp, v_cndmask and
 // every 64-bit op: v_lshrrev_b64, v_lshl_add_u64, v_mad_u64_u32, v_cmp_lt_u64) ~4.2 cycles.  A 64-bit
 // instruction therefore costs the same as one 32-bit shift, so the hash (dd_k1.h) is written in 64-bit
-// instructions and 32-bit work is steered to the cheap class.  HBM traffic is 3 bits per token
-// per k-group.  No MFMA: this is hashing, not a contraction.
+// instructions -- 18 of them, 16 where the key has one word -- and 32-bit work is steered to the cheap class.
+// Per token of a BREAK-free wave the canonical kernels issue (token-loop head + one k-pair body up to the "no register
+// rises" branch, profiles/k1_hash17.txt): 2 + 47 for k 10..16, 4 + 55 for k 17..32, 6 + 73 for k 33..48.
+// HBM traffic is 3 bits per token per k-group.  No MFMA: this is hashing, not a contraction.
 //
 // This file: the registers-in-LDS family (log2m <= 16: sweep_kernel) and the set classes (bitmap_kernel, bigmap_kernel and their
 // finish kernels).  The record path of log2m >= 17 is dd_scatter.hip; what both share (hash, windows, tile input, token walk,
@@ -39,6 +41,10 @@ DD_D void sweep_token(const Win& win, int run, int kfirst, int nk, int p, RaiseQ
     // scalar); in the CHECK variant lanes whose run is too short for k hash their window all the same and are
     // left out of the update (ok), and the ks no lane of the wave has a window for are skipped.
     constexpr bool QUEUE = KC != 0;
+    // nk as an opaque scalar copy: the odd-k test `j < nk` behind the pair loop then stays an s_cmp.  Without it the
+    // compiler hoists the loop-invariant `nk < 2` out of the caller's token loop as a lane mask and re-makes it per token
+    // with a v_cndmask_b32 + v_cmp_ne_u32 pair (profiles/k1_sliced_windows.txt, section 3).
+    asm volatile("" : "+s"(nk));
     int j = 0;
 #pragma unroll 1
     for (; j + 1 < nk; j += 2) {
