@@ -70,7 +70,7 @@ void dd_destroy(dd_ctx* c) {
     for (auto e : c->pool) (void)hipEventDestroy(e);
     for (auto& pe : c->plans) pe.jobtab.release();
     for (DevBuf* b : {&c->tokens, &c->scratch, &c->tables, &c->fasta, &c->regs, &c->ptrs, &c->hist,
-                      &c->est, &c->ord, &c->bitmaps, &c->bigmaps, &c->exact, &c->buckets, &c->gram, &c->synth, &c->masks, &c->emit, &c->hits, &c->pat[0], &c->pat[1]})
+                      &c->est, &c->ord, &c->bitmaps, &c->bigmaps, &c->exact, &c->buckets, &c->gram, &c->synth, &c->masks, &c->emit, &c->hits, &c->pat[0], &c->pat[1], &c->universe})
         b->release();
     for (StageSet& s : c->stage) {
         if (s.free) (void)hipEventDestroy(s.free);

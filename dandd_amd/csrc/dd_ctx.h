@@ -122,6 +122,10 @@ struct dd_ctx {
     DevBuf hits;   // dd_exact_locate: the jobs' hit bitmaps, off[njobs] words; dd_exact_screen: counters [ns + 1][n + nq] | the samples' seen bitmaps;
                    // dd_exact_paint: the windows' counters, off[ns] - off[0] rows of n + 2 x 32 bits
     DevBuf pat[2]; // dd_exact_patterns: the running table in mask order (masks | counts) and where the next merge puts it, in turns
+    // saturation (dd_kernels.h): sketch(U_k) for k = kSatMinK..kSatMaxK at this context's log2m and strand mode, [k - kSatMinK][m];
+    // a row is built by the first call that needs it, on that call's stream, and kept
+    DevBuf universe;
+    bool universe_built[dd::kSatMaxK - dd::kSatMinK + 1] = {};
     StageSet stage[2];
     int stage_cur = 0;  // the set of the running (or last) sketch call
     // the job tables of the last few sketch calls: a call over genomes of the same sizes and the same k range (a

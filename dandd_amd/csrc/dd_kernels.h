@@ -79,6 +79,7 @@ struct SweepGenome {            // one per genome, device-resident table
     uint8_t* regs;              // [K][m] for this genome
     uint32_t* bitmap;           // presence bitmaps of the canonical k-mers, k = 1..kBitmapMaxK (or null)
     uint32_t* bigmap;           // presence bitmaps of k = 10 (, 11) at log2m >= 19 (or null): bigmap_offset_words
+    uint32_t* sat;              // one "saturated" flag per row of the genome's slab, zeroed per call (or null: no early exit in this call)
 };
 
 // Small-k path: for k <= kBitmapMaxK there are at most 4^k <= 262144 distinct k-mers, so K1 only
@@ -136,8 +137,21 @@ struct SweepPlan {
     unsigned cap_chunks = 0;    // 1024-record chunks per row and epoch
     int nepochs = 0;
 };
+// Saturation (log2m <= 16, k = kSatMinK..kSatMaxK): the k-mer universe U_k is finite, registers are byte maxima, so a row can
+// never pass sketch(U_k) -- the row all (canonical) k-mers hashed once give -- and a row that EQUALS it is final, long before
+// the set of its k-mers is complete: only the one k-mer that holds each register's maximum has to have been seen (about
+// |U_k| (ln m + 0.58) tokens of random text).  sweep_kernel compares at its merge, raises SweepGenome::sat of the row, and
+// jobs that start later leave a flagged prefix of their group out.  universe: [k - kSatMinK][m], rows kSatMinK..universe_last_k
+// built (launch_universe); universe_last_k = 0: no row is compared or skipped.
+constexpr int kSatMinK = 10, kSatMaxK = 14;
+// |U_k|: the k-mers there are, a k-mer and its reverse complement counted once in canonical mode (even k has palindromes)
+inline constexpr size_t universe_size(int k, bool canon) {
+    return canon ? ((size_t)1 << (2 * k - 1)) + ((k & 1) ? 0 : ((size_t)1 << (k - 1))) : (size_t)1 << (2 * k);
+}
+// row_dev[m] = sketch(U_k), zeroed here; log2m <= 16
+void launch_universe(uint8_t* row_dev, int k, int log2m, int canonical, hipStream_t st);
 void launch_sweep(const SweepGenome* genomes_dev, const SweepJob* jobs_dev, int njobs, int kclass,
-                  const SweepPlan& plan, hipStream_t st);
+                  const SweepPlan& plan, const uint8_t* universe_dev, int universe_last_k, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
 // K1 for log2m >= 17 (one register array does not fit LDS twice per CU, or at all; DandD's default is -r 20,

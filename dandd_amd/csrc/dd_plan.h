@@ -31,10 +31,13 @@ struct PlanKnobs {
     size_t bucket_cap_chunks = 0;   // DD_BUCKET_CAP: 1024-record chunks per row's stream; 0 = every token of the first epoch fits
     size_t bucket_budget = (size_t)16 << 30;  // DD_BUCKET_GB: HBM for the record areas of one call
     bool bigmap_any_size = false;   // DD_BIGMAP_ANY_SIZE (tests): the exact-set class whatever the genomes' sizes
+    bool saturate_any_size = false; // DD_SATURATE_ANY_SIZE (tests): the saturation exit (plan_saturate_last_k) whatever the genomes' sizes
+    bool no_saturate = false;       // DD_NO_SATURATE: no saturation exit at all
     static PlanKnobs from_env();
     bool operator==(const PlanKnobs& o) const {
         return bucket_e0_tiles == o.bucket_e0_tiles && bucket_emax_tiles == o.bucket_emax_tiles && bucket_cap_chunks == o.bucket_cap_chunks &&
-               bucket_budget == o.bucket_budget && bigmap_any_size == o.bigmap_any_size;
+               bucket_budget == o.bucket_budget && bigmap_any_size == o.bigmap_any_size &&
+               saturate_any_size == o.saturate_any_size && no_saturate == o.no_saturate;
     }
 };
 
@@ -42,6 +45,11 @@ struct PlanKnobs {
 // (`nbytes`: the call's genomes -- an exact set only pays when a genome has several times more tokens than the
 // set can have members, because every index tile's workgroup hashes the whole set afterwards)
 bool plan_bigmap_range(int log2m, int kmin, int kmax, const PlanKnobs& knobs, const size_t* nbytes, int ngenomes, int* ka, int* kb);
+// The last k of a call whose rows are checked against sketch(U_k) (dd_kernels.h, saturation), 0: none.  The ks are those of
+// the call's range in kSatMinK..kSatMaxK for which some genome has nbytes >= 8 |U_k|: below that a row is not expected to
+// saturate (random text needs |U_k| (ln m + 0.58) tokens) and the compare at every merge would only cost.  |U_k| grows with
+// k, so they are a prefix of the hashed ks: max(kmin, kSatMinK) .. the value returned.  log2m <= 16 only (registers in LDS).
+int plan_saturate_last_k(int log2m, int canonical, int kmin, int kmax, const PlanKnobs& knobs, const size_t* nbytes, int ngenomes);
 std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbytes, int ngenomes, int kmin,
                                    int kmax, const PlanKnobs& knobs);
 

@@ -14,6 +14,8 @@ namespace dd {
 PlanKnobs PlanKnobs::from_env() {
     PlanKnobs k;
     k.bigmap_any_size = getenv("DD_BIGMAP_ANY_SIZE") != nullptr;
+    k.saturate_any_size = getenv("DD_SATURATE_ANY_SIZE") != nullptr;
+    k.no_saturate = getenv("DD_NO_SATURATE") != nullptr;
     if (const char* e = getenv("DD_BUCKET_E0")) k.bucket_e0_tiles = (size_t)std::max(1, atoi(e));
     if (const char* e = getenv("DD_BUCKET_EMAX")) k.bucket_emax_tiles = (size_t)std::max(1, atoi(e));
     if (const char* e = getenv("DD_BUCKET_CAP")) k.bucket_cap_chunks = (size_t)std::max(1, atoi(e));
@@ -59,6 +61,15 @@ bool plan_bigmap_range(int log2m, int kmin, int kmax, const PlanKnobs& knobs, co
     if (ka) *ka = a;
     if (kb) *kb = b;
     return true;
+}
+
+int plan_saturate_last_k(int log2m, int canonical, int kmin, int kmax, const PlanKnobs& knobs, const size_t* nbytes, int ngenomes) {
+    if (knobs.no_saturate || log2m < 4 || log2m >= kBucketFromLog2m || ngenomes <= 0) return 0;
+    size_t longest = 0;
+    for (int g = 0; g < ngenomes; ++g) longest = std::max(longest, nbytes[g]);
+    int last = std::min(kmax, kSatMaxK);
+    while (!knobs.saturate_any_size && last >= kSatMinK && longest < 8 * universe_size(last, canonical != 0)) --last;
+    return last >= std::max(kmin, kSatMinK) ? last : 0;
 }
 
 std::vector<SweepClass> plan_sweep(int log2m, int canonical, const size_t* nbytes, int ngenomes, int kmin,

@@ -34,14 +34,17 @@ struct SideLanes {
 
 // The presence-bitmap workspaces of a call, reserved and zeroed: for the small-k class (k <= 9) and for k = 10 (, 11) at
 // log2m >= 19 (dd_kernels.h).  Genome g's are at small + g * kBitmapStride and big + g * big_stride; null: class not planned.
-struct Bitmaps { uint32_t* small = nullptr; uint32_t* big = nullptr; size_t big_stride = 0; };
-static int reserve_bitmaps(dd_ctx* c, const dd::PlanKnobs& knobs, const size_t* nbytes, int ngenomes, int kmin, int kmax, Bitmaps& bm) {
+// sat (sat_words of them, 0: none): the call's saturation flags (dd_kernels.h), one per row, behind the small bitmaps in the same
+// allocation and zeroed by the same memset -- by one of their own only in a call that has flags and no small-k class.
+struct Bitmaps { uint32_t* small = nullptr; uint32_t* big = nullptr; size_t big_stride = 0; uint32_t* sat = nullptr; };
+static int reserve_bitmaps(dd_ctx* c, const dd::PlanKnobs& knobs, const size_t* nbytes, int ngenomes, int kmin, int kmax, size_t sat_words, Bitmaps& bm) {
     int rc, ka = 0, kb = 0;
-    if (kmin <= dd::kBitmapMaxK) {
-        const size_t bbytes = (size_t)ngenomes * dd::kBitmapStride * sizeof(uint32_t);
+    if (kmin <= dd::kBitmapMaxK || sat_words) {
+        const size_t words = kmin <= dd::kBitmapMaxK ? (size_t)ngenomes * dd::kBitmapStride : 0, bbytes = (words + sat_words) * sizeof(uint32_t);
         if ((rc = c->bitmaps.reserve(bbytes))) return rc;
-        bm.small = static_cast<uint32_t*>(c->bitmaps.p);
-        DD_HIP(hipMemsetAsync(bm.small, 0, bbytes, c->stream));
+        if (words) bm.small = static_cast<uint32_t*>(c->bitmaps.p);
+        if (sat_words) bm.sat = static_cast<uint32_t*>(c->bitmaps.p) + words;
+        DD_HIP(hipMemsetAsync(c->bitmaps.p, 0, bbytes, c->stream));
     }
     if (dd::plan_bigmap_range(c->p, kmin, kmax, knobs, nbytes, ngenomes, &ka, &kb)) {
         bm.big_stride = dd::bigmap_offset_words(kb + 1, c->canonical != 0);
@@ -111,7 +114,23 @@ static int upload_bucket_rows(dd_ctx* c, StageSet& stage, const std::vector<dd::
     return DD_OK;
 }
 
-static void launch_lds_class(dd_ctx* c, const dd::SweepClass& sc, const dd::SweepGenome* gt, const dd::SweepJob* jt, int ngenomes, int kmin, hipStream_t ks) {
+// The rows of sketch(U_k) that a call compares its rows with (dd_kernels.h, saturation): max(kfirst, kSatMinK) .. last_k, built here on the
+// call's stream where this context has not built them yet.  last_k = 0: the call has no saturation exit.
+static int ensure_universe(dd_ctx* c, int kfirst, int last_k) {
+    if (!last_k) return DD_OK;
+    const size_t m = (size_t)1 << c->p;
+    int rc;
+    if ((rc = c->universe.reserve((size_t)(dd::kSatMaxK - dd::kSatMinK + 1) * m))) return rc;
+    for (int k = std::max(kfirst, dd::kSatMinK); k <= last_k; ++k) {
+        if (c->universe_built[k - dd::kSatMinK]) continue;
+        dd::launch_universe(static_cast<uint8_t*>(c->universe.p) + (size_t)(k - dd::kSatMinK) * m, k, c->p, c->canonical, c->stream);
+        DD_HIP(hipGetLastError());
+        c->universe_built[k - dd::kSatMinK] = true;
+    }
+    return DD_OK;
+}
+
+static void launch_lds_class(dd_ctx* c, const dd::SweepClass& sc, const dd::SweepGenome* gt, const dd::SweepJob* jt, int ngenomes, int kmin, int sat_last_k, hipStream_t ks) {
     if (sc.kclass == dd::kBitmapClass) {
         dd::launch_bitmap(gt, jt, (int)sc.jobs.size(), sc.kfirst, sc.klast, c->canonical, ks);
         dd::launch_bitmap_finish(gt, ngenomes, sc.kfirst, sc.klast, kmin, c->p, ks);
@@ -119,7 +138,7 @@ static void launch_lds_class(dd_ctx* c, const dd::SweepClass& sc, const dd::Swee
         dd::launch_bigmap(gt, jt, (int)sc.jobs.size(), c->canonical, ks);
         dd::launch_bigmap_finish(gt, ngenomes, sc.kfirst, sc.klast, kmin, c->p, c->canonical, ks);
     } else {
-        dd::launch_sweep(gt, jt, (int)sc.jobs.size(), sc.kclass, sc.plan, ks);
+        dd::launch_sweep(gt, jt, (int)sc.jobs.size(), sc.kclass, sc.plan, static_cast<const uint8_t*>(c->universe.p), sat_last_k, ks);
     }
 }
 
@@ -137,7 +156,7 @@ static void launch_lds_class(dd_ctx* c, const dd::SweepClass& sc, const dd::Swee
 // kernels (profiles/r04_bucket_path.txt); calls with filtered epochs keep the side streams (26.8 against 24.9 ms without).
 // The plan lists its LDS classes before its bucket classes (tests/test_plan.py), so pipelines on the caller's stream start
 // behind the joins of the LDS classes.  *blocks: the workgroups launched.
-static int launch_classes(dd_ctx* c, const dd_ctx::PlanEntry& plan, const dd::SweepGenome* gtab, const dd::BucketRow* rows, int ngenomes, int kmin, int kmax, int* blocks) {
+static int launch_classes(dd_ctx* c, const dd_ctx::PlanEntry& plan, const dd::SweepGenome* gtab, const dd::BucketRow* rows, int ngenomes, int kmin, int kmax, int sat_last_k, int* blocks) {
     const int K = kmax - kmin + 1;
     size_t lds_jobs = 0;
     int lds_classes = 0, nepochs = 0, rc;
@@ -159,7 +178,7 @@ static int launch_classes(dd_ctx* c, const dd_ctx::PlanEntry& plan, const dd::Sw
         rc = lanes.run(on_lane, [&](hipStream_t ks) {
             if (!bucket) {
                 Span span(c, DD_KERNEL_SWEEP, !on_lane);
-                launch_lds_class(c, sc, gtab, jobs, ngenomes, kmin, ks);
+                launch_lds_class(c, sc, gtab, jobs, ngenomes, kmin, sat_last_k, ks);
             }
             const dd::ScatterParams sp{rows, K, sc.plan.logg, sc.plan.cap_chunks, sc.plan.nb_log2};
             for (int e = 0; bucket && e < sc.plan.nepochs; ++e) {
@@ -205,13 +224,16 @@ int dd_sketch_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* n
     Bitmaps bm;
     int rc;
     if ((rc = layout_tokens(c, fasta_dev, nbytes, ngenomes, ptab, max_chunks))) return rc;
-    if ((rc = reserve_bitmaps(c, knobs, nbytes, ngenomes, kmin, kmax, bm))) return rc;
+    const int sat_last_k = dd::plan_saturate_last_k(c->p, c->canonical, kmin, kmax, knobs, nbytes, ngenomes);
+    if ((rc = reserve_bitmaps(c, knobs, nbytes, ngenomes, kmin, kmax, sat_last_k ? (size_t)ngenomes * K : 0, bm))) return rc;
+    if ((rc = ensure_universe(c, kmin, sat_last_k))) return rc;
     std::vector<dd::SweepGenome> gtab(ngenomes);
     for (int g = 0; g < ngenomes; ++g) {
         const dd::TokenStream& ts = ptab[g].out;
         gtab[g] = dd::SweepGenome{ts.codes, ts.bad, ts.ntok, regs_dev + (size_t)g * K * m,
                                   bm.small ? bm.small + (size_t)g * dd::kBitmapStride : nullptr,
-                                  bm.big ? bm.big + (size_t)g * bm.big_stride : nullptr};
+                                  bm.big ? bm.big + (size_t)g * bm.big_stride : nullptr,
+                                  bm.sat ? bm.sat + (size_t)g * K : nullptr};
     }
 
     // genome tables up, K0 launched: the K1 job tables are planned on the host meanwhile
@@ -237,7 +259,7 @@ int dd_sketch_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* n
     if ((rc = cached_plan(c, stage, knobs, nbytes, ngenomes, kmin, kmax, &plan))) return rc;
     if ((rc = upload_bucket_rows(c, stage, plan->classes, ngenomes, kmin, kmax, regs_dev, &rows_dev))) return rc;
     DD_HIP(hipEventRecord(stage.free, c->stream));
-    if ((rc = launch_classes(c, *plan, reinterpret_cast<const dd::SweepGenome*>(tdev), rows_dev, ngenomes, kmin, kmax, &blocks))) return rc;
+    if ((rc = launch_classes(c, *plan, reinterpret_cast<const dd::SweepGenome*>(tdev), rows_dev, ngenomes, kmin, kmax, sat_last_k, &blocks))) return rc;
     c->st_tokens = tokens_ub;
     c->st_updates = tokens_ub * (uint64_t)K;
     c->st_blocks = blocks;

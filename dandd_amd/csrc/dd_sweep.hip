@@ -24,6 +24,9 @@
 // rises" branch, profiles/k1_hash17.txt): 2 + 47 for k 10..16, 4 + 55 for k 17..32, 6 + 73 for k 33..48.
 // HBM traffic is 3 bits per token per k-group.  No MFMA: this is hashing, not a contraction.
 //
+// Rows of k = 10..14 that have reached sketch(U_k), the row of all k-mers (universe_kernel), are flagged at the merge and left
+// out by the jobs that start later (dd_kernels.h, saturation; profiles/k1_saturation.txt): outside the token loop.
+//
 // This file: the registers-in-LDS family (log2m <= 16: sweep_kernel) and the set classes (bitmap_kernel, bigmap_kernel and their
 // finish kernels).  The record path of log2m >= 17 is dd_scatter.hip; what both share (hash, windows, tile input, token walk,
 // launch helpers) is dd_k1.h.
@@ -65,14 +68,39 @@ DD_D void sweep_token(const Win& win, int run, int kfirst, int nk, int p, RaiseQ
 // The registers of the job's k-group live in LDS (2^p * nk bytes <= 160 KiB): log2m <= 16.
 template <int KC, bool CANON>
 __global__ __launch_bounds__(1024) void sweep_kernel(const SweepGenome* __restrict__ genomes,
-                                                    const SweepJob* __restrict__ jobs, int p, uint32_t queue_off) {
+                                                    const SweepJob* __restrict__ jobs, int p, uint32_t queue_off,
+                                                    const uint8_t* __restrict__ universe, int universe_last_k) {
     lds_starts_at_zero();
     const SweepJob job = jobs[blockIdx.x];
     const SweepGenome g = genomes[job.genome];
-    const int nk = job.nk, kfirst = job.kfirst;
+    int nk = job.nk, kfirst = job.kfirst, krow = job.krow;
     const uint32_t m = 1u << p;
+
+    // Saturation (dd_kernels.h; the 32-bit class only: universe rows exist for k <= kSatMaxK): the first nsat rows of the group
+    // have a universe row.  Those of them that earlier jobs found equal to it are final: a flagged PREFIX of the group is left
+    // out (smaller k saturates first, and the ks that remain stay consecutive, the LDS layout compact).
+    // ONE thread reads the flags for the workgroup (bitmap_kernel: waves that read at different times would disagree), and
+    // the count goes through a word of g_lds -- this kernel has no static LDS (lds_starts_at_zero) --, with a barrier on
+    // each side before the warm start overwrites it.  A flag raised after this point changes nothing for the job.
+    int nsat = 0;
+    if constexpr (KC == 0) {
+        if (g.sat && kfirst <= universe_last_k) nsat = min(nk, universe_last_k - kfirst + 1);
+        if (nsat) {
+            uint32_t* const word = reinterpret_cast<uint32_t*>(g_lds);
+            if (threadIdx.x == 0) {
+                uint32_t d = 0;
+                while (d < (uint32_t)nsat && load4_fresh(g.sat + krow + d)) ++d;
+                *word = d;
+            }
+            __syncthreads();
+            const int d = __builtin_amdgcn_readfirstlane((int)*word);
+            __syncthreads();
+            kfirst += d, nk -= d, krow += d, nsat -= d;
+            if (nk == 0) return;  // (before anything is loaded)
+        }
+    }
     const unsigned long long ntok = gload8u(g.ntok);
-    uint8_t* const slab = g.regs + ((size_t)job.krow << p);
+    uint8_t* const slab = g.regs + ((size_t)krow << p);
 
     // (the loads of tile t+1 are issued before tile t is processed, and those of the first tile before the warm start below)
     TileIn next;
@@ -123,11 +151,22 @@ __global__ __launch_bounds__(1024) void sweep_kernel(const SweepGenome* __restri
     const uint4* l4 = reinterpret_cast<const uint4*>(g_lds);
     uint32_t* gw = reinterpret_cast<uint32_t*>(slab);
     const uint32_t n16 = (uint32_t)nk * (m >> 4);
+    // Saturation: mx, the value that stands in the slab word when this thread leaves it, is compared with the universe word.
+    // A slab word only ever grows and never passes the universe word, so a stale `old` cannot make a word look equal that
+    // is not.  short_rows: bit j = this thread saw a word of row j below its universe word.
+    const uint32_t nsat16 = (uint32_t)nsat * (m >> 4);
+    const uint8_t* const urow = universe + ((size_t)(kfirst - kSatMinK) << p);
+    uint32_t short_rows = 0;
     for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) {
         const uint4 lv = l4[i];
         const uint4 gv = load16_fresh(slab + (size_t)i * 16);
         const uint32_t l[4] = {lv.x, lv.y, lv.z, lv.w};
         const uint32_t o[4] = {gv.x, gv.y, gv.z, gv.w};
+        uint32_t u[4] = {0u, 0u, 0u, 0u}, below = 0;
+        if (KC == 0 && i < nsat16) {
+            const uint4 uv = gload16(urow + (size_t)i * 16);
+            u[0] = uv.x, u[1] = uv.y, u[2] = uv.z, u[3] = uv.w;
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             uint32_t old = o[q];
@@ -138,6 +177,22 @@ __global__ __launch_bounds__(1024) void sweep_kernel(const SweepGenome* __restri
                 old = prev;
                 mx = bmax4(old, l[q]);
             }
+            below |= mx ^ u[q];
+        }
+        if (KC == 0 && i < nsat16 && below) short_rows |= 1u << (i >> (p - 4));
+    }
+    if constexpr (KC == 0) {
+        if (nsat) {
+            // no word of a row below over the whole workgroup: the row is final.  (The OR goes through a word of g_lds, once
+            // every thread has read its registers.  The flag is raised by an agent-scope atomic: a plain store would stay
+            // in this XCD's L2, out of sight of the other seven's flag reads.)
+            uint32_t* const word = reinterpret_cast<uint32_t*>(g_lds);
+            __syncthreads();
+            if (threadIdx.x == 0) *word = 0u;
+            __syncthreads();
+            if (short_rows) atomicOr(word, short_rows);
+            __syncthreads();
+            if (threadIdx.x < (uint32_t)nsat && !((*word >> threadIdx.x) & 1u)) gor32(g.sat + krow + threadIdx.x, 1u);
         }
     }
 }
@@ -395,7 +450,61 @@ __global__ __launch_bounds__(1024) void bigmap_finish_kernel(const SweepGenome* 
     });
 }
 
+// ---- saturation: sketch(U_k), the row every (canonical) k-mer hashed once gives (dd_kernels.h) ------------------------------
+// Each workgroup hashes its share of x in [0, 4^k) -- in canonical mode only the x that are the smaller of (x, reverse
+// complement), which is what sweep_kernel hashes -- into a row in LDS and byte-max-merges it into the row in HBM (zeroed by the
+// launcher), as sweep_kernel merges its groups.
+template <bool CANON>
+__global__ __launch_bounds__(1024) void universe_kernel(uint8_t* __restrict__ row, int k, int p) {
+    lds_starts_at_zero();
+    const uint32_t m = 1u << p;
+    uint4* z = reinterpret_cast<uint4*>(g_lds);
+    for (uint32_t i = threadIdx.x; i < (m >> 4); i += blockDim.x) z[i] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    const uint32_t n = 1u << (2 * k);  // k <= kSatMaxK = 14
+    for (uint32_t x = blockIdx.x * blockDim.x + threadIdx.x; x < n; x += gridDim.x * blockDim.x) {
+        if (CANON) {
+            uint32_t r = __brev(x);  // bases reversed, the two bits of each swapped
+            r = ((r >> 1) & 0x55555555u) | ((r & 0x55555555u) << 1);
+            r = (~r) >> (32 - 2 * k);
+            if (r < x) continue;
+        }
+        const Probe q = probe(wang64_fast<true>(x), p);
+        lds_raise(q.hi >> (32 - p), rho_of(q, p));
+    }
+    __syncthreads();
+    const uint4* l4 = reinterpret_cast<const uint4*>(g_lds);
+    uint32_t* gw = reinterpret_cast<uint32_t*>(row);
+    for (uint32_t i = threadIdx.x; i < (m >> 4); i += blockDim.x) {
+        const uint4 lv = l4[i];
+        const uint4 gv = load16_fresh(row + (size_t)i * 16);
+        const uint32_t l[4] = {lv.x, lv.y, lv.z, lv.w};
+        const uint32_t o[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint32_t old = o[q];
+            uint32_t mx = bmax4(old, l[q]);
+            while (mx != old) {
+                uint32_t prev = gcas32(&gw[4 * i + q], old, mx);
+                if (prev == old) break;
+                old = prev;
+                mx = bmax4(old, l[q]);
+            }
+        }
+    }
+}
+
 }  // namespace
+
+void launch_universe(uint8_t* row_dev, int k, int log2m, int canonical, hipStream_t st) {
+    if (k < kSatMinK || k > kSatMaxK || log2m < 4 || log2m > 16) return;
+    (void)hipMemsetAsync(row_dev, 0, (size_t)1 << log2m, st);
+    // 2^16 k-mers per workgroup, 1024 workgroups at the most (k = 14: 2^18 each)
+    const unsigned grid = std::min(1024u, 1u << (2 * k - 16));
+    dispatch_bool(canonical != 0, [&](auto cn) {
+        hipLaunchKernelGGL(universe_kernel<decltype(cn)::value>, dim3(grid), dim3(1024), (size_t)1 << log2m, st, row_dev, k, log2m);
+    });
+}
 
 int sweep_max_lds_bytes() { return 160 * 1024; }
 
@@ -436,11 +545,12 @@ void launch_bigmap_finish(const SweepGenome* genomes, int ngenomes, int kfirst, 
 }
 
 void launch_sweep(const SweepGenome* genomes, const SweepJob* jobs, int njobs, int kclass,
-                  const SweepPlan& plan, hipStream_t st) {
+                  const SweepPlan& plan, const uint8_t* universe, int universe_last_k, hipStream_t st) {
     if (njobs <= 0) return;
+    if (!universe || kclass != 0) universe_last_k = 0;
     dispatch_kc_canon(kclass, plan.canonical, [&](auto kc, auto cn) {
         launch_full_lds<sweep_kernel<decltype(kc)::value, decltype(cn)::value>>(dim3((unsigned)njobs), dim3((unsigned)plan.threads), (size_t)plan.lds_bytes, st,
-                                                                                genomes, jobs, plan.log2m, (uint32_t)plan.queue_off);
+                                                                                genomes, jobs, plan.log2m, (uint32_t)plan.queue_off, universe, universe_last_k);
     });
 }
 
