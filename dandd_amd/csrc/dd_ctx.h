@@ -118,7 +118,7 @@ struct dd_ctx {
     // workspaces
     DevBuf tokens, scratch, tables, fasta, regs, ptrs, hist, est, ord, bitmaps, bigmaps, exact, buckets, gram, synth;
     DevBuf masks;  // dd_exact_greedy: cursor and overflow word | gains [64][64] | the mask streams of every k of the call
-    DevBuf emit;   // dd_exact_select_kmers, dd_exact_locate (exact_emit_records): cursor (256 B) | lo | hi | mask, `cap` records each
+    DevBuf emit;   // dd_exact_select_kmers, dd_exact_locate (exact_records): cursor (256 B) | lo | hi | mask, `cap` records each
     DevBuf hits;   // dd_exact_locate: the jobs' hit bitmaps, off[njobs] words; dd_exact_screen: counters [ns + 1][n + nq] | the samples' seen bitmaps;
                    // dd_exact_paint: the windows' counters, off[ns] - off[0] rows of n + 2 x 32 bits
     DevBuf pat[2]; // dd_exact_patterns: the running table in mask order (masks | counts) and where the next merge puts it, in turns

@@ -1,9 +1,11 @@
 // dd_exact_emit_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h) that hand k-mers out instead of counting
-// them: the selected k-mers themselves (dd_exact_select_kmers), where they lie in each genome (dd_exact_locate), the
-// record index of a file that turns those places into names (dd_fasta_index), and what samples that are no inputs hold of
-// them (dd_exact_screen) and where along themselves (dd_exact_paint).  Those four exact entries are one emission
-// (exact_emit_records, dd_exact_host.h) and one ordering of its records on the device (launch_exact_emit_order).  And the table of the distinct masks with their multiplicities
-// (dd_exact_patterns), which hands out no k-mer but is ragged like the others: one k per call, a cap and a count.
+// them.  Four look k-mers up in the ordered records of one emission: the selected k-mers themselves (dd_exact_select_kmers),
+// where they lie in each genome (dd_exact_locate), what samples that are no inputs hold of them (dd_exact_screen) and where
+// along themselves (dd_exact_paint).  Each is its own argument rules, the ordered-record step of dd_exact_host.h
+// (exact_records, then ExactRecords::order inside the entry's timing span) and the one kernel that reads the ordered set;
+// screen and paint also share the frame below: K0 over the universe and the samples, a sort that sees the universe only.
+// dd_exact_patterns hands out no k-mer but is ragged like the others -- one k per call, a cap and a count -- and
+// dd_fasta_index is the record index of a file that turns places into names.
 // Host-side orchestration only; the kernels are in dd_exact_sched.hip (emit_kernel, AccPatterns), dd_exact_locate.hip,
 // dd_exact_screen.hip, dd_exact_paint.hip and dd_exact_patterns.hip.
 #include "dd_exact_host.h"
@@ -29,22 +31,18 @@ int dd_exact_select_kmers_device(dd_ctx* c, const uint8_t* const* fasta_dev, con
     if ((rc = exact_prepare(c, fasta_dev, nbytes, n, in))) return rc;
     c->st_blocks = 0;
     if (!in.slots) return DD_OK;
-    const size_t dcap = std::min(cap, in.slots);   // (no more distinct k-mers than slots)
-    if (c->emit.reserve(exact_emit_bytes(dcap)))
-        return fail(DD_ENOMEM, "exact select k-mers: no device memory for an output of %zu records (24 bytes each); ask with a smaller cap", dcap);
-    dd::ExactEmit e{};
-    unsigned long long total = 0;
-    if ((rc = exact_emit_records(c, in, n, k, "exact select k-mers", nq, table.data(), table.size() * sizeof(uint64_t), dcap, e, &total))) return rc;
-    *found = total;
-    if (!total || total > cap) return DD_OK;   // (more than the caller has room for: the count is the answer, nothing was kept whole)
-    if ((rc = exact_emit_order_room(c, "exact select k-mers", total, k))) return rc;
+    ExactRecords rec;   // (no more distinct k-mers than slots)
+    if ((rc = exact_records(c, in, n, k, "exact select k-mers", nullptr, nq, table.data(), table.size() * sizeof(uint64_t), std::min(cap, in.slots), rec)))
+        return rc;
+    *found = rec.found;
+    if (!rec.kept) return DD_OK;   // (none, or more than the caller has room for: the count is the answer)
     dd::LocateSet set{};
     {
         Span sp(c, DD_KERNEL_EXACT);
-        DD_HIP(dd::launch_exact_emit_order(e.lo, e.hi, e.mask, (size_t)total, k, c->exact.p, st, &set));
+        DD_HIP(rec.order(c, k, &set));
     }
     const bool wide = k > 32;
-    const size_t m = (size_t)total;
+    const size_t m = (size_t)rec.found;
     std::vector<uint64_t> lo(m), hi(wide ? m : 0), mk(m);
     DD_HIP(hipMemcpyAsync(lo.data(), set.lo, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (wide) DD_HIP(hipMemcpyAsync(hi.data(), set.hi, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -70,12 +68,8 @@ namespace {
 // every genome's ntok, for the shape of the answer: each job's share of off[] checked against it
 int locate_shape(dd_ctx* c, const ExactInputs& in, int n, const int32_t* genome, int njobs, const uint64_t* off,
                  std::vector<unsigned long long>& ntok, size_t& max_segments) {
-    ntok.assign((size_t)n, 0ull);
-    if (in.slots) {
-        for (int g = 0; g < n; ++g)
-            DD_HIP(hipMemcpyAsync(&ntok[(size_t)g], in.etab[(size_t)g].ntok, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        DD_HIP(hipStreamSynchronize(c->stream));
-    }
+    int rc;
+    if ((rc = exact_read_ntok(c, in, 0, n, ntok))) return rc;
     max_segments = 0;
     for (int j = 0; j < njobs; ++j) {
         const uint64_t want = (ntok[(size_t)genome[j]] + dd::kSegTokens - 1) / dd::kSegTokens;
@@ -113,10 +107,9 @@ int dd_exact_locate_device(dd_ctx* c, const uint8_t* const* fasta_dev, const siz
     if (exact_frame(c, fasta_dev, nbytes, n, 64, k, k, found, !all || !none || !genome || !off)) return DD_EINVAL;
     if (njobs < 1 || njobs > dd::kEmitMaxQueries)
         return fail(DD_EINVAL, "njobs=%d outside 1..%d (what one launch holds); split the jobs over calls", njobs, dd::kEmitMaxQueries);
-    const uint64_t outside = n == 64 ? 0ull : ~((1ull << n) - 1ull);
     for (int j = 0; j < njobs; ++j) {
         if (genome[j] < 0 || genome[j] >= n) return fail(DD_EINVAL, "job %d: genome %d outside 0..%d", j, genome[j], n - 1);
-        if ((all[j] | none[j]) & outside) return fail(DD_EINVAL, "job %d: a bit outside 0..%d is set", j, n - 1);
+        if (exact_check_bits("job", j, all[j], none[j], n)) return DD_EINVAL;
     }
     if (off[njobs] < off[0]) return fail(DD_EINVAL, "off[] must ascend");
     const uint64_t words = off[njobs] - off[0];   // (each job's own share is checked once the inputs' token counts are known)
@@ -138,10 +131,6 @@ int dd_exact_locate_device(dd_ctx* c, const uint8_t* const* fasta_dev, const siz
     size_t max_segments = 0;
     if ((rc = locate_shape(c, in, n, genome, njobs, off, ntok, max_segments))) return rc;
     if (!in.slots) return DD_OK;   // (no input holds a token)
-    const size_t dcap = in.slots;
-    if (c->emit.reserve(exact_emit_bytes(dcap)))
-        return fail(DD_ENOMEM, "exact locate: no device memory for the %zu bytes of the record area (24 bytes per k-mer slot of the inputs)",
-                    exact_emit_bytes(dcap));
     // one image for both tables: (all, none) [nq][2] | LocateUnit[]
     std::vector<dd::LocateUnit> units;
     locate_units(in, ntok, all, none, genome, njobs, off, units);
@@ -154,17 +143,14 @@ int dd_exact_locate_device(dd_ctx* c, const uint8_t* const* fasta_dev, const siz
     memcpy(image.data() + pbytes, units.data(), sizeof(dd::LocateUnit) * units.size());
     if ((rc = c->hits.reserve(words * sizeof(uint64_t)))) return rc;
     uint64_t* hits_dev = static_cast<uint64_t*>(c->hits.p);
-    dd::ExactEmit e{};
-    unsigned long long total = 0;
-    if ((rc = exact_emit_records(c, in, n, k, "exact locate", nq, image.data(), image.size(), dcap, e, &total))) return rc;
-    if (total > dcap) return fail(DD_EHIP, "exact locate: %llu records emitted, the inputs have %zu k-mer slots", total, dcap);
-    if (!total || !words) {
+    ExactRecords rec;
+    if ((rc = exact_records(c, in, n, k, "exact locate", &kSlotsOfInputs, nq, image.data(), image.size(), in.slots, rec))) return rc;
+    if (!rec.kept || !words) {
         if (words) DD_HIP(hipMemsetAsync(hits_dev, 0, words * sizeof(uint64_t), st));   // nothing matches: no search
     } else {
-        if ((rc = exact_emit_order_room(c, "exact locate", total, k))) return rc;
         Span sp(c, DD_KERNEL_EXACT);
         dd::LocateSet set{};
-        DD_HIP(dd::launch_exact_emit_order(e.lo, e.hi, e.mask, (size_t)total, k, c->exact.p, st, &set));
+        DD_HIP(rec.order(c, k, &set));
         const dd::LocateUnit* units_dev = reinterpret_cast<const dd::LocateUnit*>(static_cast<const char*>(c->ord.p) + pbytes);
         dd::launch_exact_locate(units_dev, (int)units.size(), max_segments, k, c->canonical, set, hits_dev, st);
         DD_HIP(hipGetLastError());
@@ -173,7 +159,7 @@ int dd_exact_locate_device(dd_ctx* c, const uint8_t* const* fasta_dev, const siz
     if (words) DD_HIP(hipMemcpyAsync(host.data(), hits_dev, words * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     DD_HIP(hipStreamSynchronize(st));
     if (words) memcpy(hits + off[0], host.data(), words * sizeof(uint64_t));   // (nothing is written before everything is known)
-    *found = total;
+    *found = rec.found;
     return DD_OK;
 }
 
@@ -184,23 +170,68 @@ int dd_exact_locate(dd_ctx* c, const char* const* paths, int n, int k, const uin
     });
 }
 
+// ------------------------------------------------------------------- the universe and the samples: what screen and paint share
+// K0 runs over the universe's n inputs AND the ns samples behind them, once.  The sort and the emission see the universe
+// alone -- the samples stay out of the sort and out of the slot count that sizes the record area -- with the single query
+// (0, 0); the entry's own table rides behind that query in the image the emission stages.
+namespace {
+
+// the argument rules of both, in front of the entry's own ...
+int universe_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const void* found) {
+    if (exact_args(c, inputs, n, 64, k, k, found)) return DD_EINVAL;
+    if (ns < 1 || ns > 1024) return fail(DD_EINVAL, "ns=%d outside 1..1024 samples in one call; split them over calls", ns);
+    return DD_OK;
+}
+
+// ... and, in a device form, behind them
+int universe_buffers(const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns) {
+    return nbytes ? exact_check_inputs(fasta_dev, nbytes, n + ns) : fail(DD_EINVAL, "null argument");
+}
+
+// K0 over everything; then in.slots and in.max_segments are the universe's alone (in.slots = 0: it holds no token, nothing is
+// sorted), while in.etab still lists the samples behind the universe
+int universe_prepare(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns, ExactInputs& in) {
+    int rc;
+    if ((rc = exact_prepare(c, fasta_dev, nbytes, n + ns, in))) return rc;
+    c->st_blocks = 0;
+    in.slots = 0, in.max_segments = 0;
+    for (int g = 0; g < n; ++g) {
+        const size_t segs = (nbytes[g] + dd::kSegTokens - 1) / dd::kSegTokens;
+        in.slots += segs * dd::kSegTokens, in.max_segments = std::max(in.max_segments, segs);
+    }
+    return DD_OK;
+}
+
+// one image for both tables: the emission's single query (0, 0) | the entry's own table, kOwnTable bytes into the image on the
+// host and into c->ord once it is staged
+constexpr size_t kOwnTable = 256;
+void* own_table(void* image) { return static_cast<char*>(image) + kOwnTable; }
+
+// a path form behind the entry's argument rules: the universe's files and the samples read and uploaded as one list
+int universe_path_form(dd_ctx* c, const char* const* paths, int n, const char* const* samples, int ns, const ExactDeviceForm& device_form) {
+    if (!samples) return fail(DD_EINVAL, "null argument");
+    std::vector<const char*> files((size_t)(n + ns));
+    for (int i = 0; i < n + ns; ++i)
+        if (!(files[(size_t)i] = i < n ? paths[i] : samples[i - n])) return fail(DD_EINVAL, "null argument");
+    return exact_upload_files(c, files.data(), n + ns, device_form);
+}
+
+}  // namespace
+
 // ------------------------------------------------------------------- samples screened against the universe
-// dd_exact_screen.hip: K0 over the universe's inputs AND the samples, the sort and the emission of dd_exact_locate over the
-// universe alone (the samples stay out of the sort and out of the slot count that sizes the record area) with the single
-// query (0, 0), the records put in key order, one walk of every sample that marks the records it holds, one tally of the
-// marks.  The ordered set may lie in the exact workspace: no sort runs there before the tally has finished.
+// dd_exact_screen.hip: the records of the universe put in key order, one walk of every sample that marks the records it
+// holds, one tally of the marks.  The ordered set may lie in the exact workspace: no sort runs there before the tally has
+// finished.
 namespace {
 
 int screen_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const uint64_t* all, const uint64_t* none, int nq,
                 const uint64_t* shared, const uint64_t* match, const uint64_t* found) {
-    if (exact_args(c, inputs, n, 64, k, k, found)) return DD_EINVAL;
-    if (ns < 1 || ns > 1024) return fail(DD_EINVAL, "ns=%d outside 1..1024 samples in one call; split them over calls", ns);
+    if (universe_args(c, inputs, n, ns, k, found)) return DD_EINVAL;
     if (nq < 0 || nq > dd::kScreenMaxQueries)
         return fail(DD_EINVAL, "nq=%d outside 0..%d (what one launch holds); split the queries over calls", nq, dd::kScreenMaxQueries);
     if (!shared || (nq && (!all || !none || !match))) return fail(DD_EINVAL, "null argument");
-    const uint64_t outside = n == 64 ? 0ull : ~((1ull << n) - 1ull);
     for (int q = 0; q < nq; ++q)
-        if ((all[q] | none[q]) & outside) return fail(DD_EINVAL, "query %d: a bit outside 0..%d is set", q, n - 1);
+        if (exact_check_bits("query", q, all[q], none[q], n)) return DD_EINVAL;
     return DD_OK;
 }
 
@@ -209,50 +240,30 @@ int screen_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const uint6
 int dd_exact_screen_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns, int k, const uint64_t* all,
                            const uint64_t* none, int nq, uint64_t* shared, uint64_t* match, uint64_t* found) {
     if (screen_args(c, fasta_dev, n, ns, k, all, none, nq, shared, match, found)) return DD_EINVAL;
-    if (!nbytes) return fail(DD_EINVAL, "null argument");
-    if (exact_check_inputs(fasta_dev, nbytes, n + ns)) return DD_EINVAL;
+    if (universe_buffers(fasta_dev, nbytes, n, ns)) return DD_EINVAL;
     DeviceGuard guard(c->device);
     hipStream_t st = c->stream;
     int rc;
     ExactInputs in;
-    if ((rc = exact_prepare(c, fasta_dev, nbytes, n + ns, in))) return rc;   // K0 over everything, once
-    c->st_blocks = 0;
-    const bool tokens = in.slots != 0;
-    // the sort sees the universe only
-    in.slots = 0, in.max_segments = 0;
+    if ((rc = universe_prepare(c, fasta_dev, nbytes, n, ns, in))) return rc;
     size_t sample_segments = 0;
-    for (int g = 0; g < n + ns; ++g) {
-        const size_t segs = (nbytes[g] + dd::kSegTokens - 1) / dd::kSegTokens;
-        if (g < n) in.slots += segs * dd::kSegTokens, in.max_segments = std::max(in.max_segments, segs);
-        else sample_segments = std::max(sample_segments, segs);
-    }
+    for (int g = n; g < n + ns; ++g) sample_segments = std::max(sample_segments, (nbytes[g] + dd::kSegTokens - 1) / dd::kSegTokens);
     const size_t rows = (size_t)ns + 1, ncount = rows * ((size_t)n + (size_t)nq);
     std::vector<unsigned long long> host(ncount, 0ull);
-    unsigned long long total = 0;
-    dd::ExactEmit e{};
-    if (tokens && in.slots) {
-        const size_t dcap = in.slots;
-        if (c->emit.reserve(exact_emit_bytes(dcap)))
-            return fail(DD_ENOMEM, "exact screen: no device memory for the %zu bytes of the record area (24 bytes per k-mer slot of the universe)",
-                        exact_emit_bytes(dcap));
-        // one image for both tables: the emission's single query (0, 0) | the caller's (all, none) [nq][2]
-        const size_t pbytes = 256;
-        std::vector<char> image(pbytes + sizeof(uint64_t) * 2 * (size_t)nq, 0);
-        for (int q = 0; q < nq; ++q) {
-            uint64_t* t = reinterpret_cast<uint64_t*>(image.data() + pbytes) + 2 * (size_t)q;
-            t[0] = all[q], t[1] = none[q];
-        }
-        if ((rc = exact_emit_records(c, in, n, k, "exact screen", 1, image.data(), image.size(), dcap, e, &total))) return rc;
-        if (total > dcap) return fail(DD_EHIP, "exact screen: %llu records emitted, the universe has %zu k-mer slots", total, dcap);
+    ExactRecords rec;
+    if (in.slots) {
+        std::vector<char> image(kOwnTable + sizeof(uint64_t) * 2 * (size_t)nq, 0);   // the caller's (all, none) [nq][2]
+        uint64_t* pairs = static_cast<uint64_t*>(own_table(image.data()));
+        for (int q = 0; q < nq; ++q) pairs[2 * q] = all[q], pairs[2 * q + 1] = none[q];
+        if ((rc = exact_records(c, in, n, k, "exact screen", &kSlotsOfUniverse, 1, image.data(), image.size(), in.slots, rec))) return rc;
     }
-    if (total) {
+    if (rec.kept) {
         // counters [ns + 1][n] | [ns + 1][nq], then the seen bitmaps [ns][words]
-        const size_t words = ((size_t)total + 31) / 32, cbytes = align_up(ncount * sizeof(unsigned long long), 256),
+        const size_t words = ((size_t)rec.found + 31) / 32, cbytes = align_up(ncount * sizeof(unsigned long long), 256),
                      sbytes = (size_t)ns * words * sizeof(uint32_t);
         if (c->hits.reserve(cbytes + sbytes))
             return fail(DD_ENOMEM, "exact screen: no device memory for the %zu bytes of the samples' seen bitmaps (%d samples x %zu words of 32 records)",
                         sbytes, ns, words);
-        if ((rc = exact_emit_order_room(c, "exact screen", total, k))) return rc;
         unsigned long long* shared_dev = static_cast<unsigned long long*>(c->hits.p);
         unsigned long long* match_dev = shared_dev + rows * (size_t)n;
         uint32_t* seen_dev = reinterpret_cast<uint32_t*>(static_cast<char*>(c->hits.p) + cbytes);
@@ -260,11 +271,10 @@ int dd_exact_screen_device(dd_ctx* c, const uint8_t* const* fasta_dev, const siz
         {
             Span sp(c, DD_KERNEL_EXACT);
             dd::LocateSet set{};
-            DD_HIP(dd::launch_exact_emit_order(e.lo, e.hi, e.mask, (size_t)total, k, c->exact.p, st, &set));
+            DD_HIP(rec.order(c, k, &set));
             dd::launch_exact_screen(in.etab_dev + n, ns, sample_segments, k, c->canonical, set, seen_dev, words, st);
             DD_HIP(hipGetLastError());
-            const uint64_t* pairs_dev = reinterpret_cast<const uint64_t*>(static_cast<const char*>(c->ord.p) + 256);
-            dd::launch_exact_tally(set, seen_dev, words, ns, n, nq, pairs_dev, shared_dev, match_dev, st);
+            dd::launch_exact_tally(set, seen_dev, words, ns, n, nq, static_cast<const uint64_t*>(own_table(c->ord.p)), shared_dev, match_dev, st);
             DD_HIP(hipGetLastError());
         }
         DD_HIP(hipMemcpyAsync(host.data(), shared_dev, ncount * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -273,32 +283,26 @@ int dd_exact_screen_device(dd_ctx* c, const uint8_t* const* fasta_dev, const siz
     // (nothing is written before everything is known)
     for (size_t i = 0; i < rows * (size_t)n; ++i) shared[i] = host[i];
     for (size_t i = 0; i < rows * (size_t)nq; ++i) match[i] = host[rows * (size_t)n + i];
-    *found = total;
+    *found = rec.found;
     return DD_OK;
 }
 
 int dd_exact_screen(dd_ctx* c, const char* const* paths, int n, const char* const* samples, int ns, int k, const uint64_t* all,
                     const uint64_t* none, int nq, uint64_t* shared, uint64_t* match, uint64_t* found) {
     if (screen_args(c, paths, n, ns, k, all, none, nq, shared, match, found)) return DD_EINVAL;
-    if (!samples) return fail(DD_EINVAL, "null argument");
-    std::vector<const char*> files((size_t)(n + ns));
-    for (int i = 0; i < n + ns; ++i)
-        if (!(files[(size_t)i] = i < n ? paths[i] : samples[i - n])) return fail(DD_EINVAL, "null argument");
-    return exact_upload_files(c, files.data(), n + ns, [&](auto p, auto s) {
+    return universe_path_form(c, paths, n, samples, ns, [&](auto p, auto s) {
         return dd_exact_screen_device(c, p, s, n, ns, k, all, none, nq, shared, match, found);
     });
 }
 
 // ------------------------------------------------------------------- samples painted window by window
-// dd_exact_paint.hip: everything of dd_exact_screen up to the ordered records -- K0 over the universe's inputs and the samples,
-// the sort and the emission over the universe alone with the single query (0, 0), the records put in key order --, then one
-// walk of every sample that keeps the position: a row of n + 2 counters per window of the sample's token stream, in c->hits.
-// The shape of the answer is checked like dd_exact_locate's: each sample's share of off[] against its token count.
+// dd_exact_paint.hip: the records of the universe put in key order, then one walk of every sample that keeps the position: a
+// row of n + 2 counters per window of the sample's token stream, in c->hits.  The shape of the answer is checked like
+// dd_exact_locate's: each sample's share of off[] against its token count.
 namespace {
 
 int paint_args(dd_ctx* c, const void* inputs, int n, int ns, int k, uint64_t window, const uint64_t* off, const uint64_t* found) {
-    if (exact_args(c, inputs, n, 64, k, k, found)) return DD_EINVAL;
-    if (ns < 1 || ns > 1024) return fail(DD_EINVAL, "ns=%d outside 1..1024 samples in one call; split them over calls", ns);
+    if (universe_args(c, inputs, n, ns, k, found)) return DD_EINVAL;
     if (window < dd::kSegTokens || window > dd::kPaintMaxWindow || window % dd::kSegTokens)
         return fail(DD_EINVAL, "window=%llu: a multiple of %d in %d..%zu tokens (a window is whole 64-token segments)", (unsigned long long)window,
                     (int)dd::kSegTokens, (int)dd::kSegTokens, dd::kPaintMaxWindow);
@@ -311,8 +315,7 @@ int paint_args(dd_ctx* c, const void* inputs, int n, int ns, int k, uint64_t win
 int dd_exact_paint_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns, int k, uint64_t window,
                           const uint64_t* off, uint32_t* counts, uint64_t* found) {
     if (paint_args(c, fasta_dev, n, ns, k, window, off, found)) return DD_EINVAL;
-    if (!nbytes) return fail(DD_EINVAL, "null argument");
-    if (exact_check_inputs(fasta_dev, nbytes, n + ns)) return DD_EINVAL;
+    if (universe_buffers(fasta_dev, nbytes, n, ns)) return DD_EINVAL;
     if (off[ns] < off[0]) return fail(DD_EINVAL, "off[] must ascend");
     const uint64_t rows = off[ns] - off[0];   // (each sample's own share is checked once the samples' token counts are known)
     if (rows && !counts) return fail(DD_EINVAL, "null argument");
@@ -320,20 +323,11 @@ int dd_exact_paint_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size
     hipStream_t st = c->stream;
     int rc;
     ExactInputs in;
-    if ((rc = exact_prepare(c, fasta_dev, nbytes, n + ns, in))) return rc;   // K0 over everything, once
-    c->st_blocks = 0;
-    const bool tokens = in.slots != 0;
-    // the shape of the answer: every sample's ntok
-    std::vector<unsigned long long> ntok((size_t)ns, 0ull);
-    if (tokens) {
-        for (int s = 0; s < ns; ++s)
-            DD_HIP(hipMemcpyAsync(&ntok[(size_t)s], in.etab[(size_t)(n + s)].ntok, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        DD_HIP(hipStreamSynchronize(st));
-    }
-    // one image for both tables: the emission's single query (0, 0) | the first row of every sample [ns]
-    const size_t pbytes = 256;
-    std::vector<char> image(pbytes + sizeof(unsigned long long) * (size_t)ns, 0);
-    unsigned long long* row0 = reinterpret_cast<unsigned long long*>(image.data() + pbytes);
+    if ((rc = universe_prepare(c, fasta_dev, nbytes, n, ns, in))) return rc;
+    std::vector<unsigned long long> ntok;   // the shape of the answer: every sample's ntok
+    if ((rc = exact_read_ntok(c, in, n, ns, ntok))) return rc;
+    std::vector<char> image(kOwnTable + sizeof(unsigned long long) * (size_t)ns, 0);   // the first row of every sample [ns]
+    unsigned long long* row0 = static_cast<unsigned long long*>(own_table(image.data()));
     size_t sample_segments = 0;
     for (int s = 0; s < ns; ++s) {
         const uint64_t want = (ntok[(size_t)s] + window - 1) / window;
@@ -343,22 +337,10 @@ int dd_exact_paint_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size
         row0[s] = off[s] - off[0];
         sample_segments = std::max(sample_segments, (size_t)((ntok[(size_t)s] + dd::kSegTokens - 1) / dd::kSegTokens));
     }
-    // the sort sees the universe only
-    in.slots = 0, in.max_segments = 0;
-    for (int g = 0; g < n; ++g) {
-        const size_t segs = (nbytes[g] + dd::kSegTokens - 1) / dd::kSegTokens;
-        in.slots += segs * dd::kSegTokens, in.max_segments = std::max(in.max_segments, segs);
-    }
     const size_t ncol = (size_t)n + 2, cbytes = (size_t)rows * ncol * sizeof(uint32_t);
-    unsigned long long total = 0;
-    dd::ExactEmit e{};
-    if (tokens && in.slots) {
-        const size_t dcap = in.slots;
-        if (c->emit.reserve(exact_emit_bytes(dcap)))
-            return fail(DD_ENOMEM, "exact paint: no device memory for the %zu bytes of the record area (24 bytes per k-mer slot of the universe)",
-                        exact_emit_bytes(dcap));
-        if ((rc = exact_emit_records(c, in, n, k, "exact paint", 1, image.data(), image.size(), dcap, e, &total))) return rc;
-        if (total > dcap) return fail(DD_EHIP, "exact paint: %llu records emitted, the universe has %zu k-mer slots", total, dcap);
+    ExactRecords rec;
+    if (in.slots) {
+        if ((rc = exact_records(c, in, n, k, "exact paint", &kSlotsOfUniverse, 1, image.data(), image.size(), in.slots, rec))) return rc;
     } else if (rows) {
         if ((rc = stage_table(c, c->ord, image.data(), image.size()))) return rc;   // (no emission has staged it)
     }
@@ -367,34 +349,28 @@ int dd_exact_paint_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size
         if (c->hits.reserve(cbytes))
             return fail(DD_ENOMEM, "exact paint: no device memory for the %zu bytes of the windows' counters (%llu rows x %zu columns of 4 bytes)",
                         cbytes, (unsigned long long)rows, ncol);
-        if (total && (rc = exact_emit_order_room(c, "exact paint", total, k))) return rc;
         uint32_t* counts_dev = static_cast<uint32_t*>(c->hits.p);
         DD_HIP(hipMemsetAsync(counts_dev, 0, cbytes, st));
         {
             Span sp(c, DD_KERNEL_EXACT);
             dd::LocateSet set{};   // (an empty universe: no record, column 0 alone)
-            if (total) DD_HIP(dd::launch_exact_emit_order(e.lo, e.hi, e.mask, (size_t)total, k, c->exact.p, st, &set));
-            const unsigned long long* row0_dev = reinterpret_cast<const unsigned long long*>(static_cast<const char*>(c->ord.p) + pbytes);
-            dd::launch_exact_paint(in.etab_dev + n, ns, sample_segments, k, c->canonical, set, n, (size_t)(window / dd::kSegTokens), row0_dev,
-                                   counts_dev, st);
+            if (rec.kept) DD_HIP(rec.order(c, k, &set));
+            dd::launch_exact_paint(in.etab_dev + n, ns, sample_segments, k, c->canonical, set, n, (size_t)(window / dd::kSegTokens),
+                                   static_cast<const unsigned long long*>(own_table(c->ord.p)), counts_dev, st);
             DD_HIP(hipGetLastError());
         }
         DD_HIP(hipMemcpyAsync(host.data(), counts_dev, cbytes, hipMemcpyDeviceToHost, st));
         DD_HIP(hipStreamSynchronize(st));
         memcpy(counts + off[0] * ncol, host.data(), cbytes);   // (nothing is written before everything is known)
     }
-    *found = total;
+    *found = rec.found;
     return DD_OK;
 }
 
 int dd_exact_paint(dd_ctx* c, const char* const* paths, int n, const char* const* samples, int ns, int k, uint64_t window,
                    const uint64_t* off, uint32_t* counts, uint64_t* found) {
     if (paint_args(c, paths, n, ns, k, window, off, found)) return DD_EINVAL;
-    if (!samples) return fail(DD_EINVAL, "null argument");
-    std::vector<const char*> files((size_t)(n + ns));
-    for (int i = 0; i < n + ns; ++i)
-        if (!(files[(size_t)i] = i < n ? paths[i] : samples[i - n])) return fail(DD_EINVAL, "null argument");
-    return exact_upload_files(c, files.data(), n + ns, [&](auto p, auto s) {
+    return universe_path_form(c, paths, n, samples, ns, [&](auto p, auto s) {
         return dd_exact_paint_device(c, p, s, n, ns, k, window, off, counts, found);
     });
 }

@@ -1,5 +1,6 @@
 // dd_exact_host.h -- what the exact entry points share on the host (defined in dd_exact_passes.hip; called by dd_exact_api.hip
-// and dd_exact_emit_api.hip): the call frame, the path forms' upload, K0 over the inputs, the pass driver and the emission.
+// and dd_exact_emit_api.hip): the call frame, the path forms' upload, K0 over the inputs and their token counts read back, the
+// pass driver, and the ordered-record step: the emission, its sanity check and the room that puts the records in order.
 #pragma once
 #include <functional>
 #include "dd_ctx.h"
@@ -10,6 +11,8 @@ int exact_args(dd_ctx* c, const void* inputs, int n, int nmax, int kmin, int kma
 int exact_frame(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int nmax, int kmin, int kmax,
                 const void* out, bool more_null = false);
 int exact_check_inputs(const uint8_t* const* fasta_dev, const size_t* nbytes, int n);
+// query (job) i of a call over n inputs sets no bit outside 0..n-1; `who`: "query" / "job", for the message
+int exact_check_bits(const char* who, int i, uint64_t all, uint64_t none, int n);
 // select's argument rules -> the (all, none) pairs its accumulator and the emission read
 int select_table(const uint64_t* all, const uint64_t* none, int nq, int n, std::vector<uint64_t>& table);
 using ExactDeviceForm = std::function<int(const uint8_t* const* fasta_dev, const size_t* nbytes)>;
@@ -25,6 +28,8 @@ struct ExactInputs {
     std::vector<dd::ExactGenome> etab;    // the host's copy of etab_dev (dd_exact_locate: where each stream and its ntok lie)
 };
 int exact_prepare(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, ExactInputs& in);
+// ntok of the inputs first .. first + count - 1, read back from where K0 left them (all 0 where no input has a token)
+int exact_read_ntok(dd_ctx* c, const ExactInputs& in, int first, int count, std::vector<unsigned long long>& ntok);
 size_t exact_budget(const char* env_mb = "DD_EXACT_MB");   // bytes of k-mers a pass may hold: 24 GiB, or what the variable says
 
 // What a caller of exact_passes says about its part of the k-mer workspace.
@@ -57,13 +62,23 @@ int exact_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const ExactLayo
 using ExactSortedThen = std::function<hipError_t(const dd::ExactSorted& sorted, size_t count, void* scratch)>;
 int exact_sorted_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, const ExactSortedThen& then);
 
-// The distinct k-mers of one k whose mask matches a query, left in c->emit (cursor (256 B) | lo | hi | mask, dcap records
-// each; the caller has reserved exact_emit_bytes(dcap)) in the order the chunks of the sort finished, over all passes.
+// The ordered-record step.  exact_records reserves c->emit (cursor (256 B) | lo | hi | mask, dcap records each) and leaves
+// there the distinct k-mers of one k whose mask matches a query, in the order the chunks of the sort finished, over all passes.
 // `image` is staged into c->ord: its first 2 nq words are the (all, none) pairs, what the caller appended follows there.
-// *found = the cursor: it counts on past dcap, and then no record was kept whole.  `what` names the entry in the messages.
-inline size_t exact_emit_bytes(size_t dcap) { return 256 + 3 * align_up(dcap * sizeof(uint64_t), 256); }
-int exact_emit_records(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, int nq, const void* image, size_t image_bytes,
-                       size_t dcap, dd::ExactEmit& e, unsigned long long* found);
-// room in c->exact -- free after the last pass, grown if a multi-pass call found more than a pass holds -- for
-// launch_exact_emit_order to put `found` records in ascending (hi, lo) order
-int exact_emit_order_room(dd_ctx* c, const char* what, unsigned long long found, int k);
+// found = the cursor.  `slots` says whose k-mer slots dcap counts: more records than slots is DD_EHIP.  Null: dcap is the
+// caller's own cap, the cursor counts on past it, and then no record was kept whole: the count is the answer.
+// kept: 0 < found <= dcap, and c->exact -- free after the last pass, grown if a multi-pass call found more than a pass holds --
+// has room for order(): ascending (hi, lo), launched by the caller inside its timing span, in front of the kernel that reads
+// the set.  `what` names the entry in the messages.
+struct ExactSlotsOf { const char *of, *have; };
+constexpr ExactSlotsOf kSlotsOfInputs{"inputs", "inputs have"}, kSlotsOfUniverse{"universe", "universe has"};
+struct ExactRecords {
+    dd::ExactEmit e{};
+    unsigned long long found = 0;
+    bool kept = false;
+    hipError_t order(dd_ctx* c, int k, dd::LocateSet* set) const {
+        return dd::launch_exact_emit_order(e.lo, e.hi, e.mask, (size_t)found, k, c->exact.p, c->stream, set);
+    }
+};
+int exact_records(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, const ExactSlotsOf* slots, int nq, const void* image,
+                  size_t image_bytes, size_t dcap, ExactRecords& r);

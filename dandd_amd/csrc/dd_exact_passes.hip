@@ -1,6 +1,7 @@
 // dd_exact_passes.hip -- the host side that every exact entry point stands on (dd_exact_host.h): the call frame and the path
 // forms' upload, K0 over the inputs, the pass driver (extract -> the caller's sort and what follows, in one pass or in
-// passes over disjoint parts of the k-mer space) and the emission of the selected k-mers.  No kernels here.
+// passes over disjoint parts of the k-mer space) and the ordered-record step (the emission of the selected k-mers, its
+// sanity check, the room for their order).  No kernels here.
 #include "dd_exact_host.h"
 
 // ------------------------------------------------------------------------ the call frame
@@ -30,13 +31,17 @@ int exact_check_inputs(const uint8_t* const* fasta_dev, const size_t* nbytes, in
     return DD_OK;
 }
 
+int exact_check_bits(const char* who, int i, uint64_t all, uint64_t none, int n) {
+    const uint64_t outside = n == 64 ? 0ull : ~((1ull << n) - 1ull);
+    return (all | none) & outside ? fail(DD_EINVAL, "%s %d: a bit outside 0..%d is set", who, i, n - 1) : DD_OK;
+}
+
 int select_table(const uint64_t* all, const uint64_t* none, int nq, int n, std::vector<uint64_t>& table) {
     if (!all || !none) return fail(DD_EINVAL, "null argument");
     if (nq < 1) return fail(DD_EINVAL, "nq=%d: at least one query", nq);
-    const uint64_t outside = n == 64 ? 0ull : ~((1ull << n) - 1ull);
     table.resize((size_t)2 * nq);
     for (int q = 0; q < nq; ++q) {
-        if ((all[q] | none[q]) & outside) return fail(DD_EINVAL, "query %d: a bit outside 0..%d is set", q, n - 1);
+        if (exact_check_bits("query", q, all[q], none[q], n)) return DD_EINVAL;
         table[(size_t)2 * q] = all[q], table[(size_t)2 * q + 1] = none[q];
     }
     return DD_OK;
@@ -102,6 +107,15 @@ int exact_prepare(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbyt
         dd::launch_pack_batch(reinterpret_cast<const dd::PackGenome*>(tdev), n, max_chunks, c->stream);
     }
     in.etab_dev = reinterpret_cast<const dd::ExactGenome*>(tdev + pbytes);
+    return DD_OK;
+}
+
+int exact_read_ntok(dd_ctx* c, const ExactInputs& in, int first, int count, std::vector<unsigned long long>& ntok) {
+    ntok.assign((size_t)count, 0ull);
+    if (in.etab.empty()) return DD_OK;   // (no input has a token: K0 did not run)
+    for (int i = 0; i < count; ++i)
+        DD_HIP(hipMemcpyAsync(&ntok[(size_t)i], in.etab[(size_t)(first + i)].ntok, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    DD_HIP(hipStreamSynchronize(c->stream));
     return DD_OK;
 }
 
@@ -231,13 +245,17 @@ int exact_sorted_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const ch
     });
 }
 
-// ------------------------------------------------------------------------ the emission
-int exact_emit_records(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, int nq, const void* image, size_t image_bytes,
-                       size_t dcap, dd::ExactEmit& e, unsigned long long* found) {
+// ------------------------------------------------------------------------ the ordered-record step
+int exact_records(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, const ExactSlotsOf* slots, int nq, const void* image,
+                  size_t image_bytes, size_t dcap, ExactRecords& r) {
     hipStream_t st = c->stream;
     int rc;
-    const size_t stride = align_up(dcap * sizeof(uint64_t), 256);
+    const size_t stride = align_up(dcap * sizeof(uint64_t), 256), bytes = 256 + 3 * stride;
+    if (c->emit.reserve(bytes))
+        return slots ? fail(DD_ENOMEM, "%s: no device memory for the %zu bytes of the record area (24 bytes per k-mer slot of the %s)", what, bytes, slots->of)
+                     : fail(DD_ENOMEM, "%s: no device memory for an output of %zu records (24 bytes each); ask with a smaller cap", what, dcap);
     char* eb = static_cast<char*>(c->emit.p);
+    dd::ExactEmit& e = r.e;
     e = dd::ExactEmit{n, nq, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<unsigned long long*>(eb), dcap};
     if (dcap) {
         e.lo = reinterpret_cast<uint64_t*>(eb + 256);
@@ -251,14 +269,12 @@ int exact_emit_records(dd_ctx* c, const ExactInputs& in, int n, int k, const cha
         return dd::launch_exact_emit(sorted, count, k, e, scratch, st);
     });
     if (rc) return rc;
-    DD_HIP(hipMemcpyAsync(found, e.cursor, sizeof *found, hipMemcpyDeviceToHost, st));
+    DD_HIP(hipMemcpyAsync(&r.found, e.cursor, sizeof r.found, hipMemcpyDeviceToHost, st));
     DD_HIP(hipStreamSynchronize(st));
-    return DD_OK;
-}
-
-// (a pass holds an arbitrary part of the k-mer space and its chunks finish in any order: one ordering, after the last)
-int exact_emit_order_room(dd_ctx* c, const char* what, unsigned long long found, int k) {
-    const size_t bytes = dd::exact_emit_order_bytes((size_t)found, k);
-    if (c->exact.reserve(bytes)) return fail(DD_ENOMEM, "%s: no device memory for the %zu bytes that put %llu records in order", what, bytes, found);
+    if (slots && r.found > dcap) return fail(DD_EHIP, "%s: %llu records emitted, the %s %zu k-mer slots", what, r.found, slots->have, dcap);
+    r.kept = r.found && r.found <= dcap;
+    // (a pass holds an arbitrary part of the k-mer space and its chunks finish in any order: one ordering, after the last)
+    const size_t room = r.kept ? dd::exact_emit_order_bytes((size_t)r.found, k) : 0;
+    if (c->exact.reserve(room)) return fail(DD_ENOMEM, "%s: no device memory for the %zu bytes that put %llu records in order", what, room, r.found);
     return DD_OK;
 }

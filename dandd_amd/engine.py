@@ -189,14 +189,14 @@ def load_library(path=None):
         fn = getattr(lib, name)
         fn.restype = i32
         fn.argtypes = [vp] + src + [i32, i32, vp, vp, vp, i32, vp, vp, C.POINTER(u64)]
-    lib.dd_exact_screen.restype = i32
-    lib.dd_exact_screen.argtypes = [vp, paths_t, i32, paths_t, i32, i32, vp, vp, i32, vp, vp, C.POINTER(u64)]
-    lib.dd_exact_screen_device.restype = i32
-    lib.dd_exact_screen_device.argtypes = [vp, ptrs_t, sizes_t, i32, i32, i32, vp, vp, i32, vp, vp, C.POINTER(u64)]
-    lib.dd_exact_paint.restype = i32
-    lib.dd_exact_paint.argtypes = [vp, paths_t, i32, paths_t, i32, i32, u64, vp, vp, C.POINTER(u64)]
-    lib.dd_exact_paint_device.restype = i32
-    lib.dd_exact_paint_device.argtypes = [vp, ptrs_t, sizes_t, i32, i32, i32, u64, vp, vp, C.POINTER(u64)]
+    # a universe and samples: (paths, n, samples, ns) | (ptrs, sizes, n, ns)
+    for name, src, extra in (("dd_exact_screen", [paths_t, i32, paths_t, i32], [vp, vp, i32, vp, vp]),
+                             ("dd_exact_paint", [paths_t, i32, paths_t, i32], [u64, vp, vp]),
+                             ("dd_exact_screen_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, i32, vp, vp]),
+                             ("dd_exact_paint_device", [ptrs_t, sizes_t, i32, i32], [u64, vp, vp])):
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = [vp] + src + [i32] + extra + [C.POINTER(u64)]
     for name, src in (("dd_exact_patterns", [paths_t]), ("dd_exact_patterns_device", [ptrs_t, sizes_t])):
         fn = getattr(lib, name)
         fn.restype = i32
@@ -710,11 +710,18 @@ class Engine:
         return d.value
 
     # -- exact union schedules: one sort of all n inputs per k (dd_exact_sched.hip) -----------
-    def _exact_src(self, paths=None, fasta_ptrs=None, nbytes=None):
+    def _exact_src(self, paths=None, fasta_ptrs=None, nbytes=None, samples=None, n=None):
+        """-> (the arguments that name an exact entry's inputs, n, the entry's suffix).  A universe and samples -- `samples`
+        beside paths, or the first `n` of the device buffers the universe and the rest the samples -- -> (.., n, ns, suffix),
+        the arguments with both counts behind them as dd_exact_screen and dd_exact_paint take them."""
         if paths is not None:
-            return [(C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])], len(paths), ""
-        n = len(fasta_ptrs)
-        return [(C.c_void_p * n)(*[int(x) for x in fasta_ptrs]), (C.c_size_t * n)(*[int(x) for x in nbytes])], n, "_device"
+            names = lambda files: (C.c_char_p * max(len(files), 1))(*[os.fsencode(p) for p in files])
+            if samples is None:
+                return [names(paths)], len(paths), ""
+            return [names(paths), len(paths), names(samples), len(samples)], len(paths), len(samples), ""
+        total = len(fasta_ptrs)
+        args = [(C.c_void_p * total)(*[int(x) for x in fasta_ptrs]), (C.c_size_t * total)(*[int(x) for x in nbytes])]
+        return (args, total, "_device") if n is None else (args + [int(n), total - int(n)], int(n), total - int(n), "_device")
 
     def _exact_sched(self, what, src, shape, kmin, kmax, *extra):
         args, n, suffix = src
@@ -879,13 +886,14 @@ class Engine:
 
     # -- samples that are no leaves, screened against the universe's records (dd_exact_screen.hip) ------------------------
     last_screen_found = None   # of the last exact_screen call: the distinct k-mers of the universe
-    def _exact_screen(self, call, n, ns, k, all_masks, none_masks):
+    def _exact_screen(self, src, k, all_masks, none_masks):
+        args, n, ns, suffix = src
         al, no, nq = self._query_masks(all_masks, none_masks)
         shared = np.zeros((max(ns, 0) + 1, max(n, 0)), dtype=np.uint64)
         match = np.zeros((max(ns, 0) + 1, nq), dtype=np.uint64)
         found = C.c_uint64()
-        self._check(call(int(k), al.ctypes.data if nq else None, no.ctypes.data if nq else None, nq, shared.ctypes.data,
-                         match.ctypes.data if nq else None, C.byref(found)))
+        self._check(getattr(self._lib, f"dd_exact_screen{suffix}")(self._ctx, *args, int(k), al.ctypes.data if nq else None, no.ctypes.data if nq else None,
+                                                                  nq, shared.ctypes.data, match.ctypes.data if nq else None, C.byref(found)))
         self.last_screen_found = int(found.value)
         return shared, match
 
@@ -894,21 +902,16 @@ class Engine:
         queries -> (shared uint64 [ns+1][n], match uint64 [ns+1][nq]): shared[s][i] the distinct k-mers of sample s that
         file i also holds, match[s][q] those whose universe mask contains all_masks[q] and meets none_masks[q] nowhere; row
         ns is the universe itself (|file i|; what exact_select counts).  last_screen_found: the universe's distinct k-mers."""
-        pa = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
-        sa = (C.c_char_p * max(len(samples), 1))(*[os.fsencode(p) for p in samples])
-        return self._exact_screen(lambda *rest: self._lib.dd_exact_screen(self._ctx, pa, len(paths), sa, len(samples), *rest),
-                                  len(paths), len(samples), k, all_masks, none_masks)
+        return self._exact_screen(self._exact_src(paths=paths, samples=samples), k, all_masks, none_masks)
 
     def exact_screen_device(self, fasta_ptrs, nbytes, n, k, all_masks, none_masks):
         """exact_screen over FASTA bytes on the device: the n universe inputs first, the samples behind them."""
-        args, total, _ = self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes)
-        ns = total - int(n)
-        return self._exact_screen(lambda *rest: self._lib.dd_exact_screen_device(self._ctx, *args, int(n), ns, *rest),
-                                  int(n), ns, k, all_masks, none_masks)
+        return self._exact_screen(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes, n=n), k, all_masks, none_masks)
 
     # -- samples painted window by window: the same records, then a walk that keeps the position (dd_exact_paint.hip) ------
     last_paint_found = None   # of the last exact_paint call: the distinct k-mers of the universe
-    def _exact_paint(self, call, n, ns, k, window, ntok):
+    def _exact_paint(self, src, k, window, ntok):
+        args, n, ns, suffix = src
         window = int(window)
         off = np.zeros(max(ns, 0) + 1, dtype=np.uint64)
         for s in range(ns):
@@ -916,7 +919,7 @@ class Engine:
         rows = int(off[max(ns, 0)])
         counts = np.zeros((max(rows, 1), max(n, 0) + 2), dtype=np.uint32)
         found = C.c_uint64()
-        self._check(call(int(k), window, off.ctypes.data, counts.ctypes.data, C.byref(found)))
+        self._check(getattr(self._lib, f"dd_exact_paint{suffix}")(self._ctx, *args, int(k), window, off.ctypes.data, counts.ctypes.data, C.byref(found)))
         self.last_paint_found = int(found.value)
         return [counts[int(off[s]):int(off[s + 1])].copy() for s in range(ns)]
 
@@ -929,18 +932,12 @@ class Engine:
         fasta_index per sample.  last_paint_found: the universe's distinct k-mers."""
         if ntok is None:                                              # the shape of the answer: the samples' token counts
             ntok = [fasta_index(p)[3] for p in samples]
-        pa = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
-        sa = (C.c_char_p * max(len(samples), 1))(*[os.fsencode(p) for p in samples])
-        return self._exact_paint(lambda *rest: self._lib.dd_exact_paint(self._ctx, pa, len(paths), sa, len(samples), *rest),
-                                 len(paths), len(samples), k, window, ntok)
+        return self._exact_paint(self._exact_src(paths=paths, samples=samples), k, window, ntok)
 
     def exact_paint_device(self, fasta_ptrs, nbytes, n, k, window, ntok):
         """exact_paint over FASTA bytes on the device: the n universe inputs first, the samples behind them; ntok: every
         sample's token count (the library checks them)."""
-        args, total, _ = self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes)
-        ns = total - int(n)
-        return self._exact_paint(lambda *rest: self._lib.dd_exact_paint_device(self._ctx, *args, int(n), ns, *rest),
-                                 int(n), ns, k, window, ntok)
+        return self._exact_paint(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes, n=n), k, window, ntok)
 
     # -- the membership-pattern table: the distinct masks and how many k-mers carry each (dd_exact_patterns.hip) ------------
     last_patterns_stats = None   # of the last exact_patterns call: (distinct k-mers, pairs written to HBM, forced flushes, single masks)

@@ -235,9 +235,10 @@ class HipExactBackend:
     # takes the object path.
     MAX_LEAVES, MAX_SUBSET_LEAVES = 64, 16
 
-    def _leaf_window(self, leaf_paths, limit):
+    def _leaf_window(self, leaf_paths, limit=MAX_LEAVES, k=None):
         """-> (dbs [n][K], files [n], kmin, kmax) of leaf databases leaf_paths[i][kk] (one member each, consecutive k per row,
-        the same ks in every row), or None when there are more than `limit` leaves."""
+        the same ks in every row), or None when there are more than `limit` leaves.  k: the one k of the call, which must
+        lie in the window."""
         if not 1 <= len(leaf_paths) <= limit:
             return None
         dbs = [[self._read(p) for p in row] for row in leaf_paths]
@@ -252,6 +253,8 @@ class HipExactBackend:
                 if len(db["members"]) != 1 or db["members"][0]["name"] != row[0]["members"][0]["name"]:
                     raise ValueError(f"{p} is not a database of the one genome {row[0]['members'][0]['name']}")
             files.append(self._find(row[0]["members"][0]))
+        if k is not None and not ks[0] <= int(k) <= ks[-1]:
+            raise ValueError(f"k={k} outside the window {ks[0]}..{ks[-1]} of the leaf databases")
         return dbs, files, ks[0], ks[-1]
 
     def _seed_leaves(self, leaf_paths, dbs, files, counts):
@@ -266,8 +269,7 @@ class HipExactBackend:
 
     def pairwise_cards(self, leaf_paths):
         """|leaf_i U leaf_j| for all pairs and every k column: float64 [n][n][K]"""
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths)) is None:
             return None
         dbs, files, kmin, kmax = win
         table = self.engine.exact_pairwise(files, kmin, kmax)
@@ -276,8 +278,7 @@ class HipExactBackend:
 
     def progressive_cards(self, leaf_paths, orderings):
         """|union of the first j+1 leaves of ordering o| : float64 [o][n][K]"""
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths)) is None:
             return None
         _, files, kmin, kmax = win
         return self.engine.exact_progressive(files, kmin, kmax, orderings).astype(np.float64)
@@ -285,8 +286,7 @@ class HipExactBackend:
     def leave_out_cards(self, leaf_paths, group):
         """|union of every leaf whose group != g| for g < G, and the union of all leaves as row G: float64 [G+1][K].
         group[i] = -1: leaf i is in every union."""
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths)) is None:
             return None
         _, files, kmin, kmax = win
         group = np.asarray(group, dtype=np.int64).reshape(len(leaf_paths))
@@ -295,8 +295,7 @@ class HipExactBackend:
     def subset_cards(self, leaf_paths):
         """|union of the leaves i with bit i of s set| for every s < 2^n (n <= 16) and every k column: float64 [2^n][K], row 0
         (the empty set) 0.0."""
-        win = self._leaf_window(leaf_paths, self.MAX_SUBSET_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths, self.MAX_SUBSET_LEAVES)) is None:
             return None
         dbs, files, kmin, kmax = win
         table = self.engine.exact_subsets(files, kmin, kmax)
@@ -307,24 +306,21 @@ class HipExactBackend:
     # a cardinality estimate, and no object path stands behind them -- None (more than 64 leaves) ends the command.
     def spectrum_counts(self, leaf_paths):
         """distinct k-mers held by exactly j of the leaves: uint64 [n+1][K], row 0 all 0"""
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths)) is None:
             return None
         _, files, kmin, kmax = win
         return self.engine.exact_spectrum(files, kmin, kmax)
 
     def core_progressive_counts(self, leaf_paths, orderings):
         """k-mers held by every one of the first j+1 leaves of ordering o: uint64 [o][n][K]"""
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths)) is None:
             return None
         _, files, kmin, kmax = win
         return self.engine.exact_core_progressive(files, kmin, kmax, orderings)
 
     def select_counts(self, leaf_paths, all_masks, none_masks):
         """k-mers held by every leaf of all_masks[q] and by no leaf of none_masks[q] (bit i: leaf i): uint64 [nq][K]"""
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths)) is None:
             return None
         _, files, kmin, kmax = win
         return self.engine.exact_select(files, kmin, kmax, all_masks, none_masks)
@@ -333,12 +329,9 @@ class HipExactBackend:
         """the k-mers select_counts counts at one k of the window, themselves: (kmers uint64 [m][2] (lo, hi), masks uint64 [m]),
         ascending, a k-mer that matches several queries once.  More than `limit` of them is a ValueError that carries the count."""
         from ..engine import EngineError
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths, k=k)) is None:
             return None
-        _, files, kmin, kmax = win
-        if not kmin <= int(k) <= kmax:
-            raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
+        files = win[1]
         try:
             return self.engine.exact_select_kmers(files, int(k), all_masks, none_masks, cap=int(limit))
         except EngineError as e:
@@ -353,12 +346,9 @@ class HipExactBackend:
         ([(names, seq_len, tok_start, ntok)] per leaf, [uint64 bitmap over the leaf's tokens] per job); bit t of a
         bitmap: a k-mer of the job's query ends at token t of that leaf's file (engine.regions_from_hits makes intervals)."""
         from ..engine import fasta_index
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths, k=k)) is None:
             return None
-        _, files, kmin, kmax = win
-        if not kmin <= int(k) <= kmax:
-            raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
+        files = win[1]
         index = [fasta_index(f) for f in files]
         return index, self.engine.exact_locate(files, int(k), jobs, ntok=[ix[3] for ix in index])
 
@@ -367,12 +357,9 @@ class HipExactBackend:
         (shared uint64 [ns+1][n], match uint64 [ns+1][nq]); shared[s][i]: the distinct k-mers of sample s that leaf i also
         holds, match[s][q]: those whose membership mask contains all_masks[q] and meets none_masks[q] nowhere; row ns: the
         leaves themselves (|leaf i|; what select_counts counts)."""
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths, k=k)) is None:
             return None
-        _, files, kmin, kmax = win
-        if not kmin <= int(k) <= kmax:
-            raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
+        files = win[1]
         return self.engine.exact_screen(files, [str(f) for f in sample_files], int(k), all_masks, none_masks)
 
     def paint_counts(self, leaf_paths, k, sample_files, window):
@@ -381,12 +368,9 @@ class HipExactBackend:
         the sample's token stream: the positions where a valid k-mer ends, where the leaves hold it at all, and where leaf i
         holds it (engine.paint_windows places the windows in the records)."""
         from ..engine import fasta_index
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths, k=k)) is None:
             return None
-        _, files, kmin, kmax = win
-        if not kmin <= int(k) <= kmax:
-            raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
+        files = win[1]
         index = [fasta_index(str(f)) for f in sample_files]
         return index, self.engine.exact_paint(files, [str(f) for f in sample_files], int(k), int(window), ntok=[ix[3] for ix in index])
 
@@ -395,12 +379,9 @@ class HipExactBackend:
         (dd_exact_patterns): -> (masks uint64 [m], counts uint64 [m], found, distinct), count descending, ties by mask
         ascending; found: the number of distinct masks, m = min(found, limit) (limit None: every row), distinct: the
         distinct k-mers of the leaves together, in the rows or not."""
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths, k=k)) is None:
             return None
-        _, files, kmin, kmax = win
-        if not kmin <= int(k) <= kmax:
-            raise ValueError(f"k={k} outside the window {kmin}..{kmax} of the leaf databases")
+        files = win[1]
         masks, counts, found = self.engine.exact_patterns(files, int(k), cap=None if limit is None else int(limit))
         return masks, counts, found, int(self.engine.last_patterns_stats[0])
 
@@ -412,8 +393,7 @@ class HipExactBackend:
         from ..engine import ENOMEM, GREEDY_MAX, GREEDY_MIN, EngineError
         if len(leaf_paths) <= self.MAX_SUBSET_LEAVES:
             return None
-        win = self._leaf_window(leaf_paths, self.MAX_LEAVES)
-        if win is None:
+        if (win := self._leaf_window(leaf_paths)) is None:
             return None
         _, files, first, last = win
         if int(kmin) != first:

@@ -16,6 +16,7 @@ import test_core as cpuc
 import test_core_regions as cpur
 import test_exact_schedules as cpu
 import test_gpu_exact_greedy as greedy
+import test_gpu_screen as gpus
 
 pytestmark = pytest.mark.gpu
 
@@ -240,6 +241,25 @@ def test_device_form_equals_path_form(engine_factory, torch_cuda, fixture_paths)
         dev, path = eng.exact_locate_device(ptrs, sizes, k, jobs, ntok), eng.exact_locate(fixture_paths, k, jobs)
         assert any(w.any() for w in path)
         assert all(np.array_equal(x, y) for x, y in zip(dev, path)), k
+
+
+@pytest.mark.parametrize("kind", ["no record", "no token"])
+def test_inputs_without_a_record(engine_factory, torch_cuda, tmp_path, kind):
+    """test_gpu_screen's barren universes as the inputs, one (0, 0) job per file: bitmaps of the right length, all zero --
+    one word each where the emission ran and found nothing, no word where no input holds a token."""
+    paths, _, fas = gpus.barren_files(tmp_path, kind)
+    bufs, ptrs, sizes = gpus.on_device(torch_cuda, fas[:3])
+    ntok = [cpur.index_of(fa)[2] for fa in fas[:3]]
+    assert ntok == ([21] * 3 if kind == "no record" else [0] * 3)
+    jobs = [(0, 0, g) for g in range(3)]
+    for canonical in (True, False):
+        eng = engine_factory(canonical=canonical)
+        for k in gpus.BARREN_KS:
+            got = eng.exact_locate(paths, k, jobs)
+            assert eng.last_locate_found == 0 and len(got) == 3
+            assert all(w.shape == ((nt + 63) // 64,) and not w.any() for w, nt in zip(got, ntok)), (kind, canonical, k)
+    dev = eng.exact_locate_device(ptrs, sizes, k, jobs, ntok)
+    assert eng.last_locate_found == 0 and [w.tolist() for w in dev] == [w.tolist() for w in got]
 
 
 # ---- G6. the command ------------------------------------------------------------------------------------------------------------------

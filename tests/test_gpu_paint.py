@@ -224,6 +224,31 @@ def test_device_form_equals_path_form(engine_factory, torch_cuda, fixture_paths,
         assert all(d.tobytes() == p.tobytes() and d.shape == p.shape for d, p in zip(dev, path)), k
 
 
+@pytest.mark.parametrize("kind", ["no record", "no token"])
+def test_universe_without_a_record(engine_factory, torch_cuda, tmp_path, kind):
+    """test_gpu_screen's barren universes: column 0 is the sample's own, every other column is zero.  Without a token in the
+    universe no emission stages the table of the samples' first rows: the entry does."""
+    paths, smp, fas = gpus.barren_files(tmp_path, kind)
+    bufs, ptrs, sizes = gpus.on_device(torch_cuda, fas)
+    texts = [gpus.samples()[j][2] for j in gpus.BARREN_SAMPLES]
+    nt = [cpur.index_of(text)[2] for text in texts]
+    assert nt == [6001, 0, 41]
+    for canonical in (True, False):
+        eng = engine_factory(canonical=canonical)
+        for k in gpus.BARREN_KS:
+            for window in (64, 4096):
+                got = eng.exact_paint(paths, smp, k, window, ntok=nt)
+                assert eng.last_paint_found == 0 and len(got) == 3
+                for text, rows in zip(texts, got):
+                    want = paint_ref.rows(text, k, canonical, {}, 3, window)
+                    assert rows.shape == (len(want), 5) and rows[:, 0].tolist() == [w[0] for w in want], (kind, canonical, k, window)
+                    assert not rows[:, 1:].any()
+                assert got[0][:, 0].sum() == 6000 - k + 1
+    dev = eng.exact_paint_device(ptrs, sizes, 3, k, window, nt)
+    assert eng.last_paint_found == 0 and len(dev) == 3
+    assert all(d.tolist() == p.tolist() and d.shape == p.shape for d, p in zip(dev, got))
+
+
 # ---- 6. the argument rules -----------------------------------------------------------------------------------------------------------
 def test_argument_rules(engine_factory, fixture_paths, sample_paths):
     from dandd_amd.host.backend import HipExactBackend

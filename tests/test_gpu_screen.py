@@ -3,7 +3,8 @@ the fixture of test_core_regions (7 inputs: an identical pair, a three-record fi
 empty file) and seven samples -- a leaf byte for byte, a relative longer than one workgroup of segments, gzip FASTQ reads that
 overlap, an empty file, one shorter than most k, unrelated text, and one record that hits the smallest and (non-canonical) the
 all-ones key; the universe's own row against dd_exact_select; distinctness; 70 samples in one call; records accumulated over
-passes; the argument rules; and `screen` end to end on a real `--exact` tree."""
+passes; the argument rules; a universe that emits no record and one without a token; and `screen` end to end on a real
+`--exact` tree."""
 import ctypes
 import functools
 import gzip
@@ -264,7 +265,50 @@ def test_device_form_equals_path_form(engine_factory, torch_cuda, fixture_paths,
         assert path[0].any() and dev[0].tolist() == path[0].tolist() and dev[1].tolist() == path[1].tolist(), k
 
 
-# ---- 6. the command -----------------------------------------------------------------------------------------------------------------
+# ---- 6. a universe that leaves the emission nothing ----------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def barren():
+    """-> {name: three universe files}: one 20-base record each (tokens, but no k-mer at k = 21 or 33: the emission runs and
+    finds no record), and 0 bytes each (no token: no emission at all)"""
+    rng = np.random.default_rng(2133)
+    short = tuple(fasta("".join("ACGT"[c] for c in rng.integers(0, 4, 20)), f"u{i}") for i in range(3))
+    assert all(cpur.index_of(fa)[2] == 21 for fa in short)
+    return {"no record": short, "no token": (b"", b"", b"")}
+
+
+BARREN_SAMPLES = (0, 3, 4)                                               # a leaf of the big fixture, the empty file, 40 bases
+BARREN_KS = (21, 33)
+
+
+def barren_files(tmp_path, kind):
+    """-> (universe paths, sample paths, the texts of both in the device forms' order)"""
+    fas = list(barren()[kind]) + [samples()[j][1] for j in BARREN_SAMPLES]
+    paths = greedy.write(tmp_path, fas[:3]) + greedy.write(tmp_path, fas[3:], tag="s")
+    return paths[:3], paths[3:], fas
+
+
+def on_device(torch, fas):
+    """-> (the tensors, their addresses, the texts' sizes): each text with 16 bytes behind it, as the device forms ask"""
+    bufs = [torch.from_numpy(np.frombuffer(f + b"\0" * 16, dtype=np.uint8).copy()).cuda() for f in fas]
+    return bufs, [b.data_ptr() for b in bufs], [len(f) for f in fas]
+
+
+@pytest.mark.parametrize("kind", ["no record", "no token"])
+def test_universe_without_a_record(engine_factory, torch_cuda, tmp_path, kind):
+    paths, smp, fas = barren_files(tmp_path, kind)
+    bufs, ptrs, sizes = on_device(torch_cuda, fas)
+    al, no = [0, 7, 1], [0, 0, 6]
+    for canonical in (True, False):
+        eng = engine_factory(canonical=canonical)
+        for k in BARREN_KS:
+            shared, match = eng.exact_screen(paths, smp, k, al, no)
+            assert shared.shape == (4, 3) and match.shape == (4, 3)
+            assert not shared.any() and not match.any() and eng.last_screen_found == 0, (kind, canonical, k)
+    dev = eng.exact_screen_device(ptrs, sizes, 3, BARREN_KS[-1], al, no)
+    assert eng.last_screen_found == 0 and dev[0].tolist() == shared.tolist() and dev[1].tolist() == match.tolist()
+
+
+# ---- 7. the command -----------------------------------------------------------------------------------------------------------------
 def test_cli_end_to_end(tmp_path, torch_cuda):
     """`screen` on a real `--exact` tree (HipExactBackend), as a process of its own: the three CSVs equal the tables
     test_screen computes from the files' text."""
