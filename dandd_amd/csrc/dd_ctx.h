@@ -1,8 +1,8 @@
 // dd_ctx.h -- the context behind the C ABI's opaque dd_ctx, and the host-side helpers the ABI's sources share
 // (dd_api.hip: context, timing and stats, synth, dd_plan_sweep; dd_sketch_api.hip: sketch; dd_k2_api.hip: union, card and the
-// HLL schedules; dd_exact_api.hip: exact count, schedules and greedy; dd_exact_emit_api.hip: the selected k-mers, where they lie, the samples screened against them and the pattern table, all
-// over dd_exact_host.h / dd_exact_passes.hip: call frame, pass driver, emission; dd_ingest.hip: the file-ingestion pipeline; dd_comm.hip: RCCL).
-// Callers see dandd_hip.h only.
+// HLL schedules, one body each over its slab frame -- Slab, slab_dev -- and its histogram step, hist_step;
+// dd_exact_api.hip: exact count, schedules and greedy; dd_exact_emit_api.hip: the selected k-mers, where they lie, the samples screened against them and the pattern table, all
+// over dd_exact_host.h / dd_exact_passes.hip: call frame, pass driver, emission; dd_ingest.hip: the file-ingestion pipeline; dd_comm.hip: RCCL).  Callers see dandd_hip.h only.
 #pragma once
 #include "../../include/dandd_hip.h"
 #include <sched.h>

@@ -123,42 +123,22 @@ def load_library(path=None):
     lib.dd_last_ingest_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(u64)]
     lib.dd_sketch_device.restype = i32
     lib.dd_sketch_device.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), i32, i32, i32, vp]
-    lib.dd_union.restype = i32
-    lib.dd_union.argtypes = [vp, C.POINTER(vp), i32, sz, vp]
-    lib.dd_union_device.restype = i32
-    lib.dd_union_device.argtypes = [vp, C.POINTER(vp), i32, sz, vp]
+    # the entries on register slabs, each in two forms: the slab (dd_union: the rows) in host memory, or `_device`, in HBM
+    for name, args in (("dd_union", [C.POINTER(vp), i32, sz, vp]), ("dd_card_batch", [vp, i32, vp]),
+                       ("dd_progressive", [vp, i32, i32, vp, i32, vp]), ("dd_pairwise", [vp, i32, i32, vp]),
+                       ("dd_leave_out", [vp, i32, i32, vp, i32, vp]), ("dd_subsets", [vp, i32, i32, vp]),
+                       ("dd_extend", [vp, vp, i32, i32, vp, i32, vp]),
+                       ("dd_greedy", [vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp])):
+        for suffix in ("", "_device"):
+            fn = getattr(lib, name + suffix)
+            fn.restype = i32
+            fn.argtypes = [vp] + args
     lib.dd_card.restype = i32
     lib.dd_card.argtypes = [vp, vp, C.POINTER(C.c_double)]
-    lib.dd_card_batch.restype = i32
-    lib.dd_card_batch.argtypes = [vp, vp, i32, vp]
-    lib.dd_card_batch_device.restype = i32
-    lib.dd_card_batch_device.argtypes = [vp, vp, i32, vp]
     lib.dd_hist_batch_device.restype = i32
     lib.dd_hist_batch_device.argtypes = [vp, vp, i32, vp]
     lib.dd_ertl_mle.restype = C.c_double
     lib.dd_ertl_mle.argtypes = [vp, i32]
-    lib.dd_progressive.restype = i32
-    lib.dd_progressive.argtypes = [vp, vp, i32, i32, vp, i32, vp]
-    lib.dd_progressive_device.restype = i32
-    lib.dd_progressive_device.argtypes = [vp, vp, i32, i32, vp, i32, vp]
-    lib.dd_pairwise.restype = i32
-    lib.dd_pairwise.argtypes = [vp, vp, i32, i32, vp]
-    lib.dd_pairwise_device.restype = i32
-    lib.dd_pairwise_device.argtypes = [vp, vp, i32, i32, vp]
-    lib.dd_leave_out.restype = i32
-    lib.dd_leave_out.argtypes = [vp, vp, i32, i32, vp, i32, vp]
-    lib.dd_leave_out_device.restype = i32
-    lib.dd_leave_out_device.argtypes = [vp, vp, i32, i32, vp, i32, vp]
-    lib.dd_subsets.restype = i32
-    lib.dd_subsets.argtypes = [vp, vp, i32, i32, vp]
-    lib.dd_subsets_device.restype = i32
-    lib.dd_subsets_device.argtypes = [vp, vp, i32, i32, vp]
-    for fn in (lib.dd_extend, lib.dd_extend_device):
-        fn.restype = i32
-        fn.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp]
-    for fn in (lib.dd_greedy, lib.dd_greedy_device):
-        fn.restype = i32
-        fn.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp]
     lib.dd_exact_count.restype = i32
     lib.dd_exact_count.argtypes = [vp, C.POINTER(C.c_char_p), i32, i32, C.POINTER(u64)]
     lib.dd_exact_count_device.restype = i32
@@ -584,114 +564,109 @@ class Engine:
         self._check(self._lib.dd_hist_batch_device(self._ctx, C.c_void_p(int(regs_ptr)), njobs, h.ctypes.data))
         return h
 
-    # -- progressive / pairwise -----------------------------------------------------------
+    # -- the schedules on register slabs: one body each, the slab in host memory or in HBM (dd_k2_api.hip) -----------------
+    def _slab_src(self, leaf=None, leaf_ptr=None, n=None, K=None):
+        """-> (the argument that names a slab entry's slab, n, K, the entry's suffix): a host array [n][K][m] (the argument
+        keeps it alive for the call), or the device address of one with its n and K."""
+        if leaf_ptr is not None:
+            return C.c_void_p(int(leaf_ptr)), int(n), int(K), "_device"
+        leaf = _u8(leaf)
+        return leaf.ctypes, leaf.shape[0], leaf.shape[1], ""
+
+    def _slab_sched(self, what, src, shape, *extra):
+        leaf, n, K, suffix = src
+        card = np.empty(shape + (K,), dtype=np.float64)
+        self._check(getattr(self._lib, f"dd_{what}{suffix}")(self._ctx, leaf, n, K, *extra, card.ctypes.data))
+        return card
+
+    def _progressive(self, src, orderings):
+        n = src[1]
+        ords = np.ascontiguousarray(orderings, dtype=np.int32).reshape(-1, n)
+        return self._slab_sched("progressive", src, (ords.shape[0], n), ords.ctypes.data, ords.shape[0])
+
+    def _pairwise(self, src):
+        return self._slab_sched("pairwise", src, (src[1], src[1]))
+
+    def _subsets(self, src):
+        return self._slab_sched("subsets", src, (1 << min(max(src[1], 0), 16),))
+
+    def _leave_out(self, src, group, ngroups):
+        grp = np.ascontiguousarray(group, dtype=np.int32).reshape(src[1])
+        ngroups = int(grp.max()) + 1 if ngroups is None else int(ngroups)
+        return self._slab_sched("leave_out", src, (max(ngroups, 0) + 1,), grp.ctypes.data, ngroups)
+
+    def _extend(self, src, base, rows):
+        leaf, n, K, suffix = src
+        if rows is None:
+            rows_ptr, nrows = None, n
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+            rows_ptr, nrows = rows.ctypes.data, rows.size
+        card = np.empty((max(nrows, 0), K), dtype=np.float64)
+        self._check(getattr(self._lib, "dd_extend" + suffix)(self._ctx, base, leaf, n, K, rows_ptr, nrows, card.ctypes.data))
+        return card
+
+    def _greedy(self, src, kmin, mode, cand, nfixed, nsteps):
+        leaf, n, K, suffix = src
+        cand = np.ascontiguousarray(np.arange(n) if cand is None else cand, dtype=np.int32).reshape(-1)
+        nsteps = cand.size if nsteps is None else int(nsteps)
+        order = np.empty(max(nsteps, 0), dtype=np.int32)
+        card = np.empty((max(nsteps, 0), K), dtype=np.float64)
+        self._check(getattr(self._lib, "dd_greedy" + suffix)(self._ctx, leaf, n, K, int(kmin), int(mode), cand.ctypes.data, cand.size,
+                                                             int(nfixed), nsteps, order.ctypes.data, card.ctypes.data))
+        return order, card
+
     def progressive(self, leaf, orderings):
         """leaf [n][K][m] uint8 (host), orderings [o][n] int -> card [o][n][K] float64."""
-        leaf = _u8(leaf)
-        n, K = leaf.shape[0], leaf.shape[1]
-        ords = np.ascontiguousarray(orderings, dtype=np.int32).reshape(-1, n)
-        card = np.empty((ords.shape[0], n, K), dtype=np.float64)
-        self._check(self._lib.dd_progressive(self._ctx, leaf.ctypes.data, n, K, ords.ctypes.data,
-                                             ords.shape[0], card.ctypes.data))
-        return card
+        return self._progressive(self._slab_src(leaf), orderings)
 
     def progressive_device(self, leaf_ptr, n, K, orderings):
-        ords = np.ascontiguousarray(orderings, dtype=np.int32).reshape(-1, n)
-        card = np.empty((ords.shape[0], n, K), dtype=np.float64)
-        self._check(self._lib.dd_progressive_device(self._ctx, C.c_void_p(int(leaf_ptr)), n, K,
-                                                    ords.ctypes.data, ords.shape[0], card.ctypes.data))
-        return card
+        return self._progressive(self._slab_src(None, leaf_ptr, n, K), orderings)
 
     def pairwise(self, leaf):
-        leaf = _u8(leaf)
-        n, K = leaf.shape[0], leaf.shape[1]
-        card = np.empty((n, n, K), dtype=np.float64)
-        self._check(self._lib.dd_pairwise(self._ctx, leaf.ctypes.data, n, K, card.ctypes.data))
-        return card
+        return self._pairwise(self._slab_src(leaf))
 
     def pairwise_device(self, leaf_ptr, n, K):
-        card = np.empty((n, n, K), dtype=np.float64)
-        self._check(self._lib.dd_pairwise_device(self._ctx, C.c_void_p(int(leaf_ptr)), n, K, card.ctypes.data))
-        return card
+        return self._pairwise(self._slab_src(None, leaf_ptr, n, K))
 
     def leave_out(self, leaf, group, ngroups=None):
         """leaf [n][K][m] uint8 (host), group [n] int (-1: in every union) -> card [G+1][K] float64: row g the union of the
         leaves outside group g, row G the union of all.  G = max(group) + 1 unless given."""
-        leaf = _u8(leaf)
-        n, K = leaf.shape[0], leaf.shape[1]
-        grp = np.ascontiguousarray(group, dtype=np.int32).reshape(n)
-        ngroups = int(grp.max()) + 1 if ngroups is None else int(ngroups)
-        card = np.empty((max(ngroups, 0) + 1, K), dtype=np.float64)
-        self._check(self._lib.dd_leave_out(self._ctx, leaf.ctypes.data, n, K, grp.ctypes.data, ngroups, card.ctypes.data))
-        return card
+        return self._leave_out(self._slab_src(leaf), group, ngroups)
 
     def leave_out_device(self, leaf_ptr, n, K, group, ngroups=None):
-        grp = np.ascontiguousarray(group, dtype=np.int32).reshape(n)
-        ngroups = int(grp.max()) + 1 if ngroups is None else int(ngroups)
-        card = np.empty((max(ngroups, 0) + 1, K), dtype=np.float64)
-        self._check(self._lib.dd_leave_out_device(self._ctx, C.c_void_p(int(leaf_ptr)), n, K, grp.ctypes.data, ngroups,
-                                                  card.ctypes.data))
-        return card
+        return self._leave_out(self._slab_src(None, leaf_ptr, n, K), group, ngroups)
 
     def subsets(self, leaf):
         """leaf [n][K][m] uint8 (host), n <= 16 -> card [2^n][K] float64: row s the union of the leaves i with bit i of s set
         (row 0, the empty set, 0.0)."""
-        leaf = _u8(leaf)
-        n, K = leaf.shape[0], leaf.shape[1]
-        card = np.empty((1 << min(max(n, 0), 16), K), dtype=np.float64)
-        self._check(self._lib.dd_subsets(self._ctx, leaf.ctypes.data, n, K, card.ctypes.data))
-        return card
+        return self._subsets(self._slab_src(leaf))
 
     def subsets_device(self, leaf_ptr, n, K):
-        card = np.empty((1 << min(max(int(n), 0), 16), int(K)), dtype=np.float64)
-        self._check(self._lib.dd_subsets_device(self._ctx, C.c_void_p(int(leaf_ptr)), int(n), int(K), card.ctypes.data))
-        return card
-
-    # -- extend / greedy ------------------------------------------------------------------
-    def _extend(self, fn, base, leaf, n, K, rows):
-        if rows is None:
-            rows_ptr, nrows = None, int(n)
-        else:
-            rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
-            rows_ptr, nrows = rows.ctypes.data, rows.size
-        card = np.empty((max(nrows, 0), int(K)), dtype=np.float64)
-        self._check(fn(self._ctx, base, leaf, int(n), int(K), rows_ptr, nrows, card.ctypes.data))
-        return card
+        return self._subsets(self._slab_src(None, leaf_ptr, n, K))
 
     def extend(self, base, leaf, rows=None):
         """base [K][m] uint8 (host) or None (the empty sketch), leaf [n][K][m] uint8 (host), rows: leaf rows (None: all, in
         order; repeats allowed) -> card [nrows][K] float64: |base U leaf[rows[r]]|."""
         leaf = _u8(leaf)
-        n, K = leaf.shape[0], leaf.shape[1]
         if base is not None:
             base = _u8(base)
             if base.size != leaf[0].size:
                 raise ValueError("base is not one [K][m] sketch row of the slab")
-        return self._extend(self._lib.dd_extend, None if base is None else base.ctypes.data, leaf.ctypes.data, n, K, rows)
+        return self._extend(self._slab_src(leaf), None if base is None else base.ctypes.data, rows)
 
     def extend_device(self, base_ptr, leaf_ptr, n, K, rows=None):
         """The same with base (0 / None: the empty sketch) and the slab in device memory."""
-        return self._extend(self._lib.dd_extend_device, C.c_void_p(int(base_ptr)) if base_ptr else None, C.c_void_p(int(leaf_ptr)),
-                            n, K, rows)
-
-    def _greedy(self, fn, leaf, n, K, kmin, mode, cand, nfixed, nsteps):
-        cand = np.ascontiguousarray(np.arange(n) if cand is None else cand, dtype=np.int32).reshape(-1)
-        nsteps = cand.size if nsteps is None else int(nsteps)
-        order = np.empty(max(nsteps, 0), dtype=np.int32)
-        card = np.empty((max(nsteps, 0), int(K)), dtype=np.float64)
-        self._check(fn(self._ctx, leaf, int(n), int(K), int(kmin), int(mode), cand.ctypes.data, cand.size, int(nfixed), nsteps,
-                       order.ctypes.data, card.ctypes.data))
-        return order, card
+        return self._extend(self._slab_src(None, leaf_ptr, n, K), C.c_void_p(int(base_ptr)) if base_ptr else None, rows)
 
     def greedy(self, leaf, kmin, mode, cand=None, nfixed=0, nsteps=None):
         """leaf [n][K][m] uint8 (host), columns k = kmin .. kmin + K - 1; mode GREEDY_MAX / GREEDY_MIN; cand: distinct leaf rows
         in tie-break order (None: all), the first nfixed of them a given start -> (order int32 [nsteps], card float64
         [nsteps][K]): the steepest (flattest) ordering by the selection rule of include/dandd_hip.h and its prefix unions."""
-        leaf = _u8(leaf)
-        return self._greedy(self._lib.dd_greedy, leaf.ctypes.data, leaf.shape[0], leaf.shape[1], kmin, mode, cand, nfixed, nsteps)
+        return self._greedy(self._slab_src(leaf), kmin, mode, cand, nfixed, nsteps)
 
     def greedy_device(self, leaf_ptr, n, K, kmin, mode, cand=None, nfixed=0, nsteps=None):
-        return self._greedy(self._lib.dd_greedy_device, C.c_void_p(int(leaf_ptr)), n, K, kmin, mode, cand, nfixed, nsteps)
+        return self._greedy(self._slab_src(None, leaf_ptr, n, K), kmin, mode, cand, nfixed, nsteps)
 
     # -- exact distinct k-mer count (KMC stand-in) ----------------------------------------
     def exact_count(self, paths, k):
