@@ -1,13 +1,14 @@
 // dd_exact_emit_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h) that hand k-mers out instead of counting
-// them.  Four look k-mers up in the ordered records of one emission: the selected k-mers themselves (dd_exact_select_kmers),
-// where they lie in each genome (dd_exact_locate), what samples that are no inputs hold of them (dd_exact_screen) and where
-// along themselves (dd_exact_paint).  Each is its own argument rules, the ordered-record step of dd_exact_host.h
-// (exact_records, then ExactRecords::order inside the entry's timing span) and the one kernel that reads the ordered set;
-// screen and paint also share the frame below: K0 over the universe and the samples, a sort that sees the universe only.
+// them.  Five look k-mers up in the ordered records of one emission: the selected k-mers themselves (dd_exact_select_kmers),
+// where they lie in each genome (dd_exact_locate), what samples that are no inputs hold of them (dd_exact_screen), where
+// along themselves (dd_exact_paint) and which genome each of their records belongs to (dd_exact_reads).  Each is its own
+// argument rules, the ordered-record step of dd_exact_host.h (exact_records, then ExactRecords::order inside the entry's
+// timing span) and the kernels that read the ordered set; screen, paint and reads also share the frame below: K0 over the
+// universe and the samples, a sort that sees the universe only.
 // dd_exact_patterns hands out no k-mer but is ragged like the others -- one k per call, a cap and a count -- and
 // dd_fasta_index is the record index of a file that turns places into names.
 // Host-side orchestration only; the kernels are in dd_exact_sched.hip (emit_kernel, AccPatterns), dd_exact_locate.hip,
-// dd_exact_screen.hip, dd_exact_paint.hip and dd_exact_patterns.hip.
+// dd_exact_screen.hip, dd_exact_paint.hip, dd_exact_reads.hip and dd_exact_patterns.hip.
 #include "dd_exact_host.h"
 
 extern "C" {
@@ -170,7 +171,7 @@ int dd_exact_locate(dd_ctx* c, const char* const* paths, int n, int k, const uin
     });
 }
 
-// ------------------------------------------------------------------- the universe and the samples: what screen and paint share
+// ------------------------------------------------------------------- the universe and the samples: what screen, paint and reads share
 // K0 runs over the universe's n inputs AND the ns samples behind them, once.  The sort and the emission see the universe
 // alone -- the samples stay out of the sort and out of the slot count that sizes the record area -- with the single query
 // (0, 0); the entry's own table rides behind that query in the image the emission stages.
@@ -372,6 +373,117 @@ int dd_exact_paint(dd_ctx* c, const char* const* paths, int n, const char* const
     if (paint_args(c, paths, n, ns, k, window, off, found)) return DD_EINVAL;
     return universe_path_form(c, paths, n, samples, ns, [&](auto p, auto s) {
         return dd_exact_paint_device(c, p, s, n, ns, k, window, off, counts, found);
+    });
+}
+
+// ------------------------------------------------------------------- samples called row by row
+// dd_exact_reads.hip: paint's frame with the caller's borders for rows -- the records of a read set or of a draft assembly,
+// or any intervals -- then the vote over every row's counters and the tally of the votes per sample, all in c->hits:
+// counters [rows][n + 2] u32 | borders [rows] u64 | calls [rows][6] u32 | sets [rows][2] u64 | tally [ns][n + 3] u64, the
+// call arrays only where the caller takes them.  The borders are checked against the samples' token counts on the host.
+namespace {
+
+int reads_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const uint64_t* off, const uint64_t* start, uint32_t min_hits,
+               const uint64_t* tally, const uint64_t* found) {
+    if (universe_args(c, inputs, n, ns, k, found)) return DD_EINVAL;
+    if (!min_hits) return fail(DD_EINVAL, "min_hits=0: a call needs at least one position of its genome (min_hits >= 1)");
+    if (!off || !tally) return fail(DD_EINVAL, "null argument");
+    for (int s = 0; s < ns; ++s)
+        if (off[s + 1] < off[s]) return fail(DD_EINVAL, "off[] must ascend");
+    if (off[ns] > off[0] && !start) return fail(DD_EINVAL, "null argument");
+    return DD_OK;
+}
+
+}  // namespace
+
+int dd_exact_reads_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns, int k, const uint64_t* off,
+                          const uint64_t* start, uint32_t min_hits, uint32_t* calls, uint64_t* sets, uint32_t* counts, uint64_t* tally,
+                          uint64_t* found) {
+    if (reads_args(c, fasta_dev, n, ns, k, off, start, min_hits, tally, found)) return DD_EINVAL;
+    if (universe_buffers(fasta_dev, nbytes, n, ns)) return DD_EINVAL;
+    const uint64_t rows = off[ns] - off[0];
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    ExactInputs in;
+    if ((rc = universe_prepare(c, fasta_dev, nbytes, n, ns, in))) return rc;
+    std::vector<unsigned long long> ntok;   // what the borders are checked against: every sample's ntok
+    if ((rc = exact_read_ntok(c, in, n, ns, ntok))) return rc;
+    std::vector<char> image(kOwnTable + sizeof(unsigned long long) * ((size_t)ns + 1), 0);   // the first row of every sample, and the end [ns + 1]
+    unsigned long long* off0 = static_cast<unsigned long long*>(own_table(image.data()));
+    size_t sample_segments = 0, sample_rows = 0;
+    for (int s = 0; s < ns; ++s) {
+        for (uint64_t r = off[s]; r < off[s + 1]; ++r) {
+            if (r > off[s] && start[r] <= start[r - 1])
+                return fail(DD_EINVAL, "sample %d, row %llu: start = %llu does not ascend strictly (the row in front starts at %llu)", s,
+                            (unsigned long long)(r - off[s]), (unsigned long long)start[r], (unsigned long long)start[r - 1]);
+            if (start[r] > ntok[(size_t)s])
+                return fail(DD_EINVAL, "sample %d, row %llu: start = %llu lies behind the sample's %llu tokens", s, (unsigned long long)(r - off[s]),
+                            (unsigned long long)start[r], ntok[(size_t)s]);
+        }
+        off0[s] = off[s] - off[0], off0[s + 1] = off[s + 1] - off[0];
+        sample_rows = std::max(sample_rows, (size_t)(off[s + 1] - off[s]));
+        if (off[s + 1] > off[s]) sample_segments = std::max(sample_segments, (size_t)((ntok[(size_t)s] + dd::kSegTokens - 1) / dd::kSegTokens));
+    }
+    const size_t ncol = (size_t)n + 2, nbin = (size_t)n + 3;
+    const size_t cbytes = align_up((size_t)rows * ncol * sizeof(uint32_t), 256), bbytes = align_up((size_t)rows * sizeof(uint64_t), 256),
+                 lbytes = calls ? align_up((size_t)rows * 6 * sizeof(uint32_t), 256) : 0,
+                 sbytes = sets ? align_up((size_t)rows * 2 * sizeof(uint64_t), 256) : 0, tbytes = (size_t)ns * nbin * sizeof(uint64_t);
+    ExactRecords rec;
+    if (in.slots) {
+        if ((rc = exact_records(c, in, n, k, "exact reads", &kSlotsOfUniverse, 1, image.data(), image.size(), in.slots, rec))) return rc;
+    } else if (rows) {
+        if ((rc = stage_table(c, c->ord, image.data(), image.size()))) return rc;   // (no emission has staged it)
+    }
+    std::vector<uint64_t> tally_host((size_t)ns * nbin, 0);
+    std::vector<uint32_t> calls_host(calls ? (size_t)rows * 6 : 0), counts_host(counts ? (size_t)rows * ncol : 0);
+    std::vector<uint64_t> sets_host(sets ? (size_t)rows * 2 : 0);
+    if (rows) {
+        const size_t total = cbytes + bbytes + lbytes + sbytes + tbytes;
+        if (c->hits.reserve(total))
+            return fail(DD_ENOMEM, "exact reads: no device memory for the %zu bytes of the rows (%llu rows: %zu of counters, %zu columns of 4 bytes, %zu of "
+                                   "borders, %zu of calls and sets) and of the tally",
+                        total, (unsigned long long)rows, cbytes, ncol, bbytes, lbytes + sbytes);
+        char* base = static_cast<char*>(c->hits.p);
+        uint32_t* counts_dev = reinterpret_cast<uint32_t*>(base);
+        unsigned long long* start_dev = reinterpret_cast<unsigned long long*>(base + cbytes);
+        uint32_t* calls_dev = calls ? reinterpret_cast<uint32_t*>(base + cbytes + bbytes) : nullptr;
+        uint64_t* sets_dev = sets ? reinterpret_cast<uint64_t*>(base + cbytes + bbytes + lbytes) : nullptr;
+        unsigned long long* tally_dev = reinterpret_cast<unsigned long long*>(base + cbytes + bbytes + lbytes + sbytes);
+        DD_HIP(hipMemsetAsync(counts_dev, 0, cbytes, st));
+        DD_HIP(hipMemsetAsync(tally_dev, 0, tbytes, st));
+        DD_HIP(hipMemcpyAsync(start_dev, start + off[0], (size_t)rows * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        {
+            Span sp(c, DD_KERNEL_EXACT);
+            dd::LocateSet set{};   // (an empty universe: no record, column 0 alone)
+            if (rec.kept) DD_HIP(rec.order(c, k, &set));
+            const unsigned long long* off_dev = static_cast<const unsigned long long*>(own_table(c->ord.p));
+            dd::launch_exact_reads(in.etab_dev + n, ns, sample_segments, k, c->canonical, set, n, off_dev, start_dev, counts_dev, st);
+            DD_HIP(hipGetLastError());
+            dd::launch_exact_vote(counts_dev, off_dev, ns, sample_rows, n, min_hits, calls_dev, sets_dev, tally_dev, st);
+            DD_HIP(hipGetLastError());
+        }
+        DD_HIP(hipMemcpyAsync(tally_host.data(), tally_dev, tbytes, hipMemcpyDeviceToHost, st));
+        if (calls) DD_HIP(hipMemcpyAsync(calls_host.data(), calls_dev, calls_host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (sets) DD_HIP(hipMemcpyAsync(sets_host.data(), sets_dev, sets_host.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        if (counts) DD_HIP(hipMemcpyAsync(counts_host.data(), counts_dev, counts_host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        DD_HIP(hipStreamSynchronize(st));
+    }
+    // (nothing is written before everything is known)
+    if (calls && rows) memcpy(calls + off[0] * 6, calls_host.data(), calls_host.size() * sizeof(uint32_t));
+    if (sets && rows) memcpy(sets + off[0] * 2, sets_host.data(), sets_host.size() * sizeof(uint64_t));
+    if (counts && rows) memcpy(counts + off[0] * ncol, counts_host.data(), counts_host.size() * sizeof(uint32_t));
+    memcpy(tally, tally_host.data(), tally_host.size() * sizeof(uint64_t));
+    *found = rec.found;
+    return DD_OK;
+}
+
+int dd_exact_reads(dd_ctx* c, const char* const* paths, int n, const char* const* samples, int ns, int k, const uint64_t* off,
+                   const uint64_t* start, uint32_t min_hits, uint32_t* calls, uint64_t* sets, uint32_t* counts, uint64_t* tally,
+                   uint64_t* found) {
+    if (reads_args(c, paths, n, ns, k, off, start, min_hits, tally, found)) return DD_EINVAL;
+    return universe_path_form(c, paths, n, samples, ns, [&](auto p, auto s) {
+        return dd_exact_reads_device(c, p, s, n, ns, k, off, start, min_hits, calls, sets, counts, tally, found);
     });
 }
 

@@ -33,22 +33,6 @@
 namespace dd {
 namespace {
 
-// genome i's count out of a thread's planes
-DD_D uint32_t plane_count(const uint64_t (&p)[kPaintPlanes], int i) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < kPaintPlanes; ++j) c |= (uint32_t)((p[j] >> i) & 1ull) << j;
-    return c;
-}
-
-// the sum over the wave of a per-lane count below 2^kPaintPlanes, from one ballot per bit; the same in every lane
-DD_D uint32_t wave_sum(uint32_t v) {
-    uint32_t sum = 0;
-#pragma unroll
-    for (int j = 0; j < kPaintPlanes; ++j) sum += (uint32_t)__builtin_popcountll(__ballot((v >> j) & 1u)) << j;
-    return sum;
-}
-
 template <bool CANON, bool WIDE>
 __global__ __launch_bounds__(256) void paint_kernel(const ExactGenome* __restrict__ samples, int k, LocateSet set, int n,
                                                    unsigned long long wsegs, const unsigned long long* __restrict__ row0,

@@ -1,7 +1,8 @@
 // dd_exact_walk.h -- what more than one kernel of the exact device path does, once: the key masks of a k, the query test
-// on a membership mask, the token walk of a 64-token segment (kmer_extract_kernel, locate_kernel, screen_kernel, paint_kernel),
-// the lookup of a key in the ordered records (locate_kernel, screen_kernel, paint_kernel) and the wave-aggregated append (kmer_extract_kernel,
-// sched_kernel, emit_kernel).  Everything here is inlined into its caller: no kernel calls across files.
+// on a membership mask, the token walk of a 64-token segment (kmer_extract_kernel, locate_kernel, screen_kernel, paint_kernel,
+// reads_kernel), the lookup of a key in the ordered records (locate_kernel, screen_kernel, paint_kernel, reads_kernel), the
+// read-out of the bit-sliced per-genome counter (paint_kernel, reads_kernel) and the wave-aggregated append
+// (kmer_extract_kernel, sched_kernel, emit_kernel).  Everything here is inlined into its caller: no kernel calls across files.
 #pragma once
 #include "dd_common.h"
 #include "dd_kernels.h"
@@ -100,6 +101,23 @@ DD_D bool find_record(const LocateSet& set, uint64_t ah, uint64_t al, unsigned l
     at = first;
     if (first >= set.found || set.lo[first] != al) return false;
     return !WIDE || set.hi[first] == ah;
+}
+
+// The bit-sliced per-genome counter of paint_kernel and reads_kernel: kPaintPlanes 64-bit planes per thread, bit i of plane
+// j = bit j of genome i's count.  Genome i's count out of a thread's planes:
+DD_D uint32_t plane_count(const uint64_t (&p)[kPaintPlanes], int i) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < kPaintPlanes; ++j) c |= (uint32_t)((p[j] >> i) & 1ull) << j;
+    return c;
+}
+
+// the sum over the wave of a per-lane count below 2^kPaintPlanes, from one ballot per bit; the same in every lane
+DD_D uint32_t wave_sum(uint32_t v) {
+    uint32_t sum = 0;
+#pragma unroll
+    for (int j = 0; j < kPaintPlanes; ++j) sum += (uint32_t)__builtin_popcountll(__ballot((v >> j) & 1u)) << j;
+    return sum;
 }
 
 // Dense append by the lanes of a wave that `take`: one atomicAdd on the counter (uint32_t in LDS, unsigned long long in

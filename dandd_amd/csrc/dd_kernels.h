@@ -447,6 +447,25 @@ void launch_exact_paint(const ExactGenome* samples_dev, int ns, size_t max_segme
                         size_t window_segments, const unsigned long long* row0_dev, uint32_t* counts_dev, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// samples that are no leaves, called row by row (dd_exact_reads.hip), behind launch_exact_emit_order: paint's walk and
+// counters with rows from the caller's borders, then the vote over each row and the tally of the votes.
+// ---------------------------------------------------------------------------------------
+constexpr int kReadsClasses = 64 + 3;     // bins of a sample's tally: unique to genome i < n | ambiguous | unclassified | no valid k-mer
+// samples_dev[ns]: the samples' token streams (`base` is not read).  off_dev [ns + 1]: sample s owns the rows off[s] ..
+// off[s+1]-1 of start_dev and counts_dev; start_dev: row r of a sample covers its tokens start[r] .. start[r+1]-1, its last
+// row runs to ntok -- strictly ascending within a sample and <= ntok (the caller has checked both), the tokens in front of a
+// sample's first border in no row.  counts_dev [rows][n + 2] u32, zeroed by the caller: launch_exact_paint's columns, a
+// k-mer counting in the row that holds its end token.  An empty set (found = 0, no array read) gives column 0 alone.
+void launch_exact_reads(const ExactGenome* samples_dev, int ns, size_t max_segments, int k, int canonical, const LocateSet& set, int n,
+                        const unsigned long long* off_dev, const unsigned long long* start_dev, uint32_t* counts_dev, hipStream_t st);
+// Behind launch_exact_reads on the same stream.  calls_dev [rows][6] u32 (valid, hit, best, best_count, second,
+// second_count; 0xFFFFFFFF: no such genome) and sets_dev [rows][2] u64 (ties, full): either may be null and is then not
+// written.  tally_dev [ns][n + 3] u64, zeroed by the caller: += the rows of sample s in each class, a row with a valid k-mer
+// being classified where its best column reaches min_hits.  max_rows: the rows of the sample that owns most.
+void launch_exact_vote(const uint32_t* counts_dev, const unsigned long long* off_dev, int ns, size_t max_rows, int n, uint32_t min_hits,
+                       uint32_t* calls_dev, uint64_t* sets_dev, unsigned long long* tally_dev, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // exact greedy walk (dd_exact_greedy.hip) over the mask streams of kSchedStream: one launch per step of the walk reads
 // every stream once.  gain[kk][b] += masks of stream kk (store[seg.off[kk] .. seg.off[kk + 1])) that meet `chosen` nowhere
 // and hold bit b, for every b < 64 (a bit of `chosen` gains 0).  gain_dev [K][64], zeroed by the caller.

@@ -38,6 +38,7 @@ EXPORTS = [
     "dd_exact_locate", "dd_exact_locate_device", "dd_fasta_index",
     "dd_exact_screen", "dd_exact_screen_device",
     "dd_exact_paint", "dd_exact_paint_device",
+    "dd_exact_reads", "dd_exact_reads_device",
     "dd_exact_patterns", "dd_exact_patterns_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
@@ -173,7 +174,9 @@ def load_library(path=None):
     for name, src, extra in (("dd_exact_screen", [paths_t, i32, paths_t, i32], [vp, vp, i32, vp, vp]),
                              ("dd_exact_paint", [paths_t, i32, paths_t, i32], [u64, vp, vp]),
                              ("dd_exact_screen_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, i32, vp, vp]),
-                             ("dd_exact_paint_device", [ptrs_t, sizes_t, i32, i32], [u64, vp, vp])):
+                             ("dd_exact_paint_device", [ptrs_t, sizes_t, i32, i32], [u64, vp, vp]),
+                             ("dd_exact_reads", [paths_t, i32, paths_t, i32], [vp, vp, C.c_uint32, vp, vp, vp, vp]),
+                             ("dd_exact_reads_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, C.c_uint32, vp, vp, vp, vp])):
         fn = getattr(lib, name)
         fn.restype = i32
         fn.argtypes = [vp] + src + [i32] + extra + [C.POINTER(u64)]
@@ -302,6 +305,26 @@ def paint_windows(nwin, window, tok_start, seq_len):
         start[has] = np.maximum(lo[has] - fs[at[has]], 0)
         end[has] = np.minimum(hi[has], fe[at[has]]) - fs[at[has]]
     return record, start, end, count.astype(np.int64)
+
+
+NO_GENOME = 0xFFFFFFFF   # exact_reads' calls: no best / no second genome
+
+
+def read_classes(calls, sets, min_hits, n=64):
+    """Host-side, pure numpy: the call arrays of exact_reads (calls uint32 [r][6], sets uint64 [r][2]) over n genomes (64: the
+    most a universe holds) ->
+    (classes int64 [r], tally uint64 [n+3]).  A row's class: n + 2 without a valid k-mer, n + 1 unclassified (its best column
+    is below min_hits), the best genome's index where exactly one genome holds the best column, n -- ambiguous -- where
+    several do.  tally[c]: the rows of class c, what the device counts per sample."""
+    n, min_hits = int(n), int(min_hits)
+    if min_hits < 1:
+        raise ValueError("min_hits must be at least 1")
+    calls = np.asarray(calls, dtype=np.uint32).reshape(-1, 6)
+    ties = np.asarray(sets, dtype=np.uint64).reshape(-1, 2)[:, 0]
+    several = (ties & (ties - np.uint64(1))) != 0                        # (ties = 0 only below min_hits: best_count = 0)
+    classes = np.where(calls[:, 0] == 0, n + 2,
+                       np.where(calls[:, 3] < min_hits, n + 1, np.where(several, n, calls[:, 2].astype(np.int64)))).astype(np.int64)
+    return classes, np.bincount(classes, minlength=n + 3).astype(np.uint64)
 
 
 def kmer_text(kmers, k):
@@ -913,6 +936,49 @@ class Engine:
         """exact_paint over FASTA bytes on the device: the n universe inputs first, the samples behind them; ntok: every
         sample's token count (the library checks them)."""
         return self._exact_paint(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes, n=n), k, window, ntok)
+
+    # -- samples called row by row: paint's walk with the caller's borders, a vote per row, a tally per sample (dd_exact_reads.hip)
+    last_reads_found = None   # of the last exact_reads call: the distinct k-mers of the universe
+    def _exact_reads(self, src, k, min_hits, rows, calls, counts):
+        args, n, ns, suffix = src
+        if len(rows) != ns:
+            raise ValueError(f"{len(rows)} border arrays for {ns} samples")
+        starts = [np.ascontiguousarray(r, dtype=np.uint64).reshape(-1) for r in rows]
+        off = np.zeros(max(ns, 0) + 1, dtype=np.uint64)
+        off[1:ns + 1] = np.cumsum([len(r) for r in starts], dtype=np.uint64) if ns > 0 else []
+        total = int(off[max(ns, 0)])
+        start = np.concatenate(starts + [np.zeros(1, dtype=np.uint64)])
+        call_arr = np.zeros((max(total, 1), 6), dtype=np.uint32) if calls else None
+        set_arr = np.zeros((max(total, 1), 2), dtype=np.uint64) if calls else None
+        count_arr = np.zeros((max(total, 1), max(n, 0) + 2), dtype=np.uint32) if counts else None
+        tally = np.zeros((max(ns, 1), max(n, 0) + 3), dtype=np.uint64)
+        found = C.c_uint64()
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(getattr(self._lib, f"dd_exact_reads{suffix}")(self._ctx, *args, int(k), off.ctypes.data, start.ctypes.data, int(min_hits),
+                                                                 ptr(call_arr), ptr(set_arr), ptr(count_arr), tally.ctypes.data, C.byref(found)))
+        self.last_reads_found = int(found.value)
+        cut = lambda a, s: None if a is None else a[int(off[s]):int(off[s + 1])].copy()
+        return [(cut(call_arr, s), cut(set_arr, s), cut(count_arr, s)) for s in range(ns)], tally[:max(ns, 0)]
+
+    def exact_reads(self, paths, samples, k, min_hits=1, index=None, rows=None, calls=True, counts=False):
+        """FASTA files (n <= 64: the universe), sample files (FASTA / FASTQ, plain or gzip, ns <= 1024), one k -> (per sample
+        (calls uint32 [r][6], sets uint64 [r][2], counts uint32 [r][n+2] or None), tally uint64 [ns][n+3]).  By default a
+        row is a record of the sample -- a read, a contig: the borders are tok_start of fasta_index(sample), or of `index`
+        where the caller has it ([(names, seq_len, tok_start, ntok)] per sample); rows= gives per-sample border arrays of
+        its own (tokens, strictly ascending, <= ntok; row r runs to the next border, the last to the sample's end).
+        counts: exact_paint's columns per row.  calls: valid, hit, best, best_count, second, second_count (NO_GENOME: none);
+        sets: the genomes tied at best_count, the genomes that hold every universe position of the row.  tally[s]: the rows
+        uniquely called to genome i, then the ambiguous, the unclassified (best_count < min_hits) and those without a valid
+        k-mer (read_classes).  calls=False returns (None, None, counts) per sample: with counts=False the tally alone comes
+        back from the device.  last_reads_found: the universe's distinct k-mers."""
+        if rows is None:
+            rows = [ix[2] for ix in (index if index is not None else [fasta_index(p) for p in samples])]
+        return self._exact_reads(self._exact_src(paths=paths, samples=samples), k, min_hits, rows, calls, counts)
+
+    def exact_reads_device(self, fasta_ptrs, nbytes, n, k, rows, min_hits=1, calls=True, counts=False):
+        """exact_reads over FASTA bytes on the device: the n universe inputs first, the samples behind them; rows: every
+        sample's borders (the library checks them against the token counts)."""
+        return self._exact_reads(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes, n=n), k, min_hits, rows, calls, counts)
 
     # -- the membership-pattern table: the distinct masks and how many k-mers carry each (dd_exact_patterns.hip) ------------
     last_patterns_stats = None   # of the last exact_patterns call: (distinct k-mers, pairs written to HBM, forced flushes, single masks)

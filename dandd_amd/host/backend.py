@@ -374,6 +374,22 @@ class HipExactBackend:
         index = [fasta_index(str(f)) for f in sample_files]
         return index, self.engine.exact_paint(files, [str(f) for f in sample_files], int(k), int(window), ntok=[ix[3] for ix in index])
 
+    def read_calls(self, leaf_paths, k, sample_files, min_hits, want_calls):
+        """files that are no leaves called record by record with the leaves' k-mers at one k of the window (dd_exact_reads):
+        -> ([(names, seq_len, tok_start, ntok)] per sample, [(calls uint32 [r][6], sets uint64 [r][2]) or None] per sample,
+        tally uint64 [ns][n+3]); a row per record of the sample: valid, hit, best, best_count, second, second_count and the
+        sets of the tied and of the consistent leaves; tally[s]: the records uniquely called to leaf i, the ambiguous, the
+        unclassified (fewer than min_hits positions of the best leaf), those without a valid k-mer.  want_calls False: the
+        tally alone comes back from the device."""
+        from ..engine import fasta_index
+        if (win := self._leaf_window(leaf_paths, k=k)) is None:
+            return None
+        files = win[1]
+        index = [fasta_index(str(f)) for f in sample_files]
+        per, tally = self.engine.exact_reads(files, [str(f) for f in sample_files], int(k), min_hits=int(min_hits), index=index,
+                                             calls=bool(want_calls))
+        return index, [(c, s) if want_calls else None for c, s, _ in per], tally
+
     def pattern_counts(self, leaf_paths, k, limit):
         """the distinct membership masks of the leaves at one k of the window and how many k-mers carry each
         (dd_exact_patterns): -> (masks uint64 [m], counts uint64 [m], found, distinct), count descending, ties by mask

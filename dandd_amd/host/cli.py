@@ -2,6 +2,9 @@
 defaults and output files as /root/reference/lib/dandd_cmd.py (flags :141-286, handlers :43-132); only the
 sketching backend differs.  (deltadelta, abba, greedy, core, screen and patterns are this package's own: the reference has none of them.)  Run as  python -m dandd_amd.host.cli <subcommand> ...
 `screen --paint W` adds where along each sample the collection's k-mers lie: one row per window of W bases.
+`screen --reads` adds which genome each record of a sample -- a read, a contig -- belongs to and how many records go to each
+genome (<prefix>.reads_summary.csv); `--reads-calls` writes the call of every record too (<prefix>.reads.csv), and
+`--reads-min-hits H` asks H positions of a genome for a call.
 """
 import argparse
 import os
@@ -478,7 +481,9 @@ def screen_command(args):
     genome a sample contains and the other way round, which genome it is closest to, how much of it is in the pan-genome and
     the core, and with -g which group's core, private k-mers and signature it carries.  Counts are over distinct k-mers;
     the samples enter no sort and change none of the collection's numbers.  --paint W adds the positional answer: every
-    sample in windows of W bases, counted over positions (_paint_rows)."""
+    sample in windows of W bases, counted over positions (_paint_rows).  --reads adds the answer for a read set or a draft
+    assembly: every record called to the genome that holds most of its k-mer positions, and the sample's abundance profile
+    over the genomes, voted and tallied on the device (_reads_rows)."""
     tree, outfile = _open_tree("screen", args, exact=True)
     ks = sorted(set(int(k) for k in args.ks)) if args.ks else [int(tree.root_k())]
     for k in ks:
@@ -488,6 +493,10 @@ def screen_command(args):
         sys.exit(f"screen: --paint {args.paint}: a window is a multiple of 64 bases in 64..{1 << 22}")
     if args.paint_matrix and args.paint is None:
         sys.exit("screen: --paint-matrix goes with --paint")
+    if args.reads_calls and not args.reads:
+        sys.exit("screen: --reads-calls goes with --reads")
+    if args.reads_min_hits < 1:
+        sys.exit(f"screen: --reads-min-hits {args.reads_min_hits}: a call needs at least one position (H >= 1)")
     names = list(args.samples)
     if args.query_loc:
         if not os.path.isfile(args.query_loc):
@@ -509,6 +518,7 @@ def screen_command(args):
     try:
         res = tree.screen_tables(fastas, samples, ks, groups)
         painted = tree.paint_tables(fastas, samples, ks, args.paint) if args.paint is not None else None
+        called = tree.reads_tables(fastas, samples, ks, args.reads_min_hits, args.reads_calls) if args.reads else None
     except (ValueError, OSError) as e:
         sys.exit("screen: " + " ".join(str(e).split()))
 
@@ -546,6 +556,12 @@ def screen_command(args):
                                                      "in_pan", "best_shared"], segments)
         if args.paint_matrix:
             _write_csv(outfile + ".paint_matrix.csv", ["sample", "k", "window", *fastas], matrix)
+    if called is not None:
+        profile, records = _reads_rows(samples, fastas, called)
+        _write_csv(outfile + ".reads_summary.csv", ["sample", "k", "target", "reads", "fraction"], profile)
+        if args.reads_calls:
+            _write_csv(outfile + ".reads.csv", ["sample", "k", "record", "name", "length", "valid", "in_pan", "class", "best_fasta", "best_shared",
+                                                "second_fasta", "second_shared", "ties", "consistent"], records)
     _finish(tree)
 
 
@@ -581,6 +597,39 @@ def _paint_rows(samples, fastas, painted):
                 if best is not None:
                     seg[9] += cols[best]
     return windows, segments, matrix
+
+
+READ_CLASSES = ("ambiguous", "unclassified", "no_kmer")    # the tally's bins behind the genomes', and a record's class beside "unique"
+
+
+def _reads_rows(samples, fastas, called):
+    """reads_tables' answer -> the rows of <prefix>.reads_summary.csv (per sample and k: the records uniquely called to each
+    genome, then the ambiguous, the unclassified and those without a valid k-mer, each with its share of the sample's
+    records; an empty cell for a sample without a record) and of .reads.csv (one per sample, k and record: its name and
+    length, the positions with a valid k-mer and those the collection holds, its class, the two genomes that share most
+    positions with it -- ties: the earlier genome of the universe; empty cells where nothing is shared --, how many genomes
+    tie for the best count and how many hold every shared position; no row without the calls)."""
+    from ..engine import NO_GENOME, read_classes
+    n = len(fastas)
+    profile, records = [], []
+    for s, sample in enumerate(samples):
+        names, seq_len, _, _ = called["index"][s]
+        for kk, k in enumerate(called["ks"]):
+            tally = [int(v) for v in called["tally"][kk][s]]
+            total = sum(tally)
+            for target, reads in zip([*fastas, *READ_CLASSES], tally):
+                profile.append([sample, k, target, reads, reads / total if total else None])
+            if called["calls"][kk][s] is None:
+                continue
+            calls, sets = called["calls"][kk][s]
+            classes, _ = read_classes(calls, sets, called["min_hits"], n)
+            for r, (row, (ties, full), cls) in enumerate(zip(calls.tolist(), sets.tolist(), classes.tolist())):
+                valid, hit, best, best_count, second, second_count = row
+                records.append([sample, k, r, names[r], int(seq_len[r]), valid, hit, "unique" if cls < n else READ_CLASSES[cls - n],
+                                None if best == NO_GENOME else fastas[best], None if best == NO_GENOME else best_count,
+                                None if second == NO_GENOME else fastas[second], None if second == NO_GENOME else second_count,
+                                bin(ties).count("1"), bin(full).count("1")])
+    return profile, records
 
 
 def patterns_command(args):
@@ -880,6 +929,15 @@ def build_parser():
                          "the same best genome, novel stretches among them (<prefix>.paint_segments.csv)")
     sc.add_argument("--paint-matrix", dest="paint_matrix", default=False, action="store_true",
                     help="with --paint: also write every genome's shared positions per window (<prefix>.paint_matrix.csv)")
+    sc.add_argument("--reads", dest="reads", default=False, action="store_true",
+                    help="also call every record of every sample -- a read, a contig -- to the genome that holds most of its k-mer "
+                         "positions and write how many records go to each genome, how many are ambiguous (several genomes tie), "
+                         "unclassified or without a k-mer (<prefix>.reads_summary.csv)")
+    sc.add_argument("--reads-calls", dest="reads_calls", default=False, action="store_true",
+                    help="with --reads: also write every record's call, its best and second genome and how many genomes tie "
+                         "(<prefix>.reads.csv)")
+    sc.add_argument("--reads-min-hits", dest="reads_min_hits", type=int, default=1, metavar="H",
+                    help="with --reads: call a record only where its best genome holds at least H of its positions (default 1)")
     sc.add_argument("samples", nargs="*", metavar="SAMPLE", help="FASTA / FASTQ files, plain or gzip, that are no leaves of the tree")
     sc.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     sc.add_argument("-l", "--label", dest="label", default="")

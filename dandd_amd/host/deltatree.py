@@ -1303,6 +1303,39 @@ class DeltaTree:
                     out["counts"][kk][j] = u.table(rows, (nwin, n + 2)).astype(np.uint32)
         return out
 
+    def reads_tables(self, fastas, samples, ks, min_hits=1, want_calls=False):
+        """Which genome of the universe `fastas` (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]) each record of each
+        of `samples` (files that are no leaves: a read set, a draft assembly; FASTA / FASTQ, plain or gzip) belongs to, at
+        every k of `ks`, and how many records of a sample go to each genome.  A record is called to the genome that holds
+        most of its k-mer positions where those are at least `min_hits`; several genomes with that count make it ambiguous.
+        The samples go to the backend's read_calls in screen_tables' batches.  There is no object path: a backend without
+        read_calls, or without a table for these leaves, is a ValueError.
+        -> dict: ks, min_hits, index [ns] of (names, seq_len, tok_start, ntok), tally [K] of uint64 [ns][n+3] (unique to
+        genome i | ambiguous | unclassified | no valid k-mer), calls [K][ns] of (calls uint32 [r][6], sets uint64 [r][2]),
+        None without want_calls"""
+        n, ns, min_hits = len(fastas), len(samples), int(min_hits)
+        ks = [int(k) for k in ks]
+        for k in ks:
+            if not 1 <= k <= 64:
+                raise ValueError(f"k={k} is outside 1..64")
+        if min_hits < 1:
+            raise ValueError(f"min_hits={min_hits}: a call needs at least one position")
+        batches = self._sample_batches(samples)
+        out = {"ks": ks, "min_hits": min_hits, "index": [None] * ns, "tally": [np.zeros((ns, n + 3), dtype=np.uint64) for _ in ks],
+               "calls": [[None] * ns for _ in ks]}
+        for kk, k in enumerate(ks):
+            u = self._universe(fastas, k, k)
+            u.need("read_calls", why="calling records needs")
+            for batch in batches:
+                index, per, tally = u.table(u.be.read_calls(u.paths, k, [samples[j] for j in batch], min_hits, bool(want_calls)))
+                out["tally"][kk][batch] = u.table(tally, (len(batch), n + 3))
+                for j, ix, got in zip(batch, index, per):
+                    out["index"][j] = ix
+                    if want_calls:
+                        r = len(ix[2])
+                        out["calls"][kk][j] = (u.table(got[0], (r, 6)).astype(np.uint32), u.table(got[1], (r, 2)).astype(np.uint64))
+        return out
+
     # ---- which sets of genomes share k-mers (`dandd patterns`) --------------------------------------------------------------
     def pattern_tables(self, fastas, ks, top=None):
         """The membership patterns of the universe `fastas` (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]) at every

@@ -362,6 +362,44 @@ int dd_exact_paint(dd_ctx *, const char *const *paths, int n, const char *const 
                    uint32_t *counts /*[off[ns]][n+2]*/, uint64_t *found);
 int dd_exact_paint_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
                           uint64_t window, const uint64_t *off, uint32_t *counts, uint64_t *found);
+/* ---- samples called row by row -------------------------------------------------------------------------------------
+ * dd_exact_paint cuts a sample into fixed windows; a read set, or a draft assembly, comes in records.  Here the rows are the
+ * caller's (dd_exact_reads.hip): sample s owns the rows off[s] .. off[s+1]-1 (it may own none), and row r covers the tokens
+ * start[r] .. start[r+1]-1 of the sample's token stream as K0 lays it out, the sample's last row running to its ntok; the
+ * tokens in front of a sample's first border belong to no row.  With start = tok_start of dd_fasta_index the rows are the
+ * file's records -- reads, contigs --, but the borders need not be record starts: the intervals of an annotation, or two
+ * mates as one row, work as well.  A k-mer belongs to the row that holds its END token (dd_exact_locate's convention; K0
+ * puts a BREAK in front of every record, so with record borders it lies whole inside that record).  ONE k per call,
+ * 1 <= k <= 64, 1 <= n <= 64 universe inputs, 1 <= ns <= 1024 samples, min_hits >= 1; off must ascend, and within a sample
+ * start must ascend strictly and stay <= that sample's ntok (start[first] = 0 is legal): anything else is DD_EINVAL with a
+ * message, for the borders one that names the sample and the row.
+ *   counts[r]  dd_exact_paint's columns for row r: column 0 the tokens of the row at which a valid k-mer ends, column 1 those
+ *              whose k-mer the universe holds, column 2 + i those whose k-mer input i holds.  Counts are over POSITIONS.
+ *   calls[r]   valid, hit (columns 0 and 1), best, best_count, second, second_count.  best: the input with the largest
+ *              column, a tie to the lower index, 0xFFFFFFFF when hit == 0; second: the largest NON-ZERO column among the
+ *              inputs other than best, a tie to the lower index, 0xFFFFFFFF (and a count of 0) when there is none.
+ *   sets[r]    ties, full.  ties: the inputs whose column equals best_count, 0 when best_count == 0; full: the inputs whose
+ *              column equals hit -- they hold every one of the row's universe positions --, 0 when hit == 0.
+ *   The class of a row: no valid k-mer (valid == 0) | unclassified (valid > 0, best_count < min_hits) | unique
+ *   (best_count >= min_hits, one bit in ties) | ambiguous (best_count >= min_hits, more than one bit in ties).
+ *   tally[s]   [0 .. n-1] the rows of sample s uniquely called to input i, [n] the ambiguous, [n+1] the unclassified, [n+2]
+ *              those without a valid k-mer: it sums to off[s+1] - off[s].  Voted and tallied on the device.
+ *   *found     the distinct k-mers of the universe
+ * tally and found must not be null.  calls, sets and counts may each be null: a null array is neither kept nor copied back,
+ * and the tally-only call moves ns x (n + 3) x 8 bytes.  Nothing is written unless the call returns DD_OK.  An empty universe
+ * gives column 0 only: every row with a valid k-mer is unclassified.  Two calls on the same inputs return identical bytes
+ * (integer sums).  The device form takes n + ns buffers: the n universe inputs first, the ns samples behind them.
+ * The sort, the masks, the emission and the ordering are dd_exact_screen's, so are budget and passes (DD_EXACT_MB),
+ * dd_last_sketch_stats' third value and the DD_KERNEL_EXACT timer.  The rows wait in HBM: rows x (n + 2) x 4 bytes of
+ * counters, rows x 8 of borders, rows x 24 and rows x 16 for calls and sets where asked for (DD_ENOMEM with a message
+ * naming the bytes when that cannot be had; the rows are not chunked). */
+int dd_exact_reads(dd_ctx *, const char *const *paths, int n, const char *const *samples, int ns, int k,
+                   const uint64_t *off /*[ns+1], in rows*/, const uint64_t *start /*[off[ns]], tokens*/,
+                   uint32_t min_hits, uint32_t *calls /*[off[ns]][6] or null*/, uint64_t *sets /*[off[ns]][2] or null*/,
+                   uint32_t *counts /*[off[ns]][n+2] or null*/, uint64_t *tally /*[ns][n+3]*/, uint64_t *found);
+int dd_exact_reads_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
+                          const uint64_t *off, const uint64_t *start, uint32_t min_hits, uint32_t *calls, uint64_t *sets,
+                          uint32_t *counts, uint64_t *tally, uint64_t *found);
 /* ---- the membership-pattern table ------------------------------------------------------------------------------
  * Which sets of inputs share k-mers, and how many: the DISTINCT membership masks of the universe with their multiplicities
  * (the table behind an UpSet plot; every other mask statistic above -- spectrum, select, a subset union -- is a sum over
@@ -430,7 +468,7 @@ int dd_exact_greedy_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen; the emission, ordering and window walk of dd_exact_paint; the accumulation, merges and ordering of dd_exact_patterns */
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen; the emission, ordering and window walk of dd_exact_paint; the emission, ordering, row walk and vote of dd_exact_reads; the accumulation, merges and ordering of dd_exact_patterns */
 #define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);
