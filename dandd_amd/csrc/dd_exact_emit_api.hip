@@ -1,14 +1,15 @@
 // dd_exact_emit_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h) that hand k-mers out instead of counting
-// them.  Five look k-mers up in the ordered records of one emission: the selected k-mers themselves (dd_exact_select_kmers),
+// them.  Six look k-mers up in the ordered records of one emission: the selected k-mers themselves (dd_exact_select_kmers),
 // where they lie in each genome (dd_exact_locate), what samples that are no inputs hold of them (dd_exact_screen), where
-// along themselves (dd_exact_paint) and which genome each of their records belongs to (dd_exact_reads).  Each is its own
+// along themselves (dd_exact_paint), which genome each of their records belongs to (dd_exact_reads) and how many times they
+// hold each (dd_exact_depth).  Each is its own
 // argument rules, the ordered-record step of dd_exact_host.h (exact_records, then ExactRecords::order inside the entry's
-// timing span) and the kernels that read the ordered set; screen, paint and reads also share the frame below: K0 over the
+// timing span) and the kernels that read the ordered set; screen, paint, reads and depth also share the frame below: K0 over the
 // universe and the samples, a sort that sees the universe only.
 // dd_exact_patterns hands out no k-mer but is ragged like the others -- one k per call, a cap and a count -- and
 // dd_fasta_index is the record index of a file that turns places into names.
 // Host-side orchestration only; the kernels are in dd_exact_sched.hip (emit_kernel, AccPatterns), dd_exact_locate.hip,
-// dd_exact_screen.hip, dd_exact_paint.hip, dd_exact_reads.hip and dd_exact_patterns.hip.
+// dd_exact_screen.hip, dd_exact_paint.hip, dd_exact_reads.hip, dd_exact_depth.hip and dd_exact_patterns.hip.
 #include "dd_exact_host.h"
 
 extern "C" {
@@ -171,7 +172,7 @@ int dd_exact_locate(dd_ctx* c, const char* const* paths, int n, int k, const uin
     });
 }
 
-// ------------------------------------------------------------------- the universe and the samples: what screen, paint and reads share
+// ------------------------------------------------------------------- the universe and the samples: what screen, paint, reads and depth share
 // K0 runs over the universe's n inputs AND the ns samples behind them, once.  The sort and the emission see the universe
 // alone -- the samples stay out of the sort and out of the slot count that sizes the record area -- with the single query
 // (0, 0); the entry's own table rides behind that query in the image the emission stages.
@@ -181,6 +182,19 @@ namespace {
 int universe_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const void* found) {
     if (exact_args(c, inputs, n, 64, k, k, found)) return DD_EINVAL;
     if (ns < 1 || ns > 1024) return fail(DD_EINVAL, "ns=%d outside 1..1024 samples in one call; split them over calls", ns);
+    return DD_OK;
+}
+
+// ... with the (all, none) queries of a tally over the records (screen, depth): 0..kScreenMaxQueries of them, their bits
+// inside n; out_null: one of the entry's own outputs is missing
+int universe_query_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const uint64_t* all, const uint64_t* none, int nq, bool out_null,
+                        const void* found) {
+    if (universe_args(c, inputs, n, ns, k, found)) return DD_EINVAL;
+    if (nq < 0 || nq > dd::kScreenMaxQueries)
+        return fail(DD_EINVAL, "nq=%d outside 0..%d (what one launch holds); split the queries over calls", nq, dd::kScreenMaxQueries);
+    if (out_null || (nq && (!all || !none))) return fail(DD_EINVAL, "null argument");
+    for (int q = 0; q < nq; ++q)
+        if (exact_check_bits("query", q, all[q], none[q], n)) return DD_EINVAL;
     return DD_OK;
 }
 
@@ -227,13 +241,7 @@ namespace {
 
 int screen_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const uint64_t* all, const uint64_t* none, int nq,
                 const uint64_t* shared, const uint64_t* match, const uint64_t* found) {
-    if (universe_args(c, inputs, n, ns, k, found)) return DD_EINVAL;
-    if (nq < 0 || nq > dd::kScreenMaxQueries)
-        return fail(DD_EINVAL, "nq=%d outside 0..%d (what one launch holds); split the queries over calls", nq, dd::kScreenMaxQueries);
-    if (!shared || (nq && (!all || !none || !match))) return fail(DD_EINVAL, "null argument");
-    for (int q = 0; q < nq; ++q)
-        if (exact_check_bits("query", q, all[q], none[q], n)) return DD_EINVAL;
-    return DD_OK;
+    return universe_query_args(c, inputs, n, ns, k, all, none, nq, !shared || (nq && !match), found);
 }
 
 }  // namespace
@@ -484,6 +492,112 @@ int dd_exact_reads(dd_ctx* c, const char* const* paths, int n, const char* const
     if (reads_args(c, paths, n, ns, k, off, start, min_hits, tally, found)) return DD_EINVAL;
     return universe_path_form(c, paths, n, samples, ns, [&](auto p, auto s) {
         return dd_exact_reads_device(c, p, s, n, ns, k, off, start, min_hits, calls, sets, counts, tally, found);
+    });
+}
+
+// ------------------------------------------------------------------- samples counted record by record
+// dd_exact_depth.hip: screen's frame with a 32-bit counter per (sample, record) where screen keeps a bit, and a tally that
+// bins the counters by depth.  The universe is sorted, emitted, ordered and its rows sized (launch_exact_tally without a
+// sample: |G_i| and every query class) once per call; the samples are then taken in ROUNDS of as many counter rows as
+// DD_DEPTH_MB holds, each round a memset, the walk and the tally.  c->hits: sizes [n + nq] u64 | per round hist
+// [per][n + nq][bins] u64 | overflow [per][n + nq] u64 | counters [per][found] u32.
+namespace {
+
+int depth_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const uint64_t* all, const uint64_t* none, int nq, int bins,
+               const uint64_t* hist, const uint64_t* total, const uint64_t* found) {
+    if (universe_query_args(c, inputs, n, ns, k, all, none, nq, !hist || !total, found)) return DD_EINVAL;
+    if (bins < 2 || bins > dd::kDepthMaxBins)
+        return fail(DD_EINVAL, "bins=%d outside 2..%d: bin 0, then at least the clipped bin (depth >= bins - 1)", bins, dd::kDepthMaxBins);
+    return DD_OK;
+}
+
+}  // namespace
+
+int dd_exact_depth_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns, int k, const uint64_t* all,
+                          const uint64_t* none, int nq, int bins, uint64_t* hist, uint64_t* total, uint64_t* found) {
+    if (depth_args(c, fasta_dev, n, ns, k, all, none, nq, bins, hist, total, found)) return DD_EINVAL;
+    if (universe_buffers(fasta_dev, nbytes, n, ns)) return DD_EINVAL;
+    for (int g = n; g < n + ns; ++g)
+        if ((unsigned long long)nbytes[g] >> 32)
+            return fail(DD_EINVAL, "sample %d: %zu bytes, a sample must stay below 2^32 bytes (a record's depth is a 32-bit counter); split it over calls",
+                        g - n, nbytes[g]);
+    const size_t budget = exact_budget("DD_DEPTH_MB", (size_t)8 << 30);
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    ExactInputs in;
+    if ((rc = universe_prepare(c, fasta_dev, nbytes, n, ns, in))) return rc;
+    const size_t nrow = (size_t)n + (size_t)nq, B = (size_t)bins;
+    std::vector<unsigned long long> hist_host((size_t)ns * nrow * B, 0ull), over_host((size_t)ns * nrow, 0ull), size_host(nrow, 0ull);
+    ExactRecords rec;
+    if (in.slots) {
+        std::vector<char> image(kOwnTable + sizeof(uint64_t) * 2 * (size_t)nq, 0);   // the caller's (all, none) [nq][2]
+        uint64_t* pairs = static_cast<uint64_t*>(own_table(image.data()));
+        for (int q = 0; q < nq; ++q) pairs[2 * q] = all[q], pairs[2 * q + 1] = none[q];
+        if ((rc = exact_records(c, in, n, k, "exact depth", &kSlotsOfUniverse, 1, image.data(), image.size(), in.slots, rec))) return rc;
+    }
+    if (rec.kept) {
+        // a round's row: the sample's counters and its histograms
+        const size_t fnd = (size_t)rec.found, row_bytes = fnd * sizeof(uint32_t) + nrow * (B + 1) * sizeof(unsigned long long);
+        if (budget < row_bytes)
+            return fail(DD_ENOMEM, "exact depth: one sample needs %zu bytes of counters (%zu records x 4 bytes, and %zu rows x %d bins x 8), "
+                                   "DD_DEPTH_MB holds %zu MiB now",
+                        row_bytes, fnd, nrow, bins, budget >> 20);
+        const size_t per = std::min((size_t)ns, budget / row_bytes);
+        const size_t zbytes = align_up(nrow * sizeof(unsigned long long), 256), hbytes = align_up(per * nrow * B * sizeof(unsigned long long), 256),
+                     obytes = align_up(per * nrow * sizeof(unsigned long long), 256), cbytes = per * fnd * sizeof(uint32_t);
+        if (c->hits.reserve(zbytes + hbytes + obytes + cbytes))
+            return fail(DD_ENOMEM, "exact depth: no device memory for the %zu bytes of a round's counters (%zu samples x %zu records x 4 bytes) and the "
+                                   "%zu of its histograms; a smaller DD_DEPTH_MB (%zu MiB now) makes smaller rounds",
+                        cbytes, per, fnd, hbytes + obytes, budget >> 20);
+        char* base = static_cast<char*>(c->hits.p);
+        unsigned long long* size_dev = reinterpret_cast<unsigned long long*>(base);
+        unsigned long long* hist_dev = reinterpret_cast<unsigned long long*>(base + zbytes);
+        unsigned long long* over_dev = reinterpret_cast<unsigned long long*>(base + zbytes + hbytes);
+        uint32_t* count_dev = reinterpret_cast<uint32_t*>(base + zbytes + hbytes + obytes);
+        const uint64_t* table_dev = static_cast<const uint64_t*>(own_table(c->ord.p));
+        DD_HIP(hipMemsetAsync(size_dev, 0, zbytes, st));
+        Span sp(c, DD_KERNEL_EXACT);
+        dd::LocateSet set{};
+        DD_HIP(rec.order(c, k, &set));
+        dd::launch_exact_tally(set, nullptr, 0, 0, n, nq, table_dev, size_dev, size_dev + n, st);   // (no sample: the universe's row alone)
+        DD_HIP(hipGetLastError());
+        DD_HIP(hipMemcpyAsync(size_host.data(), size_dev, nrow * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        for (size_t s0 = 0; s0 < (size_t)ns; s0 += per) {
+            const size_t take = std::min(per, (size_t)ns - s0);
+            size_t sample_segments = 0;
+            for (size_t s = s0; s < s0 + take; ++s)
+                sample_segments = std::max(sample_segments, (nbytes[(size_t)n + s] + dd::kSegTokens - 1) / dd::kSegTokens);
+            DD_HIP(hipMemsetAsync(hist_dev, 0, hbytes + obytes + take * fnd * sizeof(uint32_t), st));
+            dd::launch_exact_depth(in.etab_dev + n + s0, (int)take, sample_segments, k, c->canonical, set, count_dev, st);
+            DD_HIP(hipGetLastError());
+            dd::launch_exact_depth_tally(set, count_dev, (int)take, n, nq, bins, table_dev, hist_dev, over_dev, st);
+            DD_HIP(hipGetLastError());
+            DD_HIP(hipMemcpyAsync(hist_host.data() + s0 * nrow * B, hist_dev, take * nrow * B * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            DD_HIP(hipMemcpyAsync(over_host.data() + s0 * nrow, over_dev, take * nrow * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            DD_HIP(hipStreamSynchronize(st));   // (the next round clears what these copies read)
+        }
+    }
+    // bin 0: the row's records less those the sample holds; the total from the bins and the clipped records' overflow
+    // (nothing is written before everything is known)
+    for (size_t s = 0; s < (size_t)ns; ++s)
+        for (size_t r = 0; r < nrow; ++r) {
+            unsigned long long* h = hist_host.data() + (s * nrow + r) * B;
+            unsigned long long held = 0, sum = over_host[s * nrow + r];
+            for (size_t d = 1; d < B; ++d) held += h[d], sum += d * h[d];
+            h[0] = size_host[r] - held;
+            total[s * nrow + r] = sum;
+        }
+    for (size_t i = 0; i < hist_host.size(); ++i) hist[i] = hist_host[i];
+    *found = rec.found;
+    return DD_OK;
+}
+
+int dd_exact_depth(dd_ctx* c, const char* const* paths, int n, const char* const* samples, int ns, int k, const uint64_t* all,
+                   const uint64_t* none, int nq, int bins, uint64_t* hist, uint64_t* total, uint64_t* found) {
+    if (depth_args(c, paths, n, ns, k, all, none, nq, bins, hist, total, found)) return DD_EINVAL;
+    return universe_path_form(c, paths, n, samples, ns, [&](auto p, auto s) {
+        return dd_exact_depth_device(c, p, s, n, ns, k, all, none, nq, bins, hist, total, found);
     });
 }
 

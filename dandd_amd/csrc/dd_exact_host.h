@@ -30,7 +30,7 @@ struct ExactInputs {
 int exact_prepare(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, ExactInputs& in);
 // ntok of the inputs first .. first + count - 1, read back from where K0 left them (all 0 where no input has a token)
 int exact_read_ntok(dd_ctx* c, const ExactInputs& in, int first, int count, std::vector<unsigned long long>& ntok);
-size_t exact_budget(const char* env_mb = "DD_EXACT_MB");   // bytes of k-mers a pass may hold: 24 GiB, or what the variable says
+size_t exact_budget(const char* env_mb = "DD_EXACT_MB", size_t unset = (size_t)24 << 30);   // bytes of k-mers a pass may hold: 24 GiB, or what the variable says (MiB)
 
 // What a caller of exact_passes says about its part of the k-mer workspace.
 struct ExactLayout {

@@ -119,8 +119,8 @@ int exact_read_ntok(dd_ctx* c, const ExactInputs& in, int first, int count, std:
     return DD_OK;
 }
 
-size_t exact_budget(const char* env_mb) {
-    size_t budget = (size_t)24 << 30;
+size_t exact_budget(const char* env_mb, size_t unset) {
+    size_t budget = unset;
     if (const char* e = getenv(env_mb)) budget = (size_t)std::max(1, atoi(e)) << 20;
     return budget;
 }

@@ -466,6 +466,27 @@ void launch_exact_vote(const uint32_t* counts_dev, const unsigned long long* off
                        uint32_t* calls_dev, uint64_t* sets_dev, unsigned long long* tally_dev, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// samples that are no leaves, counted record by record (dd_exact_depth.hip), behind launch_exact_emit_order: screen's walk
+// with a counter where screen keeps a bit, then the counters binned by depth per genome and per query.
+// ---------------------------------------------------------------------------------------
+constexpr int kDepthMaxBins = 256;        // bins of a row's histogram at the most (the last one clipped)
+constexpr size_t kDepthTileBytes = 72 * 1024;   // LDS of a tally workgroup's rows: two workgroups to a CU's 160 KiB
+// samples_dev[ns]: the samples' token streams (`base` is not read).  count_dev [ns][found] u32, zeroed by the caller:
+// += the tokens of sample s at which a valid k-mer ends that is record r.  A sample must hold fewer than 2^32 tokens (the
+// caller has checked its bytes).  Nothing is launched for an empty set.
+void launch_exact_depth(const ExactGenome* samples_dev, int ns, size_t max_segments, int k, int canonical, const LocateSet& set,
+                        uint32_t* count_dev, hipStream_t st);
+// the rows (genomes and queries) whose histograms of `bins` bins one tally workgroup holds in LDS
+int exact_depth_rows_tile(int bins);
+// Behind launch_exact_depth on the same stream.  Row i < n: the records whose mask has bit i; row n + q: those that match
+// pair q of table_dev [nq][2].  hist_dev [ns][n + nq][bins] u64 += the records of the row that sample s holds d times, for
+// 1 <= d < bins - 1, and bins - 1 times or more in the last bin; bin 0 is NOT written (the size of the row less the other
+// bins).  over_dev [ns][n + nq] u64 += c - (bins - 1) over the row's records with c >= bins - 1.  Both zeroed by the caller;
+// 2 <= bins <= kDepthMaxBins.
+void launch_exact_depth_tally(const LocateSet& set, const uint32_t* count_dev, int ns, int n, int nq, int bins, const uint64_t* table_dev,
+                              unsigned long long* hist_dev, unsigned long long* over_dev, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // exact greedy walk (dd_exact_greedy.hip) over the mask streams of kSchedStream: one launch per step of the walk reads
 // every stream once.  gain[kk][b] += masks of stream kk (store[seg.off[kk] .. seg.off[kk + 1])) that meet `chosen` nowhere
 // and hold bit b, for every b < 64 (a bit of `chosen` gains 0).  gain_dev [K][64], zeroed by the caller.

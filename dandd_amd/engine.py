@@ -39,6 +39,7 @@ EXPORTS = [
     "dd_exact_screen", "dd_exact_screen_device",
     "dd_exact_paint", "dd_exact_paint_device",
     "dd_exact_reads", "dd_exact_reads_device",
+    "dd_exact_depth", "dd_exact_depth_device",
     "dd_exact_patterns", "dd_exact_patterns_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
@@ -176,7 +177,9 @@ def load_library(path=None):
                              ("dd_exact_screen_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, i32, vp, vp]),
                              ("dd_exact_paint_device", [ptrs_t, sizes_t, i32, i32], [u64, vp, vp]),
                              ("dd_exact_reads", [paths_t, i32, paths_t, i32], [vp, vp, C.c_uint32, vp, vp, vp, vp]),
-                             ("dd_exact_reads_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, C.c_uint32, vp, vp, vp, vp])):
+                             ("dd_exact_reads_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, C.c_uint32, vp, vp, vp, vp]),
+                             ("dd_exact_depth", [paths_t, i32, paths_t, i32], [vp, vp, i32, i32, vp, vp]),
+                             ("dd_exact_depth_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, i32, i32, vp, vp])):
         fn = getattr(lib, name)
         fn.restype = i32
         fn.argtypes = [vp] + src + [i32] + extra + [C.POINTER(u64)]
@@ -325,6 +328,35 @@ def read_classes(calls, sets, min_hits, n=64):
     classes = np.where(calls[:, 0] == 0, n + 2,
                        np.where(calls[:, 3] < min_hits, n + 1, np.where(several, n, calls[:, 2].astype(np.int64)))).astype(np.int64)
     return classes, np.bincount(classes, minlength=n + 3).astype(np.uint64)
+
+
+def depth_stats(hist, total):
+    """Host-side, pure numpy: the arrays of exact_depth (hist [...][bins], total [...]) -> a dict of arrays over the leading
+    indices.  kmers (int64): the row's k-mers, the sum of all bins; covered (int64): those the sample holds, the bins >= 1;
+    breadth = covered / kmers; mean = total / kmers; mean_covered = total / covered; median: the lower median of the depths
+    of ALL the row's k-mers, zeros included -- the smallest d with hist[0] + .. + hist[d] >= (kmers + 1) // 2 --;
+    median_covered: the same over the k-mers with depth >= 1; clipped (bool): a median lies in the last bin and is a lower
+    bound only.  The five ratios and medians are float64 and NaN where they have nothing to stand on: all five for a row
+    without a k-mer, mean_covered and median_covered for a row the sample holds nothing of (never None, never a raise)."""
+    hist = np.asarray(hist, dtype=np.uint64).astype(np.int64)
+    total = np.asarray(total, dtype=np.uint64).astype(np.float64)
+    if hist.ndim < 1 or hist.shape[-1] < 2 or total.shape != hist.shape[:-1]:
+        raise ValueError(f"hist {hist.shape} needs at least two bins and total {total.shape} its leading shape")
+    last = hist.shape[-1] - 1
+    kmers, covered = hist.sum(-1), hist[..., 1:].sum(-1)
+
+    def ratio(a, b):
+        return np.divide(a, b, out=np.full(b.shape, np.nan), where=b > 0)
+
+    def median(h, count):   # the first bin at which the running sum reaches the lower median's rank; NaN without a record
+        at = (np.cumsum(h, axis=-1) >= ((count + 1) // 2)[..., None]).argmax(-1)
+        return np.where(count > 0, at, np.nan).astype(np.float64)
+    med = median(hist, kmers)
+    head = hist.copy()
+    head[..., 0] = 0
+    med_cov = median(head, covered)
+    return {"kmers": kmers, "covered": covered, "breadth": ratio(covered.astype(np.float64), kmers), "mean": ratio(total, kmers),
+            "mean_covered": ratio(total, covered), "median": med, "median_covered": med_cov, "clipped": (med == last) | (med_cov == last)}
 
 
 def kmer_text(kmers, k):
@@ -979,6 +1011,33 @@ class Engine:
         """exact_reads over FASTA bytes on the device: the n universe inputs first, the samples behind them; rows: every
         sample's borders (the library checks them against the token counts)."""
         return self._exact_reads(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes, n=n), k, min_hits, rows, calls, counts)
+
+    # -- samples counted record by record: screen's walk with a counter per record, binned by depth (dd_exact_depth.hip) -------
+    last_depth_found = None   # of the last exact_depth call: the distinct k-mers of the universe
+    def _exact_depth(self, src, k, all_masks, none_masks, bins):
+        args, n, ns, suffix = src
+        al, no, nq = self._query_masks(all_masks, none_masks)
+        rows, bins = max(n, 0) + nq, int(bins)
+        hist = np.zeros((max(ns, 1), max(rows, 1), min(max(bins, 1), 1 << 16)), dtype=np.uint64)
+        total = np.zeros((max(ns, 1), max(rows, 1)), dtype=np.uint64)
+        found = C.c_uint64()
+        self._check(getattr(self._lib, f"dd_exact_depth{suffix}")(self._ctx, *args, int(k), al.ctypes.data if nq else None, no.ctypes.data if nq else None,
+                                                                 nq, bins, hist.ctypes.data, total.ctypes.data, C.byref(found)))
+        self.last_depth_found = int(found.value)
+        return hist, total
+
+    def exact_depth(self, paths, samples, k, alls=(), nones=(), bins=64):
+        """FASTA files (n <= 64: the universe), sample files (FASTA / FASTQ, plain or gzip, ns <= 1024), one k, at most 1024
+        queries, 2 <= bins <= 256 -> (hist uint64 [ns][n+nq][bins], total uint64 [ns][n+nq]).  Row i < n: the distinct k-mers
+        of file i; row n + q: those whose universe mask contains alls[q] and meets nones[q] nowhere.  hist[s][row][d]:
+        the k-mers of the row that stand d times in sample s (positions, as exact_paint counts them; d = 0: the sample lacks
+        them), the last bin taking every depth >= bins - 1; total: the sum of the depths, unclipped (depth_stats turns both
+        into breadth, mean and median).  last_depth_found: the universe's distinct k-mers."""
+        return self._exact_depth(self._exact_src(paths=paths, samples=samples), k, alls, nones, bins)
+
+    def exact_depth_device(self, fasta_ptrs, nbytes, n, k, alls=(), nones=(), bins=64):
+        """exact_depth over FASTA bytes on the device: the n universe inputs first, the samples behind them."""
+        return self._exact_depth(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes, n=n), k, alls, nones, bins)
 
     # -- the membership-pattern table: the distinct masks and how many k-mers carry each (dd_exact_patterns.hip) ------------
     last_patterns_stats = None   # of the last exact_patterns call: (distinct k-mers, pairs written to HBM, forced flushes, single masks)

@@ -390,6 +390,17 @@ class HipExactBackend:
                                              calls=bool(want_calls))
         return index, [(c, s) if want_calls else None for c, s, _ in per], tally
 
+    def depth_hists(self, leaf_paths, k, sample_files, all_masks, none_masks, bins):
+        """files that are no leaves counted against the leaves' k-mers at one k of the window (dd_exact_depth): ->
+        (hist uint64 [ns][n+nq][bins], total uint64 [ns][n+nq]); row i < n: the distinct k-mers of leaf i, row n + q: those
+        whose membership mask contains all_masks[q] and meets none_masks[q] nowhere; hist[s][row][d]: the k-mers of the row
+        that stand d times in sample s (positions; d = 0: the sample lacks them), the last bin every depth >= bins - 1;
+        total: the sum of the depths, unclipped (engine.depth_stats reads both)."""
+        if (win := self._leaf_window(leaf_paths, k=k)) is None:
+            return None
+        files = win[1]
+        return self.engine.exact_depth(files, [str(f) for f in sample_files], int(k), all_masks, none_masks, bins=int(bins))
+
     def pattern_counts(self, leaf_paths, k, limit):
         """the distinct membership masks of the leaves at one k of the window and how many k-mers carry each
         (dd_exact_patterns): -> (masks uint64 [m], counts uint64 [m], found, distinct), count descending, ties by mask

@@ -5,6 +5,10 @@ sketching backend differs.  (deltadelta, abba, greedy, core, screen and patterns
 `screen --reads` adds which genome each record of a sample -- a read, a contig -- belongs to and how many records go to each
 genome (<prefix>.reads_summary.csv); `--reads-calls` writes the call of every record too (<prefix>.reads.csv), and
 `--reads-min-hits H` asks H positions of a genome for a call.
+`screen --depth` adds how many times a sample holds the k-mers of each genome, of its private k-mers, of the pan-genome and of
+the core: breadth, mean and median depth per row (<prefix>.depth.csv); `--depth-bins B` sets the bins of the histogram
+behind them (2..256, default 64: depths from B-1 on share the last bin) and `--depth-hist` writes its non-zero bins too
+(<prefix>.depth_hist.csv).
 """
 import argparse
 import os
@@ -483,7 +487,8 @@ def screen_command(args):
     the samples enter no sort and change none of the collection's numbers.  --paint W adds the positional answer: every
     sample in windows of W bases, counted over positions (_paint_rows).  --reads adds the answer for a read set or a draft
     assembly: every record called to the genome that holds most of its k-mer positions, and the sample's abundance profile
-    over the genomes, voted and tallied on the device (_reads_rows)."""
+    over the genomes, voted and tallied on the device (_reads_rows).  --depth adds how many times the sample holds the k-mers
+    of every genome and class: a histogram of depths per row, counted and binned on the device (_depth_rows)."""
     tree, outfile = _open_tree("screen", args, exact=True)
     ks = sorted(set(int(k) for k in args.ks)) if args.ks else [int(tree.root_k())]
     for k in ks:
@@ -497,6 +502,11 @@ def screen_command(args):
         sys.exit("screen: --reads-calls goes with --reads")
     if args.reads_min_hits < 1:
         sys.exit(f"screen: --reads-min-hits {args.reads_min_hits}: a call needs at least one position (H >= 1)")
+    if (args.depth_bins is not None or args.depth_hist) and not args.depth:
+        sys.exit(f"screen: {'--depth-bins' if args.depth_bins is not None else '--depth-hist'} goes with --depth")
+    bins = 64 if args.depth_bins is None else args.depth_bins
+    if not 2 <= bins <= 256:
+        sys.exit(f"screen: --depth-bins {bins}: bin 0, then at least the clipped bin, 256 bins at the most (B in 2..256)")
     names = list(args.samples)
     if args.query_loc:
         if not os.path.isfile(args.query_loc):
@@ -519,6 +529,7 @@ def screen_command(args):
         res = tree.screen_tables(fastas, samples, ks, groups)
         painted = tree.paint_tables(fastas, samples, ks, args.paint) if args.paint is not None else None
         called = tree.reads_tables(fastas, samples, ks, args.reads_min_hits, args.reads_calls) if args.reads else None
+        depths = tree.depth_tables(fastas, samples, ks, groups, bins) if args.depth else None
     except (ValueError, OSError) as e:
         sys.exit("screen: " + " ".join(str(e).split()))
 
@@ -562,7 +573,42 @@ def screen_command(args):
         if args.reads_calls:
             _write_csv(outfile + ".reads.csv", ["sample", "k", "record", "name", "length", "valid", "in_pan", "class", "best_fasta", "best_shared",
                                                 "second_fasta", "second_shared", "ties", "consistent"], records)
+    if depths is not None:
+        stats, hists = _depth_rows(samples, fastas, labels, tree.KMER_CLASSES, depths)
+        _write_csv(outfile + ".depth.csv", DEPTH_COLUMNS, stats)
+        if args.depth_hist:
+            _write_csv(outfile + ".depth_hist.csv", ["sample", "k", "target", "class", "depth", "kmers"], hists)
     _finish(tree)
+
+
+DEPTH_COLUMNS = ["sample", "k", "target", "class", "kmers", "covered", "breadth", "mean_depth", "mean_covered", "median_depth", "median_covered",
+                 "clipped"]
+
+
+def _depth_rows(samples, fastas, labels, classes, depths):
+    """depth_tables' answer -> the rows of <prefix>.depth.csv (per sample and k: every genome's k-mers (`all`) and its
+    private ones, the pan-genome, the core, and every group's classes; engine.depth_stats' columns, an empty cell where a
+    number has nothing to stand on -- a row without a k-mer, the covered columns of a row the sample holds nothing of) and
+    of .depth_hist.csv (the non-zero bins of the same rows, the last bin's depth written as >=B-1)."""
+    from ..engine import depth_stats
+    n, B = len(fastas), int(depths["bins"])
+    targets = [(fasta, cls, row) for i, fasta in enumerate(fastas) for cls, row in (("all", i), ("private", n + 2 + i))]   # rows: n genomes | pan | core | n private | groups
+    targets += [("pan", "all", n), ("core", "all", n + 1)]
+    targets += [(label, cls, 2 * n + 2 + len(classes) * gi + c) for gi, label in enumerate(labels) for c, cls in enumerate(classes)]
+    st = depth_stats(depths["hist"], depths["total"])
+    cell = lambda v, as_int=False: None if v != v else int(v) if as_int else float(v)   # (NaN: an empty cell)
+    stats, hists = [], []
+    for s, sample in enumerate(samples):
+        for kk, k in enumerate(depths["ks"]):
+            for target, cls, row in targets:
+                at = (kk, s, row)
+                stats.append([sample, k, target, cls, int(st["kmers"][at]), int(st["covered"][at]), cell(st["breadth"][at]), cell(st["mean"][at]),
+                              cell(st["mean_covered"][at]), cell(st["median"][at], True), cell(st["median_covered"][at], True),
+                              bool(st["clipped"][at])])
+                for d, v in enumerate(depths["hist"][at].tolist()):
+                    if v:
+                        hists.append([sample, k, target, cls, f">={d}" if d == B - 1 else d, v])
+    return stats, hists
 
 
 def _paint_rows(samples, fastas, painted):
@@ -938,6 +984,15 @@ def build_parser():
                          "(<prefix>.reads.csv)")
     sc.add_argument("--reads-min-hits", dest="reads_min_hits", type=int, default=1, metavar="H",
                     help="with --reads: call a record only where its best genome holds at least H of its positions (default 1)")
+    sc.add_argument("--depth", dest="depth", default=False, action="store_true",
+                    help="also count how many times every sample holds each k-mer of the collection and write, per genome, per "
+                         "genome's private k-mers, for the pan-genome, the core and with -g every group's classes, breadth, mean and "
+                         "median depth (<prefix>.depth.csv)")
+    sc.add_argument("--depth-bins", dest="depth_bins", type=int, default=None, metavar="B",
+                    help="with --depth: the bins of the depth histogram, 2..256 (default 64); depths from B-1 on share the last bin, "
+                         "a median that lies there is marked clipped")
+    sc.add_argument("--depth-hist", dest="depth_hist", default=False, action="store_true",
+                    help="with --depth: also write the non-zero bins of every histogram (<prefix>.depth_hist.csv)")
     sc.add_argument("samples", nargs="*", metavar="SAMPLE", help="FASTA / FASTQ files, plain or gzip, that are no leaves of the tree")
     sc.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     sc.add_argument("-l", "--label", dest="label", default="")

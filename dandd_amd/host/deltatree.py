@@ -1336,6 +1336,40 @@ class DeltaTree:
                         out["calls"][kk][j] = (u.table(got[0], (r, 6)).astype(np.uint32), u.table(got[1], (r, 2)).astype(np.uint64))
         return out
 
+    def depth_tables(self, fastas, samples, ks, groups=None, bins=64):
+        """How many times each of `samples` (files that are no leaves: a read set, an assembly; FASTA / FASTQ, plain or gzip)
+        holds the k-mers of the universe `fastas` (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]), at every k of
+        `ks`: per row of k-mers a histogram of `bins` depths (positions of the sample per distinct k-mer; bin 0: k-mers the
+        sample lacks, the last bin: depth >= bins - 1) and the sum of the depths.  The rows are the n genomes, then the queries
+        (0, 0) -- the pan-genome --, (full, 0) -- the core --, every genome's private k-mers (1 << i, full ^ (1 << i)), then
+        the core, private and signature k-mers (KMER_QUERIES, in that order) of every group of `groups` (lists of FASTAs).
+        The samples go to the backend's depth_hists in screen_tables' batches.  There is no object path: a backend without
+        depth_hists, or without a table for these leaves, is a ValueError.
+        -> dict: ks, bins, hist [K][ns][n+nq][bins], total [K][ns][n+nq] (engine.depth_stats turns them into breadth, mean
+        and median); nq = 2 + n + 3 * len(groups)"""
+        n, ns, bins = len(fastas), len(samples), int(bins)
+        nq = 2 + n + len(self.KMER_CLASSES) * len(groups or [])
+        ks = [int(k) for k in ks]
+        for k in ks:
+            if not 1 <= k <= 64:
+                raise ValueError(f"k={k} is outside 1..64")
+        if not 2 <= bins <= 256:
+            raise ValueError(f"bins={bins} is outside 2..256")
+        batches = self._sample_batches(samples)
+        out = {"ks": ks, "bins": bins, "hist": np.zeros((len(ks), ns, n + nq, bins), dtype=np.uint64),
+               "total": np.zeros((len(ks), ns, n + nq), dtype=np.uint64)}
+        for kk, k in enumerate(ks):
+            u = self._universe(fastas, k, k)
+            u.need("depth_hists", why="depth needs")
+            alls, nones = group_queries(u.masks(groups or []), u.full)
+            alls = [0, u.full] + [1 << i for i in range(n)] + alls
+            nones = [0, 0] + [u.full ^ (1 << i) for i in range(n)] + nones
+            for batch in batches:
+                got = u.table(u.be.depth_hists(u.paths, k, [samples[j] for j in batch], alls, nones, bins))
+                out["hist"][kk, batch] = u.table(got[0], (len(batch), n + nq, bins))
+                out["total"][kk, batch] = u.table(got[1], (len(batch), n + nq))
+        return out
+
     # ---- which sets of genomes share k-mers (`dandd patterns`) --------------------------------------------------------------
     def pattern_tables(self, fastas, ks, top=None):
         """The membership patterns of the universe `fastas` (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]) at every

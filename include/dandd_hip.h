@@ -400,6 +400,34 @@ int dd_exact_reads(dd_ctx *, const char *const *paths, int n, const char *const 
 int dd_exact_reads_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
                           const uint64_t *off, const uint64_t *start, uint32_t min_hits, uint32_t *calls, uint64_t *sets,
                           uint32_t *counts, uint64_t *tally, uint64_t *found);
+/* ---- samples counted record by record ---------------------------------------------------------------------------
+ * dd_exact_screen counts a k-mer of the universe as present or absent in a sample; this says HOW MANY TIMES the sample holds
+ * it (dd_exact_depth.hip), as a histogram of depths per universe input and per query.  For sample s and distinct k-mer r of
+ * the universe, c[s][r] is the number of tokens of the sample's stream at which a valid k-mer ends that is r (canonical per
+ * the context): POSITIONS, as in dd_exact_paint.  ONE k per call, 1 <= k <= 64, 1 <= n <= 64 universe inputs,
+ * 1 <= ns <= 1024 samples, 0 <= nq <= 1024 queries (nq == 0: all and none may be null), 2 <= bins <= 256; the bit rules
+ * are dd_exact_select's.  Row i < n takes the k-mers whose mask has bit i, row n + q those whose mask m has
+ * (m & all[q]) == all[q] and (m & none[q]) == 0.
+ *   hist[s][row][d]       d < bins - 1: the k-mers of the row with c == d; d = 0 are the k-mers of the row that the sample
+ *                         lacks, so every row of hist sums to the size of the row (dd_exact_screen's row ns)
+ *   hist[s][row][bins-1]  the k-mers of the row with c >= bins - 1 (the clipped bin)
+ *   total[s][row]         the sum of c over the row's k-mers, unclipped
+ *   *found                the distinct k-mers of the universe
+ * A universe that holds no k-mer gives zeros; a sample that is empty or without a valid k-mer has everything in bin 0; a
+ * sample may be byte-identical to an input.  Nothing is written unless the call returns DD_OK; two calls on the same inputs
+ * return identical bytes (integer sums).  The device form takes n + ns buffers: the n universe inputs first, the ns samples
+ * behind them.  A depth is a 32-bit counter: a sample of 2^32 bytes or more is DD_EINVAL.
+ * The sort, the masks, the emission, the ordering and the sizes of the rows are dd_exact_screen's and are paid once per
+ * call, so are budget and passes (DD_EXACT_MB), dd_last_sketch_stats' third value and the DD_KERNEL_EXACT timer.  The
+ * samples are taken in rounds: as many as DD_DEPTH_MB (read on every call, MiB, 8192 unless set) holds of found x 4 bytes
+ * of counters and (n + nq) x (bins + 1) x 8 bytes of histograms each.  A budget that does not hold one sample, or memory
+ * that cannot be had, is DD_ENOMEM with a message naming the bytes. */
+int dd_exact_depth(dd_ctx *, const char *const *paths, int n, const char *const *samples, int ns, int k,
+                   const uint64_t *all /*[nq]*/, const uint64_t *none /*[nq]*/, int nq, int bins,
+                   uint64_t *hist /*[ns][n+nq][bins]*/, uint64_t *total /*[ns][n+nq]*/, uint64_t *found);
+int dd_exact_depth_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
+                          const uint64_t *all, const uint64_t *none, int nq, int bins, uint64_t *hist, uint64_t *total,
+                          uint64_t *found);
 /* ---- the membership-pattern table ------------------------------------------------------------------------------
  * Which sets of inputs share k-mers, and how many: the DISTINCT membership masks of the universe with their multiplicities
  * (the table behind an UpSet plot; every other mask statistic above -- spectrum, select, a subset union -- is a sum over
@@ -468,7 +496,7 @@ int dd_exact_greedy_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen; the emission, ordering and window walk of dd_exact_paint; the emission, ordering, row walk and vote of dd_exact_reads; the accumulation, merges and ordering of dd_exact_patterns */
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen; the emission, ordering and window walk of dd_exact_paint; the emission, ordering, row walk and vote of dd_exact_reads; the emission, ordering, counting walk and depth tally of dd_exact_depth (every round); the accumulation, merges and ordering of dd_exact_patterns */
 #define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);
