@@ -122,7 +122,8 @@ struct dd_ctx {
     DevBuf hits;   // dd_exact_locate: the jobs' hit bitmaps, off[njobs] words; dd_exact_screen: counters [ns + 1][n + nq] | the samples' seen bitmaps;
                    // dd_exact_paint: the windows' counters, off[ns] - off[0] rows of n + 2 x 32 bits; dd_exact_reads: the rows' counters |
                    // borders | calls | sets | the samples' tallies; dd_exact_depth: the sizes of the rows | a round's histograms | overflow sums |
-                   // counters [samples of the round][found] x 32 bits
+                   // counters [samples of the round][found] x 32 bits; dd_exact_cover: the targets' index, a word per token slot | a
+                   // round's rows [samples][off[nt] - off[0]][6] x 32 bits | the same counters
     DevBuf pat[2]; // dd_exact_patterns: the running table in mask order (masks | counts) and where the next merge puts it, in turns
     // saturation (dd_kernels.h): sketch(U_k) for k = kSatMinK..kSatMaxK at this context's log2m and strand mode, [k - kSatMinK][m];
     // a row is built by the first call that needs it, on that call's stream, and kept

@@ -1,15 +1,15 @@
 // dd_exact_emit_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h) that hand k-mers out instead of counting
-// them.  Six look k-mers up in the ordered records of one emission: the selected k-mers themselves (dd_exact_select_kmers),
+// them.  Seven look k-mers up in the ordered records of one emission: the selected k-mers themselves (dd_exact_select_kmers),
 // where they lie in each genome (dd_exact_locate), what samples that are no inputs hold of them (dd_exact_screen), where
-// along themselves (dd_exact_paint), which genome each of their records belongs to (dd_exact_reads) and how many times they
-// hold each (dd_exact_depth).  Each is its own
+// along themselves (dd_exact_paint), which genome each of their records belongs to (dd_exact_reads), how many times they
+// hold each (dd_exact_depth) and where along each genome, and how deep (dd_exact_cover).  Each is its own
 // argument rules, the ordered-record step of dd_exact_host.h (exact_records, then ExactRecords::order inside the entry's
-// timing span) and the kernels that read the ordered set; screen, paint, reads and depth also share the frame below: K0 over the
-// universe and the samples, a sort that sees the universe only.
+// timing span) and the kernels that read the ordered set; screen, paint, reads, depth and cover also share the frame below: K0
+// over the universe and the samples, a sort that sees the universe only.
 // dd_exact_patterns hands out no k-mer but is ragged like the others -- one k per call, a cap and a count -- and
 // dd_fasta_index is the record index of a file that turns places into names.
 // Host-side orchestration only; the kernels are in dd_exact_sched.hip (emit_kernel, AccPatterns), dd_exact_locate.hip,
-// dd_exact_screen.hip, dd_exact_paint.hip, dd_exact_reads.hip, dd_exact_depth.hip and dd_exact_patterns.hip.
+// dd_exact_screen.hip, dd_exact_paint.hip, dd_exact_reads.hip, dd_exact_depth.hip, dd_exact_cover.hip and dd_exact_patterns.hip.
 #include "dd_exact_host.h"
 
 extern "C" {
@@ -310,11 +310,17 @@ int dd_exact_screen(dd_ctx* c, const char* const* paths, int n, const char* cons
 // dd_exact_locate's: each sample's share of off[] against its token count.
 namespace {
 
-int paint_args(dd_ctx* c, const void* inputs, int n, int ns, int k, uint64_t window, const uint64_t* off, const uint64_t* found) {
-    if (universe_args(c, inputs, n, ns, k, found)) return DD_EINVAL;
+// the rule of a window of tokens (paint: of a sample's stream; cover: of a target's)
+int window_args(uint64_t window) {
     if (window < dd::kSegTokens || window > dd::kPaintMaxWindow || window % dd::kSegTokens)
         return fail(DD_EINVAL, "window=%llu: a multiple of %d in %d..%zu tokens (a window is whole 64-token segments)", (unsigned long long)window,
                     (int)dd::kSegTokens, (int)dd::kSegTokens, dd::kPaintMaxWindow);
+    return DD_OK;
+}
+
+int paint_args(dd_ctx* c, const void* inputs, int n, int ns, int k, uint64_t window, const uint64_t* off, const uint64_t* found) {
+    if (universe_args(c, inputs, n, ns, k, found)) return DD_EINVAL;
+    if (window_args(window)) return DD_EINVAL;
     if (!off) return fail(DD_EINVAL, "null argument");
     return DD_OK;
 }
@@ -511,16 +517,22 @@ int depth_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const uint64
     return DD_OK;
 }
 
+// a counter of depth_kernel holds the positions of one sample, which are fewer than its bytes (depth, cover)
+int depth_sample_bytes(const size_t* nbytes, int n, int ns) {
+    for (int g = n; g < n + ns; ++g)
+        if ((unsigned long long)nbytes[g] >> 32)
+            return fail(DD_EINVAL, "sample %d: %zu bytes, a sample must stay below 2^32 bytes (a record's depth is a 32-bit counter); split it over calls",
+                        g - n, nbytes[g]);
+    return DD_OK;
+}
+
 }  // namespace
 
 int dd_exact_depth_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns, int k, const uint64_t* all,
                           const uint64_t* none, int nq, int bins, uint64_t* hist, uint64_t* total, uint64_t* found) {
     if (depth_args(c, fasta_dev, n, ns, k, all, none, nq, bins, hist, total, found)) return DD_EINVAL;
     if (universe_buffers(fasta_dev, nbytes, n, ns)) return DD_EINVAL;
-    for (int g = n; g < n + ns; ++g)
-        if ((unsigned long long)nbytes[g] >> 32)
-            return fail(DD_EINVAL, "sample %d: %zu bytes, a sample must stay below 2^32 bytes (a record's depth is a 32-bit counter); split it over calls",
-                        g - n, nbytes[g]);
+    if (depth_sample_bytes(nbytes, n, ns)) return DD_EINVAL;
     const size_t budget = exact_budget("DD_DEPTH_MB", (size_t)8 << 30);
     DeviceGuard guard(c->device);
     hipStream_t st = c->stream;
@@ -598,6 +610,137 @@ int dd_exact_depth(dd_ctx* c, const char* const* paths, int n, const char* const
     if (depth_args(c, paths, n, ns, k, all, none, nq, bins, hist, total, found)) return DD_EINVAL;
     return universe_path_form(c, paths, n, samples, ns, [&](auto p, auto s) {
         return dd_exact_depth_device(c, p, s, n, ns, k, all, none, nq, bins, hist, total, found);
+    });
+}
+
+// ------------------------------------------------------------------- samples laid along the genomes of the universe
+// dd_exact_cover.hip: depth's frame -- the universe sorted, emitted and ordered once per call, the samples in rounds under
+// DD_DEPTH_MB, each round a memset and depth_kernel as it is -- with the record of every target position looked up ONCE, in
+// front of the rounds, and a kernel per round that gathers the round's counters through that index into window rows.  The
+// shape of the answer is checked like dd_exact_paint's: each target's share of off[] against its token count.
+// c->hits: index [the targets' token slots] u32 | per round rows [per][off[nt] - off[0]][6] u32 | counters [per][found] u32.
+namespace {
+
+int cover_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const int32_t* target, int nt, uint64_t window, uint32_t clip,
+               const uint64_t* off, const uint64_t* found) {
+    if (universe_args(c, inputs, n, ns, k, found)) return DD_EINVAL;
+    if (nt < 1 || nt > n) return fail(DD_EINVAL, "nt=%d outside 1..%d: the targets are inputs of the universe, each once", nt, n);
+    if (!target || !off) return fail(DD_EINVAL, "null argument");
+    uint64_t seen = 0;
+    for (int t = 0; t < nt; ++t) {
+        if (target[t] < 0 || target[t] >= n) return fail(DD_EINVAL, "target %d: input %d outside 0..%d", t, target[t], n - 1);
+        if (seen >> target[t] & 1ull) {
+            int first = 0;
+            while (target[first] != target[t]) ++first;
+            return fail(DD_EINVAL, "target %d: input %d is target %d already (a target is laid out once)", t, target[t], first);
+        }
+        seen |= 1ull << target[t];
+    }
+    if (window_args(window)) return DD_EINVAL;
+    if (clip < 1 || clip > dd::kCoverMaxClip)
+        return fail(DD_EINVAL, "clip=%u outside 1..%u (a depth counts as min(depth, clip): a window's sum stays inside 32 bits)", clip, dd::kCoverMaxClip);
+    for (int t = 0; t < nt; ++t)
+        if (off[t + 1] < off[t]) return fail(DD_EINVAL, "off[] must ascend");
+    return DD_OK;
+}
+
+}  // namespace
+
+int dd_exact_cover_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns, int k, const int32_t* target, int nt,
+                          uint64_t window, uint32_t clip, const uint64_t* off, uint32_t* counts, uint64_t* found) {
+    if (cover_args(c, fasta_dev, n, ns, k, target, nt, window, clip, off, found)) return DD_EINVAL;
+    if (universe_buffers(fasta_dev, nbytes, n, ns)) return DD_EINVAL;
+    if (depth_sample_bytes(nbytes, n, ns)) return DD_EINVAL;
+    const uint64_t rows = off[nt] - off[0];   // of one sample (each target's own share is checked once the inputs' token counts are known)
+    if (rows && !counts) return fail(DD_EINVAL, "null argument");
+    const size_t budget = exact_budget("DD_DEPTH_MB", (size_t)8 << 30);
+    DeviceGuard guard(c->device);
+    hipStream_t st = c->stream;
+    int rc;
+    ExactInputs in;
+    if ((rc = universe_prepare(c, fasta_dev, nbytes, n, ns, in))) return rc;
+    std::vector<unsigned long long> ntok;   // the shape of the answer: every input's ntok
+    if ((rc = exact_read_ntok(c, in, 0, n, ntok))) return rc;
+    // the targets that hold a token, one launch unit each; the entry's own table
+    std::vector<char> image(kOwnTable + sizeof(dd::CoverUnit) * (size_t)nt, 0);
+    dd::CoverUnit* units = static_cast<dd::CoverUnit*>(own_table(image.data()));
+    int nunits = 0;
+    size_t target_segments = 0, words = 0;
+    for (int t = 0; t < nt; ++t) {
+        const unsigned long long tokens = ntok[(size_t)target[t]];
+        const uint64_t want = (tokens + window - 1) / window;
+        if (off[t + 1] - off[t] != want)
+            return fail(DD_EINVAL, "target %d: off[%d] - off[%d] = %llu rows, %llu expected (input %d holds %llu tokens, %llu to a window)", t, t + 1, t,
+                        (unsigned long long)(off[t + 1] - off[t]), (unsigned long long)want, target[t], tokens, (unsigned long long)window);
+        if (!tokens) continue;   // (it owns no row)
+        const dd::ExactGenome& eg = in.etab[(size_t)target[t]];
+        const size_t segs = (size_t)((tokens + dd::kSegTokens - 1) / dd::kSegTokens);
+        dd::CoverUnit& u = units[nunits++];
+        u.codes = eg.codes, u.bad = eg.bad, u.ntok = eg.ntok, u.index = words, u.row0 = off[t] - off[0], u.genome = target[t];
+        words += segs * dd::kSegTokens, target_segments = std::max(target_segments, segs);
+    }
+    ExactRecords rec;
+    if (in.slots) {
+        if ((rc = exact_records(c, in, n, k, "exact cover", &kSlotsOfUniverse, 1, image.data(), image.size(), in.slots, rec))) return rc;
+    }
+    if (rec.found >> 31)
+        return fail(DD_EINVAL, "exact cover: the universe holds %llu distinct k-mers, a position's index word holds a record below 2^31 (and the "
+                               "private flag); lay the samples along a smaller universe",
+                    rec.found);
+    const size_t R = (size_t)rows, row_words = R * dd::kCoverColumns;
+    std::vector<uint32_t> host((size_t)ns * row_words, 0u);
+    if (rec.kept && R) {
+        // a round's row: the sample's counters and its windows
+        const size_t fnd = (size_t)rec.found, ibytes = align_up(words * sizeof(uint32_t), 256),
+                     row_bytes = fnd * sizeof(uint32_t) + row_words * sizeof(uint32_t);
+        if (budget < row_bytes)
+            return fail(DD_ENOMEM, "exact cover: one sample needs %zu bytes (%zu records x 4 bytes of counters, and %zu windows x %d columns x 4), "
+                                   "DD_DEPTH_MB holds %zu MiB now",
+                        row_bytes, fnd, R, dd::kCoverColumns, budget >> 20);
+        const size_t per = std::min((size_t)ns, budget / row_bytes);
+        const size_t wbytes = align_up(per * row_words * sizeof(uint32_t), 256), cbytes = per * fnd * sizeof(uint32_t);
+        if (c->hits.reserve(ibytes + wbytes + cbytes))
+            return fail(DD_ENOMEM, "exact cover: no device memory for the %zu bytes of the targets' index (%zu token slots x 4 bytes), the %zu of a round's "
+                                   "counters (%zu samples x %zu records x 4 bytes) and the %zu of its windows; a smaller DD_DEPTH_MB (%zu MiB now) makes "
+                                   "smaller rounds",
+                        ibytes, words, cbytes, per, fnd, wbytes, budget >> 20);
+        char* base = static_cast<char*>(c->hits.p);
+        uint32_t* index_dev = reinterpret_cast<uint32_t*>(base);
+        uint32_t* rows_dev = reinterpret_cast<uint32_t*>(base + ibytes);
+        uint32_t* count_dev = reinterpret_cast<uint32_t*>(base + ibytes + wbytes);
+        const dd::CoverUnit* units_dev = static_cast<const dd::CoverUnit*>(own_table(c->ord.p));
+        Span sp(c, DD_KERNEL_EXACT);
+        dd::LocateSet set{};
+        DD_HIP(rec.order(c, k, &set));
+        dd::launch_exact_cover_index(units_dev, nunits, target_segments, k, c->canonical, set, index_dev, st);
+        DD_HIP(hipGetLastError());
+        for (size_t s0 = 0; s0 < (size_t)ns; s0 += per) {
+            const size_t take = std::min(per, (size_t)ns - s0);
+            size_t sample_segments = 0;
+            for (size_t s = s0; s < s0 + take; ++s)
+                sample_segments = std::max(sample_segments, (nbytes[(size_t)n + s] + dd::kSegTokens - 1) / dd::kSegTokens);
+            DD_HIP(hipMemsetAsync(rows_dev, 0, wbytes + take * fnd * sizeof(uint32_t), st));
+            dd::launch_exact_depth(in.etab_dev + n + s0, (int)take, sample_segments, k, c->canonical, set, count_dev, st);
+            DD_HIP(hipGetLastError());
+            dd::launch_exact_cover(units_dev, nunits, target_segments, index_dev, count_dev, fnd, (int)take, (size_t)(window / dd::kSegTokens), clip, R,
+                                   rows_dev, st);
+            DD_HIP(hipGetLastError());
+            DD_HIP(hipMemcpyAsync(host.data() + s0 * row_words, rows_dev, take * row_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            DD_HIP(hipStreamSynchronize(st));   // (the next round clears what this copy reads)
+        }
+    }
+    // sample s owns counts[s][off[0] .. off[nt]-1] of its off[nt] rows (nothing is written before everything is known)
+    for (size_t s = 0; s < (size_t)ns && R; ++s)
+        memcpy(counts + (s * (size_t)off[nt] + (size_t)off[0]) * dd::kCoverColumns, host.data() + s * row_words, row_words * sizeof(uint32_t));
+    *found = rec.found;
+    return DD_OK;
+}
+
+int dd_exact_cover(dd_ctx* c, const char* const* paths, int n, const char* const* samples, int ns, int k, const int32_t* target, int nt,
+                   uint64_t window, uint32_t clip, const uint64_t* off, uint32_t* counts, uint64_t* found) {
+    if (cover_args(c, paths, n, ns, k, target, nt, window, clip, off, found)) return DD_EINVAL;
+    return universe_path_form(c, paths, n, samples, ns, [&](auto p, auto s) {
+        return dd_exact_cover_device(c, p, s, n, ns, k, target, nt, window, clip, off, counts, found);
     });
 }
 

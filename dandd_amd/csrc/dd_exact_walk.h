@@ -1,7 +1,7 @@
 // dd_exact_walk.h -- what more than one kernel of the exact device path does, once: the key masks of a k, the query test
 // on a membership mask, the token walk of a 64-token segment (kmer_extract_kernel, locate_kernel, screen_kernel, paint_kernel,
-// reads_kernel, depth_kernel), the lookup of a key in the ordered records (locate_kernel, screen_kernel, paint_kernel,
-// reads_kernel, depth_kernel), the
+// reads_kernel, depth_kernel, cover_index_kernel), the lookup of a key in the ordered records (locate_kernel, screen_kernel,
+// paint_kernel, reads_kernel, depth_kernel, cover_index_kernel), the
 // read-out of the bit-sliced per-genome counter (paint_kernel, reads_kernel) and the wave-aggregated append
 // (kmer_extract_kernel, sched_kernel, emit_kernel).  Everything here is inlined into its caller: no kernel calls across files.
 #pragma once

@@ -487,6 +487,34 @@ void launch_exact_depth_tally(const LocateSet& set, const uint32_t* count_dev, i
                               unsigned long long* hist_dev, unsigned long long* over_dev, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// samples that are no leaves, laid along the genomes of the universe (dd_exact_cover.hip), behind launch_exact_emit_order
+// and launch_exact_depth: the record of every position of a target genome, once; then per sample the counters of
+// launch_exact_depth gathered through it into rows of six columns per window of the target.
+// ---------------------------------------------------------------------------------------
+constexpr int kCoverColumns = 6;          // valid | covered | depth | private | private_covered | private_depth
+constexpr uint32_t kCoverMaxClip = 1023;  // a depth counts as min(c, clip): a window of kPaintMaxWindow positions stays inside 32 bits
+constexpr uint32_t kCoverNone = 0xFFFFFFFFu;      // an index word: no valid k-mer ends at this token
+constexpr uint32_t kCoverPrivate = 0x80000000u;   // ... or the record's index, and this bit: its mask is exactly 1 << genome
+struct CoverUnit {                  // one per gridDim.y of both launches, device-resident table
+    const uint32_t* codes;          // the target's token stream (ExactGenome)
+    const uint32_t* bad;
+    const unsigned long long* ntok;
+    unsigned long long index;       // first word of the target in the index; ceil(ntok / 64) * 64 words follow
+    unsigned long long row0;        // first row of the target in a sample's rows; ceil(ntok / (64 window_segments)) follow
+    int genome, pad;                // the target's bit in the masks
+};
+// index_dev: every live thread writes the kSegTokens words of its segment, the index needs no zeroing.  found < 2^31 (the
+// caller has checked).  Nothing is launched for an empty set.
+void launch_exact_cover_index(const CoverUnit* units_dev, int nunits, size_t max_segments, int k, int canonical, const LocateSet& set,
+                              uint32_t* index_dev, hipStream_t st);
+// Behind launch_exact_cover_index and launch_exact_depth on the same stream.  count_dev [ns][found] u32: launch_exact_depth's.
+// rows_dev [ns][nrows][kCoverColumns] u32, zeroed by the caller: row u.row0 + w of sample s takes the tokens of window w of
+// target u at which a valid k-mer ends, record r, c = count[s][r]: column 0 += 1, 1 += (c >= 1), 2 += min(c, clip), and
+// 3, 4, 5 the same over the tokens whose word has kCoverPrivate.  1 <= clip <= kCoverMaxClip.
+void launch_exact_cover(const CoverUnit* units_dev, int nunits, size_t max_segments, const uint32_t* index_dev, const uint32_t* count_dev,
+                        size_t found, int ns, size_t window_segments, uint32_t clip, size_t nrows, uint32_t* rows_dev, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // exact greedy walk (dd_exact_greedy.hip) over the mask streams of kSchedStream: one launch per step of the walk reads
 // every stream once.  gain[kk][b] += masks of stream kk (store[seg.off[kk] .. seg.off[kk + 1])) that meet `chosen` nowhere
 // and hold bit b, for every b < 64 (a bit of `chosen` gains 0).  gain_dev [K][64], zeroed by the caller.

@@ -40,6 +40,7 @@ EXPORTS = [
     "dd_exact_paint", "dd_exact_paint_device",
     "dd_exact_reads", "dd_exact_reads_device",
     "dd_exact_depth", "dd_exact_depth_device",
+    "dd_exact_cover", "dd_exact_cover_device",
     "dd_exact_patterns", "dd_exact_patterns_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
@@ -179,7 +180,9 @@ def load_library(path=None):
                              ("dd_exact_reads", [paths_t, i32, paths_t, i32], [vp, vp, C.c_uint32, vp, vp, vp, vp]),
                              ("dd_exact_reads_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, C.c_uint32, vp, vp, vp, vp]),
                              ("dd_exact_depth", [paths_t, i32, paths_t, i32], [vp, vp, i32, i32, vp, vp]),
-                             ("dd_exact_depth_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, i32, i32, vp, vp])):
+                             ("dd_exact_depth_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, i32, i32, vp, vp]),
+                             ("dd_exact_cover", [paths_t, i32, paths_t, i32], [vp, i32, u64, C.c_uint32, vp, vp]),
+                             ("dd_exact_cover_device", [ptrs_t, sizes_t, i32, i32], [vp, i32, u64, C.c_uint32, vp, vp])):
         fn = getattr(lib, name)
         fn.restype = i32
         fn.argtypes = [vp] + src + [i32] + extra + [C.POINTER(u64)]
@@ -357,6 +360,26 @@ def depth_stats(hist, total):
     med_cov = median(head, covered)
     return {"kmers": kmers, "covered": covered, "breadth": ratio(covered.astype(np.float64), kmers), "mean": ratio(total, kmers),
             "mean_covered": ratio(total, covered), "median": med, "median_covered": med_cov, "clipped": (med == last) | (med_cov == last)}
+
+
+COVER_EMPTY, COVER_PRESENT, COVER_ABSENT = 0, 1, 2   # cover_states' states of a window
+
+
+def cover_states(counts, min_percent):
+    """Host-side, pure numpy: one sample's rows of exact_cover along one target (uint32 [nwin][6]) -> (states int64 [nwin],
+    runs int64 [m][3]).  A window's state: COVER_EMPTY where no valid k-mer ends in it (valid == 0), COVER_PRESENT where the
+    sample holds at least min_percent per cent of its positions -- 100 * covered >= min_percent * valid, in integers --,
+    COVER_ABSENT otherwise.  runs: the maximal runs of consecutive windows with the same state, in order, as (state, first
+    window, windows); an empty window is a run of its own kind, it joins no neighbour."""
+    min_percent = int(min_percent)
+    if not 1 <= min_percent <= 100:
+        raise ValueError(f"min_percent={min_percent} is outside 1..100")
+    rows = np.asarray(counts, dtype=np.uint32).reshape(-1, 6).astype(np.int64)
+    valid, covered = rows[:, 0], rows[:, 1]
+    states = np.where(valid == 0, COVER_EMPTY, np.where(100 * covered >= min_percent * valid, COVER_PRESENT, COVER_ABSENT)).astype(np.int64)
+    first = np.flatnonzero(np.append(True, states[1:] != states[:-1])) if states.size else np.zeros(0, dtype=np.int64)
+    length = np.diff(np.append(first, states.size))
+    return states, np.stack([states[first], first, length], axis=1).astype(np.int64).reshape(-1, 3)
 
 
 def kmer_text(kmers, k):
@@ -1038,6 +1061,45 @@ class Engine:
     def exact_depth_device(self, fasta_ptrs, nbytes, n, k, alls=(), nones=(), bins=64):
         """exact_depth over FASTA bytes on the device: the n universe inputs first, the samples behind them."""
         return self._exact_depth(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes, n=n), k, alls, nones, bins)
+
+    # -- samples laid along the genomes of the universe: depth's counters gathered per window of a target (dd_exact_cover.hip) --
+    last_cover_found = None   # of the last exact_cover call: the distinct k-mers of the universe
+    def _exact_cover(self, src, k, window, targets, clip, ntok):
+        args, n, ns, suffix = src
+        window = int(window)
+        targets = list(range(max(n, 0))) if targets is None else [int(t) for t in targets]
+        nt = len(targets)
+        tg = np.array(targets or [0], dtype=np.int32)
+        off = np.zeros(nt + 1, dtype=np.uint64)
+        for j, t in enumerate(targets):
+            off[j + 1] = off[j] + np.uint64(-(-int(ntok[t]) // window) if window > 0 and 0 <= t < len(ntok) else 0)
+        rows = int(off[nt])
+        counts = np.zeros((max(ns, 1), max(rows, 1), 6), dtype=np.uint32)
+        found = C.c_uint64()
+        self._check(getattr(self._lib, f"dd_exact_cover{suffix}")(self._ctx, *args, int(k), tg.ctypes.data, nt, window, int(clip), off.ctypes.data,
+                                                                 counts.ctypes.data, C.byref(found)))
+        self.last_cover_found = int(found.value)
+        return [counts[:max(ns, 0), int(off[j]):int(off[j + 1])].copy() for j in range(nt)]
+
+    def exact_cover(self, paths, samples, k, window, targets=None, clip=255, ntok=None):
+        """FASTA files (n <= 64: the universe), sample files (FASTA / FASTQ, plain or gzip, ns <= 1024), one k, a window of
+        `window` tokens (a multiple of 64 in 64 .. 2^22), targets: indices of `paths`, each once (None: all of them), 1 <= clip
+        <= 1023 -> list of uint32 [ns][nwin_t][6] arrays, one per target, a row per sample and window of the TARGET's token
+        stream (paint_windows gives the windows' places in its records).  With c the times the sample holds the k-mer that
+        ends at a position (exact_depth's depth): column 0 the positions of the window at which a valid k-mer ends, column 1
+        those with c >= 1, column 2 the sum of min(c, clip) over them; columns 3..5 the same over the positions whose k-mer no
+        other file of the universe holds.  Columns 0 and 3 do not depend on the sample (cover_states turns a sample's rows
+        into present / absent windows and their runs).  ntok: the token counts of `paths` where the caller has them, else
+        one fasta_index per target.  last_cover_found: the universe's distinct k-mers."""
+        if ntok is None:                                              # the shape of the answer: the targets' token counts
+            want = range(len(paths)) if targets is None else [int(t) for t in targets]
+            ntok = [fasta_index(p)[3] if i in want else 0 for i, p in enumerate(paths)]
+        return self._exact_cover(self._exact_src(paths=paths, samples=samples), k, window, targets, clip, ntok)
+
+    def exact_cover_device(self, fasta_ptrs, nbytes, n, k, window, ntok, targets=None, clip=255):
+        """exact_cover over FASTA bytes on the device: the n universe inputs first, the samples behind them; ntok: every
+        universe input's token count (the library checks the targets')."""
+        return self._exact_cover(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes, n=n), k, window, targets, clip, ntok)
 
     # -- the membership-pattern table: the distinct masks and how many k-mers carry each (dd_exact_patterns.hip) ------------
     last_patterns_stats = None   # of the last exact_patterns call: (distinct k-mers, pairs written to HBM, forced flushes, single masks)

@@ -401,6 +401,22 @@ class HipExactBackend:
         files = win[1]
         return self.engine.exact_depth(files, [str(f) for f in sample_files], int(k), all_masks, none_masks, bins=int(bins))
 
+    def cover_counts(self, leaf_paths, k, sample_files, window, targets, clip):
+        """files that are no leaves laid along the leaves `targets` (indices, each once) at one k of the window
+        (dd_exact_cover): -> ([(names, seq_len, tok_start, ntok)] per target, [uint32 [ns][nwin][6]] per target); a row per
+        sample and per `window` tokens of the TARGET's token stream: the positions where a valid k-mer ends, those the sample
+        holds, their depths clipped at `clip` and summed, and the same three over the positions whose k-mer no other leaf
+        holds (engine.paint_windows places the windows in the target's records, engine.cover_states reads the rows)."""
+        from ..engine import fasta_index
+        if (win := self._leaf_window(leaf_paths, k=k)) is None:
+            return None
+        files = win[1]
+        targets = [int(t) for t in targets]
+        index = {t: fasta_index(str(files[t])) for t in targets}
+        ntok = [index[i][3] if i in index else 0 for i in range(len(files))]
+        counts = self.engine.exact_cover(files, [str(f) for f in sample_files], int(k), int(window), targets=targets, clip=int(clip), ntok=ntok)
+        return [index[t] for t in targets], counts
+
     def pattern_counts(self, leaf_paths, k, limit):
         """the distinct membership masks of the leaves at one k of the window and how many k-mers carry each
         (dd_exact_patterns): -> (masks uint64 [m], counts uint64 [m], found, distinct), count descending, ties by mask

@@ -9,6 +9,12 @@ genome (<prefix>.reads_summary.csv); `--reads-calls` writes the call of every re
 the core: breadth, mean and median depth per row (<prefix>.depth.csv); `--depth-bins B` sets the bins of the histogram
 behind them (2..256, default 64: depths from B-1 on share the last bin) and `--depth-hist` writes its non-zero bins too
 (<prefix>.depth_hist.csv).
+`screen --cover W` adds where along each GENOME of the collection a sample lies, and how deep: one row per sample, genome and
+window of W bases of the genome (<prefix>.cover.csv), the runs of windows that are present, absent or empty
+(<prefix>.cover_regions.csv: the absent runs are the deleted or missing stretches) and one row per sample and genome
+(<prefix>.cover_summary.csv).  `--cover-fastas LIST` lays the samples along the genomes LIST names (one per line; default:
+the whole universe), `--cover-clip C` counts a position's depth as at most C (1..1023, default 255), `--cover-min P` calls a
+window present where the sample holds at least P per cent of its positions (1..100, default 50).
 """
 import argparse
 import os
@@ -488,7 +494,9 @@ def screen_command(args):
     sample in windows of W bases, counted over positions (_paint_rows).  --reads adds the answer for a read set or a draft
     assembly: every record called to the genome that holds most of its k-mer positions, and the sample's abundance profile
     over the genomes, voted and tallied on the device (_reads_rows).  --depth adds how many times the sample holds the k-mers
-    of every genome and class: a histogram of depths per row, counted and binned on the device (_depth_rows)."""
+    of every genome and class: a histogram of depths per row, counted and binned on the device (_depth_rows).  --cover W turns
+    the view round: every genome of the collection in windows of W bases, and per sample how much of each window it holds and
+    how deep (_cover_rows)."""
     tree, outfile = _open_tree("screen", args, exact=True)
     ks = sorted(set(int(k) for k in args.ks)) if args.ks else [int(tree.root_k())]
     for k in ks:
@@ -507,6 +515,19 @@ def screen_command(args):
     bins = 64 if args.depth_bins is None else args.depth_bins
     if not 2 <= bins <= 256:
         sys.exit(f"screen: --depth-bins {bins}: bin 0, then at least the clipped bin, 256 bins at the most (B in 2..256)")
+    if args.cover is not None and (args.cover < 64 or args.cover % 64 or args.cover > 1 << 22):
+        sys.exit(f"screen: --cover {args.cover}: a window is a multiple of 64 bases in 64..{1 << 22}")
+    for flag, value in (("--cover-fastas", args.cover_fastas), ("--cover-clip", args.cover_clip), ("--cover-min", args.cover_min)):
+        if value is not None and args.cover is None:
+            sys.exit(f"screen: {flag} goes with --cover")
+    clip = 255 if args.cover_clip is None else args.cover_clip
+    if not 1 <= clip <= 1023:
+        sys.exit(f"screen: --cover-clip {clip}: a position's depth counts as at most C, C in 1..1023")
+    cover_min = 50 if args.cover_min is None else args.cover_min
+    if not 1 <= cover_min <= 100:
+        sys.exit(f"screen: --cover-min {cover_min}: the per cent of a window's positions a sample must hold, P in 1..100")
+    if args.cover_fastas is not None and not os.path.isfile(args.cover_fastas):
+        sys.exit(f"screen: {args.cover_fastas} (--cover-fastas) not found")
     names = list(args.samples)
     if args.query_loc:
         if not os.path.isfile(args.query_loc):
@@ -525,11 +546,24 @@ def screen_command(args):
     fastas = _universe_or_exit("screen", tree, args, least=1, most=64, most_why=MASK_BITS)
     ns = len(samples)
     groups, labels = _groups_in_universe("screen", args, leaf_of, fastas)
+    cover_targets = None                                                 # --cover-fastas: the genomes the samples are laid along
+    if args.cover_fastas is not None:
+        cover_targets = []
+        for name in _lines(args.cover_fastas):
+            f = leaf_of(name.strip())
+            if f not in fastas:
+                sys.exit(f"screen: {f} (--cover-fastas) is not in the universe of this run (-f)")
+            if f in cover_targets:
+                sys.exit(f"screen: {f} stands twice in {args.cover_fastas} (--cover-fastas)")
+            cover_targets.append(f)
+        if not cover_targets:
+            sys.exit(f"screen: {args.cover_fastas} (--cover-fastas) names no genome")
     try:
         res = tree.screen_tables(fastas, samples, ks, groups)
         painted = tree.paint_tables(fastas, samples, ks, args.paint) if args.paint is not None else None
         called = tree.reads_tables(fastas, samples, ks, args.reads_min_hits, args.reads_calls) if args.reads else None
         depths = tree.depth_tables(fastas, samples, ks, groups, bins) if args.depth else None
+        covered = tree.cover_tables(fastas, samples, ks, args.cover, cover_targets, clip) if args.cover is not None else None
     except (ValueError, OSError) as e:
         sys.exit("screen: " + " ".join(str(e).split()))
 
@@ -578,7 +612,58 @@ def screen_command(args):
         _write_csv(outfile + ".depth.csv", DEPTH_COLUMNS, stats)
         if args.depth_hist:
             _write_csv(outfile + ".depth_hist.csv", ["sample", "k", "target", "class", "depth", "kmers"], hists)
+    if covered is not None:
+        for name, rows in zip(COVER_COLUMNS, _cover_rows(samples, covered, cover_min)):
+            _write_csv(f"{outfile}.{name}.csv", COVER_COLUMNS[name], rows)
     _finish(tree)
+
+
+COVER_COLUMNS = {
+    "cover": ["sample", "k", "fasta", "window", "record", "start", "end", "records", "valid", "covered", "depth", "private", "private_covered",
+              "private_depth"],
+    "cover_regions": ["sample", "k", "fasta", "state", "first_window", "windows", "record", "start", "end_record", "end", "valid", "covered",
+                      "depth"],
+    "cover_summary": ["sample", "k", "fasta", "windows", "valid", "covered", "breadth", "depth", "mean_covered_depth", "private", "private_covered",
+                      "private_breadth", "private_mean_covered_depth", "present_windows", "absent_windows", "empty_windows",
+                      "longest_absent_windows"],
+}
+COVER_STATES = ("empty", "present", "absent")     # engine.cover_states' states, as the files name them
+
+
+def _cover_rows(samples, covered, min_percent):
+    """cover_tables' counters -> the rows of <prefix>.cover.csv (one per sample, k, genome and window of the genome: where the
+    window lies in the genome's records -- engine.paint_windows -- and its six counts), of .cover_regions.csv (the runs of
+    consecutive windows with the same state -- engine.cover_states: present, absent, empty --: the record and base the run
+    starts at, the record and base its last window ends at, the sums of its windows) and of .cover_summary.csv (one per sample,
+    k and genome: the sums over its windows, breadth = covered / valid, the mean depth of the covered positions, the same of
+    the private positions, the windows of each state and the longest absent run; an empty cell where a ratio has nothing to
+    stand on)."""
+    from ..engine import COVER_ABSENT, cover_states, paint_windows
+    W = covered["window"]
+    ratio = lambda a, b: a / b if b else None
+    windows, regions, summary = [], [], []
+    for s, sample in enumerate(samples):
+        for kk, k in enumerate(covered["ks"]):
+            for t, fasta in enumerate(covered["targets"]):
+                names, seq_len, tok_start, _ = covered["index"][t]
+                rows = covered["counts"][kk][t][s]
+                record, start, end, records = paint_windows(len(rows), W, tok_start, seq_len)
+                name_of = lambda w: names[record[w]] if record[w] >= 0 else None
+                body = rows.astype("int64").tolist()
+                for w, row in enumerate(body):
+                    windows.append([sample, k, fasta, w, name_of(w), int(start[w]), int(end[w]), int(records[w]), *row])
+                states, runs = cover_states(rows, min_percent)
+                for state, first, length in runs.tolist():
+                    last = first + length - 1
+                    valid, cov, depth = (sum(r[c] for r in body[first:last + 1]) for c in range(3))
+                    regions.append([sample, k, fasta, COVER_STATES[state], first, length, name_of(first), int(start[first]), name_of(last),
+                                    int(end[last]), valid, cov, depth])
+                tot = [sum(r[c] for r in body) for c in range(6)]
+                per = [int((states == st).sum()) for st in range(3)]
+                longest = max((length for state, _, length in runs.tolist() if state == COVER_ABSENT), default=0)
+                summary.append([sample, k, fasta, len(body), tot[0], tot[1], ratio(tot[1], tot[0]), tot[2], ratio(tot[2], tot[1]), tot[3], tot[4],
+                                ratio(tot[4], tot[3]), ratio(tot[5], tot[4]), per[1], per[2], per[0], longest])
+    return windows, regions, summary
 
 
 DEPTH_COLUMNS = ["sample", "k", "target", "class", "kmers", "covered", "breadth", "mean_depth", "mean_covered", "median_depth", "median_covered",
@@ -993,6 +1078,19 @@ def build_parser():
                          "a median that lies there is marked clipped")
     sc.add_argument("--depth-hist", dest="depth_hist", default=False, action="store_true",
                     help="with --depth: also write the non-zero bins of every histogram (<prefix>.depth_hist.csv)")
+    sc.add_argument("--cover", dest="cover", type=int, default=None, metavar="W",
+                    help="also lay every sample along every genome of the collection in windows of W bases of the genome (a multiple "
+                         "of 64): per window the positions whose k-mer the sample holds, their depth, and the same for the k-mers no "
+                         "other genome holds (<prefix>.cover.csv), the runs of present, absent and empty windows "
+                         "(<prefix>.cover_regions.csv) and a row per sample and genome (<prefix>.cover_summary.csv)")
+    sc.add_argument("--cover-fastas", dest="cover_fastas", type=str, default=None, metavar="LIST",
+                    help="with --cover: a file of genomes of the universe, one per line, to lay the samples along (default: all of it)")
+    sc.add_argument("--cover-clip", dest="cover_clip", type=int, default=None, metavar="C",
+                    help="with --cover: a position's depth counts as at most C, 1..1023 (default 255), so that one repeat does not "
+                         "carry a window's mean")
+    sc.add_argument("--cover-min", dest="cover_min", type=int, default=None, metavar="P",
+                    help="with --cover: a window is present where the sample holds at least P per cent of its positions, 1..100 "
+                         "(default 50)")
     sc.add_argument("samples", nargs="*", metavar="SAMPLE", help="FASTA / FASTQ files, plain or gzip, that are no leaves of the tree")
     sc.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     sc.add_argument("-l", "--label", dest="label", default="")

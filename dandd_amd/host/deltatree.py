@@ -1370,6 +1370,48 @@ class DeltaTree:
                 out["total"][kk, batch] = u.table(got[1], (len(batch), n + nq))
         return out
 
+    def cover_tables(self, fastas, samples, ks, window, targets=None, clip=255):
+        """Where along the genomes `targets` (FASTAs of the universe; None: all of it) each of `samples` (files that are no
+        leaves: a read set, an assembly; FASTA / FASTQ, plain or gzip) lies, and how deep, at every k of `ks`; the universe
+        `fastas` is 1..64 leaf FASTAs of an exact tree.  The TARGET's token stream (one BREAK in front of every record's bases)
+        goes in windows of `window` tokens, a multiple of 64, and per sample and window six counts over the positions where
+        a valid k-mer ends: valid, covered (the sample holds the k-mer), depth (the times it holds it, at most `clip` a
+        position, summed), and private, private_covered, private_depth -- the same over the positions whose k-mer no other
+        genome of the universe holds.  The samples go to the backend's cover_counts in screen_tables' batches.  There is no
+        object path: a backend without cover_counts, or without a table for these leaves, is a ValueError.
+        -> dict: ks, window, clip, targets (FASTAs), index [nt] of (names, seq_len, tok_start, ntok), counts [K][nt] of uint32
+        [ns][nwin_t][6]"""
+        n, ns, window, clip = len(fastas), len(samples), int(window), int(clip)
+        ks = [int(k) for k in ks]
+        for k in ks:
+            if not 1 <= k <= 64:
+                raise ValueError(f"k={k} is outside 1..64")
+        if window < 64 or window % 64 or window > 1 << 22:
+            raise ValueError(f"a window of {window} tokens: a multiple of 64 in 64..{1 << 22} is needed")
+        if not 1 <= clip <= 1023:
+            raise ValueError(f"clip={clip} is outside 1..1023")
+        targets = list(fastas) if targets is None else list(targets)
+        for f in targets:
+            if f not in fastas:
+                raise ValueError(f"{f} is not in the universe")
+        if not targets or len(set(targets)) != len(targets):
+            raise ValueError("the targets are genomes of the universe, each once, at least one")
+        at = [fastas.index(f) for f in targets]
+        batches = self._sample_batches(samples)
+        out = {"ks": ks, "window": window, "clip": clip, "targets": targets, "index": [None] * len(at), "counts": [[None] * len(at) for _ in ks]}
+        for kk, k in enumerate(ks):
+            u = self._universe(fastas, k, k)
+            u.need("cover_counts", why="coverage needs")
+            for batch in batches:
+                index, counts = u.table(u.be.cover_counts(u.paths, k, [samples[j] for j in batch], window, at, clip))
+                for t, (ix, rows) in enumerate(zip(index, counts)):
+                    nwin = -(-int(ix[3]) // window)
+                    out["index"][t] = ix
+                    if out["counts"][kk][t] is None:
+                        out["counts"][kk][t] = np.zeros((ns, nwin, 6), dtype=np.uint32)
+                    out["counts"][kk][t][batch] = u.table(rows, (len(batch), nwin, 6))
+        return out
+
     # ---- which sets of genomes share k-mers (`dandd patterns`) --------------------------------------------------------------
     def pattern_tables(self, fastas, ks, top=None):
         """The membership patterns of the universe `fastas` (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]) at every

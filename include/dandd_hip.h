@@ -428,6 +428,45 @@ int dd_exact_depth(dd_ctx *, const char *const *paths, int n, const char *const 
 int dd_exact_depth_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
                           const uint64_t *all, const uint64_t *none, int nq, int bins, uint64_t *hist, uint64_t *total,
                           uint64_t *found);
+/* ---- samples laid along the genomes of the universe ----------------------------------------------------------------
+ * dd_exact_paint says where along a SAMPLE the universe's k-mers lie, dd_exact_depth how many times a sample holds the
+ * k-mers of an input as a whole; this says where along an INPUT the sample lies, and how deep (dd_exact_cover.hip): the
+ * coverage track of a read-mapping workflow, exact and alignment-free.  target[t] names an input of the universe; its token
+ * stream as K0 lays it out (dd_exact_paint's, dd_fasta_index gives the records' places) is cut into windows of `window`
+ * tokens, and every window gets, per sample, a row of six counters.  A k-mer belongs to the window that holds its END token.
+ * With c the depth dd_exact_depth counts -- the positions of the sample at which the k-mer stands -- the columns count the
+ * tokens of the window
+ *   column 0  valid            at which a valid k-mer of the target ends (the same for every sample)
+ *   column 1  covered          ... with c >= 1
+ *   column 2  depth            the sum of min(c, clip) over them
+ *   column 3  private          whose k-mer's membership mask is exactly 1 << target[t]: no other input holds it (the same
+ *                              for every sample)
+ *   column 4  private_covered  ... of those, with c >= 1
+ *   column 5  private_depth    the sum of min(c, clip) over those
+ * The clip keeps one repeat from carrying a window's mean, and a window of 2^22 positions inside 32 bits; with clip == 1
+ * columns 2 and 5 equal columns 1 and 4.  ONE k per call, 1 <= k <= 64, 1 <= n <= 64 universe inputs, 1 <= ns <= 1024
+ * samples, 1 <= nt <= n targets in 0..n-1, each once (a repeat is DD_EINVAL naming both places); `window` a multiple of 64 in
+ * 64 .. 1 << 22; 1 <= clip <= 1023; off must ascend and off[t+1] - off[t] be ceil(ntok / window) of input target[t], else
+ * DD_EINVAL with a message naming the target and the number expected; a sample of 2^32 bytes or more is DD_EINVAL
+ * (dd_exact_depth's counter).  Sample s owns counts[s][off[0] .. off[nt]-1] of off[nt] rows; counts may be null only when
+ * no row is asked for.
+ *   *found    the distinct k-mers of the universe
+ * A target without a token owns no rows, one shorter than k has all-zero rows, a universe without a k-mer gives zeros, an
+ * empty sample gives columns 0 and 3 only; a sample may be byte-identical to an input, which it then covers everywhere.
+ * Nothing is written unless the call returns DD_OK; two calls on the same inputs return identical bytes (integer sums).
+ * The device form takes n + ns buffers: the n universe inputs first, the ns samples behind them.
+ * The sort, the masks, the emission, the ordering and the counters are dd_exact_depth's, so are budget and passes
+ * (DD_EXACT_MB), dd_last_sketch_stats' third value and the DD_KERNEL_EXACT timer.  The record of every target position is
+ * looked up once per call and kept in 4 bytes x the targets' token slots of HBM; the samples are then taken in rounds: as
+ * many as DD_DEPTH_MB (dd_exact_depth's variable) holds of found x 4 bytes of counters and off[nt] x 24 bytes of rows each.
+ * An index word holds a record below 2^31: a universe of 2^31 distinct k-mers or more is DD_EINVAL.  A budget that does not
+ * hold one sample, or memory that cannot be had, is DD_ENOMEM with a message naming the bytes. */
+int dd_exact_cover(dd_ctx *, const char *const *paths, int n, const char *const *samples, int ns, int k,
+                   const int32_t *target /*[nt]*/, int nt, uint64_t window, uint32_t clip,
+                   const uint64_t *off /*[nt+1], in windows*/, uint32_t *counts /*[ns][off[nt]][6]*/, uint64_t *found);
+int dd_exact_cover_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
+                          const int32_t *target, int nt, uint64_t window, uint32_t clip,
+                          const uint64_t *off, uint32_t *counts, uint64_t *found);
 /* ---- the membership-pattern table ------------------------------------------------------------------------------
  * Which sets of inputs share k-mers, and how many: the DISTINCT membership masks of the universe with their multiplicities
  * (the table behind an UpSet plot; every other mask statistic above -- spectrum, select, a subset union -- is a sum over
