@@ -15,19 +15,27 @@ static int ensure_side_streams(dd_ctx* c, int n) {
 }
 
 // Fork and join on the side streams: run() gives `launch` the next lane, behind the mark `side_go` on the caller's stream,
-// and puts the caller's stream behind what the lane was given -- or, without `fork`, gives it the caller's stream.
+// and puts the caller's stream behind what the lane was given -- or, without `fork`, gives it the caller's stream.  With
+// `join_now` false the caller's stream is put behind the lane only by join(): what the caller's stream is given in between runs
+// beside the lane.
 struct SideLanes {
     dd_ctx* c;
-    int lane = 0;
+    int lane = 0, joined = 0;
     template <class F>
-    int run(bool fork, F&& launch) {
+    int run(bool fork, F&& launch, bool join_now = true) {
         const int l = lane & 7;
         if (!fork) return launch(c->stream), DD_OK;
-        DD_HIP(hipStreamWaitEvent(c->side[l], c->side_go, 0));
-        launch(c->side[l]);
-        DD_HIP(hipEventRecord(c->side_done[l], c->side[l]));
-        DD_HIP(hipStreamWaitEvent(c->stream, c->side_done[l], 0));
+        // (the lane's mark is recorded whatever the wait returned, so that join() never waits on the mark of an earlier call)
+        const hipError_t waited = hipStreamWaitEvent(c->side[l], c->side_go, 0);
+        if (waited == hipSuccess) launch(c->side[l]);
+        const hipError_t marked = hipEventRecord(c->side_done[l], c->side[l]);
         ++lane;
+        DD_HIP(waited);
+        DD_HIP(marked);
+        return join_now ? join() : DD_OK;
+    }
+    int join() {
+        for (; joined < lane; ++joined) DD_HIP(hipStreamWaitEvent(c->stream, c->side_done[joined & 7], 0));
         return DD_OK;
     }
 };
@@ -142,8 +150,12 @@ static void launch_lds_class(dd_ctx* c, const dd::SweepClass& sc, const dd::Swee
     }
 }
 
-// K1.  The k classes are independent.  On a big call they are launched back to back (running them side by side
-// was measured neutral to slightly slower: they compete for the same VALUs).  On a SMALL call -- one batch of
+// K1.  The k classes are independent.  On a big call the HASHED classes are launched back to back (running them side by
+// side was measured neutral to slightly slower: they compete for the same VALUs).  The small-k class of such a call (log2m
+// <= 16, no bucket class) is bound by latency and dispatch, not by the VALUs -- most of its workgroups read their flags and
+// return --, so it goes to ONE side lane and runs beside the first hashed class instead of in front of it; the lane is joined
+// behind the last hashed class (profiles/k1_small_k_side.txt; DD_NO_SIDE_SMALLK keeps it on the caller's stream).  On a SMALL
+// call (under 12 000 LDS jobs, DD_SIDE_JOBS) -- one batch of
 // the ingestion pipeline, a single genome -- every LDS class is only a few rounds of workgroups long and ends
 // with a tail of idle CUs: there the classes go to side streams so that one's tail overlaps another's body.
 // At log2m >= 17 every bucket class is a pipeline of its own -- scatter(e), (sort(e),) replay(e), scatter(e+1) ... over its own
@@ -158,40 +170,54 @@ static void launch_lds_class(dd_ctx* c, const dd::SweepClass& sc, const dd::Swee
 // behind the joins of the LDS classes.  *blocks: the workgroups launched.
 static int launch_classes(dd_ctx* c, const dd_ctx::PlanEntry& plan, const dd::SweepGenome* gtab, const dd::BucketRow* rows, int ngenomes, int kmin, int kmax, int sat_last_k, int* blocks) {
     const int K = kmax - kmin + 1;
-    size_t lds_jobs = 0;
-    int lds_classes = 0, nepochs = 0, rc;
+    size_t lds_jobs = 0, side_jobs = 12000;
+    int lds_classes = 0, hashed_lds = 0, nbucket = 0, nepochs = 0, rc;
+    bool small_k = false;
     for (const dd::SweepClass& sc : plan.classes) {
         if (sc.plan.mode != dd::kBucketMode) lds_jobs += sc.jobs.size(), ++lds_classes;
-        else nepochs = sc.plan.nepochs;
+        else nepochs = sc.plan.nepochs, ++nbucket;
+        if (sc.kclass == dd::kBitmapClass) small_k = true;
+        else if (sc.kclass >= 0 && sc.plan.mode != dd::kBucketMode) ++hashed_lds;
     }
-    const bool side = lds_classes > 1 && lds_jobs < 12000, side_b = nepochs > 1;
-    if ((side || side_b) && (rc = ensure_side_streams(c, side_b ? (int)plan.classes.size() : lds_classes))) return rc;
+    // (both switches are read per call and are no part of the plan: the job tables are the same with and without them)
+    if (const char* s = getenv("DD_SIDE_JOBS")) side_jobs = (size_t)strtoull(s, nullptr, 10);
+    const bool side = lds_classes > 1 && lds_jobs < side_jobs, side_b = nepochs > 1;
+    const bool side_k = !side && !side_b && !nbucket && small_k && hashed_lds && c->p <= 16 && !getenv("DD_NO_SIDE_SMALLK");
+    const bool forks = side || side_b || side_k;
+    if (forks && (rc = ensure_side_streams(c, side_b ? (int)plan.classes.size() : side_k ? 1 : lds_classes))) return rc;
     // (launches that run side by side are timed as ONE span on the caller's stream: per-launch spans would overlap; it is
-    // closed on return, when every side stream has been joined into the caller's stream)
-    Span phase(c, DD_KERNEL_SWEEP, side || side_b);
-    if (side || side_b) DD_HIP(hipEventRecord(c->side_go, c->stream));
+    // closed on return, when every side stream has been joined into the caller's stream.  A call that forks its small-k
+    // class alone has no per-launch spans for the classes on the caller's stream either: they lie inside the phase's span
+    // and would be counted twice, profiles/sketch_device_split.txt, point 4)
+    Span phase(c, DD_KERNEL_SWEEP, forks);
+    if (forks) DD_HIP(hipEventRecord(c->side_go, c->stream));
     SideLanes lanes{c};
     for (size_t i = 0; i < plan.classes.size(); ++i) {
         const dd::SweepClass& sc = plan.classes[i];
         const dd::SweepJob* jobs = reinterpret_cast<const dd::SweepJob*>(static_cast<char*>(plan.jobtab.p) + plan.job_off[i]);
-        const bool bucket = sc.plan.mode == dd::kBucketMode, on_lane = side_b || (side && !bucket);
+        const bool bucket = sc.plan.mode == dd::kBucketMode;
+        const bool on_lane = side_b || (side && !bucket) || (side_k && sc.kclass == dd::kBitmapClass), timed = !on_lane && !side_k;
         rc = lanes.run(on_lane, [&](hipStream_t ks) {
             if (!bucket) {
-                Span span(c, DD_KERNEL_SWEEP, !on_lane);
+                Span span(c, DD_KERNEL_SWEEP, timed);
                 launch_lds_class(c, sc, gtab, jobs, ngenomes, kmin, sat_last_k, ks);
             }
             const dd::ScatterParams sp{rows, K, sc.plan.logg, sc.plan.cap_chunks, sc.plan.nb_log2};
             for (int e = 0; bucket && e < sc.plan.nepochs; ++e) {
                 const size_t j0 = sc.epoch_begin[e], j1 = sc.epoch_begin[e + 1];
                 if (j1 == j0) continue;
-                Span span(c, DD_KERNEL_SWEEP, !on_lane);
+                Span span(c, DD_KERNEL_SWEEP, timed);
                 dd::launch_scatter(gtab, jobs + j0, (int)(j1 - j0), sc.kclass, sc.plan, sp, ks, e == 0);
                 dd::launch_replay(rows, ngenomes, K, sc.kfirst - kmin, sc.klast - sc.kfirst + 1, sc.plan, ks, e == 0);
             }
-        });
-        if (rc) return rc;
+        }, !side_k);
+        if (rc) break;
         *blocks += (int)sc.jobs.size();
     }
+    // (the small-k lane of a big call is joined here, behind the hashed classes: the caller's union and the next call's memset of
+    // the bitmaps and flags are both on the caller's stream.  Also after an error: nothing may be left running unordered.)
+    const int jrc = lanes.join();
+    if (rc || jrc) return rc ? rc : jrc;
     DD_HIP(hipGetLastError());
     return DD_OK;
 }

@@ -233,12 +233,13 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(72))) void bit
     __shared__ uint32_t flagged;
     // ONE thread reads the flags for the workgroup: another workgroup may set a flag at any moment, and waves
     // that read it at different times would disagree on kmask -- some would return while others go on to read
-    // LDS words the returned waves were meant to load.
-    if (threadIdx.x == 0) {
-        uint32_t f = 0;
-        for (int k = kfirst; k <= klast; ++k)
-            if (load4_fresh(complete + k)) f |= 1u << k;
-        flagged = f;
+    // LDS words the returned waves were meant to load.  The reader is the first WAVE: lane k loads the flag of k, all of the
+    // job's flags in one round trip (most workgroups of a big call do nothing but this), and the ballot is the one reading.
+    if (threadIdx.x < 64) {
+        const int k = (int)threadIdx.x;
+        const uint32_t v = (k >= kfirst && k <= klast) ? load4_fresh(complete + k) : 0u;
+        const unsigned long long f = __ballot(v != 0u);
+        if (threadIdx.x == 0) flagged = (uint32_t)f;
     }
     if (threadIdx.x <= kBitmapMaxK) have[threadIdx.x] = 0;
     __syncthreads();
