@@ -1,7 +1,8 @@
 // dd_ctx.h -- the context behind the C ABI's opaque dd_ctx, and the host-side helpers the ABI's sources share
 // (dd_api.hip: context, timing and stats, synth, dd_plan_sweep; dd_sketch_api.hip: sketch; dd_k2_api.hip: union, card and the
 // HLL schedules, one body each over its slab frame -- Slab, slab_dev -- and its histogram step, hist_step;
-// dd_exact_api.hip: exact count, schedules and greedy; dd_exact_emit_api.hip: the selected k-mers, where they lie, the samples screened against them and the pattern table, all
+// dd_exact_api.hip: exact count, schedules and greedy; dd_exact_emit_api.hip: the selected k-mers, where they lie and the pattern table;
+// dd_exact_samples_api.hip: samples that are no inputs screened, painted, called, counted and laid along the genomes; all
 // over dd_exact_host.h / dd_exact_passes.hip: call frame, pass driver, emission; dd_ingest.hip: the file-ingestion pipeline; dd_comm.hip: RCCL).  Callers see dandd_hip.h only.
 #pragma once
 #include "../../include/dandd_hip.h"
@@ -119,11 +120,8 @@ struct dd_ctx {
     DevBuf tokens, scratch, tables, fasta, regs, ptrs, hist, est, ord, bitmaps, bigmaps, exact, buckets, gram, synth;
     DevBuf masks;  // dd_exact_greedy: cursor and overflow word | gains [64][64] | the mask streams of every k of the call
     DevBuf emit;   // dd_exact_select_kmers, dd_exact_locate (exact_records): cursor (256 B) | lo | hi | mask, `cap` records each
-    DevBuf hits;   // dd_exact_locate: the jobs' hit bitmaps, off[njobs] words; dd_exact_screen: counters [ns + 1][n + nq] | the samples' seen bitmaps;
-                   // dd_exact_paint: the windows' counters, off[ns] - off[0] rows of n + 2 x 32 bits; dd_exact_reads: the rows' counters |
-                   // borders | calls | sets | the samples' tallies; dd_exact_depth: the sizes of the rows | a round's histograms | overflow sums |
-                   // counters [samples of the round][found] x 32 bits; dd_exact_cover: the targets' index, a word per token slot | a
-                   // round's rows [samples][off[nt] - off[0]][6] x 32 bits | the same counters
+    DevBuf hits;   // what the kernels behind the ordered records write: dd_exact_locate's hit bitmaps, off[njobs] words; the parts each
+                   // entry of dd_exact_samples_api.hip declares (HitsCarve; the layout stands in the comment above the entry)
     DevBuf pat[2]; // dd_exact_patterns: the running table in mask order (masks | counts) and where the next merge puts it, in turns
     // saturation (dd_kernels.h): sketch(U_k) for k = kSatMinK..kSatMaxK at this context's log2m and strand mode, [k - kSatMinK][m];
     // a row is built by the first call that needs it, on that call's stream, and kept

@@ -107,8 +107,8 @@ __global__ __launch_bounds__(256) void cover_kernel(const CoverUnit* __restrict_
         for (int j = 0; j < kCoverColumns; ++j) row[j] = c[j];
         return;
     }
-    const unsigned long long end = (ntok - 1) / kSegTokens, last = first + 63 < end ? first + 63 : end, w = first / wsegs;
-    if (w == last / wsegs) {   // (the same in every lane; the lanes behind the stream hold zeros)
+    unsigned long long w;
+    if (wave_in_one_window(first, ntok, wsegs, w)) {   // (the same in every lane; the lanes behind the stream hold zeros)
         uint32_t sum = 0;
 #pragma unroll
         for (int j = 0; j < kCoverColumns; ++j) {
@@ -130,11 +130,8 @@ __global__ __launch_bounds__(256) void cover_kernel(const CoverUnit* __restrict_
 void launch_exact_cover_index(const CoverUnit* units_dev, int nunits, size_t max_segments, int k, int canonical, const LocateSet& set,
                               uint32_t* index_dev, hipStream_t st) {
     if (nunits <= 0 || !max_segments || !set.found) return;
-    const dim3 grid((unsigned)((max_segments + 255) / 256), (unsigned)nunits), block(256);
-    dispatch_bool(canonical != 0, [&](auto cn) {
-        dispatch_bool(k > 32, [&](auto wd) {
-            hipLaunchKernelGGL((cover_index_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, units_dev, k, set, index_dev);
-        });
+    launch_segment_walk((size_t)nunits, max_segments, canonical, k, [&](dim3 grid, dim3 block, auto cn, auto wd) {
+        hipLaunchKernelGGL((cover_index_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, units_dev, k, set, index_dev);
     });
 }
 

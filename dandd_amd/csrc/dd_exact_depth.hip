@@ -117,11 +117,8 @@ __global__ __launch_bounds__(kDepthTallyThreads) void depth_tally_kernel(const u
 void launch_exact_depth(const ExactGenome* samples_dev, int ns, size_t max_segments, int k, int canonical, const LocateSet& set,
                         uint32_t* count_dev, hipStream_t st) {
     if (ns <= 0 || !max_segments || !set.found) return;
-    const dim3 grid((unsigned)((max_segments + 255) / 256), (unsigned)ns), block(256);
-    dispatch_bool(canonical != 0, [&](auto cn) {
-        dispatch_bool(k > 32, [&](auto wd) {
-            hipLaunchKernelGGL((depth_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, samples_dev, k, set, count_dev);
-        });
+    launch_segment_walk((size_t)ns, max_segments, canonical, k, [&](dim3 grid, dim3 block, auto cn, auto wd) {
+        hipLaunchKernelGGL((depth_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, samples_dev, k, set, count_dev);
     });
 }
 

@@ -1,5 +1,5 @@
-// dd_exact_host.h -- what the exact entry points share on the host (defined in dd_exact_passes.hip; called by dd_exact_api.hip
-// and dd_exact_emit_api.hip): the call frame, the path forms' upload, K0 over the inputs and their token counts read back, the
+// dd_exact_host.h -- what the exact entry points share on the host (defined in dd_exact_passes.hip; called by dd_exact_api.hip,
+// dd_exact_emit_api.hip and dd_exact_samples_api.hip): the call frame, the path forms' upload, K0 over the inputs and their token counts read back, the
 // pass driver, and the ordered-record step: the emission, its sanity check and the room that puts the records in order.
 #pragma once
 #include <functional>
@@ -13,6 +13,11 @@ int exact_frame(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes
 int exact_check_inputs(const uint8_t* const* fasta_dev, const size_t* nbytes, int n);
 // query (job) i of a call over n inputs sets no bit outside 0..n-1; `who`: "query" / "job", for the message
 int exact_check_bits(const char* who, int i, uint64_t all, uint64_t none, int n);
+// The shape of a ragged answer: `who` i ("job" / "sample" / "target") owns off[i+1] - off[i] `parts` ("words" / "rows") of it,
+// one per `unit` tokens (a `unit_name`: "word" / "window") of a stream of ntok tokens.  input: the input that stream is, for
+// the message (< 0: `who` itself, "it").
+struct ExactShape { const char *who, *parts; uint64_t unit; const char* unit_name; };
+int exact_check_shape(const ExactShape& s, int i, const uint64_t* off, int input, unsigned long long ntok);
 // select's argument rules -> the (all, none) pairs its accumulator and the emission read
 int select_table(const uint64_t* all, const uint64_t* none, int nq, int n, std::vector<uint64_t>& table);
 using ExactDeviceForm = std::function<int(const uint8_t* const* fasta_dev, const size_t* nbytes)>;

@@ -63,11 +63,8 @@ __global__ __launch_bounds__(256) void locate_kernel(const LocateUnit* __restric
 void launch_exact_locate(const LocateUnit* units_dev, int nunits, size_t max_segments, int k, int canonical, const LocateSet& set,
                          uint64_t* hits_dev, hipStream_t st) {
     if (nunits <= 0 || !max_segments || !set.found) return;
-    const dim3 grid((unsigned)((max_segments + 255) / 256), (unsigned)nunits), block(256);
-    dispatch_bool(canonical != 0, [&](auto cn) {
-        dispatch_bool(k > 32, [&](auto wd) {
-            hipLaunchKernelGGL((locate_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, units_dev, k, set, hits_dev);
-        });
+    launch_segment_walk((size_t)nunits, max_segments, canonical, k, [&](dim3 grid, dim3 block, auto cn, auto wd) {
+        hipLaunchKernelGGL((locate_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, units_dev, k, set, hits_dev);
     });
 }
 

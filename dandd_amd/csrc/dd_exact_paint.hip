@@ -44,22 +44,13 @@ __global__ __launch_bounds__(256) void paint_kernel(const ExactGenome* __restric
     const unsigned long long first = seg - (unsigned)lane;   // the wave's first segment: live if any of them is
     if (first * kSegTokens >= ntok) return;
     const bool live = seg * kSegTokens < ntok;
-    uint64_t p[kPaintPlanes];
-#pragma unroll
-    for (int j = 0; j < kPaintPlanes; ++j) p[j] = 0;
+    PlaneCounter pc;
+    pc.clear();
     uint32_t valid = 0, inpan = 0;
     walk_segment<CANON, false>(u->codes, u->bad, ntok, seg, k, [&](unsigned long long, int, uint64_t ah, uint64_t al, bool) {
         ++valid;
         unsigned long long r;
-        if (!find_record<WIDE>(set, ah, al, r)) return;
-        ++inpan;
-        uint64_t carry = set.mask[r];
-#pragma unroll
-        for (int j = 0; j < kPaintPlanes; ++j) {
-            const uint64_t both = p[j] & carry;
-            p[j] ^= carry;
-            carry = both;
-        }
+        if (find_record<WIDE>(set, ah, al, r)) ++inpan, pc.add(set.mask[r]);
     });
     const unsigned long long ncol = (unsigned long long)n + 2;
     // (the host has checked that the sample owns ceil(ntok / W) rows from row0 on: a live segment's window is one of them)
@@ -68,37 +59,12 @@ __global__ __launch_bounds__(256) void paint_kernel(const ExactGenome* __restric
         if (!live) return;
         uint32_t* row = rows + seg * ncol;
         row[0] = valid, row[1] = inpan;
-        for (int i = 0; i < n; ++i) row[2 + i] = plane_count(p, i);
+        for (int i = 0; i < n; ++i) row[2 + i] = pc.count(i);
         return;
     }
-    const unsigned long long end = (ntok - 1) / kSegTokens, last = first + 63 < end ? first + 63 : end, w = first / wsegs;
-    if (w == last / wsegs) {   // (the same in every lane; the lanes behind the stream hold zeros)
-        uint32_t* row = rows + w * ncol;
-        const uint32_t v = wave_sum(valid), h = wave_sum(inpan);
-        uint32_t mine = 0;
-#pragma unroll
-        for (int j = 0; j < kPaintPlanes; ++j) {
-            const uint64_t pj = p[j];
-            if (!__ballot(pj != 0)) continue;
-            for (int i = 0; i < n; ++i) {
-                const unsigned long long col = __ballot((pj >> i) & 1ull);
-                if (lane == i) mine += (uint32_t)__builtin_popcountll(col) << j;
-            }
-        }
-        if (lane < n && mine) atomicAdd(row + 2 + lane, mine);
-        if (lane == 0 && v) atomicAdd(row, v);
-        if (lane == 1 && h) atomicAdd(row + 1, h);
-        return;
-    }
-    if (!live) return;
-    uint32_t* row = rows + (seg / wsegs) * ncol;
-    if (valid) atomicAdd(row, valid);
-    if (!inpan) return;
-    atomicAdd(row + 1, inpan);
-    for (int i = 0; i < n; ++i) {
-        const uint32_t c = plane_count(p, i);
-        if (c) atomicAdd(row + 2 + i, c);
-    }
+    unsigned long long w;
+    if (wave_in_one_window(first, ntok, wsegs, w)) pc.flush_wave(rows + w * ncol, n, lane, valid, inpan);
+    else if (live) pc.flush(rows + (seg / wsegs) * ncol, n, valid, inpan);
 }
 
 }  // namespace
@@ -106,12 +72,9 @@ __global__ __launch_bounds__(256) void paint_kernel(const ExactGenome* __restric
 void launch_exact_paint(const ExactGenome* samples_dev, int ns, size_t max_segments, int k, int canonical, const LocateSet& set, int n,
                         size_t window_segments, const unsigned long long* row0_dev, uint32_t* counts_dev, hipStream_t st) {
     if (ns <= 0 || !max_segments) return;
-    const dim3 grid((unsigned)((max_segments + 255) / 256), (unsigned)ns), block(256);
-    dispatch_bool(canonical != 0, [&](auto cn) {
-        dispatch_bool(k > 32, [&](auto wd) {
-            hipLaunchKernelGGL((paint_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, samples_dev, k, set, n,
-                               (unsigned long long)window_segments, row0_dev, counts_dev);
-        });
+    launch_segment_walk((size_t)ns, max_segments, canonical, k, [&](dim3 grid, dim3 block, auto cn, auto wd) {
+        hipLaunchKernelGGL((paint_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, samples_dev, k, set, n,
+                           (unsigned long long)window_segments, row0_dev, counts_dev);
     });
 }
 

@@ -36,6 +36,15 @@ int exact_check_bits(const char* who, int i, uint64_t all, uint64_t none, int n)
     return (all | none) & outside ? fail(DD_EINVAL, "%s %d: a bit outside 0..%d is set", who, i, n - 1) : DD_OK;
 }
 
+int exact_check_shape(const ExactShape& s, int i, const uint64_t* off, int input, unsigned long long ntok) {
+    const uint64_t have = off[i + 1] - off[i], want = (ntok + s.unit - 1) / s.unit;
+    if (have == want) return DD_OK;
+    char holder[32] = "it";
+    if (input >= 0) snprintf(holder, sizeof holder, "input %d", input);
+    return fail(DD_EINVAL, "%s %d: off[%d] - off[%d] = %llu %s, %llu expected (%s holds %llu tokens, %llu to a %s)", s.who, i, i + 1, i,
+                (unsigned long long)have, s.parts, (unsigned long long)want, holder, ntok, (unsigned long long)s.unit, s.unit_name);
+}
+
 int select_table(const uint64_t* all, const uint64_t* none, int nq, int n, std::vector<uint64_t>& table) {
     if (!all || !none) return fail(DD_EINVAL, "null argument");
     if (nq < 1) return fail(DD_EINVAL, "nq=%d: at least one query", nq);

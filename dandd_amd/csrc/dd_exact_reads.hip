@@ -79,27 +79,14 @@ __global__ __launch_bounds__(256) void reads_kernel(const ExactGenome* __restric
     // is the border that ends that row
     unsigned long long have = one_row ? upto_first : borders_upto(border, nrow, seg * kSegTokens);
     unsigned long long next = have < nrow ? border[have] : ~0ull;
-    uint64_t p[kPaintPlanes];
-#pragma unroll
-    for (int j = 0; j < kPaintPlanes; ++j) p[j] = 0;
+    PlaneCounter pc;
+    pc.clear();
     uint32_t valid = 0, inpan = 0;
-    const auto flush = [&] {   // the thread's counts to its row; have >= 1
-        uint32_t* row = rows + (have - 1) * ncol;   // (have <= nrow: one of the sample's rows)
-        if (valid) atomicAdd(row, valid);
-        if (!inpan) return;
-        atomicAdd(row + 1, inpan);
-        for (int i = 0; i < n; ++i) {
-            const uint32_t c = plane_count(p, i);
-            if (c) atomicAdd(row + 2 + i, c);
-        }
-    };
     walk_segment<CANON, false>(u->codes, u->bad, ntok, seg, k, [&](unsigned long long sidx, int t, uint64_t ah, uint64_t al, bool) {
         const unsigned long long tok = sidx * kSegTokens + (unsigned)t;
         if (tok >= next) {   // (never in a wave that lies in one row)
-            if (have && valid) flush();
-            valid = 0, inpan = 0;
-#pragma unroll
-            for (int j = 0; j < kPaintPlanes; ++j) p[j] = 0;
+            if (have && valid) pc.flush(rows + (have - 1) * ncol, n, valid, inpan);   // (have <= nrow: one of the sample's rows)
+            valid = 0, inpan = 0, pc.clear();
             do {
                 ++have;
                 next = have < nrow ? border[have] : ~0ull;
@@ -107,35 +94,10 @@ __global__ __launch_bounds__(256) void reads_kernel(const ExactGenome* __restric
         }
         ++valid;
         unsigned long long r;
-        if (!find_record<WIDE>(set, ah, al, r)) return;
-        ++inpan;
-        uint64_t carry = set.mask[r];
-#pragma unroll
-        for (int j = 0; j < kPaintPlanes; ++j) {
-            const uint64_t both = p[j] & carry;
-            p[j] ^= carry;
-            carry = both;
-        }
+        if (find_record<WIDE>(set, ah, al, r)) ++inpan, pc.add(set.mask[r]);
     });
-    if (one_row) {   // (the same in every lane; the lanes behind the stream hold zeros)
-        uint32_t* row = rows + (upto_first - 1) * ncol;
-        const uint32_t v = wave_sum(valid), h = wave_sum(inpan);
-        uint32_t mine = 0;
-#pragma unroll
-        for (int j = 0; j < kPaintPlanes; ++j) {
-            const uint64_t pj = p[j];
-            if (!__ballot(pj != 0)) continue;
-            for (int i = 0; i < n; ++i) {
-                const unsigned long long col = __ballot((pj >> i) & 1ull);
-                if (lane == i) mine += (uint32_t)__builtin_popcountll(col) << j;
-            }
-        }
-        if (lane < n && mine) atomicAdd(row + 2 + lane, mine);
-        if (lane == 0 && v) atomicAdd(row, v);
-        if (lane == 1 && h) atomicAdd(row + 1, h);
-        return;
-    }
-    if (have && valid) flush();
+    if (one_row) pc.flush_wave(rows + (upto_first - 1) * ncol, n, lane, valid, inpan);   // (the same in every lane)
+    else if (have && valid) pc.flush(rows + (have - 1) * ncol, n, valid, inpan);
 }
 
 constexpr int kVoteThreads = 256;
@@ -192,12 +154,9 @@ __global__ __launch_bounds__(kVoteThreads) void vote_kernel(const uint32_t* __re
 void launch_exact_reads(const ExactGenome* samples_dev, int ns, size_t max_segments, int k, int canonical, const LocateSet& set, int n,
                         const unsigned long long* off_dev, const unsigned long long* start_dev, uint32_t* counts_dev, hipStream_t st) {
     if (ns <= 0 || !max_segments) return;
-    const dim3 grid((unsigned)((max_segments + 255) / 256), (unsigned)ns), block(256);
-    dispatch_bool(canonical != 0, [&](auto cn) {
-        dispatch_bool(k > 32, [&](auto wd) {
-            hipLaunchKernelGGL((reads_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, samples_dev, k, set, n, off_dev,
-                               start_dev, counts_dev);
-        });
+    launch_segment_walk((size_t)ns, max_segments, canonical, k, [&](dim3 grid, dim3 block, auto cn, auto wd) {
+        hipLaunchKernelGGL((reads_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, samples_dev, k, set, n, off_dev,
+                           start_dev, counts_dev);
     });
 }
 

@@ -108,12 +108,9 @@ __global__ __launch_bounds__(kTallyThreads) void tally_kernel(const uint64_t* __
 void launch_exact_screen(const ExactGenome* samples_dev, int ns, size_t max_segments, int k, int canonical, const LocateSet& set,
                          uint32_t* seen_dev, size_t words, hipStream_t st) {
     if (ns <= 0 || !max_segments || !set.found) return;
-    const dim3 grid((unsigned)((max_segments + 255) / 256), (unsigned)ns), block(256);
-    dispatch_bool(canonical != 0, [&](auto cn) {
-        dispatch_bool(k > 32, [&](auto wd) {
-            hipLaunchKernelGGL((screen_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, samples_dev, k, set, seen_dev,
-                               (unsigned long long)words);
-        });
+    launch_segment_walk((size_t)ns, max_segments, canonical, k, [&](dim3 grid, dim3 block, auto cn, auto wd) {
+        hipLaunchKernelGGL((screen_kernel<decltype(cn)::value, decltype(wd)::value>), grid, block, 0, st, samples_dev, k, set, seen_dev,
+                           (unsigned long long)words);
     });
 }
 

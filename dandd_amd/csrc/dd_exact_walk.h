@@ -2,8 +2,9 @@
 // on a membership mask, the token walk of a 64-token segment (kmer_extract_kernel, locate_kernel, screen_kernel, paint_kernel,
 // reads_kernel, depth_kernel, cover_index_kernel), the lookup of a key in the ordered records (locate_kernel, screen_kernel,
 // paint_kernel, reads_kernel, depth_kernel, cover_index_kernel), the
-// read-out of the bit-sliced per-genome counter (paint_kernel, reads_kernel) and the wave-aggregated append
-// (kmer_extract_kernel, sched_kernel, emit_kernel).  Everything here is inlined into its caller: no kernel calls across files.
+// bit-sliced per-genome counter and its two flushes (paint_kernel, reads_kernel), the window a wave's counts go to
+// (paint_kernel, cover_kernel), the wave-aggregated append (kmer_extract_kernel, sched_kernel, emit_kernel) and, on the host,
+// the launch of a segment walk.  Everything here is inlined into its caller: no kernel calls across files.
 #pragma once
 #include "dd_common.h"
 #include "dd_kernels.h"
@@ -104,21 +105,80 @@ DD_D bool find_record(const LocateSet& set, uint64_t ah, uint64_t al, unsigned l
     return !WIDE || set.hi[first] == ah;
 }
 
-// The bit-sliced per-genome counter of paint_kernel and reads_kernel: kPaintPlanes 64-bit planes per thread, bit i of plane
-// j = bit j of genome i's count.  Genome i's count out of a thread's planes:
-DD_D uint32_t plane_count(const uint64_t (&p)[kPaintPlanes], int i) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < kPaintPlanes; ++j) c |= (uint32_t)((p[j] >> i) & 1ull) << j;
-    return c;
-}
-
 // the sum over the wave of a per-lane count below 2^kPaintPlanes, from one ballot per bit; the same in every lane
 DD_D uint32_t wave_sum(uint32_t v) {
     uint32_t sum = 0;
 #pragma unroll
     for (int j = 0; j < kPaintPlanes; ++j) sum += (uint32_t)__builtin_popcountll(__ballot((v >> j) & 1u)) << j;
     return sum;
+}
+
+// The per-genome counter of a thread of paint_kernel and reads_kernel between two flushes: of the k-mers that are records,
+// those whose mask has genome i's bit -- a bit-sliced VERTICAL counter, kPaintPlanes 64-bit planes, bit i of plane j = bit j
+// of genome i's count.  A run of at most 64 k-mers: seven planes hold it.  A row is n + 2 columns: the k-mers that end
+// (valid), those that are records (inpan), the genomes.  The two plain counts stay the kernel's own variables and come to the
+// flushes as arguments: as members they cost reads_kernel 3 to 5 VGPRs (profiles/sample_entries_refactor.txt).
+struct PlaneCounter {
+    uint64_t p[kPaintPlanes];
+    DD_D void clear() {
+#pragma unroll
+        for (int j = 0; j < kPaintPlanes; ++j) p[j] = 0;
+    }
+    // a k-mer that is a record with this mask: a ripple carry over the planes, no loop over genomes
+    DD_D void add(uint64_t mask) {
+        uint64_t carry = mask;
+#pragma unroll
+        for (int j = 0; j < kPaintPlanes; ++j) {
+            const uint64_t both = p[j] & carry;
+            p[j] ^= carry;
+            carry = both;
+        }
+    }
+    // genome i's count
+    DD_D uint32_t count(int i) const {
+        uint32_t c = 0;
+#pragma unroll
+        for (int j = 0; j < kPaintPlanes; ++j) c |= (uint32_t)((p[j] >> i) & 1ull) << j;
+        return c;
+    }
+    // the thread's non-zero counts added to a row others add to
+    DD_D void flush(uint32_t* row, int n, uint32_t valid, uint32_t inpan) const {
+        if (valid) atomicAdd(row, valid);
+        if (!inpan) return;
+        atomicAdd(row + 1, inpan);
+        for (int i = 0; i < n; ++i) {
+            const uint32_t c = count(i);
+            if (c) atomicAdd(row + 2 + i, c);
+        }
+    }
+    // the whole wave's counts added to ONE row, by every lane of the wave (the lanes behind the stream hold zeros): column
+    // i of plane j over the wave is one __ballot, lane i adds its popcount shifted by the plane's weight, and the wave
+    // issues one no-return atomicAdd per non-zero column.  A plane that is zero in every lane costs one ballot.
+    DD_D void flush_wave(uint32_t* row, int n, int lane, uint32_t valid, uint32_t inpan) const {
+        const uint32_t v = wave_sum(valid), h = wave_sum(inpan);
+        uint32_t mine = 0;
+#pragma unroll
+        for (int j = 0; j < kPaintPlanes; ++j) {
+            const uint64_t pj = p[j];
+            if (!__ballot(pj != 0)) continue;
+            for (int i = 0; i < n; ++i) {
+                const unsigned long long col = __ballot((pj >> i) & 1ull);
+                if (lane == i) mine += (uint32_t)__builtin_popcountll(col) << j;
+            }
+        }
+        if (lane < n && mine) atomicAdd(row + 2 + lane, mine);
+        if (lane == 0 && v) atomicAdd(row, v);
+        if (lane == 1 && h) atomicAdd(row + 1, h);
+    }
+};
+
+// Do the live segments of a wave, 64 consecutive ones from `first` on, lie in ONE window of wsegs segments of a stream of
+// ntok tokens (always so when the window is a multiple of 4096 tokens)?  The same in every lane.  w: that window.
+// (paint_kernel, cover_kernel: where it is so the wave adds its counts to the window's row once, for all its lanes)
+DD_D bool wave_in_one_window(unsigned long long first, unsigned long long ntok, unsigned long long wsegs, unsigned long long& w) {
+    const unsigned long long end = (ntok - 1) / kSegTokens, last = first + 63 < end ? first + 63 : end;
+    w = first / wsegs;
+    return w == last / wsegs;
 }
 
 // Dense append by the lanes of a wave that `take`: one atomicAdd on the counter (uint32_t in LDS, unsigned long long in
@@ -134,6 +194,15 @@ DD_D T wave_append(bool take, T* counter) {
     if ((int)lane == leader) base = atomicAdd(counter, (T)__builtin_popcountll(mask));
     base = __shfl(base, leader);
     return base + (T)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
+}
+
+// host: the launch of a kernel that walks segments -- one thread per 64-token segment of the longest stream, 256 to a
+// workgroup, one launch unit (gridDim.y) per stream.  f(grid, block, canon, wide) launches the caller's kernel, the two
+// std::bool_constants its template arguments.
+template <class F>
+void launch_segment_walk(size_t units, size_t max_segments, int canonical, int k, const F& f) {
+    const dim3 grid((unsigned)((max_segments + 255) / 256), (unsigned)units), block(256);
+    dispatch_bool(canonical != 0, [&](auto cn) { dispatch_bool(k > 32, [&](auto wd) { f(grid, block, cn, wd); }); });
 }
 
 }  // namespace dd

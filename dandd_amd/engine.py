@@ -904,10 +904,26 @@ class Engine:
     def exact_select_kmers_device(self, fasta_ptrs, nbytes, k, all_masks, none_masks, cap=None):
         return self._exact_select_kmers(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), k, all_masks, none_masks, cap)
 
+    # -- the entries that look k-mers up in the ordered records: locate, and the five over samples that are no leaves --------
+    def _exact_lookup(self, what, src, *rest):
+        """dd_exact_{what} in the source's form: (ctx, the source's arguments, *rest, &found), checked; last_{what}_found = found."""
+        found = C.c_uint64()
+        self._check(getattr(self._lib, f"dd_exact_{what}{src[-1]}")(self._ctx, *src[0], *rest, C.byref(found)))
+        setattr(self, f"last_{what}_found", int(found.value))
+
+    @staticmethod
+    def _window_offsets(ntok, which, window):
+        """off uint64 [len(which) + 1]: stream which[j] owns ceil(ntok[which[j]] / window) rows from off[j] on; none where the
+        window is no count or which[j] no stream, so that the library, not numpy, refuses them."""
+        off = np.zeros(len(which) + 1, dtype=np.uint64)
+        for j, t in enumerate(which):
+            off[j + 1] = off[j] + np.uint64(-(-int(ntok[t]) // window) if window > 0 and 0 <= t < len(ntok) else 0)
+        return off
+
     # -- where the selected k-mers lie: the same sort and emission, then every position looked up (dd_exact_locate.hip) ---
     last_locate_found = None   # of the last exact_locate call: the distinct k-mers that match at least one job's query
     def _exact_locate(self, src, k, jobs, ntok):
-        args, n, suffix = src
+        _, n, _ = src
         jobs = [(int(a), int(b), int(g)) for a, b, g in jobs]
         nj = len(jobs)
         al = np.array([a for a, _, _ in jobs] or [0], dtype=np.uint64)
@@ -917,10 +933,7 @@ class Engine:
         for j, (_, _, g) in enumerate(jobs):
             off[j + 1] = off[j] + np.uint64((int(ntok[g]) + 63) // 64 if 0 <= g < len(ntok) else 0)
         hits = np.zeros(max(int(off[nj]), 1), dtype=np.uint64)
-        found = C.c_uint64()
-        self._check(getattr(self._lib, f"dd_exact_locate{suffix}")(self._ctx, *args, n, int(k), al.ctypes.data, no.ctypes.data, ge.ctypes.data, nj,
-                                                                  off.ctypes.data, hits.ctypes.data, C.byref(found)))
-        self.last_locate_found = int(found.value)
+        self._exact_lookup("locate", src, n, int(k), al.ctypes.data, no.ctypes.data, ge.ctypes.data, nj, off.ctypes.data, hits.ctypes.data)
         return [hits[int(off[j]):int(off[j + 1])].copy() for j in range(nj)]
 
     def exact_locate(self, paths, k, jobs, ntok=None):
@@ -940,14 +953,12 @@ class Engine:
     # -- samples that are no leaves, screened against the universe's records (dd_exact_screen.hip) ------------------------
     last_screen_found = None   # of the last exact_screen call: the distinct k-mers of the universe
     def _exact_screen(self, src, k, all_masks, none_masks):
-        args, n, ns, suffix = src
+        _, n, ns, _ = src
         al, no, nq = self._query_masks(all_masks, none_masks)
         shared = np.zeros((max(ns, 0) + 1, max(n, 0)), dtype=np.uint64)
         match = np.zeros((max(ns, 0) + 1, nq), dtype=np.uint64)
-        found = C.c_uint64()
-        self._check(getattr(self._lib, f"dd_exact_screen{suffix}")(self._ctx, *args, int(k), al.ctypes.data if nq else None, no.ctypes.data if nq else None,
-                                                                  nq, shared.ctypes.data, match.ctypes.data if nq else None, C.byref(found)))
-        self.last_screen_found = int(found.value)
+        self._exact_lookup("screen", src, int(k), al.ctypes.data if nq else None, no.ctypes.data if nq else None, nq, shared.ctypes.data,
+                           match.ctypes.data if nq else None)
         return shared, match
 
     def exact_screen(self, paths, samples, k, all_masks, none_masks):
@@ -964,16 +975,11 @@ class Engine:
     # -- samples painted window by window: the same records, then a walk that keeps the position (dd_exact_paint.hip) ------
     last_paint_found = None   # of the last exact_paint call: the distinct k-mers of the universe
     def _exact_paint(self, src, k, window, ntok):
-        args, n, ns, suffix = src
+        _, n, ns, _ = src
         window = int(window)
-        off = np.zeros(max(ns, 0) + 1, dtype=np.uint64)
-        for s in range(ns):
-            off[s + 1] = off[s] + np.uint64(-(-int(ntok[s]) // window) if window > 0 and s < len(ntok) else 0)
-        rows = int(off[max(ns, 0)])
-        counts = np.zeros((max(rows, 1), max(n, 0) + 2), dtype=np.uint32)
-        found = C.c_uint64()
-        self._check(getattr(self._lib, f"dd_exact_paint{suffix}")(self._ctx, *args, int(k), window, off.ctypes.data, counts.ctypes.data, C.byref(found)))
-        self.last_paint_found = int(found.value)
+        off = self._window_offsets(ntok, range(ns), window)
+        counts = np.zeros((max(int(off[-1]), 1), max(n, 0) + 2), dtype=np.uint32)
+        self._exact_lookup("paint", src, int(k), window, off.ctypes.data, counts.ctypes.data)
         return [counts[int(off[s]):int(off[s + 1])].copy() for s in range(ns)]
 
     def exact_paint(self, paths, samples, k, window, ntok=None):
@@ -995,7 +1001,7 @@ class Engine:
     # -- samples called row by row: paint's walk with the caller's borders, a vote per row, a tally per sample (dd_exact_reads.hip)
     last_reads_found = None   # of the last exact_reads call: the distinct k-mers of the universe
     def _exact_reads(self, src, k, min_hits, rows, calls, counts):
-        args, n, ns, suffix = src
+        _, n, ns, _ = src
         if len(rows) != ns:
             raise ValueError(f"{len(rows)} border arrays for {ns} samples")
         starts = [np.ascontiguousarray(r, dtype=np.uint64).reshape(-1) for r in rows]
@@ -1007,11 +1013,9 @@ class Engine:
         set_arr = np.zeros((max(total, 1), 2), dtype=np.uint64) if calls else None
         count_arr = np.zeros((max(total, 1), max(n, 0) + 2), dtype=np.uint32) if counts else None
         tally = np.zeros((max(ns, 1), max(n, 0) + 3), dtype=np.uint64)
-        found = C.c_uint64()
         ptr = lambda a: None if a is None else a.ctypes.data
-        self._check(getattr(self._lib, f"dd_exact_reads{suffix}")(self._ctx, *args, int(k), off.ctypes.data, start.ctypes.data, int(min_hits),
-                                                                 ptr(call_arr), ptr(set_arr), ptr(count_arr), tally.ctypes.data, C.byref(found)))
-        self.last_reads_found = int(found.value)
+        self._exact_lookup("reads", src, int(k), off.ctypes.data, start.ctypes.data, int(min_hits), ptr(call_arr), ptr(set_arr), ptr(count_arr),
+                           tally.ctypes.data)
         cut = lambda a, s: None if a is None else a[int(off[s]):int(off[s + 1])].copy()
         return [(cut(call_arr, s), cut(set_arr, s), cut(count_arr, s)) for s in range(ns)], tally[:max(ns, 0)]
 
@@ -1038,15 +1042,13 @@ class Engine:
     # -- samples counted record by record: screen's walk with a counter per record, binned by depth (dd_exact_depth.hip) -------
     last_depth_found = None   # of the last exact_depth call: the distinct k-mers of the universe
     def _exact_depth(self, src, k, all_masks, none_masks, bins):
-        args, n, ns, suffix = src
+        _, n, ns, _ = src
         al, no, nq = self._query_masks(all_masks, none_masks)
         rows, bins = max(n, 0) + nq, int(bins)
         hist = np.zeros((max(ns, 1), max(rows, 1), min(max(bins, 1), 1 << 16)), dtype=np.uint64)
         total = np.zeros((max(ns, 1), max(rows, 1)), dtype=np.uint64)
-        found = C.c_uint64()
-        self._check(getattr(self._lib, f"dd_exact_depth{suffix}")(self._ctx, *args, int(k), al.ctypes.data if nq else None, no.ctypes.data if nq else None,
-                                                                 nq, bins, hist.ctypes.data, total.ctypes.data, C.byref(found)))
-        self.last_depth_found = int(found.value)
+        self._exact_lookup("depth", src, int(k), al.ctypes.data if nq else None, no.ctypes.data if nq else None, nq, bins, hist.ctypes.data,
+                           total.ctypes.data)
         return hist, total
 
     def exact_depth(self, paths, samples, k, alls=(), nones=(), bins=64):
@@ -1065,20 +1067,14 @@ class Engine:
     # -- samples laid along the genomes of the universe: depth's counters gathered per window of a target (dd_exact_cover.hip) --
     last_cover_found = None   # of the last exact_cover call: the distinct k-mers of the universe
     def _exact_cover(self, src, k, window, targets, clip, ntok):
-        args, n, ns, suffix = src
+        _, n, ns, _ = src
         window = int(window)
         targets = list(range(max(n, 0))) if targets is None else [int(t) for t in targets]
         nt = len(targets)
         tg = np.array(targets or [0], dtype=np.int32)
-        off = np.zeros(nt + 1, dtype=np.uint64)
-        for j, t in enumerate(targets):
-            off[j + 1] = off[j] + np.uint64(-(-int(ntok[t]) // window) if window > 0 and 0 <= t < len(ntok) else 0)
-        rows = int(off[nt])
-        counts = np.zeros((max(ns, 1), max(rows, 1), 6), dtype=np.uint32)
-        found = C.c_uint64()
-        self._check(getattr(self._lib, f"dd_exact_cover{suffix}")(self._ctx, *args, int(k), tg.ctypes.data, nt, window, int(clip), off.ctypes.data,
-                                                                 counts.ctypes.data, C.byref(found)))
-        self.last_cover_found = int(found.value)
+        off = self._window_offsets(ntok, targets, window)
+        counts = np.zeros((max(ns, 1), max(int(off[nt]), 1), 6), dtype=np.uint32)
+        self._exact_lookup("cover", src, int(k), tg.ctypes.data, nt, window, int(clip), off.ctypes.data, counts.ctypes.data)
         return [counts[:max(ns, 0), int(off[j]):int(off[j + 1])].copy() for j in range(nt)]
 
     def exact_cover(self, paths, samples, k, window, targets=None, clip=255, ntok=None):

@@ -345,34 +345,43 @@ class HipExactBackend:
         """where the k-mers select_kmers writes lie, at one k of the window: jobs = (all_mask, none_mask, leaf index) ->
         ([(names, seq_len, tok_start, ntok)] per leaf, [uint64 bitmap over the leaf's tokens] per job); bit t of a
         bitmap: a k-mer of the job's query ends at token t of that leaf's file (engine.regions_from_hits makes intervals)."""
-        from ..engine import fasta_index
         if (win := self._leaf_window(leaf_paths, k=k)) is None:
             return None
         files = win[1]
-        index = [fasta_index(f) for f in files]
+        index = self._record_index(files)
         return index, self.engine.exact_locate(files, int(k), jobs, ntok=[ix[3] for ix in index])
+
+    # ---- files that are no leaves, looked up in the leaves' k-mers at one k of the window
+    def _leaves_and_samples(self, leaf_paths, k, sample_files):
+        """-> (the leaves' files, the samples' paths as str), or None where _leaf_window has none"""
+        if (win := self._leaf_window(leaf_paths, k=k)) is None:
+            return None
+        return win[1], [str(f) for f in sample_files]
+
+    @staticmethod
+    def _record_index(files):
+        """[(names, seq_len, tok_start, ntok)] per file"""
+        from ..engine import fasta_index
+        return [fasta_index(str(f)) for f in files]
 
     def screen_counts(self, leaf_paths, k, sample_files, all_masks, none_masks):
         """files that are no leaves screened against the leaves' k-mers at one k of the window (dd_exact_screen): ->
         (shared uint64 [ns+1][n], match uint64 [ns+1][nq]); shared[s][i]: the distinct k-mers of sample s that leaf i also
         holds, match[s][q]: those whose membership mask contains all_masks[q] and meets none_masks[q] nowhere; row ns: the
         leaves themselves (|leaf i|; what select_counts counts)."""
-        if (win := self._leaf_window(leaf_paths, k=k)) is None:
+        if (got := self._leaves_and_samples(leaf_paths, k, sample_files)) is None:
             return None
-        files = win[1]
-        return self.engine.exact_screen(files, [str(f) for f in sample_files], int(k), all_masks, none_masks)
+        return self.engine.exact_screen(*got, int(k), all_masks, none_masks)
 
     def paint_counts(self, leaf_paths, k, sample_files, window):
         """files that are no leaves painted window by window with the leaves' k-mers at one k of the window (dd_exact_paint):
         -> ([(names, seq_len, tok_start, ntok)] per sample, [uint32 [nwin][n+2]] per sample); a row per `window` tokens of
         the sample's token stream: the positions where a valid k-mer ends, where the leaves hold it at all, and where leaf i
         holds it (engine.paint_windows places the windows in the records)."""
-        from ..engine import fasta_index
-        if (win := self._leaf_window(leaf_paths, k=k)) is None:
+        if (got := self._leaves_and_samples(leaf_paths, k, sample_files)) is None:
             return None
-        files = win[1]
-        index = [fasta_index(str(f)) for f in sample_files]
-        return index, self.engine.exact_paint(files, [str(f) for f in sample_files], int(k), int(window), ntok=[ix[3] for ix in index])
+        index = self._record_index(got[1])
+        return index, self.engine.exact_paint(*got, int(k), int(window), ntok=[ix[3] for ix in index])
 
     def read_calls(self, leaf_paths, k, sample_files, min_hits, want_calls):
         """files that are no leaves called record by record with the leaves' k-mers at one k of the window (dd_exact_reads):
@@ -381,13 +390,10 @@ class HipExactBackend:
         sets of the tied and of the consistent leaves; tally[s]: the records uniquely called to leaf i, the ambiguous, the
         unclassified (fewer than min_hits positions of the best leaf), those without a valid k-mer.  want_calls False: the
         tally alone comes back from the device."""
-        from ..engine import fasta_index
-        if (win := self._leaf_window(leaf_paths, k=k)) is None:
+        if (got := self._leaves_and_samples(leaf_paths, k, sample_files)) is None:
             return None
-        files = win[1]
-        index = [fasta_index(str(f)) for f in sample_files]
-        per, tally = self.engine.exact_reads(files, [str(f) for f in sample_files], int(k), min_hits=int(min_hits), index=index,
-                                             calls=bool(want_calls))
+        index = self._record_index(got[1])
+        per, tally = self.engine.exact_reads(*got, int(k), min_hits=int(min_hits), index=index, calls=bool(want_calls))
         return index, [(c, s) if want_calls else None for c, s, _ in per], tally
 
     def depth_hists(self, leaf_paths, k, sample_files, all_masks, none_masks, bins):
@@ -396,10 +402,9 @@ class HipExactBackend:
         whose membership mask contains all_masks[q] and meets none_masks[q] nowhere; hist[s][row][d]: the k-mers of the row
         that stand d times in sample s (positions; d = 0: the sample lacks them), the last bin every depth >= bins - 1;
         total: the sum of the depths, unclipped (engine.depth_stats reads both)."""
-        if (win := self._leaf_window(leaf_paths, k=k)) is None:
+        if (got := self._leaves_and_samples(leaf_paths, k, sample_files)) is None:
             return None
-        files = win[1]
-        return self.engine.exact_depth(files, [str(f) for f in sample_files], int(k), all_masks, none_masks, bins=int(bins))
+        return self.engine.exact_depth(*got, int(k), all_masks, none_masks, bins=int(bins))
 
     def cover_counts(self, leaf_paths, k, sample_files, window, targets, clip):
         """files that are no leaves laid along the leaves `targets` (indices, each once) at one k of the window
@@ -407,14 +412,12 @@ class HipExactBackend:
         sample and per `window` tokens of the TARGET's token stream: the positions where a valid k-mer ends, those the sample
         holds, their depths clipped at `clip` and summed, and the same three over the positions whose k-mer no other leaf
         holds (engine.paint_windows places the windows in the target's records, engine.cover_states reads the rows)."""
-        from ..engine import fasta_index
-        if (win := self._leaf_window(leaf_paths, k=k)) is None:
+        if (got := self._leaves_and_samples(leaf_paths, k, sample_files)) is None:
             return None
-        files = win[1]
         targets = [int(t) for t in targets]
-        index = {t: fasta_index(str(files[t])) for t in targets}
-        ntok = [index[i][3] if i in index else 0 for i in range(len(files))]
-        counts = self.engine.exact_cover(files, [str(f) for f in sample_files], int(k), int(window), targets=targets, clip=int(clip), ntok=ntok)
+        index = dict(zip(targets, self._record_index([got[0][t] for t in targets])))
+        ntok = [index[i][3] if i in index else 0 for i in range(len(got[0]))]
+        counts = self.engine.exact_cover(*got, int(k), int(window), targets=targets, clip=int(clip), ntok=ntok)
         return [index[t] for t in targets], counts
 
     def pattern_counts(self, leaf_paths, k, limit):

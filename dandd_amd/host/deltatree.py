@@ -1237,31 +1237,52 @@ class DeltaTree:
         -> dict: ks, shared [K][ns+1][n], match [K][ns+1][nq] (row ns: the universe itself), sample_kmers [K][ns]"""
         import tempfile
         n, ns, nq = len(fastas), len(samples), 2 + len(self.KMER_CLASSES) * len(groups or [])
+        ks = self._ks(ks)
+        out = {"ks": ks, "shared": np.zeros((len(ks), ns + 1, n), dtype=np.uint64), "match": np.zeros((len(ks), ns + 1, nq), dtype=np.uint64),
+               "sample_kmers": np.zeros((len(ks), ns), dtype=np.uint64)}
+        be = {}      # the backend of every k's universe
+        for kk, k, u, batch, files in self._sample_calls(fastas, samples, ks, "screen_counts", "containment needs"):
+            be[k] = u.be
+            alls, nones = group_queries(u.masks(groups or []), u.full)
+            got = u.table(u.be.screen_counts(u.paths, k, files, [0, u.full] + alls, [0, 0] + nones))
+            shared, match = u.table(got[0], (len(batch) + 1, n)), u.table(got[1], (len(batch) + 1, nq))
+            out["shared"][kk, batch] = shared[:-1]
+            out["match"][kk, batch] = match[:-1]
+            out["shared"][kk, ns], out["match"][kk, ns] = shared[-1], match[-1]      # (the same in every batch)
+        with tempfile.TemporaryDirectory(prefix="dandd_screen_") as tmp:
+            for kk, k in enumerate(ks):
+                for j, f in enumerate(samples):
+                    db = os.path.join(tmp, f"s{j}.k{k}")
+                    be[k].leaf(f, [k], [db])
+                    out["sample_kmers"][kk, j] = int(be[k].card(db))
+        return out
+
+    @staticmethod
+    def _ks(ks):
+        """`ks` as a list of ints, each a k of the engine"""
         ks = [int(k) for k in ks]
         for k in ks:
             if not 1 <= k <= 64:
                 raise ValueError(f"k={k} is outside 1..64")
+        return ks
+
+    @staticmethod
+    def _window(window):
+        """a window of tokens (paint: of a sample's stream; cover: of a target's): whole 64-token segments"""
+        window = int(window)
+        if window < 64 or window % 64 or window > 1 << 22:
+            raise ValueError(f"a window of {window} tokens: a multiple of 64 in 64..{1 << 22} is needed")
+        return window
+
+    def _sample_calls(self, fastas, samples, ks, entry, why):
+        """The backend calls of a table over samples that are no leaves, one per k of `ks` (checked: _ks) and batch of
+        `samples` (_sample_batches): (kk, k, the universe at that k -- whose backend has `entry` --, the batch's indices, its files)"""
         batches = self._sample_batches(samples)
-        out = {"ks": ks, "shared": np.zeros((len(ks), ns + 1, n), dtype=np.uint64), "match": np.zeros((len(ks), ns + 1, nq), dtype=np.uint64),
-               "sample_kmers": np.zeros((len(ks), ns), dtype=np.uint64)}
         for kk, k in enumerate(ks):
             u = self._universe(fastas, k, k)
-            u.need("screen_counts", why="containment needs")
-            be, paths = u.be, u.paths
-            alls, nones = group_queries(u.masks(groups or []), u.full)
-            alls, nones = [0, u.full] + alls, [0, 0] + nones
+            u.need(entry, why=why)
             for batch in batches:
-                got = u.table(be.screen_counts(paths, k, [samples[j] for j in batch], alls, nones))
-                shared, match = u.table(got[0], (len(batch) + 1, n)), u.table(got[1], (len(batch) + 1, nq))
-                out["shared"][kk, batch] = shared[:-1]
-                out["match"][kk, batch] = match[:-1]
-                out["shared"][kk, ns], out["match"][kk, ns] = shared[-1], match[-1]      # (the same in every batch)
-            with tempfile.TemporaryDirectory(prefix="dandd_screen_") as tmp:
-                for j, f in enumerate(samples):
-                    db = os.path.join(tmp, f"s{j}.k{k}")
-                    be.leaf(f, [k], [db])
-                    out["sample_kmers"][kk, j] = int(be.card(db))
-        return out
+                yield kk, k, u, batch, [samples[j] for j in batch]
 
     def _sample_batches(self, samples):
         """indices of `samples` in batches of at most SCREEN_BATCH_FILES files or SCREEN_BATCH_BYTES bytes, whichever comes first"""
@@ -1283,24 +1304,14 @@ class DeltaTree:
         distinct k-mers.  The samples go to the backend's paint_counts in screen_tables' batches.  There is no object path:
         a backend without paint_counts, or without a table for these leaves, is a ValueError.
         -> dict: ks, window, index [ns] of (names, seq_len, tok_start, ntok), counts [K][ns] of uint32 [nwin_s][n+2]"""
-        n, ns, window = len(fastas), len(samples), int(window)
-        ks = [int(k) for k in ks]
-        for k in ks:
-            if not 1 <= k <= 64:
-                raise ValueError(f"k={k} is outside 1..64")
-        if window < 64 or window % 64 or window > 1 << 22:
-            raise ValueError(f"a window of {window} tokens: a multiple of 64 in 64..{1 << 22} is needed")
-        batches = self._sample_batches(samples)
+        n, ns, ks, window = len(fastas), len(samples), self._ks(ks), self._window(window)
         out = {"ks": ks, "window": window, "index": [None] * ns, "counts": [[None] * ns for _ in ks]}
-        for kk, k in enumerate(ks):
-            u = self._universe(fastas, k, k)
-            u.need("paint_counts", why="painting needs")
-            for batch in batches:
-                index, counts = u.table(u.be.paint_counts(u.paths, k, [samples[j] for j in batch], window))
-                for j, ix, rows in zip(batch, index, counts):
-                    nwin = -(-int(ix[3]) // window)
-                    out["index"][j] = ix
-                    out["counts"][kk][j] = u.table(rows, (nwin, n + 2)).astype(np.uint32)
+        for kk, k, u, batch, files in self._sample_calls(fastas, samples, ks, "paint_counts", "painting needs"):
+            index, counts = u.table(u.be.paint_counts(u.paths, k, files, window))
+            for j, ix, rows in zip(batch, index, counts):
+                nwin = -(-int(ix[3]) // window)
+                out["index"][j] = ix
+                out["counts"][kk][j] = u.table(rows, (nwin, n + 2)).astype(np.uint32)
         return out
 
     def reads_tables(self, fastas, samples, ks, min_hits=1, want_calls=False):
@@ -1313,27 +1324,19 @@ class DeltaTree:
         -> dict: ks, min_hits, index [ns] of (names, seq_len, tok_start, ntok), tally [K] of uint64 [ns][n+3] (unique to
         genome i | ambiguous | unclassified | no valid k-mer), calls [K][ns] of (calls uint32 [r][6], sets uint64 [r][2]),
         None without want_calls"""
-        n, ns, min_hits = len(fastas), len(samples), int(min_hits)
-        ks = [int(k) for k in ks]
-        for k in ks:
-            if not 1 <= k <= 64:
-                raise ValueError(f"k={k} is outside 1..64")
+        n, ns, ks, min_hits = len(fastas), len(samples), self._ks(ks), int(min_hits)
         if min_hits < 1:
             raise ValueError(f"min_hits={min_hits}: a call needs at least one position")
-        batches = self._sample_batches(samples)
         out = {"ks": ks, "min_hits": min_hits, "index": [None] * ns, "tally": [np.zeros((ns, n + 3), dtype=np.uint64) for _ in ks],
                "calls": [[None] * ns for _ in ks]}
-        for kk, k in enumerate(ks):
-            u = self._universe(fastas, k, k)
-            u.need("read_calls", why="calling records needs")
-            for batch in batches:
-                index, per, tally = u.table(u.be.read_calls(u.paths, k, [samples[j] for j in batch], min_hits, bool(want_calls)))
-                out["tally"][kk][batch] = u.table(tally, (len(batch), n + 3))
-                for j, ix, got in zip(batch, index, per):
-                    out["index"][j] = ix
-                    if want_calls:
-                        r = len(ix[2])
-                        out["calls"][kk][j] = (u.table(got[0], (r, 6)).astype(np.uint32), u.table(got[1], (r, 2)).astype(np.uint64))
+        for kk, k, u, batch, files in self._sample_calls(fastas, samples, ks, "read_calls", "calling records needs"):
+            index, per, tally = u.table(u.be.read_calls(u.paths, k, files, min_hits, bool(want_calls)))
+            out["tally"][kk][batch] = u.table(tally, (len(batch), n + 3))
+            for j, ix, got in zip(batch, index, per):
+                out["index"][j] = ix
+                if want_calls:
+                    r = len(ix[2])
+                    out["calls"][kk][j] = (u.table(got[0], (r, 6)).astype(np.uint32), u.table(got[1], (r, 2)).astype(np.uint64))
         return out
 
     def depth_tables(self, fastas, samples, ks, groups=None, bins=64):
@@ -1347,27 +1350,19 @@ class DeltaTree:
         depth_hists, or without a table for these leaves, is a ValueError.
         -> dict: ks, bins, hist [K][ns][n+nq][bins], total [K][ns][n+nq] (engine.depth_stats turns them into breadth, mean
         and median); nq = 2 + n + 3 * len(groups)"""
-        n, ns, bins = len(fastas), len(samples), int(bins)
+        n, ns, ks, bins = len(fastas), len(samples), self._ks(ks), int(bins)
         nq = 2 + n + len(self.KMER_CLASSES) * len(groups or [])
-        ks = [int(k) for k in ks]
-        for k in ks:
-            if not 1 <= k <= 64:
-                raise ValueError(f"k={k} is outside 1..64")
         if not 2 <= bins <= 256:
             raise ValueError(f"bins={bins} is outside 2..256")
-        batches = self._sample_batches(samples)
         out = {"ks": ks, "bins": bins, "hist": np.zeros((len(ks), ns, n + nq, bins), dtype=np.uint64),
                "total": np.zeros((len(ks), ns, n + nq), dtype=np.uint64)}
-        for kk, k in enumerate(ks):
-            u = self._universe(fastas, k, k)
-            u.need("depth_hists", why="depth needs")
+        for kk, k, u, batch, files in self._sample_calls(fastas, samples, ks, "depth_hists", "depth needs"):
             alls, nones = group_queries(u.masks(groups or []), u.full)
             alls = [0, u.full] + [1 << i for i in range(n)] + alls
             nones = [0, 0] + [u.full ^ (1 << i) for i in range(n)] + nones
-            for batch in batches:
-                got = u.table(u.be.depth_hists(u.paths, k, [samples[j] for j in batch], alls, nones, bins))
-                out["hist"][kk, batch] = u.table(got[0], (len(batch), n + nq, bins))
-                out["total"][kk, batch] = u.table(got[1], (len(batch), n + nq))
+            got = u.table(u.be.depth_hists(u.paths, k, files, alls, nones, bins))
+            out["hist"][kk, batch] = u.table(got[0], (len(batch), n + nq, bins))
+            out["total"][kk, batch] = u.table(got[1], (len(batch), n + nq))
         return out
 
     def cover_tables(self, fastas, samples, ks, window, targets=None, clip=255):
@@ -1381,13 +1376,7 @@ class DeltaTree:
         object path: a backend without cover_counts, or without a table for these leaves, is a ValueError.
         -> dict: ks, window, clip, targets (FASTAs), index [nt] of (names, seq_len, tok_start, ntok), counts [K][nt] of uint32
         [ns][nwin_t][6]"""
-        n, ns, window, clip = len(fastas), len(samples), int(window), int(clip)
-        ks = [int(k) for k in ks]
-        for k in ks:
-            if not 1 <= k <= 64:
-                raise ValueError(f"k={k} is outside 1..64")
-        if window < 64 or window % 64 or window > 1 << 22:
-            raise ValueError(f"a window of {window} tokens: a multiple of 64 in 64..{1 << 22} is needed")
+        n, ns, ks, window, clip = len(fastas), len(samples), self._ks(ks), self._window(window), int(clip)
         if not 1 <= clip <= 1023:
             raise ValueError(f"clip={clip} is outside 1..1023")
         targets = list(fastas) if targets is None else list(targets)
@@ -1397,19 +1386,15 @@ class DeltaTree:
         if not targets or len(set(targets)) != len(targets):
             raise ValueError("the targets are genomes of the universe, each once, at least one")
         at = [fastas.index(f) for f in targets]
-        batches = self._sample_batches(samples)
         out = {"ks": ks, "window": window, "clip": clip, "targets": targets, "index": [None] * len(at), "counts": [[None] * len(at) for _ in ks]}
-        for kk, k in enumerate(ks):
-            u = self._universe(fastas, k, k)
-            u.need("cover_counts", why="coverage needs")
-            for batch in batches:
-                index, counts = u.table(u.be.cover_counts(u.paths, k, [samples[j] for j in batch], window, at, clip))
-                for t, (ix, rows) in enumerate(zip(index, counts)):
-                    nwin = -(-int(ix[3]) // window)
-                    out["index"][t] = ix
-                    if out["counts"][kk][t] is None:
-                        out["counts"][kk][t] = np.zeros((ns, nwin, 6), dtype=np.uint32)
-                    out["counts"][kk][t][batch] = u.table(rows, (len(batch), nwin, 6))
+        for kk, k, u, batch, files in self._sample_calls(fastas, samples, ks, "cover_counts", "coverage needs"):
+            index, counts = u.table(u.be.cover_counts(u.paths, k, files, window, at, clip))
+            for t, (ix, rows) in enumerate(zip(index, counts)):
+                nwin = -(-int(ix[3]) // window)
+                out["index"][t] = ix
+                if out["counts"][kk][t] is None:
+                    out["counts"][kk][t] = np.zeros((ns, nwin, 6), dtype=np.uint32)
+                out["counts"][kk][t][batch] = u.table(rows, (len(batch), nwin, 6))
         return out
 
     # ---- which sets of genomes share k-mers (`dandd patterns`) --------------------------------------------------------------
@@ -1420,10 +1405,7 @@ class DeltaTree:
         path: a backend without pattern_counts, or without a table for these leaves, is a ValueError.
         -> dict: ks, and per k of it dict(masks [int], counts [int], found: the number of distinct masks, distinct: the distinct
         k-mers of the universe)"""
-        ks = [int(k) for k in ks]
-        for k in ks:
-            if not 1 <= k <= 64:
-                raise ValueError(f"k={k} is outside 1..64")
+        ks = self._ks(ks)
         out = {"ks": ks}
         for k in ks:
             u = self._universe(fastas, k, k)
