@@ -19,6 +19,7 @@
 // that starts with '+' (dd_io.h: has_plus_line over the WHOLE text, as the host path does); if there is one, kNotFourLine.
 #include "dd_common.h"
 #include "dd_kernels.h"
+#include "dd_scan.h"
 
 namespace dd {
 namespace {
@@ -85,27 +86,16 @@ __global__ __launch_bounds__(1024) void text_offsets_kernel(const TextJob* __res
     const TextJob& t = jobs[blockIdx.x];
     if (!t.fastq) return;
     __shared__ uint32_t wsum[16];
-    __shared__ uint32_t carry_s;
-    const uint32_t nblocks = (t.n + kTextBlock - 1u) / kTextBlock, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
+    const uint32_t nblocks = (t.n + kTextBlock - 1u) / kTextBlock;
+    uint32_t carry = 0;  // newlines in front of this round of 1024 blocks
     for (uint32_t b0 = 0; b0 < nblocks; b0 += 1024u) {
         const uint32_t i = b0 + threadIdx.x, mine = i < nblocks ? t.blk_count[i] : 0u;
-        uint32_t incl = mine;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-            if ((int)lane >= d) incl += up;
-        }
-        if (lane == 63u) wsum[wave] = incl;
-        __syncthreads();
-        uint32_t before = carry_s;
-        for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
-        if (i < nblocks) t.blk_count[i] = before + incl - mine;
-        __syncthreads();
-        if (threadIdx.x == 1023u) carry_s = before + incl;
-        __syncthreads();
+        uint32_t round;
+        const uint32_t incl = block_incl_sum<16>(mine, wsum, round);
+        if (i < nblocks) t.blk_count[i] = carry + incl - mine;
+        carry += round;
     }
-    if (threadIdx.x == 0) *t.nl_total = carry_s;
+    if (threadIdx.x == 0) *t.nl_total = carry;
 }
 
 // the positions of a FASTQ text's newlines, in order: nl[offset of the block + rank inside it]
@@ -116,16 +106,9 @@ __global__ __launch_bounds__(256) void text_newlines_kernel(const TextJob* __res
     const uint32_t off = local * kTextBlock + threadIdx.x * 16u;
     const uint32_t nl = off < t.n ? exact_newline_mask(load_text16(t, off)) : 0u;
     __shared__ uint32_t wsum[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, mine = (uint32_t)__popc(nl);
-    uint32_t incl = mine;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-        if ((int)lane >= d) incl += up;
-    }
-    if (lane == 63u) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t at = t.blk_count[local] + incl - mine;
-    for (uint32_t w = 0; w < wave; ++w) at += wsum[w];
+    const uint32_t mine = (uint32_t)__popc(nl);
+    uint32_t in_block;
+    uint32_t at = t.blk_count[local] + block_incl_sum<4>(mine, wsum, in_block) - mine;
     for (uint32_t m = nl; m; m &= m - 1u, ++at) {
         if (at < t.nl_cap) t.nl[at] = off + (uint32_t)__builtin_ctz(m);
         else if (at == t.nl_cap) atomicOr(errors, kNotFourLine);   // (more lines than a FASTQ text of this size has: lines of < 8 bytes on average)

@@ -13,6 +13,7 @@
 #include "dd_common.h"
 #include "dd_deflate.h"
 #include "dd_kernels.h"
+#include "dd_scan.h"
 
 namespace dd {
 
@@ -267,11 +268,7 @@ __global__ __launch_bounds__(64) void piece_offsets_kernel(const RawFile* __rest
     uint64_t run = 0, arun = 0;
     for (uint32_t b0 = 0; b0 < rf.nguess; b0 += 64u) {
         const uint32_t i = b0 + lane, mine = i < rf.nguess ? lens[rf.piece0 + i] : 0u, amine = (i < rf.nguess && over[rf.piece0 + i]) ? mine : 0u;
-        uint64_t incl = mine, aincl = amine;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t up = (uint64_t)__shfl_up((long long)incl, d), aup = (uint64_t)__shfl_up((long long)aincl, d);
-            if ((int)lane >= d) incl += up, aincl += aup;
-        }
+        const uint64_t incl = wave_incl_sum<uint64_t>(mine), aincl = wave_incl_sum<uint64_t>(amine);
         // (offsets beyond ISIZE are clamped: nothing reads them once the error below is up, and nothing may index with a wrapped one)
         const uint64_t o = run + incl - mine, a = arun + aincl - amine;
         if (i < rf.nguess) offs[rf.piece0 + i] = (uint32_t)(o < rf.isize ? o : rf.isize), abase[rf.piece0 + i] = (uint32_t)(a < rf.isize ? a : rf.isize);

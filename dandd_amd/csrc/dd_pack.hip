@@ -15,8 +15,9 @@
 // acts on that bit as IDENTITY (no newline and no line start in it), or as a CONSTANT (it contains a
 // newline, or starts at a line start: its end state is then decided locally).  Spans compose like
 // that at every level: 64-byte thread spans inside a wave (two ballots and a find-first-set),
-// waves inside a 16 KiB chunk (LDS), chunks inside a genome (pack_scan).  Three launches, batched
-// over all genomes of a call (gridDim.y = genome):
+// waves inside a 16 KiB chunk (LDS: header_bits), chunks inside a genome (pack_scan, which keeps its own copy of the
+// pass beside its sum).  Four launches, batched over all genomes of a call (gridDim.y = genome):
+//   pack_first : per genome -> where its first '>' or '@' stands
 //   pack_stats : per chunk -> its IDENTITY/CONSTANT summary and its token count under both
 //                possible incoming states
 //   pack_scan  : one workgroup per genome: incoming state and exclusive token offset of every chunk
@@ -27,6 +28,7 @@
 // HBM-bound by design (1 B read twice + 0.375 B written per base); see DESIGN.md for the measured rate.
 #include "dd_common.h"
 #include "dd_kernels.h"
+#include "dd_scan.h"
 
 namespace dd {
 namespace {
@@ -174,6 +176,8 @@ struct ThreadSpan {
     bool plain;       // bits.plain and the whole span lies inside the file
     int kind;         // action on the header bit
     int t0, t1;       // tokens if entered outside / inside a header line
+    // the byte behind 16-byte piece j
+    DD_D uint32_t byte_after(int j) const { return j + 1 < SUB ? b[j + 1 < SUB ? j + 1 : j].at(0) : after; }
 };
 
 DD_D ThreadSpan load_span(const uint8_t* fa, size_t n, size_t pos, size_t first) {
@@ -208,7 +212,7 @@ DD_D ThreadSpan load_span(const uint8_t* fa, size_t n, size_t pos, size_t first)
         LineState s{false, t.line_start, false, 0, 0};
         uint32_t d0, d1;
 #pragma unroll
-        for (int j = 0; j < SUB; ++j) (void)scan16<false>(t.b[j], j + 1 < SUB ? t.b[j + 1 < SUB ? j + 1 : j].at(0) : t.after, s, d0, d1);
+        for (int j = 0; j < SUB; ++j) (void)scan16<false>(t.b[j], t.byte_after(j), s, d0, d1);
         t.kind = (s.seen_nl || t.line_start) ? (s.hdr ? KIND_C1 : KIND_C0) : KIND_ID;
         t.t0 = s.pre + s.rest;
         t.t1 = t.line_start ? t.t0 : s.rest + (s.seen_nl ? 1 : 0);
@@ -216,14 +220,16 @@ DD_D ThreadSpan load_span(const uint8_t* fa, size_t n, size_t pos, size_t first)
     return t;
 }
 
-// Header bit entering each thread of the workgroup, given the bit entering the chunk, and the
-// chunk's own summary.  determined = false for threads whose incoming bit is the chunk's.
+// The header-bit pass over a workgroup of NWAVES waves, one span per thread: the nearest CONSTANT span in front of a thread
+// decides the bit it is entered with; where there is none, `block_in`, the bit entering the block, does (determined = false).
+// Also the block's own summary.  Called by every thread; it ends with a barrier, so sm[NWAVES] is free again on return.
 struct Incoming {
     bool hdr;
     bool determined;
-    int chunk_kind;
+    int block_kind;
 };
-DD_D Incoming propagate(int kind, bool chunk_in, int* sm /*[NW]*/) {
+template <int NWAVES>
+DD_D Incoming header_bits(int kind, bool block_in, int* sm /*[NWAVES]*/) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const unsigned long long cm = __ballot(kind != KIND_ID), vm = __ballot(kind == KIND_C1);
     const unsigned long long below = cm & ((1ull << lane) - 1ull);
@@ -233,12 +239,12 @@ DD_D Incoming propagate(int kind, bool chunk_in, int* sm /*[NW]*/) {
     if (from_wave) val = (vm >> (63 - __builtin_clzll(below))) & 1ull;
     if (lane == 0) sm[wv] = cm ? (((vm >> (63 - __builtin_clzll(cm))) & 1ull) ? KIND_C1 : KIND_C0) : KIND_ID;
     __syncthreads();
-    bool wave_in = chunk_in, wave_det = false;
-    int ck = KIND_ID;
-    for (int w = 0; w < NW; ++w) {
+    bool wave_in = block_in, wave_det = false;
+    int bk = KIND_ID;
+    for (int w = 0; w < NWAVES; ++w) {
         const int k = sm[w];
         if (k != KIND_ID) {
-            ck = k;
+            bk = k;
             if (w < wv) {
                 wave_in = (k == KIND_C1);
                 wave_det = true;
@@ -247,33 +253,12 @@ DD_D Incoming propagate(int kind, bool chunk_in, int* sm /*[NW]*/) {
     }
     r.hdr = from_wave ? val : wave_in;
     r.determined = from_wave || wave_det;
-    r.chunk_kind = ck;
+    r.block_kind = bk;
     __syncthreads();
     return r;
 }
 
-// inclusive sum over the workgroup (32-bit); *total = workgroup sum
-DD_D int block_incl_sum(int v, int* sm /*[NW]*/, int* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) sm[wv] = inc;
-    __syncthreads();
-    int pre = 0, tot = 0;
-    for (int w = 0; w < NW; ++w) {
-        if (w < wv) pre += sm[w];
-        tot += sm[w];
-    }
-    *total = tot;
-    __syncthreads();
-    return pre + inc;
-}
-
-// scratch layout of one genome: four arrays of (nchunks + 1) int64
+// scratch layout of one genome: five arrays, four of (nchunks + 1) int64 and then `first` of one
 struct Scratch {
     long long *kind_in, *cnt0, *cnt1, *slot, *first;
     DD_D explicit Scratch(const PackGenome& g)
@@ -316,7 +301,7 @@ __global__ __launch_bounds__(T) void pack_stats(const PackGenome* __restrict__ t
     if (c >= G.nchunks) return;
     const size_t pos = c * (size_t)kPackChunk + (size_t)threadIdx.x * kPackBytesPerThread;
     const ThreadSpan t = load_span(G.fa, G.n, pos, (size_t)gload8u(Scratch(G).first));
-    const Incoming in = propagate(t.kind, false, sm);
+    const Incoming in = header_bits<NW>(t.kind, false, sm);
     int t0, t1;  // tokens if the CHUNK is entered outside / inside a header
     if (in.determined || t.line_start) {
         t0 = t1 = in.hdr ? t.t1 : t.t0;
@@ -325,17 +310,30 @@ __global__ __launch_bounds__(T) void pack_stats(const PackGenome* __restrict__ t
         t1 = t.t1;
     }
     int s0, s1;
-    block_incl_sum(t0, sm, &s0);
-    block_incl_sum(t1, sm, &s1);
+    block_incl_sum<NW>(t0, sm, s0);
+    block_incl_sum<NW>(t1, sm, s1);
     if (threadIdx.x == 0) {
         const Scratch S(G);
-        S.kind_in[c] = in.chunk_kind;
+        S.kind_in[c] = in.block_kind;
         S.cnt0[c] = s0;
         S.cnt1[c] = s1;
     }
 }
 
-// one workgroup of 1024 threads per genome: incoming header bit and token offset of every chunk
+// End of a genome's stream: the total, the zeroed boundary word of the last chunk (the one holding token `total`), and
+// the padding up to the segment end marked BREAK.  One thread.
+DD_D void finish_stream(const TokenStream& out, const Scratch& S, size_t nchunks, long long total) {
+    S.slot[nchunks] = total;
+    *out.ntok = (unsigned long long)total;
+    const long long pad_end = (total + kSegTokens - 1) / kSegTokens * kSegTokens;
+    out.codes[total >> 4] = 0;
+    out.bad[total >> 5] = 0;
+    for (long long w = total >> 4; w < (pad_end >> 4); ++w) out.codes[w] = 0;
+    for (long long w = total >> 5; w < (pad_end >> 5); ++w)
+        out.bad[w] = (w == (total >> 5)) ? (~0u << (total & 31)) : ~0u;
+}
+
+// one workgroup of 1024 threads per genome: incoming header bit and token offset of every chunk, in rounds of 1024 chunks
 __global__ __launch_bounds__(1024) void pack_scan(const PackGenome* __restrict__ tab) {
     __shared__ int smk[16];
     __shared__ long long sms[16];
@@ -344,13 +342,13 @@ __global__ __launch_bounds__(1024) void pack_scan(const PackGenome* __restrict__
     const Scratch S(G);
     const TokenStream out = G.out;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    bool carry_hdr = false;  // header bit entering the next block of 1024 chunks
-    long long carry_sum = 0;
+    bool carry_hdr = false;   // header bit entering the round
+    long long carry_sum = 0;  // tokens in front of it
     for (size_t blk = 0; blk < nchunks; blk += 1024) {
         const size_t c = blk + threadIdx.x;
         const bool live = c < nchunks;
         const int kind = live ? (int)S.kind_in[c] : KIND_ID;
-        // incoming header bit of chunk c = value of the nearest constant chunk before it
+        // (header_bits and block_incl_sum written out: here they share ONE barrier pair; the calls cost 40 % more instructions)
         const unsigned long long cm = __ballot(kind != KIND_ID), vm = __ballot(kind == KIND_C1);
         const unsigned long long below = cm & ((1ull << lane) - 1ull);
         if (lane == 0) smk[wv] = cm ? (((vm >> (63 - __builtin_clzll(cm))) & 1ull) ? KIND_C1 : KIND_C0) : KIND_ID;
@@ -365,13 +363,7 @@ __global__ __launch_bounds__(1024) void pack_scan(const PackGenome* __restrict__
         }
         if (below) hdr_in = (vm >> (63 - __builtin_clzll(below))) & 1ull;
         const long long cnt = live ? (hdr_in ? S.cnt1[c] : S.cnt0[c]) : 0;
-        // exclusive 64-bit sum
-        long long inc = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const long long o = __shfl_up(inc, d);
-            if (lane >= d) inc += o;
-        }
+        const long long inc = wave_incl_sum(cnt);
         if (lane == 63) sms[wv] = inc;
         __syncthreads();
         long long pre = 0, tot = 0;
@@ -383,25 +375,67 @@ __global__ __launch_bounds__(1024) void pack_scan(const PackGenome* __restrict__
             const long long s = carry_sum + pre + inc - cnt;
             S.kind_in[c] = hdr_in ? 1 : 0;
             S.slot[c] = s;
-            out.codes[s >> 4] = 0;
+            out.codes[s >> 4] = 0;  // boundary words: pack_write ORs into them
             out.bad[s >> 5] = 0;
         }
         carry_hdr = next_carry;
         carry_sum += tot;
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        const long long total = carry_sum;
-        S.slot[nchunks] = total;
-        *out.ntok = (unsigned long long)total;
-        const long long pad_end = (total + kSegTokens - 1) / kSegTokens * kSegTokens;
-        // the word holding `total` is a partial boundary word of the last chunk: zero it,
-        // then mark every padding token as BREAK
-        out.codes[total >> 4] = 0;
-        out.bad[total >> 5] = 0;
-        for (long long w = total >> 4; w < (pad_end >> 4); ++w) out.codes[w] = 0;
-        for (long long w = total >> 5; w < (pad_end >> 5); ++w)
-            out.bad[w] = (w == (total >> 5)) ? (~0u << (total & 31)) : ~0u;
+    if (threadIdx.x == 0) finish_stream(out, S, nchunks, carry_sum);
+}
+
+// The dense token strings of a plain span entered outside a header: every byte but the newlines is a token, so squeeze the
+// newline fields out of the 128-bit code string and the 64-bit BREAK string (highest first, so lower positions stay put).
+// The shifts fill the vacated top fields with zeros, and one zero word follows each string for or_shifted.
+DD_D void squeeze_newlines(const SpanBits& bits, uint32_t (&codes)[5], uint32_t (&breaks)[3]) {
+    uint64_t clo = pack_u64(bits.codes[1], bits.codes[0]), chi = pack_u64(bits.codes[3], bits.codes[2]);
+    uint64_t bad = pack_u64(bits.bad[1], bits.bad[0]);
+    uint64_t nl = pack_u64(bits.nl[1], bits.nl[0]);
+    while (nl) {
+        const int q = 63 - __builtin_clzll(nl);
+        nl &= ~(1ull << q);
+        const uint64_t keep = (1ull << q) - 1ull;
+        bad = (bad & keep) | ((bad >> 1) & ~keep);
+        if (q < 32) {
+            const uint64_t k2 = (1ull << (2 * q)) - 1ull;
+            clo = (clo & k2) | (((clo >> 2) | (chi << 62)) & ~k2);
+            chi >>= 2;
+        } else {
+            const uint64_t k2 = (1ull << (2 * (q - 32))) - 1ull;
+            chi = (chi & k2) | ((chi >> 2) & ~k2);
+        }
+    }
+    codes[0] = (uint32_t)clo, codes[1] = (uint32_t)(clo >> 32), codes[2] = (uint32_t)chi, codes[3] = (uint32_t)(chi >> 32), codes[4] = 0u;
+    breaks[0] = (uint32_t)bad, breaks[1] = (uint32_t)(bad >> 32), breaks[2] = 0u;
+}
+
+// OR the bit string src (N words, lowest first, the last one zero), shifted left by s < 32 bits, into words w .. w + N - 1
+// of an LDS image whose word i stands at img[idx(i)]
+template <int N, typename Idx>
+DD_D void or_shifted(uint32_t* img, Idx idx, int w, int s, const uint32_t (&src)[N]) {
+    uint32_t prev = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const uint32_t v = (uint32_t)((((uint64_t)src[i] << 32) | prev) >> (32 - s));  // funnel shift left by s
+        prev = src[i];
+        if (v) atomicOr(&img[idx(w + i)], v);
+    }
+}
+
+// The image's words of tokens S .. E-1 (2^tshift tokens per word) go out to dst.  Only the first and the last word can be
+// shared with a neighbouring chunk: those go out through atomicOr (pack_scan zeroed them), the others are plain stores.
+template <typename Idx>
+DD_D void copy_out(uint32_t* dst, const uint32_t* img, Idx idx, int tshift, long long S, long long E) {
+    const long long w0 = S >> tshift;
+    const int nw = (int)(((E - 1) >> tshift) - w0) + 1;
+    for (int i = threadIdx.x; i < nw; i += T) {
+        const long long w = w0 + i;
+        const uint32_t v = img[idx(i)];
+        if ((w << tshift) >= S && ((w + 1) << tshift) <= E)
+            dst[w] = v;
+        else if (v)
+            atomicOr(&dst[w], v);
     }
 }
 
@@ -422,98 +456,42 @@ __global__ __launch_bounds__(T) void pack_write(const PackGenome* __restrict__ t
     const TokenStream out = G.out;
     const size_t pos = c * (size_t)kPackChunk + (size_t)threadIdx.x * kPackBytesPerThread;
     const ThreadSpan t = load_span(G.fa, G.n, pos, (size_t)gload8u(SC.first));
-    const Incoming in = propagate(t.kind, SC.kind_in[c] != 0, sm);
+    const Incoming in = header_bits<NW>(t.kind, SC.kind_in[c] != 0, sm);
     const int cnt = in.hdr ? t.t1 : t.t0;
     int total;
-    const int inc = block_incl_sum(cnt, sm, &total);
+    const int inc = block_incl_sum<NW>(cnt, sm, total);
     if (total == 0) return;
     const long long S = SC.slot[c], E = S + total;  // global token range of this chunk
-    const long long cw0 = S >> 4, bw0 = S >> 5;
-    const int ncw = (int)(((E - 1) >> 4) - cw0) + 1, nbw = (int)(((E - 1) >> 5) - bw0) + 1;
     for (int i = threadIdx.x; i < 4 * ROW; i += T) lcodes[i] = 0;
     for (int i = threadIdx.x; i < 2 * ROW; i += T) lbad[i] = 0;
     __syncthreads();
     if (cnt) {
         long long tk = S + (inc - cnt);  // global index of this thread's next token
+        // where token tk stands in the image: word and bit of the code string, of the BREAK string
+        auto cword = [&] { return (int)((tk >> 4) - (S >> 4)); };
+        auto bword = [&] { return (int)((tk >> 5) - (S >> 5)); };
         if (t.plain && !in.hdr) {
-            // Every byte but the newlines is a token: squeeze the newline fields out of the 128-bit
-            // code string and the 64-bit BREAK string (highest first, so lower positions stay put),
-            // then OR the dense strings into the image at the thread's bit offset.
-            uint64_t clo = pack_u64(t.bits.codes[1], t.bits.codes[0]), chi = pack_u64(t.bits.codes[3], t.bits.codes[2]);
-            uint64_t bad = pack_u64(t.bits.bad[1], t.bits.bad[0]);
-            uint64_t nl = pack_u64(t.bits.nl[1], t.bits.nl[0]);
-            while (nl) {
-                const int q = 63 - __builtin_clzll(nl);
-                nl &= ~(1ull << q);
-                const uint64_t keep = (1ull << q) - 1ull;
-                bad = (bad & keep) | ((bad >> 1) & ~keep);
-                if (q < 32) {
-                    const uint64_t k2 = (1ull << (2 * q)) - 1ull;
-                    clo = (clo & k2) | (((clo >> 2) | (chi << 62)) & ~k2);
-                    chi >>= 2;
-                } else {
-                    const uint64_t k2 = (1ull << (2 * (q - 32))) - 1ull;
-                    chi = (chi & k2) | ((chi >> 2) & ~k2);
-                }
-            }
-            // (the shifts fill the vacated top fields with zeros: exactly cnt fields remain)
-            const int wi = (int)((tk >> 4) - cw0), sh = (int)(tk & 15) * 2;
-            const uint32_t c[5] = {(uint32_t)clo, (uint32_t)(clo >> 32), (uint32_t)chi, (uint32_t)(chi >> 32), 0u};
-            uint32_t prev = 0;
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                const uint32_t v = (uint32_t)((((uint64_t)c[i] << 32) | prev) >> (32 - sh));  // funnel shift left by sh
-                prev = c[i];
-                if (v) atomicOr(&lcodes[cidx(wi + i)], v);
-            }
-            if (bad) {
-                const int bi = (int)((tk >> 5) - bw0), bs = (int)(tk & 31);
-                const uint32_t bb[3] = {(uint32_t)bad, (uint32_t)(bad >> 32), 0u};
-                uint32_t pb = 0;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const uint32_t v = (uint32_t)((((uint64_t)bb[i] << 32) | pb) >> (32 - bs));
-                    pb = bb[i];
-                    if (v) atomicOr(&lbad[bidx(bi + i)], v);
-                }
-            }
+            uint32_t codes[5], breaks[3];
+            squeeze_newlines(t.bits, codes, breaks);
+            or_shifted(lcodes, cidx, cword(), (int)(tk & 15) * 2, codes);
+            if (breaks[0] | breaks[1]) or_shifted(lbad, bidx, bword(), (int)(tk & 31), breaks);
         } else {
             LineState s{in.hdr, t.line_start, false, 0, 0};
 #pragma unroll
             for (int j = 0; j < SUB; ++j) {
-                uint32_t pc, pb;
-                const int n16 = scan16<true>(t.b[j], j + 1 < SUB ? t.b[j + 1 < SUB ? j + 1 : j].at(0) : t.after, s, pc, pb);
+                uint32_t piece[2] = {0u, 0u}, pbad[2] = {0u, 0u};  // <= 16 tokens: one word each, and the zero word
+                const int n16 = scan16<true>(t.b[j], t.byte_after(j), s, piece[0], pbad[0]);
                 if (n16) {
-                    const int wi = (int)((tk >> 4) - cw0), sh = (int)(tk & 15) * 2;
-                    if (pc << sh) atomicOr(&lcodes[cidx(wi)], pc << sh);
-                    if (sh && (pc >> (32 - sh))) atomicOr(&lcodes[cidx(wi + 1)], pc >> (32 - sh));
-                    if (pb) {
-                        const int bi = (int)((tk >> 5) - bw0), bs = (int)(tk & 31);
-                        atomicOr(&lbad[bidx(bi)], pb << bs);
-                        if (bs > 16 && (pb >> (32 - bs))) atomicOr(&lbad[bidx(bi + 1)], pb >> (32 - bs));
-                    }
+                    or_shifted(lcodes, cidx, cword(), (int)(tk & 15) * 2, piece);
+                    if (pbad[0]) or_shifted(lbad, bidx, bword(), (int)(tk & 31), pbad);
                     tk += n16;
                 }
             }
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < ncw; i += T) {
-        const long long w = cw0 + i;
-        const uint32_t v = lcodes[cidx(i)];
-        if ((w << 4) >= S && (w << 4) + 16 <= E)
-            out.codes[w] = v;
-        else if (v)
-            atomicOr(&out.codes[w], v);
-    }
-    for (int i = threadIdx.x; i < nbw; i += T) {
-        const long long w = bw0 + i;
-        const uint32_t v = lbad[bidx(i)];
-        if ((w << 5) >= S && (w << 5) + 32 <= E)
-            out.bad[w] = v;
-        else if (v)
-            atomicOr(&out.bad[w], v);
-    }
+    copy_out(out.codes, lcodes, cidx, 4, S, E);
+    copy_out(out.bad, lbad, bidx, 5, S, E);
 }
 
 }  // namespace

@@ -72,6 +72,9 @@ RAGGED = {
     "at_headers": b">a\nACGTAGCTAGCTAGGATCGATCG\n@b looks like FASTQ\nTTGACGATCGATGCAGCAGCATCGAC\n@c\nGGGATCGAGCTAGCATCGAC\n",
     "cr_midline": b">a\nACGTAGCTAG\rCTAGGATCGATCGATTGACG\r\r\nACGTACGTAGCATCGATCGA\r\n",
     "fastq": b"@r1 desc\nACGTAGCTAGCTAGGATCGATCGATTGACG\n+\nIIIIIIIIIIIIIIIIIIIIIIIIIIIIII\n@r2\nTTGACGATCGATGCAGCAGCATCGACNACGT\n+r2\nII@>IIIIIIIIIIIIIIIIIIIIIIIIIII\n",
+    # the first header character stands at byte 35 114, not at a line start: pack_first searches in rounds of 1024 x 16 bytes
+    # = 16 KiB, so it is found in the third round (beyond 32 KiB: no round of one or of two such steps holds it)
+    "first_header_beyond_32k": b"ACGTTGCAAGCTTAGC junk text\n" * 1300 + b"ACGTTAGC more >rec1 comment\nACGTAGCTAGCTAGGATCGATCGATTGACG\nTTGACCAGTAGCAT\n>rec2\nGGCATGCATGCATCAGTTGACCATGACATG\n",
     "fastq_multiline": b"@r1\nACGTAGCTAGCTAGG\nATCGATCGATTGACG\n+\nIIIIIIIIIIIIIII\n@IIIIIIIIIIIIII\n@r2\nGGCATGCATGCATCAGT\n+\n>IIIIIIIIIIIIIIII\n>fa\nTTGACCATGACATG\n",
 }
 
@@ -207,7 +210,7 @@ def test_big_bitmap_class(engine_factory, torch_cuda, orc, canon, p, monkeypatch
 
 
 def test_sweep_parity_long_lines_and_headers(engine_factory, orc):
-    """A 20 kB header and a 50 kB single sequence line cross several 4 KiB pack chunks."""
+    """A 20 kB header and a 50 kB single sequence line cross several 16 KiB pack chunks."""
     rng = np.random.default_rng(5)
     seq = rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=50000).tobytes()
     hdr = b">" + rng.choice(np.frombuffer(b"ACGT >xyz", dtype=np.uint8), size=20000).tobytes()
@@ -215,6 +218,36 @@ def test_sweep_parity_long_lines_and_headers(engine_factory, orc):
     fa = b">r1\n" + seq + b"\n" + hdr + b"\n" + seq2 + b"\n" + hdr
     eng = engine_factory(10, True)
     _sweep_check(eng, orc, np.frombuffer(fa, dtype=np.uint8), 2, 36, True)
+
+
+def test_header_bit_and_token_sum_cross_the_scan_round(engine_factory, orc):
+    """pack_scan walks a genome's 16 KiB chunks in rounds of 1024 and carries the header bit and the token sum from round to round.
+    1026 chunks of 80-column sequence with ONE header line of 46 652 A/C/G/T letters that starts inside chunk 1022 and ends inside
+    chunk 1025: chunks 1023 and 1024 hold no newline, so chunk 1024, the first of the second round, is entered inside a header only
+    through that carry.  Dropped, the text would read as if a newline stood at byte 1024 x 16384 -- and the oracle tells the two
+    apart at both k: 2 registers of 1024 at k = 30 and 3 at k = 55 at log2m 10, and, sturdier, 11 and 16 of 16 384 at log2m 14
+    (all asserted below, so the case cannot lose its point unnoticed with another seed or oracle)."""
+    chunk = 16384
+    rng = np.random.default_rng(7)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+    def lines(nbytes):
+        a = rng.choice(acgt, size=(nbytes // 81, 81))
+        a[:, 80] = 10
+        return a.tobytes()
+
+    start, end = 1022 * chunk + 3000, 1025 * chunk + 500
+    head = b">r\n" + lines(start - 3)
+    head += b"A" * (start - len(head) - 1) + b"\n"
+    fa = np.frombuffer(head + b">" + rng.choice(acgt, size=end - start - 2).tobytes() + b"\n" + lines(4000), dtype=np.uint8)
+    assert (fa.size + chunk - 1) // chunk == 1026 and fa[start] == ord(">") and fa[end - 1] == 10 and not (fa[start:end - 1] == 10).any()
+    cut = fa.copy()
+    cut[1024 * chunk] = 10
+    for log2m in (10, 14):
+        eng = engine_factory(log2m, True)
+        for k in (30, 55):
+            got = _sweep_check(eng, orc, fa, k, k, True)
+            assert (got != orc.sketch_sweep(cut, k, k, log2m, True)).any(), (log2m, k)
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3, 4])
@@ -914,6 +947,32 @@ def test_gz_fastq_is_resolved_on_the_device(orc, torch_cuda, tmp_path, monkeypat
         assert np.array_equal(eng.sketch_files(paths[:4], 19, 21), got[:4])
     finally:
         eng.close()
+
+
+def test_gz_fastq_newline_offsets_carry_over_1024_blocks(orc, torch_cuda, tmp_path, monkeypatch):
+    """The newline offsets of a FASTQ text are summed over its 4096-byte blocks in rounds of 1024 blocks (dd_fastq.hip:
+    text_offsets_kernel), the sum carried from round to round.  One single-member .gz of 14 500 reads of 150 bases, 4.5 - 5 MB of
+    text: more than 1024 blocks, so the second round's records are found only with the carry.  DD_INFLATE_STRICT=2: nothing goes
+    to the host.  Registers == the oracle's reading of the plain bytes."""
+    import zlib
+    from dandd_amd.engine import Engine
+    monkeypatch.setenv("DD_GUNZIP_MIN_KB", "16")
+    rng = np.random.default_rng(11)
+    seq = orc.synth_fasta(SEED, 9, 1_500_000, 1).tobytes().split(b"\n", 1)[1].replace(b"\n", b"")
+    quals = rng.choice(np.frombuffer(b"ACGT@>+I#5FFFF", np.uint8), size=(14500, 150))
+    text = b"".join(b"@read%d extra\n" % i + seq[i * 97:i * 97 + 150] + b"\n+" + (b"read%d" % i if i % 3 == 0 else b"") + b"\n" + quals[i].tobytes() + b"\n"
+                    for i in range(14500))
+    assert 4_500_000 < len(text) < 5_000_000 and len(text) > 1024 * 4096
+    co = zlib.compressobj(6, zlib.DEFLATED, 31)
+    path = tmp_path / "reads.fq.gz"
+    path.write_bytes(co.compress(text) + co.flush())
+    monkeypatch.setenv("DD_INFLATE_STRICT", "2")
+    eng = Engine(device=0, log2m=10, canonical=True)
+    try:
+        got = eng.sketch_files([str(path)], 19, 21)[0]
+    finally:
+        eng.close()
+    assert np.array_equal(got, orc.sketch_sweep(np.frombuffer(text, np.uint8), 19, 21, 10))
 
 
 def test_gunzip_isize_smaller_than_the_text_cannot_write_past_the_arena(orc, torch_cuda, tmp_path, monkeypatch):
