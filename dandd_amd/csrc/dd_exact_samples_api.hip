@@ -1,8 +1,9 @@
 // dd_exact_samples_api.hip -- the exact entry points of the C ABI (include/dandd_hip.h) that look SAMPLES, files that are no
 // inputs, up in the ordered records of a universe of inputs: what the samples hold of them (dd_exact_screen), where along
 // themselves (dd_exact_paint), which genome each of their records belongs to (dd_exact_reads), how many times they hold each
-// (dd_exact_depth) and where along each genome, and how deep (dd_exact_cover).  Each entry is its own argument rules, table
-// and kernels (dd_exact_screen.hip, dd_exact_paint.hip, dd_exact_reads.hip, dd_exact_depth.hip, dd_exact_cover.hip) around
+// (dd_exact_depth), where along each genome, and how deep (dd_exact_cover) and which genomes explain them, one by one
+// (dd_exact_gather).  Each entry is its own argument rules, table and kernels (dd_exact_screen.hip, dd_exact_paint.hip,
+// dd_exact_reads.hip, dd_exact_depth.hip, dd_exact_cover.hip, dd_exact_gather.hip) around
 // four pieces: UniverseCall, HitsCarve, SampleRounds (below) and exact_check_shape (dd_exact_host.h).  It checks its
 // arguments in the order of its ABI comment, stages every result on the host and writes the caller's arrays once, at its
 // end: nothing is written before everything is known.  Host-side orchestration only.
@@ -105,6 +106,15 @@ int cover_args(dd_ctx* c, const void* inputs, int n, int ns, int k, const int32_
         return fail(DD_EINVAL, "clip=%u outside 1..%u (a depth counts as min(depth, clip): a window's sum stays inside 32 bits)", clip, dd::kCoverMaxClip);
     for (int t = 0; t < nt; ++t)
         if (off[t + 1] < off[t]) return fail(DD_EINVAL, "off[] must ascend");
+    return DD_OK;
+}
+
+int gather_args(dd_ctx* c, const void* inputs, int n, int ns, int k, uint32_t min_hits, int steps, const int32_t* pick, const uint64_t* unique,
+                const uint64_t* depth, const uint64_t* shared, const uint64_t* total, const uint64_t* found) {
+    if (universe_args(c, inputs, n, ns, k, found)) return DD_EINVAL;
+    if (!min_hits) return fail(DD_EINVAL, "min_hits=0: a pick needs at least one k-mer that no earlier pick holds (min_hits >= 1)");
+    if (steps < 1 || steps > n) return fail(DD_EINVAL, "steps=%d outside 1..%d: a step picks an input of the universe, each at most once", steps, n);
+    if (!pick || !unique || !depth || !shared || !total) return fail(DD_EINVAL, "null argument");
     return DD_OK;
 }
 
@@ -577,6 +587,88 @@ int dd_exact_cover(dd_ctx* c, const char* const* paths, int n, const char* const
     if (cover_args(c, paths, n, ns, k, target, nt, window, clip, off, found)) return DD_EINVAL;
     return universe_path_form(c, paths, n, samples, ns, [&](auto p, auto s) {
         return dd_exact_cover_device(c, p, s, n, ns, k, target, nt, window, clip, off, counts, found);
+    });
+}
+
+// ------------------------------------------------------------------- samples explained by the genomes, one by one
+// dd_exact_gather.hip: depth's rounds with a walk behind depth_kernel -- per step one pass over the round's counters and the
+// masks, one pick per sample -- and one closing pass and pick for the last pick's depth.  The whole walk is enqueued on the
+// call's stream; the host sees the round's rows once, behind it.
+// c->hits: per round state [per] | step counters [per][64] u64 | sums [per][3] u64 | pick [per][steps] i32 | unique, depth
+// [per][steps] u64 | shared [per][n] u64 | counters [per][found] u32.
+int dd_exact_gather_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int ns, int k, uint32_t min_hits, int steps,
+                           int32_t* pick, uint64_t* unique, uint64_t* depth, uint64_t* shared, uint64_t* total, uint64_t* found) {
+    if (gather_args(c, fasta_dev, n, ns, k, min_hits, steps, pick, unique, depth, shared, total, found) || universe_buffers(fasta_dev, nbytes, n, ns))
+        return DD_EINVAL;
+    if (depth_sample_bytes(nbytes, n, ns)) return DD_EINVAL;
+    SampleRounds rounds;
+    UniverseCall u(c, n, ns, k, "exact gather");
+    int rc;
+    if ((rc = u.prepare(fasta_dev, nbytes))) return rc;
+    const size_t S = (size_t)steps, N = (size_t)n;
+    std::vector<int32_t> pick_host((size_t)ns * S, -1);
+    std::vector<unsigned long long> unique_host((size_t)ns * S, 0ull), depth_host((size_t)ns * S, 0ull), shared_host((size_t)ns * N, 0ull),
+        sums_host((size_t)ns * dd::kGatherSums, 0ull);
+    u.table<uint64_t>(0);   // (no table of its own)
+    if ((rc = u.records(false))) return rc;
+    if (u.rec.kept) {
+        // a round's row: the sample's counters and its walk
+        const size_t fnd = (size_t)u.rec.found;
+        const size_t walk = sizeof(dd::GatherState) + (64 + dd::kGatherSums + 2 * S + N) * sizeof(unsigned long long) + S * sizeof(int32_t);
+        char needs[160];
+        snprintf(needs, sizeof needs, " (%zu records x 4 bytes of counters, and %zu of the walk's state and %d steps)", fnd, walk, steps);
+        if ((rc = rounds.size(u.what, ns, fnd * sizeof(uint32_t) + walk, needs))) return rc;
+        const size_t per = rounds.per;
+        HitsCarve hits(c);
+        const auto states = hits.part<dd::GatherState>(per, true);
+        const auto stepped = hits.part<unsigned long long>(per * 64, true);
+        const auto summed = hits.part<unsigned long long>(per * dd::kGatherSums, true);
+        const auto picked = hits.part<int32_t>(per * S, true);
+        const auto uniques = hits.part<unsigned long long>(per * S, true);
+        const auto depths = hits.part<unsigned long long>(per * S, true);
+        const auto shareds = hits.part<unsigned long long>(per * N, true);
+        const auto counters = hits.part<uint32_t>(per * fnd, false);
+        if (hits.reserve())
+            return fail(DD_ENOMEM, "exact gather: no device memory for the %zu bytes of a round's counters (%zu samples x %zu records x 4 bytes) and the "
+                                   "%zu of its walks; a smaller DD_DEPTH_MB (%zu MiB now) makes smaller rounds",
+                        counters.bytes, per, fnd, counters.at, rounds.budget >> 20);
+        dd::GatherState* state_dev = hits(states);
+        unsigned long long *step_dev = hits(stepped), *sums_dev = hits(summed), *unique_dev = hits(uniques), *depth_dev = hits(depths),
+                           *shared_dev = hits(shareds);
+        int32_t* pick_dev = hits(picked);
+        uint32_t* count_dev = hits(counters);
+        Span sp(c, DD_KERNEL_EXACT);
+        dd::LocateSet set{};
+        DD_HIP(u.rec.order(c, k, &set));
+        rc = rounds.run(u, nbytes, set, state_dev, counters.at, count_dev, [&](size_t s0, size_t take) -> int {
+            for (int t = 0; t <= steps; ++t) {   // (t == steps: the closing pass, for the last pick's depth)
+                dd::launch_exact_gather(set, count_dev, (int)take, n, state_dev, step_dev, sums_dev, u.st);
+                dd::launch_exact_gather_pick((int)take, n, t, steps, min_hits, state_dev, step_dev, sums_dev, pick_dev, unique_dev, depth_dev,
+                                             shared_dev, u.st);
+            }
+            DD_HIP(hipGetLastError());
+            DD_HIP(hipMemcpyAsync(pick_host.data() + s0 * S, pick_dev, take * S * sizeof(int32_t), hipMemcpyDeviceToHost, u.st));
+            DD_HIP(hipMemcpyAsync(unique_host.data() + s0 * S, unique_dev, take * S * sizeof(unsigned long long), hipMemcpyDeviceToHost, u.st));
+            DD_HIP(hipMemcpyAsync(depth_host.data() + s0 * S, depth_dev, take * S * sizeof(unsigned long long), hipMemcpyDeviceToHost, u.st));
+            DD_HIP(hipMemcpyAsync(shared_host.data() + s0 * N, shared_dev, take * N * sizeof(unsigned long long), hipMemcpyDeviceToHost, u.st));
+            DD_HIP(hipMemcpyAsync(sums_host.data() + s0 * dd::kGatherSums, sums_dev, take * dd::kGatherSums * sizeof(unsigned long long),
+                                  hipMemcpyDeviceToHost, u.st));
+            return DD_OK;
+        });
+        if (rc) return rc;
+    }
+    for (size_t i = 0; i < pick_host.size(); ++i) pick[i] = pick_host[i], unique[i] = unique_host[i], depth[i] = depth_host[i];
+    for (size_t i = 0; i < shared_host.size(); ++i) shared[i] = shared_host[i];
+    for (size_t s = 0; s < (size_t)ns; ++s)
+        total[2 * s] = sums_host[s * dd::kGatherSums + dd::kGatherHeld], total[2 * s + 1] = sums_host[s * dd::kGatherSums + dd::kGatherHeldDepth];
+    return u.done(found);
+}
+
+int dd_exact_gather(dd_ctx* c, const char* const* paths, int n, const char* const* samples, int ns, int k, uint32_t min_hits, int steps,
+                    int32_t* pick, uint64_t* unique, uint64_t* depth, uint64_t* shared, uint64_t* total, uint64_t* found) {
+    if (gather_args(c, paths, n, ns, k, min_hits, steps, pick, unique, depth, shared, total, found)) return DD_EINVAL;
+    return universe_path_form(c, paths, n, samples, ns, [&](auto p, auto s) {
+        return dd_exact_gather_device(c, p, s, n, ns, k, min_hits, steps, pick, unique, depth, shared, total, found);
     });
 }
 

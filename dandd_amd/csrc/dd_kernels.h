@@ -515,6 +515,38 @@ void launch_exact_cover(const CoverUnit* units_dev, int nunits, size_t max_segme
                         size_t found, int ns, size_t window_segments, uint32_t clip, size_t nrows, uint32_t* rows_dev, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------
+// samples that are no leaves, explained by the genomes of the universe one by one (dd_exact_gather.hip), behind
+// launch_exact_emit_order and launch_exact_depth: the greedy set cover over the records a sample holds, a pass over the
+// records and a pick per step, the walk's state on the device.
+// ---------------------------------------------------------------------------------------
+constexpr int kGatherDone = -1;           // GatherState::last1 of a walk that has stopped
+constexpr int kGatherSums = 3;            // a sample's sums: the open pick's depth | the records it holds | the sum of their depths
+constexpr int kGatherOpenDepth = 0, kGatherHeld = 1, kGatherHeldDepth = 2;
+struct GatherState {                // one per sample of the round; all-zero bytes are a fresh walk
+    uint64_t taken;                 // bit b: input b is picked and its records are out of the walk
+    int32_t last1;                  // 0: nothing picked yet; b + 1: input b is the last pick, its depth is still open (bit b is
+                                    // not in `taken` yet); kGatherDone
+    int32_t pad;
+};
+// One pass over the records for every sample of the round whose walk goes on.  count_dev [ns][found] u32: launch_exact_depth's.
+// A record of sample s is live when count > 0 and mask & taken == 0.  sums_dev[s][kGatherOpenDepth] += the counters of the
+// live records with bit `last`; step_dev[s][b] += the other live records with bit b, for every b < n outside
+// taken | 1 << last; where nothing is picked yet, sums_dev[s][kGatherHeld] += the records with count > 0 and
+// sums_dev[s][kGatherHeldDepth] += their counters.  step_dev [ns][64] and sums_dev [ns][kGatherSums] u64, zeroed by the
+// caller in front of the first pass.  Nothing is launched for an empty set.
+void launch_exact_gather(const LocateSet& set, const uint32_t* count_dev, int ns, int n, const GatherState* state_dev,
+                         unsigned long long* step_dev, unsigned long long* sums_dev, hipStream_t st);
+// Step t of 0 .. steps behind pass t on the same stream (t == steps: the closing one, which picks nothing).  Per sample:
+// depth_dev[s][t - 1] = the open pick's depth sum, cleared, and the pick folded into `taken`; then, for t < steps, the argmax
+// b of step_dev[s][0..63], the lowest index on a tie: with step_dev[s][b] >= min_hits (>= 1) pick_dev[s][t] = b,
+// unique_dev[s][t] = step_dev[s][b] and b is the open pick; otherwise pick_dev[s][t] = -1 and the walk has stopped, as it
+// has behind t == steps.  t == 0: shared_dev[s][0..n-1] = step_dev[s].  step_dev[s] is zeroed.  pick_dev [ns][steps] i32,
+// unique_dev and depth_dev [ns][steps] u64 zeroed by the caller, shared_dev [ns][n] u64.
+void launch_exact_gather_pick(int ns, int n, int t, int steps, uint32_t min_hits, GatherState* state_dev, unsigned long long* step_dev,
+                              unsigned long long* sums_dev, int32_t* pick_dev, unsigned long long* unique_dev, unsigned long long* depth_dev,
+                              unsigned long long* shared_dev, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------
 // exact greedy walk (dd_exact_greedy.hip) over the mask streams of kSchedStream: one launch per step of the walk reads
 // every stream once.  gain[kk][b] += masks of stream kk (store[seg.off[kk] .. seg.off[kk + 1])) that meet `chosen` nowhere
 // and hold bit b, for every b < 64 (a bit of `chosen` gains 0).  gain_dev [K][64], zeroed by the caller.

@@ -41,6 +41,7 @@ EXPORTS = [
     "dd_exact_reads", "dd_exact_reads_device",
     "dd_exact_depth", "dd_exact_depth_device",
     "dd_exact_cover", "dd_exact_cover_device",
+    "dd_exact_gather", "dd_exact_gather_device",
     "dd_exact_patterns", "dd_exact_patterns_device",
     "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
@@ -182,7 +183,9 @@ def load_library(path=None):
                              ("dd_exact_depth", [paths_t, i32, paths_t, i32], [vp, vp, i32, i32, vp, vp]),
                              ("dd_exact_depth_device", [ptrs_t, sizes_t, i32, i32], [vp, vp, i32, i32, vp, vp]),
                              ("dd_exact_cover", [paths_t, i32, paths_t, i32], [vp, i32, u64, C.c_uint32, vp, vp]),
-                             ("dd_exact_cover_device", [ptrs_t, sizes_t, i32, i32], [vp, i32, u64, C.c_uint32, vp, vp])):
+                             ("dd_exact_cover_device", [ptrs_t, sizes_t, i32, i32], [vp, i32, u64, C.c_uint32, vp, vp]),
+                             ("dd_exact_gather", [paths_t, i32, paths_t, i32], [C.c_uint32, i32, vp, vp, vp, vp, vp]),
+                             ("dd_exact_gather_device", [ptrs_t, sizes_t, i32, i32], [C.c_uint32, i32, vp, vp, vp, vp, vp])):
         fn = getattr(lib, name)
         fn.restype = i32
         fn.argtypes = [vp] + src + [i32] + extra + [C.POINTER(u64)]
@@ -1096,6 +1099,36 @@ class Engine:
         """exact_cover over FASTA bytes on the device: the n universe inputs first, the samples behind them; ntok: every
         universe input's token count (the library checks the targets')."""
         return self._exact_cover(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes, n=n), k, window, targets, clip, ntok)
+
+    # -- samples explained by the genomes one by one: a greedy set cover over depth's counters, walked on the device (dd_exact_gather.hip) --
+    last_gather_found = None   # of the last exact_gather call: the distinct k-mers of the universe
+    def _exact_gather(self, src, k, min_hits, steps):
+        _, n, ns, _ = src
+        steps = max(n, 0) if steps is None else int(steps)
+        if not 0 <= int(min_hits) < 1 << 32:
+            raise ValueError(f"min_hits={min_hits} is no 32-bit count")   # (ctypes would wrap it; 0 is the library's to refuse)
+        rows, cols = max(ns, 1), min(max(steps, 1), 64)                   # (room for the library to refuse what is out of range)
+        pick = np.full((rows, cols), -1, dtype=np.int32)
+        unique, depth = np.zeros((rows, cols), dtype=np.uint64), np.zeros((rows, cols), dtype=np.uint64)
+        shared, total = np.zeros((rows, max(n, 1)), dtype=np.uint64), np.zeros((rows, 2), dtype=np.uint64)
+        self._exact_lookup("gather", src, int(k), int(min_hits), steps, pick.ctypes.data, unique.ctypes.data, depth.ctypes.data, shared.ctypes.data,
+                           total.ctypes.data)
+        return pick, unique, depth, shared, total
+
+    def exact_gather(self, paths, samples, k, min_hits=1, steps=None):
+        """FASTA files (n <= 64: the universe), sample files (FASTA / FASTQ, plain or gzip, ns <= 1024), one k, min_hits >= 1,
+        1 <= steps <= n (None: n) -> (pick int32 [ns][steps], unique uint64 [ns][steps], depth uint64 [ns][steps], shared
+        uint64 [ns][n], total uint64 [ns][2]): the greedy set cover of every sample's k-mers by the files.  pick[s][t]: the
+        file that holds most of the distinct k-mers of sample s (of those the universe holds) that no earlier pick holds,
+        ties to the lowest index; unique[s][t]: how many those are, depth[s][t]: the times the sample holds them, summed
+        (exact_depth's depth).  The walk stops at a pick with fewer than min_hits k-mers; behind the stop pick = -1 and
+        zeros.  shared[s][i]: exact_screen's shared; total[s]: the sample's distinct k-mers in the universe and the sum of
+        their depths.  last_gather_found: the universe's distinct k-mers."""
+        return self._exact_gather(self._exact_src(paths=paths, samples=samples), k, min_hits, steps)
+
+    def exact_gather_device(self, fasta_ptrs, nbytes, n, k, min_hits=1, steps=None):
+        """exact_gather over FASTA bytes on the device: the n universe inputs first, the samples behind them."""
+        return self._exact_gather(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes, n=n), k, min_hits, steps)
 
     # -- the membership-pattern table: the distinct masks and how many k-mers carry each (dd_exact_patterns.hip) ------------
     last_patterns_stats = None   # of the last exact_patterns call: (distinct k-mers, pairs written to HBM, forced flushes, single masks)

@@ -420,6 +420,17 @@ class HipExactBackend:
         counts = self.engine.exact_cover(*got, int(k), int(window), targets=targets, clip=int(clip), ntok=ntok)
         return [index[t] for t in targets], counts
 
+    def gather_picks(self, leaf_paths, k, sample_files, min_hits, steps):
+        """files that are no leaves explained by the leaves one by one at one k of the window (dd_exact_gather): -> (pick int32
+        [ns][steps], unique uint64 [ns][steps], depth uint64 [ns][steps], shared uint64 [ns][n], total uint64 [ns][2]);
+        pick[s][t]: the leaf that holds most of the distinct k-mers of sample s that no earlier pick holds (ties: the lowest
+        index; -1 behind a pick with fewer than min_hits), unique: how many those are, depth: the times the sample holds
+        them, summed; shared: screen_counts' shared; total[s]: the sample's distinct k-mers among the leaves' and the sum of
+        their depths."""
+        if (got := self._leaves_and_samples(leaf_paths, k, sample_files)) is None:
+            return None
+        return self.engine.exact_gather(*got, int(k), min_hits=int(min_hits), steps=int(steps))
+
     def pattern_counts(self, leaf_paths, k, limit):
         """the distinct membership masks of the leaves at one k of the window and how many k-mers carry each
         (dd_exact_patterns): -> (masks uint64 [m], counts uint64 [m], found, distinct), count descending, ties by mask

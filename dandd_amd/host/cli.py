@@ -15,6 +15,11 @@ window of W bases of the genome (<prefix>.cover.csv), the runs of windows that a
 (<prefix>.cover_summary.csv).  `--cover-fastas LIST` lays the samples along the genomes LIST names (one per line; default:
 the whole universe), `--cover-clip C` counts a position's depth as at most C (1..1023, default 255), `--cover-min P` calls a
 window present where the sample holds at least P per cent of its positions (1..100, default 50).
+`screen --gather` adds which genomes of the collection EXPLAIN a sample, one by one: the genome that holds most of the sample's
+k-mers, then the one that holds most of what is left, and so on -- a close relative of a pick adds almost nothing --, one row
+per sample, k and pick with the k-mers it adds and how deep the sample holds them (<prefix>.gather.csv), and one row per
+sample and k (<prefix>.gather_summary.csv).  `--gather-min H` stops at a pick that adds fewer than H k-mers (default 1),
+`--gather-steps N` behind N picks (default: as many as the universe has genomes).
 """
 import argparse
 import os
@@ -496,7 +501,8 @@ def screen_command(args):
     over the genomes, voted and tallied on the device (_reads_rows).  --depth adds how many times the sample holds the k-mers
     of every genome and class: a histogram of depths per row, counted and binned on the device (_depth_rows).  --cover W turns
     the view round: every genome of the collection in windows of W bases, and per sample how much of each window it holds and
-    how deep (_cover_rows)."""
+    how deep (_cover_rows).  --gather explains every sample by the genomes one by one, a greedy set cover walked on the
+    device (_gather_rows)."""
     tree, outfile = _open_tree("screen", args, exact=True)
     ks = sorted(set(int(k) for k in args.ks)) if args.ks else [int(tree.root_k())]
     for k in ks:
@@ -526,6 +532,14 @@ def screen_command(args):
     cover_min = 50 if args.cover_min is None else args.cover_min
     if not 1 <= cover_min <= 100:
         sys.exit(f"screen: --cover-min {cover_min}: the per cent of a window's positions a sample must hold, P in 1..100")
+    for flag, value in (("--gather-min", args.gather_min), ("--gather-steps", args.gather_steps)):
+        if value is not None and not args.gather:
+            sys.exit(f"screen: {flag} goes with --gather")
+    gather_min = 1 if args.gather_min is None else args.gather_min
+    if not 1 <= gather_min < 1 << 32:
+        sys.exit(f"screen: --gather-min {gather_min}: a pick adds at least one k-mer, and the count is 32 bits wide (H in 1..{(1 << 32) - 1})")
+    if args.gather_steps is not None and args.gather_steps < 1:
+        sys.exit(f"screen: --gather-steps {args.gather_steps}: at least one pick (N >= 1)")
     if args.cover_fastas is not None and not os.path.isfile(args.cover_fastas):
         sys.exit(f"screen: {args.cover_fastas} (--cover-fastas) not found")
     names = list(args.samples)
@@ -545,6 +559,8 @@ def screen_command(args):
     leaf_of = _leaf_lookup(tree, "screen", args.delta_tree)
     fastas = _universe_or_exit("screen", tree, args, least=1, most=64, most_why=MASK_BITS)
     ns = len(samples)
+    if args.gather_steps is not None and args.gather_steps > len(fastas):
+        sys.exit(f"screen: --gather-steps {args.gather_steps}: the universe of this run has {len(fastas)} genomes (N in 1..{len(fastas)})")
     groups, labels = _groups_in_universe("screen", args, leaf_of, fastas)
     cover_targets = None                                                 # --cover-fastas: the genomes the samples are laid along
     if args.cover_fastas is not None:
@@ -564,6 +580,7 @@ def screen_command(args):
         called = tree.reads_tables(fastas, samples, ks, args.reads_min_hits, args.reads_calls) if args.reads else None
         depths = tree.depth_tables(fastas, samples, ks, groups, bins) if args.depth else None
         covered = tree.cover_tables(fastas, samples, ks, args.cover, cover_targets, clip) if args.cover is not None else None
+        gathered = tree.gather_tables(fastas, samples, ks, gather_min, args.gather_steps) if args.gather else None
     except (ValueError, OSError) as e:
         sys.exit("screen: " + " ".join(str(e).split()))
 
@@ -615,7 +632,46 @@ def screen_command(args):
     if covered is not None:
         for name, rows in zip(COVER_COLUMNS, _cover_rows(samples, covered, cover_min)):
             _write_csv(f"{outfile}.{name}.csv", COVER_COLUMNS[name], rows)
+    if gathered is not None:
+        for name, rows in zip(GATHER_COLUMNS, _gather_rows(samples, fastas, res, gathered)):
+            _write_csv(f"{outfile}.{name}.csv", GATHER_COLUMNS[name], rows)
     _finish(tree)
+
+
+GATHER_COLUMNS = {
+    "gather": ["sample", "k", "rank", "fasta", "genome_kmers", "shared", "unique", "f_sample_unique", "f_genome_shared", "f_genome_unique",
+               "unique_depth", "mean_depth", "f_depth", "remaining"],
+    "gather_summary": ["sample", "k", "sample_kmers", "in_pan", "novel", "genomes", "explained", "unexplained", "top_fasta"],
+}
+
+
+def _gather_rows(samples, fastas, res, gathered):
+    """gather_tables' walk, with screen_tables' sizes -> the rows of <prefix>.gather.csv (one per sample, k and pick, rank 1
+    first: the genome, its k-mers, those the sample shares with it, those of them no earlier pick holds -- `unique` --, unique
+    over the sample's k-mers, shared and unique over the genome's, the times the sample holds the unique ones -- summed, per
+    k-mer, and over the depth of all the sample holds of the pan-genome --, and the sample's k-mers in the pan-genome that are
+    still unexplained behind this pick) and of .gather_summary.csv (one per sample and k: the sample's k-mers, those in the
+    pan-genome, the others, the picks, the k-mers they explain together, those they leave, the first pick; an empty cell
+    where a ratio has nothing to stand on or nothing is picked)."""
+    ns = len(samples)
+    ratio = lambda a, b: a / b if b else None
+    picks, summary = [], []
+    for s, sample in enumerate(samples):
+        for kk, k in enumerate(gathered["ks"]):
+            q, in_pan = int(res["sample_kmers"][kk, s]), int(res["match"][kk, s, 0])
+            deep = int(gathered["total"][kk, s, 1])
+            explained, chosen = 0, []
+            for t, i in enumerate(gathered["pick"][kk, s].tolist()):
+                if i < 0:
+                    break
+                g, sh = int(res["shared"][kk, ns, i]), int(gathered["shared"][kk, s, i])
+                uq, ud = int(gathered["unique"][kk, s, t]), int(gathered["depth"][kk, s, t])
+                explained += uq
+                chosen.append(fastas[i])
+                picks.append([sample, k, t + 1, fastas[i], g, sh, uq, ratio(uq, q), ratio(sh, g), ratio(uq, g), ud, ratio(ud, uq), ratio(ud, deep),
+                              in_pan - explained])
+            summary.append([sample, k, q, in_pan, q - in_pan, len(chosen), explained, in_pan - explained, chosen[0] if chosen else None])
+    return picks, summary
 
 
 COVER_COLUMNS = {
@@ -1091,6 +1147,14 @@ def build_parser():
     sc.add_argument("--cover-min", dest="cover_min", type=int, default=None, metavar="P",
                     help="with --cover: a window is present where the sample holds at least P per cent of its positions, 1..100 "
                          "(default 50)")
+    sc.add_argument("--gather", dest="gather", default=False, action="store_true",
+                    help="also explain every sample by the genomes of the collection one by one: the genome that holds most of its "
+                         "k-mers, then the one that holds most of what is left, ... with the k-mers each pick adds and their depth "
+                         "(<prefix>.gather.csv) and a row per sample (<prefix>.gather_summary.csv)")
+    sc.add_argument("--gather-min", dest="gather_min", type=int, default=None, metavar="H",
+                    help="with --gather: stop at a pick that adds fewer than H k-mers of the sample (default 1)")
+    sc.add_argument("--gather-steps", dest="gather_steps", type=int, default=None, metavar="N",
+                    help="with --gather: N picks at the most, 1..the genomes of the universe (default: all of them)")
     sc.add_argument("samples", nargs="*", metavar="SAMPLE", help="FASTA / FASTQ files, plain or gzip, that are no leaves of the tree")
     sc.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     sc.add_argument("-l", "--label", dest="label", default="")

@@ -1397,6 +1397,33 @@ class DeltaTree:
                 out["counts"][kk][t][batch] = u.table(rows, (len(batch), nwin, 6))
         return out
 
+    def gather_tables(self, fastas, samples, ks, min_hits=1, steps=None):
+        """Which genomes of the universe `fastas` (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]) explain each of
+        `samples` (files that are no leaves: a metagenome, a contaminated assembly; FASTA / FASTQ, plain or gzip), one by
+        one, at every k of `ks`: the greedy set cover of the sample's distinct k-mers.  Step t picks the genome that holds
+        most of the sample's k-mers that no earlier pick holds -- ties: the earlier genome of the universe -- and the walk
+        stops at a pick with fewer than `min_hits` such k-mers or behind `steps` picks (None: as many as there are genomes).
+        The samples go to the backend's gather_picks in screen_tables' batches.  There is no object path: a backend without
+        gather_picks, or without a table for these leaves, is a ValueError.
+        -> dict: ks, min_hits, steps, pick int32 [K][ns][steps] (-1 behind the stop), unique [K][ns][steps] (the k-mers a
+        pick adds), depth [K][ns][steps] (the times the sample holds them, summed), shared [K][ns][n] (screen_tables'
+        shared), total [K][ns][2] (the sample's distinct k-mers in the universe, the sum of their depths)"""
+        n, ns, ks, min_hits = len(fastas), len(samples), self._ks(ks), int(min_hits)
+        steps = n if steps is None else int(steps)
+        if not 1 <= min_hits < 1 << 32:
+            raise ValueError(f"min_hits={min_hits}: a pick needs at least one k-mer, and the count is 32 bits wide")
+        if not 1 <= steps <= n:
+            raise ValueError(f"steps={steps} is outside 1..{n}, the genomes of the universe")
+        out = {"ks": ks, "min_hits": min_hits, "steps": steps, "pick": np.full((len(ks), ns, steps), -1, dtype=np.int32),
+               "unique": np.zeros((len(ks), ns, steps), dtype=np.uint64), "depth": np.zeros((len(ks), ns, steps), dtype=np.uint64),
+               "shared": np.zeros((len(ks), ns, n), dtype=np.uint64), "total": np.zeros((len(ks), ns, 2), dtype=np.uint64)}
+        for kk, k, u, batch, files in self._sample_calls(fastas, samples, ks, "gather_picks", "gathering needs"):
+            got = u.table(u.be.gather_picks(u.paths, k, files, min_hits, steps))
+            out["pick"][kk, batch] = np.asarray(got[0]).astype(np.int32).reshape(len(batch), steps)     # (signed: -1 behind the stop)
+            for name, arr, cols in zip(("unique", "depth", "shared", "total"), got[1:], (steps, steps, n, 2)):
+                out[name][kk, batch] = u.table(arr, (len(batch), cols))
+        return out
+
     # ---- which sets of genomes share k-mers (`dandd patterns`) --------------------------------------------------------------
     def pattern_tables(self, fastas, ks, top=None):
         """The membership patterns of the universe `fastas` (1..64 leaf FASTAs of an exact tree; bit i is fastas[i]) at every

@@ -467,6 +467,41 @@ int dd_exact_cover(dd_ctx *, const char *const *paths, int n, const char *const 
 int dd_exact_cover_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
                           const int32_t *target, int nt, uint64_t window, uint32_t clip,
                           const uint64_t *off, uint32_t *counts, uint64_t *found);
+/* ---- samples explained by the inputs of the universe, one by one ------------------------------------------------------
+ * Every call above counts each input against the whole sample, independently: a sample that holds g3 shows a large
+ * containment in g3's close relative too.  This says how FEW inputs explain what a sample shares with the universe, and in
+ * what proportions (dd_exact_gather.hip): the greedy minimum set cover over the sample's k-mers, exact, integers only.
+ * For one sample: H is the set of distinct k-mers r of the universe that the sample holds, d_r = c[s][r] > 0 the depth
+ * dd_exact_depth counts; bit b of mask_r is input b.  taken_0 = 0, and at step t = 0, 1, ... for every input b
+ *     U_t[b] = #{ r in H : mask_r & taken_t == 0 and bit b of mask_r }
+ * The pick is b* = argmax_b U_t[b], ties to the LOWEST b.  The walk stops when U_t[b*] < min_hits or t == steps; otherwise
+ * taken_{t+1} = taken_t | 1 << b* and
+ *   pick[s][t]    b*
+ *   unique[s][t]  U_t[b*]: the k-mers of the sample that b* holds and no earlier pick does; it never increases along t
+ *   depth[s][t]   the sum of d_r over exactly those k-mers
+ * and behind the stop pick = -1, unique = 0, depth = 0.  By-products of the first step:
+ *   shared[s][b]  U_0[b], dd_exact_screen's shared[s][b]
+ *   total[s][0]   |H|;  total[s][1]  the sum of d_r over H  (with min_hits == 1 and steps == n the sums of unique[s] and of
+ *                 depth[s] equal them)
+ *   *found        the distinct k-mers of the universe
+ * An input that duplicates an earlier pick is never picked.  ONE k per call, 1 <= k <= 64, 1 <= n <= 64 universe inputs,
+ * 1 <= ns <= 1024 samples; then min_hits >= 1; then 1 <= steps <= n; then no output may be null; then, in the device form,
+ * the buffers, and a sample of 2^32 bytes or more is DD_EINVAL (dd_exact_depth's counter).  A universe that holds no k-mer,
+ * an empty sample and a sample that shares nothing give every pick = -1 and zeros.  Nothing is written unless the call
+ * returns DD_OK; two calls on the same inputs return identical bytes (integer sums).  The device form takes n + ns buffers:
+ * the n universe inputs first, the ns samples behind them.
+ * The sort, the masks, the emission, the ordering and the counters are dd_exact_depth's, so are budget and passes
+ * (DD_EXACT_MB), dd_last_sketch_stats' third value and the DD_KERNEL_EXACT timer.  The walk runs on the device, one pass
+ * over the sample's counters and one pick per step, with no host round trip inside it; the samples are taken in rounds: as
+ * many as DD_DEPTH_MB (dd_exact_depth's variable) holds of found x 4 bytes of counters and the few hundred bytes of a walk
+ * each.  A budget that does not hold one sample, or memory that cannot be had, is DD_ENOMEM with a message naming the bytes. */
+int dd_exact_gather(dd_ctx *, const char *const *paths, int n, const char *const *samples, int ns, int k,
+                    uint32_t min_hits, int steps, int32_t *pick /*[ns][steps]*/, uint64_t *unique /*[ns][steps]*/,
+                    uint64_t *depth /*[ns][steps]*/, uint64_t *shared /*[ns][n]*/, uint64_t *total /*[ns][2]*/,
+                    uint64_t *found);
+int dd_exact_gather_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int ns, int k,
+                           uint32_t min_hits, int steps, int32_t *pick, uint64_t *unique, uint64_t *depth,
+                           uint64_t *shared, uint64_t *total, uint64_t *found);
 /* ---- the membership-pattern table ------------------------------------------------------------------------------
  * Which sets of inputs share k-mers, and how many: the DISTINCT membership masks of the universe with their multiplicities
  * (the table behind an UpSet plot; every other mask statistic above -- spectrum, select, a subset union -- is a sum over
@@ -535,7 +570,7 @@ int dd_exact_greedy_device(dd_ctx *, const uint8_t *const *fasta_dev, const size
 #define DD_KERNEL_PACK 0
 #define DD_KERNEL_SWEEP 1
 #define DD_KERNEL_UNION 2
-#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen; the emission, ordering and window walk of dd_exact_paint; the emission, ordering, row walk and vote of dd_exact_reads; the emission, ordering, counting walk and depth tally of dd_exact_depth (every round); the accumulation, merges and ordering of dd_exact_patterns */
+#define DD_KERNEL_EXACT 3 /* extract + sort + count / reduce + accumulate of dd_exact_count* and the dd_exact_* schedules; the steps of dd_exact_greedy; the emission and ordering of dd_exact_select_kmers; the emission, ordering and lookup of dd_exact_locate; the same and the tally of dd_exact_screen; the emission, ordering and window walk of dd_exact_paint; the emission, ordering, row walk and vote of dd_exact_reads; the emission, ordering, counting walk and depth tally of dd_exact_depth (every round); the same walk, the index and the window gather of dd_exact_cover; the same walk and the passes and picks of dd_exact_gather; the accumulation, merges and ordering of dd_exact_patterns */
 #define DD_KERNEL_COUNT 4 /* the number of timed kinds, not a kind */
 int dd_timing_enable(dd_ctx *, int on);
 int dd_timing_read(dd_ctx *, int which, double *total_ms, int *launches);
