@@ -28,6 +28,10 @@
 // of the register ranges are stored (plain, coalesced, in the accumulator layout) and summed by gram_finish_kernel, which also
 // turns F into the histogram layout dd_union.hip's kernels write: hist[((i * n) + j) * K + kk][64], i <= j.
 //
+// The RECTANGLE of two slabs (dd_cross: new samples against a resident leaf slab, `dandd neighbors`) is the same contraction
+// with X_v taken from slab A on one side and from slab B on the other: cross_kernel and cross_finish_kernel, at the end of the
+// kernels below, share everything above with the square but the address of a stage row and the triangle rule.
+//
 // Round 3 (MI355X, 64 sketches of 2^20 registers x 31 k, ~30 thresholds per column; profiles/r03_k2_gram.txt): 2.2 ms for the
 // Gram kernel, 0.38 ms for the range pass (the slab read once at 5.6 TB/s), 0.11 ms for the finish; 14.0 ms for the streaming
 // kernel.  Round 5 (profiles/r05_k2_gram.txt):
@@ -105,7 +109,11 @@ __global__ __launch_bounds__(256) void gram_range_kernel(const uint8_t* __restri
 //   kDiag2  (round 5, n > 64) the 128 rows of super-blocks 2u, 2u + 1 against themselves: the ten blocks i <= j of its 4 x 4
 //           quarters.  A thresholded operand serves five matrix instructions instead of three (kDiag) or two (kOff): 3.2
 //           thresholding instructions per MFMA instead of 5.3 / 8 on the issue port the two share.
-enum { kOff = 0, kDiag = 1, kDiag2 = 2 };
+//   kCross  (dd_cross) the 64 rows of block P of slab A against the 64 rows of block Q of slab B, every (P, Q): kOff's four blocks
+//           and kOff's stage, with the first 64 rows of a stage from A and the others from B
+//   kCrossHalf  the same for a P block with at most 32 live rows (one to a few samples): no second A operand, blocks (0,0), (0,1),
+//           a stage of 96 rows, and room for five thresholds per wave instead of three
+enum { kOff = 0, kDiag = 1, kDiag2 = 2, kCross = 3, kCrossHalf = 4 };
 
 // unit number sp -> (P, Q): kDiag (sp, sp); kDiag2 (2 sp, 2 sp + 1); kOff counts P < Q row by row -- with `paired`, without the
 // pairs (2 u, 2 u + 1), which are inside the kDiag2 units
@@ -138,9 +146,11 @@ DD_D v4i threshold16(const uint4& x, uint32_t thr) {
 }
 template <int SHAPE>
 struct GramShape {
-    static constexpr int TS = SHAPE == kDiag ? 4 : SHAPE == kOff ? 3 : 1;   // thresholds per wave at most: TS x NB x 16 = 192 (160) accumulator registers, two waves per SIMD
-    static constexpr int NB = SHAPE == kDiag ? 3 : SHAPE == kOff ? 4 : 10;  // 32 x 32 blocks per wave
-    static constexpr int NH = SHAPE == kDiag ? 2 : 4;                       // 32-row operand sets of a stage
+    static constexpr int TS = SHAPE == kDiag ? 4 : SHAPE == kOff || SHAPE == kCross ? 3 : SHAPE == kCrossHalf ? 5 : 1;   // thresholds per wave at most: TS x NB x 16 = 192 (160) accumulator registers, two waves per SIMD
+    // (kCrossHalf: 6 x 2 x 16 = 192 as kDiag holds would fit by count, but its three operand sets of a stage -- kDiag reads two -- push
+    // a gfx950 compile to 12 bytes of scratch per lane; 5 gives 225 registers and none)
+    static constexpr int NB = SHAPE == kDiag ? 3 : SHAPE == kOff || SHAPE == kCross ? 4 : SHAPE == kCrossHalf ? 2 : 10;  // 32 x 32 blocks per wave
+    static constexpr int NH = SHAPE == kDiag ? 2 : SHAPE == kCrossHalf ? 3 : 4;                      // 32-row operand sets of a stage
     // waves of a workgroup: they stream the same rows and have their own thresholds.  kDiag2's one threshold per wave is too
     // little work per byte streamed for four (the LDS-DMA issue and the L2 -> LDS traffic set its pace: 20 matrix instructions per
     // two DMAs of a wave): eight waves, one workgroup per CU, one DMA per wave and stage
@@ -176,13 +186,16 @@ DD_D void gram_body(const uint8_t* const* src, uint8_t* ring, uint32_t ring_lds,
     constexpr int NH = GramShape<SHAPE>::NH; // 32-row operand sets of a stage
     constexpr bool DIAG = SHAPE == kDiag;
     constexpr int WAVES = GramShape<SHAPE>::WAVES;
-    constexpr int G = NH * 2 / WAVES;        // DMAs per wave and stage: NH * 2 groups of 16 rows over the waves
+    constexpr bool HALF = SHAPE == kCrossHalf;
+    constexpr int G = (NH * 2 + WAVES - 1) / WAVES;   // DMAs per wave and stage: NH * 2 groups of 16 rows over the waves
     constexpr int STAGE = NH * 32 * 64;      // bytes
     constexpr int NA = NT ? NT : 1;
+    // (kCrossHalf: six groups over four waves -- waves 0 and 1 have two DMAs per stage, waves 2 and 3 one)
     auto issue = [&](int s) {
         uint8_t* dst = ring + (s % kRingSlots) * STAGE;
 #pragma unroll
-        for (int g = 0; g < G; ++g) glds16(src[g] + (size_t)s * 64, dst + (wave + WAVES * g) * 1024);
+        for (int g = 0; g < G; ++g)
+            if (!HALF || wave + WAVES * g < NH * 2) glds16(src[g] + (size_t)s * 64, dst + (wave + WAVES * g) * 1024);
     };
     v16i acc[NA][NB];
 #pragma unroll
@@ -197,7 +210,9 @@ DD_D void gram_body(const uint8_t* const* src, uint8_t* ring, uint32_t ring_lds,
 
     for (int s = 0; s < kRingDepth && s < nst; ++s) issue(s);
     for (int i = 0; i < nst; ++i) {
-        if (nst - i >= kRingDepth)
+        if (HALF && nst - i >= kRingDepth && wave >= 2)
+            wait_vm<kRingDepth - 1>();         // (a wave with one DMA per stage)
+        else if (nst - i >= kRingDepth)
             wait_vm<(kRingDepth - 1) * G>();   // this wave's DMAs of stage i have landed ...
         else
             wait_vm<0>();
@@ -212,6 +227,14 @@ DD_D void gram_body(const uint8_t* const* src, uint8_t* ring, uint32_t ring_lds,
             asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:512\n\tds_read_b128 %2, %4 offset:2048\n\t"
                          "ds_read_b128 %3, %4 offset:2560\n\ts_waitcnt lgkmcnt(0)"
                          : "=&v"(raw[0][0]), "=&v"(raw[1][0]), "=&v"(raw[0][1]), "=&v"(raw[1][1])
+                         : "v"(st)
+                         : "memory");
+        else if (HALF)
+            asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %6 offset:512\n\tds_read_b128 %2, %6 offset:2048\n\t"
+                         "ds_read_b128 %3, %6 offset:2560\n\tds_read_b128 %4, %6 offset:4096\n\tds_read_b128 %5, %6 offset:4608\n\t"
+                         "s_waitcnt lgkmcnt(0)"
+                         : "=&v"(raw[0][0]), "=&v"(raw[1][0]), "=&v"(raw[0][1]), "=&v"(raw[1][1]), "=&v"(raw[0][2 % NH]),
+                           "=&v"(raw[1][2 % NH])
                          : "v"(st)
                          : "memory");
         else
@@ -242,6 +265,10 @@ DD_D void gram_body(const uint8_t* const* src, uint8_t* ring, uint32_t ring_lds,
 #pragma unroll
                     for (int q = 0; q < NB; ++q)
                         acc[t][q] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[diag2_bi(q)], a[diag2_bj(q)], acc[t][q], 0, 0, 0);
+                } else if (HALF) {
+                    const v4i a0 = threshold16(x[0], thr), b0 = threshold16(x[1], thr), b1 = threshold16(x[2 % NH], thr);
+                    acc[t][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc[t][0], 0, 0, 0);
+                    acc[t][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b1, acc[t][1], 0, 0, 0);
                 } else {
                     const v4i a0 = threshold16(x[0], thr), a1 = threshold16(x[1], thr);
                     const v4i b0 = threshold16(x[2], thr), b1 = threshold16(x[3], thr);
@@ -262,28 +289,19 @@ DD_D void gram_body(const uint8_t* const* src, uint8_t* ring, uint32_t ring_lds,
             for (int e = 0; e < 16; ++e) gstore4(out + ((size_t)t * NB + q) * 1024 + e * 64, (uint32_t)acc[t][q][e] >> 14);
 }
 
-// part[(((unit_sp * K + k) * RR + rr) * slots + slot) * NB * 1024 + block * 1024 + reg * 64 + lane], slot = threshold - vmin_k
-template <int SHAPE, int TS>
-__global__ __launch_bounds__(GramShape<SHAPE>::WAVES * 64, 8 / GramShape<SHAPE>::WAVES) void gram_kernel(const uint8_t* __restrict__ leaf, int n, int K, int p,
-                                                      const uint32_t* __restrict__ rng, int sp_base, int ns,
-                                                      int RR, int len, int slots, int units, int units_sp, int paired, uint32_t* __restrict__ part) {
-    constexpr int NB = GramShape<SHAPE>::NB;
-    constexpr int NH = GramShape<SHAPE>::NH;
-    constexpr int WAVES = GramShape<SHAPE>::WAVES;
-    constexpr int G = NH * 2 / WAVES;
-    constexpr int STAGE = NH * 32 * 64;
-    __shared__ __attribute__((aligned(1024))) uint8_t ring[kRingSlots * STAGE];
-    const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)ring;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // blockIdx -> (unit, k, register range, workgroup of the column): a column's thresholds vmin .. vmax-1 (F = 0 below vmin, m from
+// what one wave of workgroup `item` of a launch does: unit sp of the launch, column k, register range rr, thresholds
+// vmin + slot0 .. + nthr - 1.  false: a workgroup id beyond the workgroups there are.
+struct GramWork { int sp, k, rr, vmin, slot0, nthr; };
+template <int WAVES, int TS>
+DD_D bool gram_work(int item, int units, int K, const uint32_t* __restrict__ rng, int RR, int units_sp, int lane, int wave, GramWork& w) {
+    // item -> (unit, k, register range, workgroup of the column): a column's thresholds vmin .. vmax-1 (F = 0 below vmin, m from
     // vmax on) -- T of them -- are shared out over nq = ceil(T / (WAVES TS)) workgroups and the waves of each (one or two waves per
     // SIMD: the matrix pipes of a CU finish together).  The ids are COMPACT: the grid is sized for the widest column a sketch can
     // have (`quads` workgroups), the ids beyond the workgroups there really are leave at once, and they are the LAST ids.  Round 4
     // gave every column `quads` ids and let the unused ones leave: workgroups go round the XCDs (and the shader engines inside one)
     // in id order, a periodic pattern of empty ids leaves some of them with less work for the whole launch -- the off-diagonal
     // kernel (3 of 4 ids used) ran on six of the eight XCDs (profiles/r05_k2_gram.txt).
-    int item = blockIdx.x;
-    if (item >= units) return;
+    if (item >= units) return false;
     int k = -1, nq = 0, before_k = 0, vmin = 0, T = 0, sp = 0;
     {
         // workgroups of one unit: RR x sum_k nq_k; columns in chunks of 64 (one wave computes the running sums)
@@ -301,9 +319,9 @@ __global__ __launch_bounds__(GramShape<SHAPE>::WAVES * 64, 8 / GramShape<SHAPE>:
             per_unit += __shfl(incl, 63);
         }
         per_unit *= RR;
-        if (per_unit == 0) return;                     // (every column constant: nothing to count)
+        if (per_unit == 0) return false;               // (every column constant: nothing to count)
         sp = item / per_unit;
-        if (sp >= units_sp) return;                    // (uniform: past the last workgroup there is)
+        if (sp >= units_sp) return false;              // (uniform: past the last workgroup there is)
         int r = item - sp * per_unit, base = 0;
         for (int c0 = 0; c0 < K && k < 0; c0 += 64) {
             const int kk = c0 + lane;
@@ -340,6 +358,26 @@ __global__ __launch_bounds__(GramShape<SHAPE>::WAVES * 64, 8 / GramShape<SHAPE>:
     const int slot0 = q0 + wave * per;                                   // first threshold of this wave, relative to vmin
     const int left = mine_all - wave * per;
     const int nthr = __builtin_amdgcn_readfirstlane(left < per ? (left > 0 ? left : 0) : per);
+    w = {sp, k, rr, vmin, slot0, nthr};
+    return true;
+}
+
+// part[(((unit_sp * K + k) * RR + rr) * slots + slot) * NB * 1024 + block * 1024 + reg * 64 + lane], slot = threshold - vmin_k
+template <int SHAPE, int TS>
+__global__ __launch_bounds__(GramShape<SHAPE>::WAVES * 64, 8 / GramShape<SHAPE>::WAVES) void gram_kernel(const uint8_t* __restrict__ leaf, int n, int K, int p,
+                                                      const uint32_t* __restrict__ rng, int sp_base, int ns,
+                                                      int RR, int len, int slots, int units, int units_sp, int paired, uint32_t* __restrict__ part) {
+    constexpr int NB = GramShape<SHAPE>::NB;
+    constexpr int NH = GramShape<SHAPE>::NH;
+    constexpr int WAVES = GramShape<SHAPE>::WAVES;
+    constexpr int G = NH * 2 / WAVES;
+    constexpr int STAGE = NH * 32 * 64;
+    __shared__ __attribute__((aligned(1024))) uint8_t ring[kRingSlots * STAGE];
+    const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)ring;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    GramWork w;
+    if (!gram_work<WAVES, TS>(blockIdx.x, units, K, rng, RR, units_sp, lane, wave, w)) return;
+    const int sp = w.sp, k = w.k, rr = w.rr, vmin = w.vmin, slot0 = w.slot0, nthr = w.nthr;
     const int2 PQ = gram_pair<SHAPE>(sp_base + sp, ns, paired);
     // this lane's DMA sources: rows 16 (wave + 4 g) + lane % 16 of the stage, chunk lane / 16
     const uint8_t* src[G];
@@ -357,6 +395,50 @@ __global__ __launch_bounds__(GramShape<SHAPE>::WAVES * 64, 8 / GramShape<SHAPE>:
 #define DD_GRAM_CASE(NT) \
     case NT: gram_body<SHAPE, (NT <= TS ? NT : 0)>(src, ring, ring_lds, wave, lane, nst, thr0, out); break;   // (NT > TS never occurs)
         DD_GRAM_CASE(1) DD_GRAM_CASE(2) DD_GRAM_CASE(3) DD_GRAM_CASE(4)
+#undef DD_GRAM_CASE
+        default: gram_body<SHAPE, 0>(src, ring, ring_lds, wave, lane, nst, thr0, out); break;
+    }
+}
+
+// The rectangle (dd_cross): unit sp_base + sp = P * nsb + Q is block P of slab a (na rows) against block Q of slab b (nb rows,
+// nsb blocks).  The workgroup ids, the ring and the partial counts are gram_kernel's; rng covers BOTH slabs (a threshold below
+// the smaller slab's smallest register still counts the other slab's rows).  SHAPE kCross: 64 x 64 pairs; kCrossHalf: the P
+// block's first 32 rows only, for a block with no live row beyond them.
+template <int SHAPE>
+__global__ __launch_bounds__(256, 2) void cross_kernel(const uint8_t* __restrict__ a, int na, const uint8_t* __restrict__ b, int nb, int K, int p,
+                                                      const uint32_t* __restrict__ rng, int sp_base, int nsb,
+                                                      int RR, int len, int slots, int units, int units_sp, uint32_t* __restrict__ part) {
+    constexpr int TS = GramShape<SHAPE>::TS;
+    constexpr int NB = GramShape<SHAPE>::NB;
+    constexpr int NH = GramShape<SHAPE>::NH;
+    constexpr int WAVES = GramShape<SHAPE>::WAVES;
+    constexpr int G = (NH * 2 + WAVES - 1) / WAVES;
+    constexpr int STAGE = NH * 32 * 64;
+    constexpr int AROWS = SHAPE == kCrossHalf ? 32 : 64;   // rows of a stage that come from slab a
+    __shared__ __attribute__((aligned(1024))) uint8_t ring[kRingSlots * STAGE];
+    const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)ring;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    GramWork w;
+    if (!gram_work<WAVES, TS>(blockIdx.x, units, K, rng, RR, units_sp, lane, wave, w)) return;
+    const int P = (sp_base + w.sp) / nsb, Q = (sp_base + w.sp) - P * nsb;
+    const uint8_t* src[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        int srow = 16 * (wave + WAVES * g) + (lane & 15);
+        srow = srow < NH * 32 ? srow : 0;     // (kCrossHalf, waves 2 and 3: no second DMA; any valid row)
+        const bool in_a = srow < AROWS;
+        int row = in_a ? (P << 6) + srow : (Q << 6) + srow - AROWS;
+        const int rows = in_a ? na : nb;
+        row = row < rows ? row : rows - 1;    // rows beyond the slab: any valid row, their counts are never read
+        src[g] = (in_a ? a : b) + (((size_t)row * K + w.k) << p) + (size_t)w.rr * (size_t)len + (size_t)(lane >> 4) * 16;
+    }
+    const uint32_t thr0 = (uint32_t)(0x80 + w.vmin + w.slot0) * 0x01010101u;
+    uint32_t* out = part + ((((size_t)w.sp * K + w.k) * RR + w.rr) * slots + w.slot0) * (size_t)(NB * 1024) + lane;
+    const int nst = len >> 6;
+    switch (w.nthr) {
+#define DD_GRAM_CASE(NT) \
+    case NT: gram_body<SHAPE, (NT <= TS ? NT : 0)>(src, ring, ring_lds, wave, lane, nst, thr0, out); break;   // (NT > TS never occurs)
+        DD_GRAM_CASE(1) DD_GRAM_CASE(2) DD_GRAM_CASE(3) DD_GRAM_CASE(4) DD_GRAM_CASE(5)
 #undef DD_GRAM_CASE
         default: gram_body<SHAPE, 0>(src, ring, ring_lds, wave, lane, nst, thr0, out); break;
     }
@@ -402,6 +484,44 @@ __global__ __launch_bounds__(256) void gram_finish_kernel(const uint32_t* __rest
         if (i >= n || j >= n || i > j) continue;
         const uint32_t f = F[e][lane], prev = lane ? F[e][lane - 1] : 0u;
         gstore4(hist + (((size_t)i * n + j) * K + k) * 64 + lane, f - prev);
+    }
+}
+
+// gram_finish_kernel for the rectangle: hist[((i * nb) + j) * K + k][64] for every row i < na of a and j < nb of b -- no
+// triangle, no mirror; rows of padding are never written.  half: the partial counts of cross_kernel<kCrossHalf>.
+__global__ __launch_bounds__(256) void cross_finish_kernel(const uint32_t* __restrict__ part, int na, int nb, int K, int p,
+                                                           const uint32_t* __restrict__ rng, int half, int sp_base, int nsb,
+                                                           int RR, int slots, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t F[64][65];   // [entry][threshold]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int NB = half ? 2 : 4;
+    int b = blockIdx.x;
+    const int reg = b & 15;
+    b >>= 4;
+    const int block = b % NB;
+    b /= NB;
+    const int k = b % K;
+    const int sp = b / K;
+    const int P = (sp_base + sp) / nsb, Q = (sp_base + sp) - P * nsb;
+    const int vmin = (int)rng[2 * k], vmax = (int)rng[2 * k + 1];
+    const uint32_t m = 1u << p;
+    const uint32_t* src = part + ((size_t)sp * K + k) * RR * slots * (size_t)(NB * 1024) + (size_t)block * 1024 + reg * 64 + lane;
+    for (int v = wave; v < 64; v += 4) {
+        uint32_t f = v < vmin ? 0u : m;
+        if (v >= vmin && v < vmax) {
+            f = 0;
+            for (int rr = 0; rr < RR; ++rr) f += gload4(src + ((size_t)rr * slots + (size_t)(v - vmin)) * (size_t)(NB * 1024));
+        }
+        F[lane][v] = f;
+    }
+    __syncthreads();
+    const int bi = half ? 0 : block >> 1, bj = half ? block : block & 1;
+    for (int e = wave; e < 64; e += 4) {
+        const int i = (P << 6) + bi * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (e >> 5);
+        const int j = (Q << 6) + bj * 32 + (e & 31);
+        if (i >= na || j >= nb) continue;
+        const uint32_t f = F[e][lane], prev = lane ? F[e][lane - 1] : 0u;
+        gstore4(hist + (((size_t)i * nb + j) * K + k) * 64 + lane, f - prev);
     }
 }
 
@@ -479,6 +599,62 @@ void launch_pairwise_gram(const uint8_t* leaf_dev, int n, int K, int p, uint32_t
 #undef DD_GRAM_LAUNCH
             hipLaunchKernelGGL(gram_finish_kernel, dim3((unsigned)((size_t)cnt * K * nb * 16)), dim3(256), 0, st, part, n, K, p, rng,
                                shape, a, ns, RR, slots, d2 ? 1 : 0, hist_dev);
+        }
+    }
+}
+
+// ---- the rectangle: na rows of slab a against nb rows of slab b ---------------------------------------------------------
+bool cross_gram_usable(int p) { return p >= 12; }
+
+// rng_dev[2k], rng_dev[2k+1] = smallest / largest register of k column k over the rows of BOTH slabs
+void launch_cross_range(const uint8_t* a_dev, int na, const uint8_t* b_dev, int nb, int K, int p, uint32_t* rng_dev, hipStream_t st) {
+    const int pieces = (int)((((size_t)1 << p) + 65535) / 65536);
+    hipLaunchKernelGGL(gram_range_init_kernel, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, st, rng_dev, K);
+    hipLaunchKernelGGL(gram_range_kernel, dim3((unsigned)((size_t)na * K * pieces)), dim3(256), 0, st, a_dev, K, p, pieces, rng_dev);
+    hipLaunchKernelGGL(gram_range_kernel, dim3((unsigned)((size_t)nb * K * pieces)), dim3(256), 0, st, b_dev, K, p, pieces, rng_dev);
+}
+
+static size_t cross_rng_bytes(int K) { return ((size_t)K * 2 * sizeof(uint32_t) + 255) & ~(size_t)255; }
+
+// the ranges at the head, then the partial counts of as many units as fit ~1 GiB (at least one), in kCross's layout
+size_t cross_scratch_bytes(int na, int nb, int K, int p, int* sp_per_launch) {
+    const size_t total_sp = (size_t)((na + 63) / 64) * ((nb + 63) / 64);
+    const size_t RR = ((size_t)1 << p) / (size_t)gram_len((int)total_sp, K, p);
+    const size_t per_sp = (size_t)K * RR * (size_t)gram_slots(p) * GramShape<kCross>::NB * 1024 * sizeof(uint32_t);
+    size_t fit = ((size_t)1 << 30) / per_sp;
+    fit = fit < 1 ? 1 : fit > total_sp ? total_sp : fit;
+    if (sp_per_launch) *sp_per_launch = (int)fit;
+    return fit * per_sp + cross_rng_bytes(K);
+}
+
+// hist[((s * nb) + j) * K + k][64] for every s < na, j < nb; every word of it is written.  scratch: cross_scratch_bytes(),
+// its head as launch_cross_range left it for the slabs of the whole call (a_dev may be a round's rows of a larger slab).
+// A blocks of 64 rows take kCross; a last block of at most 32 rows -- the only one when na <= 32 -- takes kCrossHalf.
+void launch_cross_gram(const uint8_t* a_dev, int na, const uint8_t* b_dev, int nb, int K, int p, uint32_t* hist_dev, void* scratch,
+                       hipStream_t st) {
+    const int nsa = (na + 63) / 64, nsb = (nb + 63) / 64;
+    int sp_fit = 1;
+    (void)cross_scratch_bytes(na, nb, K, p, &sp_fit);
+    uint8_t* base = static_cast<uint8_t*>(scratch);
+    const uint32_t* rng = reinterpret_cast<const uint32_t*>(base);
+    uint32_t* part = reinterpret_cast<uint32_t*>(base + cross_rng_bytes(K));
+    const int slots = gram_slots(p);
+    const int len = gram_len(nsa * nsb, K, p);
+    const int RR = (int)(((size_t)1 << p) / (size_t)len);
+    const int nhalf = na - 64 * (nsa - 1) <= 32 ? 1 : 0;     // A blocks in the half-height form: the last one, or none
+    for (int half = 0; half <= 1; ++half) {
+        const int first = half ? (nsa - nhalf) * nsb : 0;    // units P * nsb + Q of this form: [first, first + total)
+        const int total = (half ? nhalf : nsa - nhalf) * nsb;
+        const int ts = half ? GramShape<kCrossHalf>::TS : GramShape<kCross>::TS;
+        const int quads = (slots + 4 * ts - 1) / (4 * ts);
+        for (int u = 0; u < total; u += sp_fit) {
+            const int cnt = std::min(sp_fit, total - u);
+            const int units = (int)((size_t)cnt * K * RR * quads);
+#define DD_CROSS_LAUNCH(S) hipLaunchKernelGGL(cross_kernel<S>, dim3((unsigned)units), dim3(256), 0, st, a_dev, na, b_dev, nb, K, p, rng, first + u, nsb, RR, len, slots, units, cnt, part)
+            if (half) DD_CROSS_LAUNCH(kCrossHalf); else DD_CROSS_LAUNCH(kCross);
+#undef DD_CROSS_LAUNCH
+            hipLaunchKernelGGL(cross_finish_kernel, dim3((unsigned)((size_t)cnt * K * (half ? 2 : 4) * 16)), dim3(256), 0, st, part, na, nb, K, p,
+                               rng, half, first + u, nsb, RR, slots, hist_dev);
         }
     }
 }

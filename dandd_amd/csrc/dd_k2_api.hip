@@ -1,5 +1,5 @@
 // dd_k2_api.hip -- the entry points of the C ABI (include/dandd_hip.h) that work on register slabs: union, card / hist and
-// the HLL schedules (progressive, pairwise, leave-out, subsets, extend, greedy).  Host-side orchestration only; the
+// the HLL schedules (progressive, pairwise, cross, leave-out, subsets, extend, greedy).  Host-side orchestration only; the
 // kernels are in dd_union, dd_pscan, dd_gram, dd_leaveout, dd_subsets and dd_extend.hip.
 //
 // Every schedule has ONE body.  It takes its slab as a Slab (the slab frame): the two extern "C" forms of an entry, at the
@@ -161,6 +161,57 @@ int pairwise(dd_ctx* c, Slab leaf, int n, int K, double* card) {
             const int a = i <= j ? i : j, b = i <= j ? j : i;
             memcpy(card + ((size_t)i * n + j) * K, tmp.data() + ((size_t)a * n + b) * K, sizeof(double) * K);
         }
+    return DD_OK;
+}
+
+// ------------------------------------------------------------------------------- cross
+// The rectangle: na rows of slab a against nb rows of slab b.  Each slab where it lies: a host slab a goes into c->regs, a host
+// slab b behind it (or to the head when a is in HBM already); a resident slab is read in place.  The na nb K histograms are
+// taken in rounds over a's 64-row blocks, as many blocks as DD_CROSS_HIST_MB (1024 when unset; read on every call) holds of
+// 64 nb K histograms -- one block at the least.
+int cross(dd_ctx* c, Slab a, int na, Slab b, int nb, int K, double* card) {
+    if (check_ctx(c)) return DD_EINVAL;
+    if (na < 1 || nb < 1 || K < 1 || !a.p || !b.p || !card) return fail(DD_EINVAL, "bad argument");
+    DeviceGuard guard(c->device);
+    const size_t abytes = ((size_t)na * K) << c->p, bbytes = ((size_t)nb * K) << c->p;
+    const uint8_t *a_dev, *b_dev;
+    int rc;
+    if ((rc = slab_dev(c, a, na, K, a_dev, b.host ? bbytes : 0))) return rc;
+    if (b.host && a.host) {
+        uint8_t* behind = static_cast<uint8_t*>(c->regs.p) + abytes;
+        DD_HIP(hipMemcpyAsync(behind, b.p, bbytes, hipMemcpyHostToDevice, c->stream));
+        b_dev = behind;
+    } else if ((rc = slab_dev(c, b, nb, K, b_dev))) {
+        return rc;
+    }
+    // the Gram form on the matrix cores (dd_gram.hip); DD_CROSS_STREAM=1 keeps the streaming kernel of dd_union.hip for A/B
+    // runs and for the equality test
+    const bool gram = dd::cross_gram_usable(c->p) && !getenv("DD_CROSS_STREAM");
+    c->k2_path = gram ? DD_K2_CROSS_GRAM : DD_K2_CROSS_STREAM;
+    const char* mb = getenv("DD_CROSS_HIST_MB");
+    const size_t budget = (size_t)(mb && atol(mb) > 0 ? atol(mb) : 1024) << 20;
+    const size_t per_block = (size_t)64 * nb * K * 64 * sizeof(uint32_t);
+    const int rows = 64 * (int)std::min<size_t>(std::max<size_t>(budget / per_block, 1), ((size_t)na + 63) / 64);   // of a, per round
+    if (gram) {   // (the first round is the largest in units, the last one may split its rows finer: room for either)
+        const int last = na % rows ? na % rows : rows;
+        if ((rc = c->gram.reserve(std::max(dd::cross_scratch_bytes(std::min(rows, na), nb, K, c->p, nullptr),
+                                           dd::cross_scratch_bytes(last, nb, K, c->p, nullptr)))))
+            return rc;
+    }
+    for (int s0 = 0; s0 < na; s0 += rows) {
+        const int cnt = std::min(rows, na - s0);
+        const uint8_t* a_round = a_dev + (((size_t)s0 * K) << c->p);
+        rc = hist_step(c, (size_t)cnt * nb * K, nullptr, 0, card + (size_t)s0 * nb * K, [&](uint32_t* hist, const int32_t*) {
+            if (!gram) {
+                dd::launch_cross_stream(a_round, cnt, b_dev, nb, K, c->p, hist, c->stream);
+                return DD_OK;
+            }
+            if (s0 == 0) dd::launch_cross_range(a_dev, na, b_dev, nb, K, c->p, static_cast<uint32_t*>(c->gram.p), c->stream);
+            dd::launch_cross_gram(a_round, cnt, b_dev, nb, K, c->p, hist, c->gram.p, c->stream);
+            return DD_OK;
+        });
+        if (rc) return rc;
+    }
     return DD_OK;
 }
 
@@ -346,6 +397,15 @@ int dd_progressive_device(dd_ctx* c, const uint8_t* leaf_dev, int n, int K, cons
 }
 int dd_pairwise(dd_ctx* c, const uint8_t* leaf, int n, int K, double* card) { return pairwise(c, {leaf, true}, n, K, card); }
 int dd_pairwise_device(dd_ctx* c, const uint8_t* dev, int n, int K, double* card) { return pairwise(c, {dev, false}, n, K, card); }
+int dd_cross(dd_ctx* c, const uint8_t* a, int na, const uint8_t* b, int nb, int K, double* card) {
+    return cross(c, {a, true}, na, {b, true}, nb, K, card);
+}
+int dd_cross_device(dd_ctx* c, const uint8_t* a_dev, int na, const uint8_t* b_dev, int nb, int K, double* card) {
+    return cross(c, {a_dev, false}, na, {b_dev, false}, nb, K, card);
+}
+int dd_cross_host_device(dd_ctx* c, const uint8_t* a, int na, const uint8_t* b_dev, int nb, int K, double* card) {
+    return cross(c, {a, true}, na, {b_dev, false}, nb, K, card);
+}
 int dd_leave_out(dd_ctx* c, const uint8_t* leaf, int n, int K, const int32_t* group, int ngroups, double* card) {
     return leave_out(c, {leaf, true}, n, K, group, ngroups, card);
 }

@@ -112,6 +112,37 @@ __global__ __launch_bounds__(1024) void pairwise_kernel(const uint8_t* __restric
     }
 }
 
+// the rectangle (dd_cross): one workgroup per (s, k, tile) -- row s of slab a against every row j of slab b
+template <int PC>
+__global__ __launch_bounds__(1024) void cross_stream_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, int nb,
+                                                            int K, int p, int tiles, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t h[kHistWords];
+    const int tile = blockIdx.x % tiles;
+    const int kk = (blockIdx.x / tiles) % K;
+    const int s = blockIdx.x / tiles / K;
+    const size_t m16 = ((size_t)1 << p) >> 4;
+    const size_t piece = (size_t)tile * blockDim.x * PC + threadIdx.x;
+    uint4 mine[PC];
+#pragma unroll
+    for (int q = 0; q < PC; ++q) {
+        mine[q] = make_uint4(0, 0, 0, 0);
+        if (piece + (size_t)q * blockDim.x < m16)
+            mine[q] = reinterpret_cast<const uint4*>(a + (((size_t)s * K + kk) << p))[piece + (size_t)q * blockDim.x];
+    }
+    for (int j = 0; j < nb; ++j) {
+        hist_zero(h);
+        __syncthreads();
+        const uint8_t* src = b + (((size_t)j * K + kk) << p);
+#pragma unroll
+        for (int q = 0; q < PC; ++q)
+            if (piece + (size_t)q * blockDim.x < m16)
+                hist_add16(h, bmax16(mine[q], reinterpret_cast<const uint4*>(src)[piece + (size_t)q * blockDim.x]));
+        __syncthreads();
+        hist_flush(h, hist + (((size_t)s * nb + j) * K + kk) * 64, tiles == 1);
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(256) void mle_kernel(const uint32_t* __restrict__ hist, size_t njobs,
                                                   int p, double relerr, double* __restrict__ est) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -177,6 +208,12 @@ void launch_pairwise(const uint8_t* leaf_dev, int n, int K, int p, uint32_t* his
     if (n <= 0 || K <= 0) return;
     (void)hipMemsetAsync(hist_dev, 0, (size_t)n * n * K * 64 * sizeof(uint32_t), st);
     launch_pc(pairwise_kernel<4>, pairwise_kernel<1>, p, (size_t)n * K, st, leaf_dev, n, K, p, tiles_for(p), hist_dev);
+}
+
+void launch_cross_stream(const uint8_t* a_dev, int na, const uint8_t* b_dev, int nb, int K, int p, uint32_t* hist_dev, hipStream_t st) {
+    if (na <= 0 || nb <= 0 || K <= 0) return;
+    if (tiles_for(p) > 1) (void)hipMemsetAsync(hist_dev, 0, (size_t)na * nb * K * 64 * sizeof(uint32_t), st);
+    launch_pc(cross_stream_kernel<4>, cross_stream_kernel<1>, p, (size_t)na * K, st, a_dev, b_dev, nb, K, p, tiles_for(p), hist_dev);
 }
 
 void launch_mle(const uint32_t* hist_dev, size_t njobs, int p, double* est_dev, hipStream_t st) {

@@ -26,6 +26,7 @@ EXPORTS = [
     "dd_sketch_buffer", "dd_sketch_fasta", "dd_sketch_files", "dd_inflate_files", "dd_last_ingest_stats", "dd_sketch_device", "dd_union", "dd_union_device",
     "dd_card", "dd_card_batch", "dd_card_batch_device", "dd_hist_batch_device", "dd_ertl_mle",
     "dd_progressive", "dd_progressive_device", "dd_pairwise", "dd_pairwise_device", "dd_leave_out", "dd_leave_out_device",
+    "dd_cross", "dd_cross_device", "dd_cross_host_device",
     "dd_subsets", "dd_subsets_device", "dd_extend", "dd_extend_device", "dd_greedy", "dd_greedy_device",
     "dd_exact_count", "dd_exact_count_device",
     "dd_exact_pairwise", "dd_exact_progressive", "dd_exact_leave_out", "dd_exact_subsets",
@@ -137,6 +138,10 @@ def load_library(path=None):
             fn = getattr(lib, name + suffix)
             fn.restype = i32
             fn.argtypes = [vp] + args
+    for name in ("dd_cross", "dd_cross_device", "dd_cross_host_device"):   # two slabs: a and b in host memory, in HBM, or a host / b HBM
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = [vp, vp, i32, vp, i32, i32, vp]
     lib.dd_card.restype = i32
     lib.dd_card.argtypes = [vp, vp, C.POINTER(C.c_double)]
     lib.dd_hist_batch_device.restype = i32
@@ -710,6 +715,30 @@ class Engine:
     def pairwise_device(self, leaf_ptr, n, K):
         return self._pairwise(self._slab_src(None, leaf_ptr, n, K))
 
+    def _cross(self, entry, a, na, b, nb, K):
+        card = np.empty((max(na, 0), max(nb, 0), max(K, 0)), dtype=np.float64)
+        self._check(getattr(self._lib, entry)(self._ctx, a, na, b, nb, K, card.ctypes.data))
+        return card
+
+    def cross(self, a, b):
+        """a [na][K][m], b [nb][K][m] uint8 (host) -> card [na][nb][K] float64: |a_s U b_j| at every k column."""
+        a, b = _u8(a), _u8(b)
+        if a.ndim != 3 or b.ndim != 3 or a.shape[1:] != b.shape[1:]:
+            raise ValueError("cross: a and b must be [rows][K][m] slabs of the same K and m")
+        return self._cross("dd_cross", a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], a.shape[1])
+
+    def cross_device(self, a_ptr, na, b_ptr, nb, K):
+        """The same with both slabs in device memory."""
+        return self._cross("dd_cross_device", C.c_void_p(int(a_ptr or 0)), int(na), C.c_void_p(int(b_ptr or 0)), int(nb), int(K))
+
+    def cross_host_device(self, a, b_ptr, nb):
+        """a [na][K][m] uint8 (host) against a slab of nb rows that stays where it is in device memory: new samples against
+        a resident leaf slab."""
+        a = _u8(a)
+        if a.ndim != 3:
+            raise ValueError("cross: a must be a [rows][K][m] slab")
+        return self._cross("dd_cross_host_device", a.ctypes.data, a.shape[0], C.c_void_p(int(b_ptr or 0)), int(nb), a.shape[1])
+
     def leave_out(self, leaf, group, ngroups=None):
         """leaf [n][K][m] uint8 (host), group [n] int (-1: in every union) -> card [G+1][K] float64: row g the union of the
         leaves outside group g, row G the union of all.  G = max(group) + 1 unless given."""
@@ -1199,7 +1228,7 @@ class Engine:
         self._check(self._lib.dd_last_sketch_stats(self._ctx, C.byref(t), C.byref(u), C.byref(b)))
         return t.value, u.value, b.value
 
-    K2_PATHS = {0: None, 1: "progressive_stream", 2: "progressive_pscan", 3: "pairwise_stream", 4: "pairwise_gram"}
+    K2_PATHS = {0: None, 1: "progressive_stream", 2: "progressive_pscan", 3: "pairwise_stream", 4: "pairwise_gram", 5: "cross_stream", 6: "cross_gram"}
 
     def last_k2_path(self):
         """Which device form the last progressive / pairwise call took (include/dandd_hip.h: DD_K2_*)."""

@@ -718,6 +718,34 @@ class HipBackend:
         table = self.engine.pairwise_device(ptr, len(leaf_paths), len(leaf_paths[0]))
         return table[np.ix_(perm, perm)]
 
+    def sample_sketches(self, files, kmin, kmax):
+        """Sketches of files that are no leaves, for k = kmin..kmax: uint8 [ns][K][m], in memory only -- nothing is written,
+        nothing is remembered (FASTA / FASTQ, plain or gzip: the ingestion path of the leaves)."""
+        return self.engine.sketch_files(list(files), int(kmin), int(kmax))
+
+    def sample_cards(self, regs):
+        """the estimates of rows of registers that have no file: float64 [rows]"""
+        return self.engine.card_batch(regs)
+
+    def cross_cards(self, sample_regs, leaf_paths, merged=False):
+        """|sample_s U leaf_j| for every sample, every leaf and every k column: float64 [ns][n][K].  sample_regs: uint8
+        [ns][K][m], the samples' sketches over the leaves' k columns, from host memory; the leaves are the slab the other
+        schedules keep in HBM (a resident server's second command finds it there) and are read where they lie.
+        merged: the samples against ONE row, the union of the leaves -> [ns][1][K]; that row goes through host memory and
+        leaves the slab in HBM alone."""
+        sample_regs = np.ascontiguousarray(sample_regs, dtype=np.uint8)
+        n, K = len(leaf_paths), len(leaf_paths[0])
+        if sample_regs.ndim != 3 or sample_regs.shape[1:] != (K, 1 << self.log2m):
+            raise ValueError(f"cross_cards: samples of shape {sample_regs.shape}, expected [ns][{K}][{1 << self.log2m}]")
+        if merged:
+            slab = self._leaf_slab(leaf_paths)
+            row = slab[0] if n == 1 else self.engine.union([slab[i] for i in range(n)]).reshape(K, -1)
+            return self.engine.cross(sample_regs, row[None])
+        ptr, perm = self._device_slab(leaf_paths)
+        if ptr is None:
+            return self.engine.cross(sample_regs, self._leaf_slab(leaf_paths))
+        return self.engine.cross_host_device(sample_regs, ptr, n)[:, perm]
+
     def progressive_cards(self, leaf_paths, orderings):
         """|union of the first j+1 leaves of ordering o| : float64 [o][n][K]"""
         ptr, perm = self._device_slab(leaf_paths)

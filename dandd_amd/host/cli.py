@@ -1,6 +1,9 @@
-"""`dandd tree | progressive | kij | deltadelta | abba | greedy | core | screen | patterns` on the MI355X engine: same sub-commands, flags,
+"""`dandd tree | progressive | kij | deltadelta | abba | greedy | core | screen | patterns | neighbors` on the MI355X engine: same sub-commands, flags,
 defaults and output files as /root/reference/lib/dandd_cmd.py (flags :141-286, handlers :43-132); only the
-sketching backend differs.  (deltadelta, abba, greedy, core, screen and patterns are this package's own: the reference has none of them.)  Run as  python -m dandd_amd.host.cli <subcommand> ...
+sketching backend differs.  (deltadelta, abba, greedy, core, screen, patterns and neighbors are this package's own: the reference has none of them.)  Run as  python -m dandd_amd.host.cli <subcommand> ...
+`neighbors` places new samples in a tree of SKETCHES (any number of genomes): each sample's genomes by K-independent Jaccard
+(<prefix>.neighbors.csv), its two closest and what it would add to the collection's delta (<prefix>.neighbors_summary.csv), and
+with `--jaccard` every k's cardinalities (<prefix>.neighbors_j.csv); the tree's own files stay as they are.
 `screen --paint W` adds where along each sample the collection's k-mers lie: one row per window of W bases.
 `screen --reads` adds which genome each record of a sample -- a read, a contig -- belongs to and how many records go to each
 genome (<prefix>.reads_summary.csv); `--reads-calls` writes the call of every record too (<prefix>.reads.csv), and
@@ -819,6 +822,82 @@ def _reads_rows(samples, fastas, called):
     return profile, records
 
 
+NEIGHBORS_COLUMNS = {
+    "neighbors": ["sample", "fasta", "sample_delta", "sample_k", "genome_delta", "genome_k", "union_delta", "union_k", "KIJ", "rank"],
+    "neighbors_summary": ["sample", "sample_delta", "sample_k", "best_fasta", "best_KIJ", "second_fasta", "second_KIJ", "collection_delta",
+                          "with_sample_delta", "delta_added"],
+    "neighbors_j": ["sample", "fasta", "kval", "Scard", "Gcard", "SGcard", "jaccard"],
+}
+
+
+def _neighbor_rows(samples, fastas, res, top=None):
+    """neighbor_tables' cards -> the rows of <prefix>.neighbors.csv (per sample the genomes by KIJ = (delta_S + delta_G -
+    delta_SG) / delta_SG descending, ties in the universe's order, rank 1 first, the first `top` of them), of
+    .neighbors_summary.csv (one per sample: its two closest genomes, the collection's delta, the delta of the collection with
+    the sample, and their difference -- the sample's deltadelta as a newcomer) and of .neighbors_j.csv (kij's .j.csv for
+    the rectangle: per sample, genome and k the three cardinalities and their Jaccard)"""
+    rows, summary, jrows = [], [], []
+    for s, sample in enumerate(samples):
+        ds, ks_ = float(res["sample_delta"][s]), int(res["sample_k"][s])
+        kij = []
+        for j in range(len(fastas)):
+            dsg = float(res["pair_delta"][s, j])
+            kij.append((ds + float(res["genome_delta"][j]) - dsg) / dsg if dsg else 0.0)       # (an empty sample against an empty genome)
+        order = sorted(range(len(fastas)), key=lambda j: -kij[j])       # (stable: ties keep the universe's order)
+        for rank, j in enumerate(order[:top], 1):
+            rows.append([sample, fastas[j], ds, ks_, float(res["genome_delta"][j]), int(res["genome_k"][j]), float(res["pair_delta"][s, j]),
+                         int(res["pair_k"][s, j]), kij[j], rank])
+        second = (fastas[order[1]], kij[order[1]]) if len(order) > 1 else (None, None)
+        whole, joined = float(res["whole_delta"]), float(res["with_delta"][s])
+        summary.append([sample, ds, ks_, fastas[order[0]], kij[order[0]], *second, whole, joined, joined - whole])
+        for j, fasta in enumerate(fastas):
+            for kk, k in enumerate(res["ks"]):
+                a, b, ab = float(res["sample"][s, kk]), float(res["genome"][j, kk]), float(res["pair"][s, j, kk])
+                jrows.append([sample, fasta, int(k), a, b, ab, (a + b - ab) / ab if ab else None])
+    return rows, summary, jrows
+
+
+def neighbors_command(args):
+    """New samples against a tree of SKETCHES, the tree DandD builds by default and the one without a limit on its genomes:
+    which genomes of the collection each sample is closest to by DandD's own K-independent Jaccard, and what the sample
+    would add to the collection's delta.  One rectangle of unions -- samples x leaves x k -- over the leaf slab; the samples
+    are sketched in memory and the tree's sketch directory, cardinality cache and pickle stay as they are."""
+    tree, outfile = _open_tree("neighbors", args)
+    if tree.experiment["tool"] == "kmc":
+        sys.exit(f"neighbors: {args.delta_tree} is an exact tree: `screen` places samples in it by exact containment; "
+                 "neighbors works on the unions of sketches")
+    window = _window_or_exit("neighbors", args, tree, why="KIJ compares deltas taken over one window")
+    if args.top is not None and args.top < 1:
+        sys.exit(f"neighbors: --top {args.top}: at least one genome per sample (N >= 1)")
+    names = list(args.samples)
+    if args.query_loc:
+        if not os.path.isfile(args.query_loc):
+            sys.exit(f"neighbors: {args.query_loc} (-q) not found")
+        names.extend(line.strip() for line in _lines(args.query_loc))
+    samples = []
+    for f in names:
+        if f not in samples:
+            samples.append(f)
+    if not samples:
+        sys.exit("neighbors: no sample: give files, or -q with one path per line")
+    for f in samples:
+        if not os.path.isfile(f):
+            sys.exit(f"neighbors: {f} not found")
+    fastas = _universe_or_exit("neighbors", tree, args, least=1)
+    if not _rank0_after_presketch(tree, window):
+        return
+    try:
+        res = tree.neighbor_tables(fastas, samples, *window)
+    except (ValueError, OSError) as e:
+        sys.exit("neighbors: " + " ".join(str(e).split()))
+    rows, summary, jrows = _neighbor_rows(samples, fastas, res, args.top)
+    os.makedirs(args.outdir, exist_ok=True)
+    _write_csv(outfile + ".neighbors.csv", NEIGHBORS_COLUMNS["neighbors"], rows)
+    _write_csv(outfile + ".neighbors_summary.csv", NEIGHBORS_COLUMNS["neighbors_summary"], summary)
+    if args.jaccard:
+        _write_csv(outfile + ".neighbors_j.csv", NEIGHBORS_COLUMNS["neighbors_j"], jrows)
+
+
 def patterns_command(args):
     """Which sets of genomes share k-mers, and how many: the distinct membership masks of the universe with the distinct
     k-mers that carry exactly each -- the table behind an UpSet plot, and what tells which groups `core -g` and `screen -g`
@@ -1159,6 +1238,22 @@ def build_parser():
     sc.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
     sc.add_argument("-l", "--label", dest="label", default="")
     sc.set_defaults(func=screen_command)
+
+    nb = subs.add_parser("neighbors", parents=[common, sweep],
+                         description="new samples (assemblies, read sets) against a tree of sketches: the closest genomes of the collection "
+                                     "by the K-independent Jaccard, and what each sample would add to the collection's delta")
+    nb.add_argument("-d", "--dtree", dest="delta_tree", required=True)
+    nb.add_argument("-s", "--tag", dest="tag", type=str)
+    nb.add_argument("-f", "--fastas", dest="flist_loc", default=None, type=str,
+                    help="the genomes of the universe (default: every leaf), in the order `progressive -f` takes them")
+    nb.add_argument("-q", "--queries", dest="query_loc", default=None, type=str, help="a file of sample paths, one per line")
+    nb.add_argument("--top", dest="top", type=int, default=None, metavar="N", help="write each sample's N closest genomes (default: all)")
+    nb.add_argument("--jaccard", dest="jaccard", default=False, action="store_true",
+                    help="also write the cardinalities and the Jaccard of every sample and genome at every k (<prefix>.neighbors_j.csv)")
+    nb.add_argument("samples", nargs="*", metavar="SAMPLE", help="FASTA / FASTQ files, plain or gzip; a leaf of the tree is allowed")
+    nb.add_argument("-o", "--outdir", dest="outdir", default=os.getcwd(), type=str)
+    nb.add_argument("-l", "--label", dest="label", default="")
+    nb.set_defaults(func=neighbors_command)
 
     pa = subs.add_parser("patterns", parents=[common],
                          description="which sets of up to 64 genomes of a `tree --exact` share k-mers, and how many: the distinct membership "

@@ -1441,6 +1441,49 @@ class DeltaTree:
             out[k] = dict(masks=[int(m) for m in masks], counts=[int(v) for v in counts], found=int(found), distinct=int(distinct))
         return out
 
+    # ---- new samples against a tree of sketches (`dandd neighbors`) ---------------------------------------------------------
+    def neighbor_tables(self, fastas, samples, mink, maxk):
+        """The union cardinalities that place each of `samples` (files that are no leaves; FASTA / FASTQ, plain or gzip) among
+        the universe `fastas` (leaf FASTAs of a tree of sketches, any number of them) over k in [max(1, mink), maxk]: every
+        sample against every genome -- the rectangle --, and against the union of them all.
+          * The leaves are brought up to date over the window as `kij` brings them; the samples are sketched by the backend
+            (sample_sketches) and kept in memory only: no sketch file, no cardinality cache entry, nothing in the pickle.
+          * |S| from sample_cards; |S U G| from ONE cross_cards call of the samples against the leaf slab; |S U all| from a
+            second one against ONE row per k, the union of the universe's leaves -- the root's sketches when the universe is
+            every leaf, else the leaves merged by the backend.
+          * A sample of empty registers rides behind the samples in both calls: max(0, g) = g, so its row holds |G| of every
+            genome and |all|, from the histograms and the estimator every other cell comes from.  A sample that is a copy of
+            a leaf therefore has |S U G| == |G| == |S| to the last bit, and KIJ 1.0.
+          * deltas over the window: _window_delta (ties to the larger k).
+        A backend without cross_cards is a ValueError.
+        -> dict: ks, sample [ns][K], genome [n][K], pair [ns][n][K], whole [K] (the universe), with [ns][K] (the universe
+        and the sample), and per name of (sample, genome, pair, whole, with) `<name>_delta` and `<name>_k` of that shape less K"""
+        u = self._universe(fastas, mink, maxk)
+        for entry in ("cross_cards", "sample_sketches", "sample_cards"):
+            if not hasattr(u.be, entry):
+                raise ValueError(f"the backend {getattr(u.be, 'name', type(u.be).__name__)} has no {entry}: "
+                                 "the samples are placed by one rectangle of unions over the leaf slab")
+        ns, n, K = len(samples), u.n, len(u.ks)
+        paths = u.paths
+        regs = np.asarray(u.be.sample_sketches(list(samples), u.lo, u.hi), dtype=np.uint8).reshape(ns, K, -1)
+        rows = np.concatenate([regs, np.zeros((1,) + regs.shape[1:], dtype=np.uint8)])
+        pair = np.asarray(u.be.cross_cards(rows, paths), dtype=np.float64).reshape(ns + 1, n, K)
+        merged = paths
+        if set(fastas) == {leaf.fastas[0] for leaf in self.leaf_nodes()} and self.root.ngen > 1:
+            self.root.ksweep_update_node(u.lo, u.hi)
+            root = [self.root.ksketches[0].sfp.with_k(k) for k in u.ks]
+            if all(sketch_exists(p) for p in root):
+                merged = [root]
+        whole = np.asarray(u.be.cross_cards(rows, merged, merged=True), dtype=np.float64).reshape(ns + 1, K)
+        out = {"ks": u.ks, "sample": np.asarray(u.be.sample_cards(regs.reshape(ns * K, -1)), dtype=np.float64).reshape(ns, K),
+               "genome": pair[ns], "pair": pair[:ns], "whole": whole[ns], "with": whole[:ns]}
+        for name in ("sample", "genome", "pair", "whole", "with"):
+            cards = out[name]
+            flat = [_window_delta(c, u.ks) for c in cards.reshape(-1, K)]
+            out[name + "_delta"] = np.array([d for d, _ in flat], dtype=np.float64).reshape(cards.shape[:-1])
+            out[name + "_k"] = np.array([k for _, k in flat], dtype=np.int64).reshape(cards.shape[:-1])
+        return out
+
     # ---- batched GPU union schedules ------------------------------------------------------------------
     def _table_window(self, experiment):
         """[lo, hi] of a union table for climbs over this tree's leaves: the --ksweep window, or a hill-climb's guess -- the

@@ -128,6 +128,20 @@ int dd_pairwise(dd_ctx *, const uint8_t *leaf /*[n][K][m]*/, int n, int K,
                 double *card /*[n][n][K]*/);
 int dd_pairwise_device(dd_ctx *, const uint8_t *leaf_dev, int n, int K, double *card);
 
+/* ---- the rectangle: new sketches against a slab ------------------------------------
+ * |a_s U b_j| at every k column: card[na][nb][K].  a: [na][K][m], b: [nb][K][m], this context's log2m.  What
+ * dd_pairwise on the na + nb rows behind one another holds at [s][na + j], without the two squares on its diagonal,
+ * without a copy of b, and with an na x nb table; the same integers behind the same estimator.  From log2m 12 on the
+ * histograms are counted on the matrix cores (dd_gram.hip: blocks of 64 rows of a against blocks of 64 rows of b; a last
+ * block of a with at most 32 rows in a half-height form); below, and with DD_CROSS_STREAM=1, by a streaming kernel.
+ * The histograms are taken in rounds over a's 64-row blocks: DD_CROSS_HIST_MB (1024 when unset; read on every call) is
+ * what a round's histograms may take, one block at the least.  The argument rules are dd_pairwise's; register bytes
+ * must be <= 63.  dd_cross_host_device takes a from host memory and b where it lies in HBM: new samples against a
+ * resident slab. */
+int dd_cross(dd_ctx *, const uint8_t *a, int na, const uint8_t *b, int nb, int K, double *card);
+int dd_cross_device(dd_ctx *, const uint8_t *a_dev, int na, const uint8_t *b_dev, int nb, int K, double *card /*host*/);
+int dd_cross_host_device(dd_ctx *, const uint8_t *a, int na, const uint8_t *b_dev, int nb, int K, double *card);
+
 /* ---- leave-out unions ------------------------------------------------------------
  * Replaces the (n-1)-way unions of DeltaTree.find_delta_delta (lib/huffman_dandd.py:559-566), one per
  * left-out set and climb step:
@@ -586,6 +600,8 @@ int dd_last_sketch_stats(dd_ctx *, uint64_t *tokens, uint64_t *updates, int *swe
 #define DD_K2_PROGRESSIVE_PSCAN 2  /* pscan_kernel: running AND of threshold bit planes (log2m >= 18, n <= 32) */
 #define DD_K2_PAIRWISE_STREAM 3    /* pairwise_kernel: one LDS atomic per register per pair */
 #define DD_K2_PAIRWISE_GRAM 4      /* gram_kernel: int8 Gram matrices on the matrix cores (log2m >= 12) */
+#define DD_K2_CROSS_STREAM 5       /* cross_stream_kernel: one LDS atomic per register per (row of a, row of b) */
+#define DD_K2_CROSS_GRAM 6         /* cross_kernel: the rectangle as int8 Gram blocks (log2m >= 12) */
 int dd_last_k2_path(dd_ctx *);
 
 /* ---- synthetic FASTA on the device (bench / tests) ----------
