@@ -13,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdandd_hip.so")
-SOURCES = ["dd_api.hip", "dd_sketch_api.hip", "dd_k2_api.hip", "dd_exact_api.hip", "dd_exact_emit_api.hip", "dd_exact_samples_api.hip", "dd_exact_passes.hip", "dd_ingest.hip", "dd_comm.hip", "dd_plan.hip", "dd_pack.hip", "dd_sweep.hip", "dd_scatter.hip", "dd_union.hip", "dd_gram.hip", "dd_leaveout.hip", "dd_extend.hip", "dd_subsets.hip", "dd_pscan.hip", "dd_synth.hip", "dd_exact.hip", "dd_exact_sched.hip", "dd_exact_patterns.hip", "dd_exact_greedy.hip", "dd_exact_locate.hip", "dd_exact_screen.hip", "dd_exact_paint.hip", "dd_exact_reads.hip", "dd_exact_depth.hip", "dd_exact_cover.hip", "dd_exact_gather.hip", "dd_ginflate.hip", "dd_gunzip.hip", "dd_fastq.hip"]
-HEADERS = ["dd_common.h", "dd_ctx.h", "dd_deflate.h", "dd_exact_host.h", "dd_exact_walk.h", "dd_io.h", "dd_inflate.h", "dd_k1.h", "dd_k2.h", "dd_kernels.h", "dd_plan.h", "dd_scan.h", os.path.join("..", "..", "include", "dandd_hip.h")]
+SOURCES = ["dd_api.hip", "dd_sketch_api.hip", "dd_k2_api.hip", "dd_exact_api.hip", "dd_exact_emit_api.hip", "dd_exact_samples_api.hip", "dd_exact_passes.hip", "dd_ingest.hip", "dd_comm.hip", "dd_plan.hip", "dd_pack.hip", "dd_sweep.hip", "dd_scatter.hip", "dd_union.hip", "dd_gram.hip", "dd_leaveout.hip", "dd_extend.hip", "dd_subsets.hip", "dd_pscan.hip", "dd_synth.hip", "dd_exact.hip", "dd_exact_sched.hip", "dd_exact_wide.hip", "dd_exact_patterns.hip", "dd_exact_greedy.hip", "dd_exact_locate.hip", "dd_exact_screen.hip", "dd_exact_paint.hip", "dd_exact_reads.hip", "dd_exact_depth.hip", "dd_exact_cover.hip", "dd_exact_gather.hip", "dd_ginflate.hip", "dd_gunzip.hip", "dd_fastq.hip"]
+HEADERS = ["dd_common.h", "dd_ctx.h", "dd_deflate.h", "dd_exact_host.h", "dd_exact_runs.h", "dd_exact_walk.h", "dd_io.h", "dd_inflate.h", "dd_k1.h", "dd_k2.h", "dd_kernels.h", "dd_plan.h", "dd_scan.h", os.path.join("..", "..", "include", "dandd_hip.h")]
 FLAGS = [
     "-O3",
     "--offload-arch=gfx950",

@@ -46,12 +46,16 @@ int dd_exact_count(dd_ctx* c, const char* const* paths, int n, int k, uint64_t* 
     return exact_upload_files(c, paths, n, [&](auto p, auto s) { return dd_exact_count_device(c, p, s, n, k, distinct); });
 }
 
+}  // extern "C"
+
 // ------------------------------------------------------------------- exact union schedules
 // dd_exact_sched.hip: one sort of the universe per k, a membership mask per distinct k-mer, one accumulator per schedule.
+// (outside the C linkage: the driver is a template over the two forms of a schedule)
 namespace {
 
 using Acc = std::vector<unsigned long long>;   // one k's accumulator, exact_sched_acc_words() counts
-// what a caller of exact_schedule does around the loop over k (dd_exact_greedy: its mask store)
+// what a caller of exact_schedule does around the loop over k (dd_exact_greedy: its mask store); with an ExactSched only --
+// a wide schedule that is given hooks is refused, not run without them
 struct ScheduleHooks {
     std::function<int(const ExactInputs&, dd::ExactSched&)> begin;   // the inputs are packed and hold a token
     std::function<int(int kk, const Acc& acc)> after_k;              // k = kmin + kk is done and waited for
@@ -59,14 +63,28 @@ struct ScheduleHooks {
 // ... and with the accumulators once every k is done: that of k = kmin + kk, of K, into the caller's array
 using ScheduleShape = std::function<void(const Acc& acc, size_t kk, size_t K)>;
 
+// the two forms of a schedule behind the sort: a 64-bit mask per distinct k-mer (dd_exact_sched.hip), a row of up to four
+// words (dd_exact_wide.hip)
+size_t sched_words(const dd::ExactSched& s) { return dd::exact_sched_acc_words(s); }
+size_t sched_words(const dd::ExactWide& s) { return dd::exact_wide_acc_words(s); }
+hipError_t sched_launch(const dd::ExactSorted& sorted, size_t count, int k, const dd::ExactSched& s, void* scratch, hipStream_t st) {
+    return dd::launch_exact_sched(sorted, count, k, s, scratch, st);
+}
+hipError_t sched_launch(const dd::ExactSorted& sorted, size_t count, int k, const dd::ExactWide& s, void* scratch, hipStream_t st) {
+    return dd::launch_exact_wide(sorted, count, k, s, scratch, st);
+}
+constexpr auto sched_scratch(const dd::ExactSched&) { return dd::exact_sched_scratch_bytes; }
+constexpr auto sched_scratch(const dd::ExactWide&) { return dd::exact_wide_scratch_bytes; }
+
 // The driver behind every schedule: K0 once, then for every k extract (with the genome's index) -> sort -> reduce +
 // accumulate through exact_passes, on the context's device.  Nothing reaches `shape` before every k is done.
-int exact_schedule(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, dd::ExactSched s,
+template <class Sched>
+int exact_schedule(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, Sched s,
                    const std::vector<uint64_t>& table, const ScheduleShape& shape, const ScheduleHooks* hooks = nullptr) {
     DeviceGuard guard(c->device);
     hipStream_t st = c->stream;
     int rc;
-    const size_t words = dd::exact_sched_acc_words(s);
+    const size_t words = sched_words(s);
     std::vector<Acc> out((size_t)(kmax - kmin + 1), Acc(words, 0ull));
     const auto done = [&] {
         for (size_t kk = 0; shape && kk < out.size(); ++kk) shape(out[kk], kk, out.size());
@@ -82,13 +100,18 @@ int exact_schedule(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nby
         if ((rc = stage_table(c, c->ord, table.data(), table.size() * sizeof(uint64_t)))) return rc;
         s.table = static_cast<const uint64_t*>(c->ord.p);
     }
-    if (hooks && (rc = hooks->begin(in, s))) return rc;
+    if constexpr (std::is_same_v<Sched, dd::ExactSched>) {
+        if (hooks && (rc = hooks->begin(in, s))) return rc;
+    } else if (hooks) {
+        return fail(DD_EINVAL, "exact schedule: hooks stand behind the one-word form only");   // (begin takes an ExactSched)
+    }
     int most_passes = 0;
     for (int k = kmin; k <= kmax; ++k) {
         DD_HIP(hipMemsetAsync(s.acc, 0, words * sizeof(unsigned long long), st));
-        rc = exact_sorted_passes(c, in, n, k, "exact schedule", [&](const dd::ExactSorted& sorted, size_t count, void* scratch) {
-            return dd::launch_exact_sched(sorted, count, k, s, scratch, st);
-        });
+        rc = exact_sorted_passes(
+            c, in, n, k, "exact schedule",
+            [&](const dd::ExactSorted& sorted, size_t count, void* scratch) { return sched_launch(sorted, count, k, s, scratch, st); },
+            sched_scratch(s));
         if (rc) return rc;
         DD_HIP(hipMemcpyAsync(out[(size_t)(k - kmin)].data(), s.acc, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         DD_HIP(hipStreamSynchronize(st));
@@ -129,6 +152,42 @@ int leave_out_table(const int32_t* group, int ngroups, int n, std::vector<uint64
     }
     for (int g = 0; g < ngroups; ++g)
         if (table[64 + g] == all) return fail(DD_EINVAL, "group %d holds every leaf: the union of the rest is empty", g);
+    return DD_OK;
+}
+
+// ... and the same rules and messages for rows of W = exact_wide_words(n) words (the wide entries, n <= 255)
+int wide_progressive_table(const int32_t* orderings, int norder, int n, std::vector<uint64_t>& table) {
+    if (norder < 1 || !orderings) return fail(DD_EINVAL, "bad argument");
+    const size_t W = (size_t)dd::exact_wide_words(n);
+    table.assign((size_t)norder * n * W, 0ull);
+    for (int o = 0; o < norder; ++o) {
+        uint64_t seen[4] = {0, 0, 0, 0};
+        for (int j = 0; j < n; ++j) {
+            const int32_t v = orderings[(size_t)o * n + j];
+            if (v < 0 || v >= n) return fail(DD_EINVAL, "ordering entry %d outside 0..%d", v, n - 1);
+            if ((seen[v >> 6] >> (v & 63)) & 1ull) return fail(DD_EINVAL, "ordering %d is not a permutation of 0..%d: %d appears twice", o, n - 1, v);
+            seen[v >> 6] |= 1ull << (v & 63);
+            for (size_t w = 0; w < W; ++w) table[((size_t)o * n + j) * W + w] = seen[w];
+        }
+    }
+    return DD_OK;
+}
+
+int wide_leave_out_table(const int32_t* group, int ngroups, int n, std::vector<uint64_t>& table) {
+    if (!group) return fail(DD_EINVAL, "bad argument");
+    if (check_groups(group, ngroups, n)) return DD_EINVAL;
+    const size_t W = (size_t)dd::exact_wide_words(n);
+    table.assign((size_t)256 + (size_t)ngroups * W, 0ull);
+    for (int i = 0; i < 256; ++i) table[i] = ~0ull;
+    std::vector<int> members((size_t)ngroups, 0);
+    for (int i = 0; i < n; ++i) {
+        if (group[i] < 0) continue;
+        table[i] = (uint64_t)group[i];
+        table[(size_t)256 + (size_t)group[i] * W + (i >> 6)] |= 1ull << (i & 63);
+        ++members[(size_t)group[i]];
+    }
+    for (int g = 0; g < ngroups; ++g)
+        if (members[(size_t)g] == n) return fail(DD_EINVAL, "group %d holds every leaf: the union of the rest is empty", g);
     return DD_OK;
 }
 
@@ -175,6 +234,8 @@ int subsets_from_hist(const unsigned long long* hist, int n, uint64_t* card, siz
 
 }  // namespace
 
+extern "C" {
+
 int dd_exact_pairwise_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, uint64_t* card) {
     if (exact_frame(c, fasta_dev, nbytes, n, 64, kmin, kmax, card)) return DD_EINVAL;
     return exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedPairwise, n, 0, 0, nullptr, nullptr}, {},
@@ -206,6 +267,51 @@ int dd_exact_subsets_device(dd_ctx* c, const uint8_t* const* fasta_dev, const si
     if (exact_frame(c, fasta_dev, nbytes, n, 16, kmin, kmax, card)) return DD_EINVAL;
     return exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactSched{dd::kSchedSubsets, n, 0, 0, nullptr, nullptr}, {},
                           [&](const Acc& a, size_t kk, size_t K) { subsets_from_hist(a.data() + 1, n, card + kk, K); });
+}
+
+// ------------------------------------------------------- exact union schedules, 65 to 255 inputs
+// dd_exact_wide.hip: the same sort, a row of up to four words per distinct k-mer.  The entries above keep their limit and
+// their messages; these take their argument lists and output shapes, and any n in 1..255.
+int dd_exact_wide_pairwise_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax, uint64_t* card) {
+    if (exact_frame(c, fasta_dev, nbytes, n, 255, kmin, kmax, card)) return DD_EINVAL;
+    return exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactWide{dd::kSchedPairwise, n, 0, 0, nullptr, nullptr}, {},
+                          [&](const Acc& a, size_t kk, size_t K) { pairwise_cards(a, n, kk, K, card); });
+}
+
+int dd_exact_wide_progressive_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax,
+                                     const int32_t* orderings, int norder, uint64_t* card) {
+    if (exact_frame(c, fasta_dev, nbytes, n, 255, kmin, kmax, card)) return DD_EINVAL;
+    std::vector<uint64_t> table;
+    if (wide_progressive_table(orderings, norder, n, table)) return DD_EINVAL;
+    return exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactWide{dd::kSchedProgressive, n, norder, 0, nullptr, nullptr}, table,
+                          [&](const Acc& a, size_t kk, size_t K) { running_sums(a, n, norder, true, kk, K, card); });
+}
+
+int dd_exact_wide_leave_out_device(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int kmin, int kmax,
+                                   const int32_t* group, int ngroups, uint64_t* card) {
+    if (exact_frame(c, fasta_dev, nbytes, n, 255, kmin, kmax, card)) return DD_EINVAL;
+    std::vector<uint64_t> table;
+    if (wide_leave_out_table(group, ngroups, n, table)) return DD_EINVAL;
+    return exact_schedule(c, fasta_dev, nbytes, n, kmin, kmax, dd::ExactWide{dd::kSchedLeaveOut, n, 0, ngroups, nullptr, nullptr}, table,
+                          [&](const Acc& a, size_t kk, size_t K) {
+                              for (int g = 0; g < ngroups; ++g) card[(size_t)g * K + kk] = a[0] - a[1 + g];
+                              card[(size_t)ngroups * K + kk] = a[0];
+                          });
+}
+
+int dd_exact_wide_pairwise(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, uint64_t* card) {
+    return exact_path_form(c, paths, n, 255, kmin, kmax, card,
+                           [&](auto p, auto s) { return dd_exact_wide_pairwise_device(c, p, s, n, kmin, kmax, card); });
+}
+
+int dd_exact_wide_progressive(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, const int32_t* orderings, int norder, uint64_t* card) {
+    return exact_path_form(c, paths, n, 255, kmin, kmax, card,
+                           [&](auto p, auto s) { return dd_exact_wide_progressive_device(c, p, s, n, kmin, kmax, orderings, norder, card); });
+}
+
+int dd_exact_wide_leave_out(dd_ctx* c, const char* const* paths, int n, int kmin, int kmax, const int32_t* group, int ngroups, uint64_t* card) {
+    return exact_path_form(c, paths, n, 255, kmin, kmax, card,
+                           [&](auto p, auto s) { return dd_exact_wide_leave_out_device(c, p, s, n, kmin, kmax, group, ngroups, card); });
 }
 
 // ---------------------------------------------------------------- exact intersection schedules

@@ -5,7 +5,7 @@
 #include <functional>
 #include "dd_ctx.h"
 
-// What every entry checks first, in this order: the context, n against the entry's limit (64; 16: all subsets), inputs and
+// What every entry checks first, in this order: the context, n against the entry's limit (64; 16: all subsets; 255: the wide rows), inputs and
 // `out` for null, the k range.  exact_frame, the device forms': then nbytes (and what else may not be null), then the buffers.
 int exact_args(dd_ctx* c, const void* inputs, int n, int nmax, int kmin, int kmax, const void* out);
 int exact_frame(dd_ctx* c, const uint8_t* const* fasta_dev, const size_t* nbytes, int n, int nmax, int kmin, int kmax,
@@ -63,9 +63,11 @@ using ExactCounted = std::function<void(const unsigned long long* h, bool single
 int exact_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const ExactLayout& L, const ExactConsume& consume,
                  const ExactCounted& counted = nullptr);
 
-// exact_passes with the consumer of the schedules and the emission: launch_exact_sort_tagged, then `then` on what it left
+// exact_passes with the consumer of the schedules and the emission: launch_exact_sort_tagged, then `then` on what it left.
+// scratch_bytes: what `then` wants behind the sort's temp (null: exact_sched_scratch_bytes, launch_exact_sched's and the emission's)
 using ExactSortedThen = std::function<hipError_t(const dd::ExactSorted& sorted, size_t count, void* scratch)>;
-int exact_sorted_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, const ExactSortedThen& then);
+int exact_sorted_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, const ExactSortedThen& then,
+                        size_t (*scratch_bytes)(size_t keys) = nullptr);
 
 // The ordered-record step.  exact_records reserves c->emit (cursor (256 B) | lo | hi | mask, dcap records each) and leaves
 // there the distinct k-mers of one k whose mask matches a query, in the order the chunks of the sort finished, over all passes.

@@ -8,8 +8,9 @@
 int exact_args(dd_ctx* c, const void* inputs, int n, int nmax, int kmin, int kmax, const void* out) {
     if (check_ctx(c)) return DD_EINVAL;
     if (n < 1 || n > nmax)
-        return nmax == 16 ? fail(DD_EINVAL, "n=%d outside 1..16: the unions of all 2^n subsets are computed", n)
-                          : fail(DD_EINVAL, "n=%d outside 1..64: a membership mask has one bit per input", n);
+        return nmax == 16    ? fail(DD_EINVAL, "n=%d outside 1..16: the unions of all 2^n subsets are computed", n)
+               : nmax == 255 ? fail(DD_EINVAL, "n=%d outside 1..255: a membership row has one bit per input, the sort one byte for it", n)
+                             : fail(DD_EINVAL, "n=%d outside 1..64: a membership mask has one bit per input", n);
     if (!inputs || !out) return fail(DD_EINVAL, "null argument");
     if (kmin < 1 || kmax > 64 || kmin > kmax) return fail(DD_EINVAL, "k range %d..%d outside 1..64", kmin, kmax);
     return DD_OK;
@@ -244,8 +245,9 @@ int exact_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const ExactLayo
     return DD_OK;
 }
 
-int exact_sorted_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, const ExactSortedThen& then) {
-    const ExactLayout L{what, dd::exact_tag_mode(k), dd::exact_sched_temp_bytes, dd::exact_sched_scratch_bytes};
+int exact_sorted_passes(dd_ctx* c, const ExactInputs& in, int n, int k, const char* what, const ExactSortedThen& then,
+                        size_t (*scratch_bytes)(size_t keys)) {
+    const ExactLayout L{what, dd::exact_tag_mode(k), dd::exact_sched_temp_bytes, scratch_bytes ? scratch_bytes : dd::exact_sched_scratch_bytes};
     return exact_passes(c, in, n, k, L, [&](const ExactArrays& a, size_t count) -> int {
         dd::ExactSorted sorted{};
         DD_HIP(dd::launch_exact_sort_tagged(a.lo, a.hi, a.lo_alt, a.hi_alt, a.g, a.g_alt, count, k, a.temp, a.temp_bytes, c->stream, &sorted));

@@ -43,121 +43,18 @@
 #include "dd_common.h"
 #include "dd_kernels.h"
 #include "dd_exact_walk.h"
+#include "dd_exact_runs.h"
 
 namespace dd {
 namespace {
 
-constexpr int kThreads = 256, kItems = 8, kChunk = kThreads * kItems;  // slots per chunk = masks an LDS tile can hold
-constexpr int kCarryThreads = 1024;
 constexpr size_t kStaticLds = (size_t)kChunk * 8 + 128;   // sched_kernel's own LDS: the tile of masks, the scan's wave totals
 constexpr int kPairSlots = 9;   // ceil(64 * 65 / 2 / 256): (i, j) pairs a thread of the pairwise accumulator owns
 constexpr int kSelectSlots = 4, kSelectBatch = kSelectSlots * kThreads;   // queries a thread owns; queries of one select launch
 
-struct SortedView {
-    const uint64_t* lo;
-    const uint64_t* hi;
-    const uint8_t* g;   // null: the genome is the top byte of the most significant word
-    uint64_t mlo, mhi;
-    size_t count;
-    int n;              // genomes: a tag outside 0..n-1 sets no bit
-};
-
-// (flag, value) pairs under  (f1, v1) o (f2, v2) = (f1 | f2, f2 ? v2 : v1 | v2): the segmented OR.  Inclusive scan over
-// the workgroup; returns the exclusive prefix of the calling thread in (ef, ev) and the workgroup's total in (tf, tv).
-template <int NWAVES>
-DD_D void block_seg_scan(uint32_t f, uint64_t v, uint32_t* sf, uint64_t* sv, uint32_t& ef, uint64_t& ev, uint32_t& tf,
-                         uint64_t& tv) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t of = __shfl_up(f, d);
-        const uint64_t ov = __shfl_up((unsigned long long)v, d);
-        if (lane >= d) {
-            if (!f) v |= ov;
-            f |= of;
-        }
-    }
-    if (lane == 63) sf[wave] = f, sv[wave] = v;
-    uint32_t xf = __shfl_up(f, 1);
-    uint64_t xv = __shfl_up((unsigned long long)v, 1);
-    if (lane == 0) xf = 0, xv = 0;
-    __syncthreads();
-    uint32_t pf = 0;
-    uint64_t pv = 0;
-    tf = 0, tv = 0;
-    for (int q = 0; q < NWAVES; ++q) {
-        const uint32_t wf = sf[q];
-        const uint64_t wv = sv[q];
-        if (q == wave) pf = tf, pv = tv;
-        tv = wf ? wv : (tv | wv);
-        tf |= wf;
-    }
-    ef = pf | xf;
-    ev = xf ? xv : (pv | xv);
-}
-
-// the calling thread's kItems consecutive slots of a chunk: which start a run, which end one, and their genome bits
-template <bool WIDE>
-DD_D void load_items(const SortedView& s, size_t first, uint32_t& head, uint32_t& tail, uint64_t (&bit)[kItems]) {
-    head = tail = 0;
-    uint64_t pl = 0, ph = 0;
-    bool pvalid = first > 0 && first - 1 < s.count;
-    if (pvalid) {
-        pl = s.lo[first - 1] & s.mlo;
-        if (WIDE) ph = s.hi[first - 1] & s.mhi;
-    }
-#pragma unroll
-    for (int j = 0; j <= kItems; ++j) {
-        const size_t i = first + j;
-        const bool valid = i < s.count;
-        uint64_t rl = 0, rh = 0;
-        if (valid) {
-            rl = s.lo[i];
-            if (WIDE) rh = s.hi[i];
-        }
-        const uint64_t cl = rl & s.mlo, ch = rh & s.mhi;
-        const bool differs = cl != pl || (WIDE && ch != ph);
-        if (j > 0 && pvalid && (!valid || differs)) tail |= 1u << (j - 1);
-        if (j < kItems) {
-            if (valid && (!pvalid || differs)) head |= 1u << j;
-            uint32_t gi = 0xFF;
-            if (valid) gi = s.g ? (uint32_t)s.g[i] : (uint32_t)((WIDE ? rh : rl) >> 56);
-            bit[j] = (gi < (uint32_t)s.n) ? (1ull << gi) : 0ull;
-        }
-        pl = cl, ph = ch, pvalid = valid;
-    }
-}
-
-DD_D void thread_summary(uint32_t head, const uint64_t (&bit)[kItems], uint32_t& f, uint64_t& v) {
-    f = head != 0;
-    v = 0;
-#pragma unroll
-    for (int j = 0; j < kItems; ++j) {
-        if ((head >> j) & 1u) v = 0;
-        v |= bit[j];
-    }
-}
-
-// The front of a chunk of the sorted array, by a whole workgroup: the calling thread's kItems slots from `first` on, and
-// the segmented OR-scan of the chunk over them.  (ef, ev): what the runs in front of the thread's slots, inside the chunk,
-// have collected; (tf, tv): the chunk's total.  Holds a barrier.
-struct ChunkScan {
-    size_t first;
-    uint32_t head, tail, ef, tf;
-    uint64_t bit[kItems], ev, tv;
-};
-template <bool WIDE>
-DD_D void chunk_scan(const SortedView& s, size_t chunk, ChunkScan& c) {
-    __shared__ uint32_t sf[kThreads / 64];
-    __shared__ uint64_t sv[kThreads / 64];
-    uint32_t f;
-    uint64_t v;
-    c.first = chunk * kChunk + (size_t)threadIdx.x * kItems;
-    load_items<WIDE>(s, c.first, c.head, c.tail, c.bit);
-    thread_summary(c.head, c.bit, f, v);
-    block_seg_scan<kThreads / 64>(f, v, sf, sv, c.ef, c.ev, c.tf, c.tv);
-}
-// ... and the runs of the chunk: f(slot, run, ends) for each of the thread's slots, in order, by whole waves -- `run` the
+// (the view of the sorted array, a thread's slots, the segmented OR-scan and chunk_scan, the front of a chunk: dd_exact_runs.h,
+// shared with the rows of dd_exact_wide.hip)
+// The runs of a chunk behind chunk_scan: f(slot, run, ends) for each of the thread's slots, in order, by whole waves -- `run` the
 // OR of the slot's run so far, the part in the chunks in front (carry) included; `ends`: the slot is the last of its run and
 // the run holds a genome.  The slots the single-pass layout never wrote set no bit: a run of them alone never ends.
 template <bool WIDE, class F>
@@ -200,21 +97,6 @@ __global__ __launch_bounds__(kCarryThreads) void sched_carry_kernel(const uint32
         run = tf ? tv : (run | tv);
         __syncthreads();
     }
-}
-
-// One round of wave aggregation for a histogram with a dominant bin (progressive: most k-mers meet an ordering at its first
-// genomes): the first valid lane's index is added once for every lane that holds it, the other lanes add for themselves.
-// Called by whole waves.  Worth 3 x to progressive at k = 21 (profiles/exact_schedules.txt).  NOT to be turned into a loop of
-// rounds until every lane is served: that form miscounts in one instantiation for a reason still open;
-// leave-out and subsets use plain LDS atomics.
-DD_D void agg_add(uint32_t* base, uint32_t idx, bool valid) {
-    const unsigned long long act = __ballot(valid);
-    if (!act) return;
-    const int leader = __builtin_ctzll(act);
-    const uint32_t v = __shfl(idx, leader);
-    const unsigned long long same = __ballot(valid && idx == v);
-    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&base[v], (uint32_t)__builtin_popcountll(same));
-    else if (valid && idx != v) atomicAdd(&base[idx], 1u);
 }
 
 struct SchedArgs {
@@ -708,8 +590,6 @@ auto with_acc(int kind, const F& f) {
 size_t sched_dyn_lds(int kind, int n, int norder) {
     return with_acc(kind, [&](auto t) { return decltype(t)::type::lds(n, norder); });
 }
-
-size_t exact_sched_chunks(size_t count) { return (count + kChunk - 1) / kChunk; }
 
 // What sched_kernel and emit_kernel both stand on: the scratch carved (open-run ORs | carries | flags, one per chunk), the
 // view of the sorted array, and the two pre-passes launched.

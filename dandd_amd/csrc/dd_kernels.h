@@ -352,6 +352,20 @@ size_t exact_sched_scratch_bytes(size_t count);
 hipError_t launch_exact_sort_tagged(uint64_t* lo, uint64_t* hi, uint64_t* lo_alt, uint64_t* hi_alt, uint8_t* g, uint8_t* g_alt,
                                     size_t n, int k, void* temp, size_t temp_bytes, hipStream_t st, ExactSorted* out);
 hipError_t launch_exact_sched(const ExactSorted& sorted, size_t count, int k, const ExactSched& s, void* scratch, hipStream_t st);
+// The union schedules for up to 255 genomes (dd_exact_wide.hip), behind launch_exact_sort_tagged like launch_exact_sched and
+// with its contract: a row of W = exact_wide_words(n) <= 4 words per distinct k-mer where the narrow form has one mask.
+struct ExactWide {
+    int kind, n;                // kSchedPairwise, kSchedProgressive or kSchedLeaveOut; 1 <= n <= 255
+    int norder;                 // progressive: orderings
+    int ngroups;                // leave-out, <= 255
+    const uint64_t* table;      // device; progressive: prefix rows [norder][n][W]; leave-out: group of bit i [256] (~0: never left
+                                //         out), then the groups' rows [ngroups][W]
+    unsigned long long* acc;    // device, exact_wide_acc_words() of them, zeroed by the caller: [0] = M, then what ExactSched's has
+};
+int exact_wide_words(int n);
+size_t exact_wide_acc_words(const ExactWide& s);
+size_t exact_wide_scratch_bytes(size_t count);   // (the temp of the sort is exact_sched_temp_bytes)
+hipError_t launch_exact_wide(const ExactSorted& sorted, size_t count, int k, const ExactWide& s, void* scratch, hipStream_t st);
 // The selected k-mers themselves (emit_kernel of dd_exact_sched.hip), behind launch_exact_sort_tagged and with the scratch
 // of launch_exact_sched: every distinct k-mer whose mask matches at least one of the nq <= kEmitMaxQueries (all, none) pairs
 // is appended once -- key in lo / hi (hi written for k > 32 only), mask in mask -- at a position reserved on *cursor, one

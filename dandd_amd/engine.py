@@ -32,6 +32,8 @@ EXPORTS = [
     "dd_exact_pairwise", "dd_exact_progressive", "dd_exact_leave_out", "dd_exact_subsets",
     "dd_exact_pairwise_device", "dd_exact_progressive_device", "dd_exact_leave_out_device", "dd_exact_subsets_device",
     "dd_exact_subsets_from_hist",
+    "dd_exact_wide_pairwise", "dd_exact_wide_progressive", "dd_exact_wide_leave_out",
+    "dd_exact_wide_pairwise_device", "dd_exact_wide_progressive_device", "dd_exact_wide_leave_out_device",
     "dd_exact_spectrum", "dd_exact_core_progressive", "dd_exact_select",
     "dd_exact_spectrum_device", "dd_exact_core_progressive_device", "dd_exact_select_device",
     "dd_exact_greedy", "dd_exact_greedy_device",
@@ -157,6 +159,10 @@ def load_library(path=None):
                              ("dd_exact_leave_out", [paths_t], [vp, i32]), ("dd_exact_subsets", [paths_t], []),
                              ("dd_exact_pairwise_device", [ptrs_t, sizes_t], []), ("dd_exact_progressive_device", [ptrs_t, sizes_t], [vp, i32]),
                              ("dd_exact_leave_out_device", [ptrs_t, sizes_t], [vp, i32]), ("dd_exact_subsets_device", [ptrs_t, sizes_t], []),
+                             ("dd_exact_wide_pairwise", [paths_t], []), ("dd_exact_wide_progressive", [paths_t], [vp, i32]),
+                             ("dd_exact_wide_leave_out", [paths_t], [vp, i32]), ("dd_exact_wide_pairwise_device", [ptrs_t, sizes_t], []),
+                             ("dd_exact_wide_progressive_device", [ptrs_t, sizes_t], [vp, i32]),
+                             ("dd_exact_wide_leave_out_device", [ptrs_t, sizes_t], [vp, i32]),
                              ("dd_exact_spectrum", [paths_t], []), ("dd_exact_core_progressive", [paths_t], [vp, i32]),
                              ("dd_exact_select", [paths_t], [vp, vp, i32]), ("dd_exact_spectrum_device", [ptrs_t, sizes_t], []),
                              ("dd_exact_core_progressive_device", [ptrs_t, sizes_t], [vp, i32]),
@@ -815,18 +821,18 @@ class Engine:
         self._check(getattr(self._lib, f"dd_exact_{what}{suffix}")(self._ctx, *args, n, int(kmin), int(kmax), *extra, card.ctypes.data))
         return card
 
-    def _exact_pairwise(self, src, kmin, kmax):
-        return self._exact_sched("pairwise", src, lambda n: (n, n), kmin, kmax)
+    def _exact_pairwise(self, src, kmin, kmax, wide=""):
+        return self._exact_sched(wide + "pairwise", src, lambda n: (n, n), kmin, kmax)
 
-    def _exact_progressive(self, src, kmin, kmax, orderings):
+    def _exact_progressive(self, src, kmin, kmax, orderings, wide=""):
         n = src[1]
         ords = np.ascontiguousarray(orderings, dtype=np.int32).reshape(-1, max(n, 1))
-        return self._exact_sched("progressive", src, lambda n: (ords.shape[0], n), kmin, kmax, ords.ctypes.data, ords.shape[0])
+        return self._exact_sched(wide + "progressive", src, lambda n: (ords.shape[0], n), kmin, kmax, ords.ctypes.data, ords.shape[0])
 
-    def _exact_leave_out(self, src, kmin, kmax, group, ngroups):
+    def _exact_leave_out(self, src, kmin, kmax, group, ngroups, wide=""):
         grp = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
         ngroups = int(grp.max()) + 1 if ngroups is None else int(ngroups)
-        return self._exact_sched("leave_out", src, lambda n: (max(ngroups, 0) + 1,), kmin, kmax, grp.ctypes.data, ngroups)
+        return self._exact_sched(wide + "leave_out", src, lambda n: (max(ngroups, 0) + 1,), kmin, kmax, grp.ctypes.data, ngroups)
 
     def _exact_subsets(self, src, kmin, kmax):
         return self._exact_sched("subsets", src, lambda n: (1 << min(max(n, 0), 16),), kmin, kmax)
@@ -851,6 +857,29 @@ class Engine:
 
     def exact_leave_out_device(self, fasta_ptrs, nbytes, kmin, kmax, group, ngroups=None):
         return self._exact_leave_out(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, group, ngroups)
+
+    # ... and for up to 255 inputs (dd_exact_wide.hip): the same arguments, shapes and numbers, a row of up to four words per
+    # distinct k-mer where the entries above keep one 64-bit mask
+    def exact_wide_pairwise(self, paths, kmin, kmax):
+        """exact_pairwise for 1 <= n <= 255 files -> uint64 [n][n][K]"""
+        return self._exact_pairwise(self._exact_src(paths=paths), kmin, kmax, "wide_")
+
+    def exact_wide_pairwise_device(self, fasta_ptrs, nbytes, kmin, kmax):
+        return self._exact_pairwise(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, "wide_")
+
+    def exact_wide_progressive(self, paths, kmin, kmax, orderings):
+        """exact_progressive for 1 <= n <= 255 files -> uint64 [o][n][K]"""
+        return self._exact_progressive(self._exact_src(paths=paths), kmin, kmax, orderings, "wide_")
+
+    def exact_wide_progressive_device(self, fasta_ptrs, nbytes, kmin, kmax, orderings):
+        return self._exact_progressive(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, orderings, "wide_")
+
+    def exact_wide_leave_out(self, paths, kmin, kmax, group, ngroups=None):
+        """exact_leave_out for 1 <= n <= 255 files -> uint64 [G+1][K]"""
+        return self._exact_leave_out(self._exact_src(paths=paths), kmin, kmax, group, ngroups, "wide_")
+
+    def exact_wide_leave_out_device(self, fasta_ptrs, nbytes, kmin, kmax, group, ngroups=None):
+        return self._exact_leave_out(self._exact_src(fasta_ptrs=fasta_ptrs, nbytes=nbytes), kmin, kmax, group, ngroups, "wide_")
 
     def exact_subsets(self, paths, kmin, kmax):
         """n <= 16 files -> uint64 [2^n][K]: row s the union of the files i with bit i of s set (row 0: 0)."""

@@ -232,7 +232,7 @@ class HipExactBackend:
     # ---- union schedules: every union of a kij / progressive / deltadelta / abba window from ONE sort of the leaves' k-mers
     # per k (dd_exact_sched.hip), where card() would read and sort every member again for every union.  Same signatures and
     # result shapes as HipBackend's; None = no schedule here (more leaves than a membership mask has bits), the caller
-    # takes the object path.
+    # asks the wide_ method of the same name, then takes the object path.
     MAX_LEAVES, MAX_SUBSET_LEAVES = 64, 16
 
     def _leaf_window(self, leaf_paths, limit=MAX_LEAVES, k=None):
@@ -291,6 +291,31 @@ class HipExactBackend:
         _, files, kmin, kmax = win
         group = np.asarray(group, dtype=np.int64).reshape(len(leaf_paths))
         return self.engine.exact_leave_out(files, kmin, kmax, group, int(group.max()) + 1).astype(np.float64)
+
+    # ... and for up to 255 leaves (dd_exact_wide.hip): what a caller asks once the three above have said None, before it takes
+    # the object path.  The same signatures, shapes and numbers; None above MAX_WIDE_LEAVES, the byte the sort has for a genome.
+    MAX_WIDE_LEAVES = 255
+
+    def wide_pairwise_cards(self, leaf_paths):
+        if (win := self._leaf_window(leaf_paths, self.MAX_WIDE_LEAVES)) is None:
+            return None
+        dbs, files, kmin, kmax = win
+        table = self.engine.exact_wide_pairwise(files, kmin, kmax)
+        self._seed_leaves(leaf_paths, dbs, files, table[np.arange(len(files)), np.arange(len(files))])
+        return table.astype(np.float64)
+
+    def wide_progressive_cards(self, leaf_paths, orderings):
+        if (win := self._leaf_window(leaf_paths, self.MAX_WIDE_LEAVES)) is None:
+            return None
+        _, files, kmin, kmax = win
+        return self.engine.exact_wide_progressive(files, kmin, kmax, orderings).astype(np.float64)
+
+    def wide_leave_out_cards(self, leaf_paths, group):
+        if (win := self._leaf_window(leaf_paths, self.MAX_WIDE_LEAVES)) is None:
+            return None
+        _, files, kmin, kmax = win
+        group = np.asarray(group, dtype=np.int64).reshape(len(leaf_paths))
+        return self.engine.exact_wide_leave_out(files, kmin, kmax, group, int(group.max()) + 1).astype(np.float64)
 
     def subset_cards(self, leaf_paths):
         """|union of the leaves i with bit i of s set| for every s < 2^n (n <= 16) and every k column: float64 [2^n][K], row 0

@@ -4,6 +4,9 @@ sketching backend differs.  (deltadelta, abba, greedy, core, screen, patterns an
 `neighbors` places new samples in a tree of SKETCHES (any number of genomes): each sample's genomes by K-independent Jaccard
 (<prefix>.neighbors.csv), its two closest and what it would add to the collection's delta (<prefix>.neighbors_summary.csv), and
 with `--jaccard` every k's cardinalities (<prefix>.neighbors_j.csv); the tree's own files stay as they are.
+`kij`, `progressive` and `deltadelta` on a `tree --exact` of up to 255 genomes take ONE sort of the leaves' k-mers per k for
+all their unions (up to 64 genomes: a 64-bit membership mask per k-mer; 65 to 255: a row of up to four such words); beyond
+255 genomes, under --safe and under DD_NO_PREFETCH every union is counted on its own.
 `screen --paint W` adds where along each sample the collection's k-mers lie: one row per window of W bases.
 `screen --reads` adds which genome each record of a sample -- a read, a contig -- belongs to and how many records go to each
 genome (<prefix>.reads_summary.csv); `--reads-calls` writes the call of every record too (<prefix>.reads.csv), and
@@ -1088,7 +1091,9 @@ def build_parser():
     t.add_argument("-C", "--no-canon", action="store_false", default=True, dest="canonicalize")
     t.set_defaults(func=tree_command)
 
-    p = subs.add_parser("progressive", parents=[common, sweep])
+    p = subs.add_parser("progressive", parents=[common, sweep],
+                        description="the growth of delta along orderings of the genomes"
+                                    " -- on a `tree --exact` of up to 255 genomes every union of a k comes from one sort of the leaves' k-mers (beyond that: one count per union)")
     p.add_argument("-d", "--dtree", dest="delta_tree", required=True)
     p.add_argument("-s", "--tag", dest="tag", type=str)
     p.add_argument("-r", "--orderings", dest="ordering_file", type=str, default=None)
@@ -1099,7 +1104,9 @@ def build_parser():
     p.add_argument("--step", dest="step", default=1, type=int)
     p.set_defaults(func=progressive_command)
 
-    k = subs.add_parser("kij", parents=[common, sweep])
+    k = subs.add_parser("kij", parents=[common, sweep],
+                        description="delta of every pair of genomes, and with --jaccard their Jaccard coefficients"
+                                    " -- on a `tree --exact` of up to 255 genomes every union of a k comes from one sort of the leaves' k-mers (beyond that: one count per union)")
     k.add_argument("-d", "--dtree", dest="delta_tree", required=True)
     k.add_argument("-s", "--tag", dest="tag", type=str)
     k.add_argument("-f", "--fastas", dest="flist_loc", default=None, type=str)
@@ -1110,7 +1117,8 @@ def build_parser():
     k.set_defaults(func=kij_command)
 
     dd = subs.add_parser("deltadelta", parents=[common, sweep],
-                         description="delta(all) - delta(all but a genome or group): each one's contribution")
+                         description="delta(all) - delta(all but a genome or group): each one's contribution"
+                                     " -- on a `tree --exact` of up to 255 genomes every union of a k comes from one sort of the leaves' k-mers (beyond that: one count per union)")
     dd.add_argument("-d", "--dtree", dest="delta_tree", required=True)
     dd.add_argument("-s", "--tag", dest="tag", type=str)
     dd.add_argument("-f", "--fastas", dest="flist_loc", default=None, type=str,

@@ -642,6 +642,16 @@ def _batched(experiment):
     return not experiment.get("safety") and not os.environ.get("DD_NO_PREFETCH")
 
 
+def _cards_or_wide(be, method, *args):
+    """A backend's union table (`method`: pairwise_cards / progressive_cards / leave_out_cards) and, where that is None --
+    more leaves than its membership mask has bits -- the table of its wide_ method of the same name, for a backend that has
+    one (exact trees of up to 255 leaves: still one sort per k).  None: the caller takes the object path."""
+    table = getattr(be, method)(*args)
+    if table is None and hasattr(be, "wide_" + method):
+        table = getattr(be, "wide_" + method)(*args)
+    return table
+
+
 # The k-mer classes of a group of genomes: membership queries (all of, none of) over the masks of a universe, from the
 # group's mask G and the universe's mask `full`.  Their order is the order of every table and CSV column that holds them.
 KMER_QUERIES = {"core": lambda G, full: (G, 0), "private": lambda G, full: (0, full ^ G), "signature": lambda G, full: (G, full ^ G)}
@@ -976,7 +986,7 @@ class DeltaTree:
             lo = max(1, lo)
             if hi >= lo:
                 group_of = [owner.get(leaf.fastas[0], -1) for leaf in leaves]
-                table = be.leave_out_cards(self._leaf_files(leaves, lo, hi), group_of)
+                table = _cards_or_wide(be, "leave_out_cards", self._leaf_files(leaves, lo, hi), group_of)
                 if table is not None:       # (None: the backend has no schedule for this many leaves)
                     sched = UnionTable(table, lo, hi)
         rows, summary = [], []
@@ -1122,7 +1132,7 @@ class DeltaTree:
         out["core"] = u.table(be.core_progressive_counts(paths, orderings), (len(orderings), n, len(ks)))
         pan = None
         if hasattr(be, "progressive_cards") and u.batched:
-            pan = be.progressive_cards(paths, orderings)
+            pan = _cards_or_wide(be, "progressive_cards", paths, orderings)
         if pan is None:
             pan = np.zeros((len(orderings), n, len(ks)))
             seen = {}
@@ -1545,12 +1555,12 @@ class DeltaTree:
         index = {id(leaf): i for i, leaf in enumerate(leaves)}
         paths = self._leaf_files(leaves, lo, hi)
         if pair_mode:
-            table, orders = be.pairwise_cards(paths), None
+            table, orders = _cards_or_wide(be, "pairwise_cards", paths), None
         else:
             ords = [[index[id(leaf)] for leaf in g] for g in groups if len(g) == len(leaves)]
             if not ords:
                 return None
-            table, orders = be.progressive_cards(paths, ords), {tuple(o): i for i, o in enumerate(ords)}
+            table, orders = _cards_or_wide(be, "progressive_cards", paths, ords), {tuple(o): i for i, o in enumerate(ords)}
         if table is None:             # (the backend has no schedule for this many leaves: the object path)
             return None
         experiment["prefetched"] = True

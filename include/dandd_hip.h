@@ -243,6 +243,27 @@ int dd_exact_subsets_device(dd_ctx *, const uint8_t *const *fasta_dev, const siz
  * card[s] = total - (k-mers whose mask avoids s), by a subset-sum transform of the histogram. */
 int dd_exact_subsets_from_hist(const uint64_t *hist /*[2^n]*/, int n, uint64_t *card /*[2^n]*/);
 
+/* ---- exact union schedules for 65 to 255 inputs ---------------------------------------------
+ * dd_exact_pairwise / _progressive / _leave_out with the limit on n lifted to what the sort carries: the input travels
+ * with its k-mer as one byte (0xFF: the slot nothing wrote), so 1 <= n <= 255, else DD_EINVAL ("n=%d outside 1..255").
+ * The same ONE sort per k; every distinct k-mer gets a membership ROW of ceil(n / 64) <= 4 words where the entries above
+ * keep one 64-bit mask (dd_exact_wide.hip).  Argument lists, output shapes, the other argument rules and their messages
+ * (k in 1..64, orderings that are permutations, group ids in -1..ngroups-1, a group that holds every input), the budget
+ * (DD_EXACT_MB), the passes and dd_last_sketch_stats' third value are those of the entries above, and for n <= 64 so are
+ * the numbers, byte for byte.  The entries above stay: their limit and its message are part of ABI version 4.  (At n = 64
+ * the wide entries measure 1.00 to 1.02 x the narrow ones on the same buffers: profiles/exact_wide.txt.) */
+int dd_exact_wide_pairwise(dd_ctx *, const char *const *paths, int n, int kmin, int kmax, uint64_t *card /*[n][n][K]*/);
+int dd_exact_wide_progressive(dd_ctx *, const char *const *paths, int n, int kmin, int kmax,
+                              const int32_t *orderings /*[norder][n]*/, int norder, uint64_t *card /*[norder][n][K]*/);
+int dd_exact_wide_leave_out(dd_ctx *, const char *const *paths, int n, int kmin, int kmax,
+                            const int32_t *group /*[n]*/, int ngroups, uint64_t *card /*[ngroups+1][K]*/);
+int dd_exact_wide_pairwise_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
+                                  uint64_t *card);
+int dd_exact_wide_progressive_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
+                                     const int32_t *orderings, int norder, uint64_t *card);
+int dd_exact_wide_leave_out_device(dd_ctx *, const uint8_t *const *fasta_dev, const size_t *nbytes, int n, int kmin, int kmax,
+                                   const int32_t *group, int ngroups, uint64_t *card);
+
 /* ---- exact intersection schedules: core genome, k-mer spectrum, marker k-mers ------------------------------
  * What the union schedules cannot give and HyperLogLog sketches cannot estimate (inclusion-exclusion over 2^n union
  * estimates amplifies their error): counts of the distinct k-mers whose membership mask CONTAINS a set of inputs, or has
