@@ -159,6 +159,11 @@ int dd_last_k2_path(dd_ctx* c) {
     return c->k2_path;
 }
 
+int dd_last_k2_launches(dd_ctx* c) {
+    if (check_ctx(c)) return DD_EINVAL;
+    return c->k2_launches;
+}
+
 // --------------------------------------------------------------------------- synthetic
 long dd_plan_sweep(int log2m, const size_t* nbytes, int ngenomes, int kmin, int kmax, dd_plan_job* out,
                    long cap) {

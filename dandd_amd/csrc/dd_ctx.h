@@ -152,6 +152,7 @@ struct dd_ctx {
     uint64_t st_tokens = 0, st_updates = 0;
     int st_blocks = 0;
     int k2_path = 0;  // DD_K2_*: what the last progressive / pairwise call ran
+    int k2_launches = 0;  // gram_kernel / cross_kernel launches of the last pairwise / cross call (0: a streaming form)
     // multi-GPU (dd_comm_*): this context's rank in an RCCL communicator, one context = one process = one GPU
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;

@@ -47,6 +47,7 @@
 #include "dd_kernels.h"
 
 #include <algorithm>
+#include <cstdlib>
 
 namespace dd {
 namespace {
@@ -548,6 +549,14 @@ static int gram_len(int nsp, int K, int p) {
     return (int)len;
 }
 
+// what the partial counts of one launch may take: DD_GRAM_PART_MB MiB (1024 when unset or <= 0; read on every call, by
+// gram_scratch_bytes and cross_scratch_bytes only -- the launchers take their units per launch from these, so what is
+// reserved and what is launched agree).  A small budget splits small shapes into several launches, for the tests.
+static size_t gram_part_budget() {
+    const char* mb = getenv("DD_GRAM_PART_MB");
+    return (size_t)(mb && atol(mb) > 0 ? atol(mb) : 1024) << 20;
+}
+
 // n > 64: the diagonal is covered by 128-row units (kDiag2) and the off-diagonal launch skips the 64 x 64 pairs inside them
 static bool gram_diag2(int n) { return n > 64; }
 
@@ -557,16 +566,17 @@ size_t gram_scratch_bytes(int n, int K, int p, int* sp_per_launch) {
     const size_t total_sp = (size_t)ns * (ns + 1) / 2;
     const size_t m = (size_t)1 << p;
     const size_t RR = m / (size_t)gram_len(d2 ? 4 * ((ns + 1) / 2) : ns, K, p);   // (the diagonal launch has the fewest units: its split is the finest)
-    // a launch covers as many units as fit ~1 GiB of partial counts (at least one)
+    // a launch covers as many units as fit ~1 GiB of partial counts (gram_part_budget; at least one)
     const size_t per_sp = (size_t)K * RR * (size_t)gram_slots(p) * (d2 ? 10 : 4) * 1024 * sizeof(uint32_t);
-    size_t fit = ((size_t)1 << 30) / per_sp;
+    size_t fit = gram_part_budget() / per_sp;
     fit = fit < 1 ? 1 : fit > total_sp ? total_sp : fit;
     if (sp_per_launch) *sp_per_launch = (int)fit;
     return fit * per_sp + (((size_t)K * 2 * sizeof(uint32_t) + 255) & ~(size_t)255);
 }
 
 // hist_dev must have been zeroed by the caller (the lower triangle stays zero).  scratch: gram_scratch_bytes().
-void launch_pairwise_gram(const uint8_t* leaf_dev, int n, int K, int p, uint32_t* hist_dev, void* scratch,
+// Returns the number of gram_kernel launches it enqueued.
+int launch_pairwise_gram(const uint8_t* leaf_dev, int n, int K, int p, uint32_t* hist_dev, void* scratch,
                           hipStream_t st) {
     const int ns = (n + 63) / 64;
     const bool d2 = gram_diag2(n);
@@ -582,6 +592,7 @@ void launch_pairwise_gram(const uint8_t* leaf_dev, int n, int K, int p, uint32_t
     const int slots = gram_slots(p);
     const int len = gram_len(d2 ? 4 * ((ns + 1) / 2) : ns, K, p);
     const int RR = (int)(m / (size_t)len);
+    int launches = 0;
     for (int diag = 1; diag >= 0; --diag) {
         const int shape = diag ? (d2 ? kDiag2 : kDiag) : kOff;
         const int total = shape == kDiag ? ns : shape == kDiag2 ? (ns + 1) / 2 : ns * (ns - 1) / 2 - (d2 ? ns / 2 : 0);
@@ -597,10 +608,12 @@ void launch_pairwise_gram(const uint8_t* leaf_dev, int n, int K, int p, uint32_t
 #define DD_GRAM_LAUNCH(S) hipLaunchKernelGGL((gram_kernel<S, GramShape<S>::TS>), dim3(grid), dim3(GramShape<S>::WAVES * 64), 0, st, leaf_dev, n, K, p, rng, a, ns, RR, len, slots, units, cnt, (S == kOff ? paired_off : 0), part)
             if (shape == kDiag) DD_GRAM_LAUNCH(kDiag); else if (shape == kDiag2) DD_GRAM_LAUNCH(kDiag2); else DD_GRAM_LAUNCH(kOff);
 #undef DD_GRAM_LAUNCH
+            ++launches;
             hipLaunchKernelGGL(gram_finish_kernel, dim3((unsigned)((size_t)cnt * K * nb * 16)), dim3(256), 0, st, part, n, K, p, rng,
                                shape, a, ns, RR, slots, d2 ? 1 : 0, hist_dev);
         }
     }
+    return launches;
 }
 
 // ---- the rectangle: na rows of slab a against nb rows of slab b ---------------------------------------------------------
@@ -621,7 +634,7 @@ size_t cross_scratch_bytes(int na, int nb, int K, int p, int* sp_per_launch) {
     const size_t total_sp = (size_t)((na + 63) / 64) * ((nb + 63) / 64);
     const size_t RR = ((size_t)1 << p) / (size_t)gram_len((int)total_sp, K, p);
     const size_t per_sp = (size_t)K * RR * (size_t)gram_slots(p) * GramShape<kCross>::NB * 1024 * sizeof(uint32_t);
-    size_t fit = ((size_t)1 << 30) / per_sp;
+    size_t fit = gram_part_budget() / per_sp;
     fit = fit < 1 ? 1 : fit > total_sp ? total_sp : fit;
     if (sp_per_launch) *sp_per_launch = (int)fit;
     return fit * per_sp + cross_rng_bytes(K);
@@ -630,7 +643,8 @@ size_t cross_scratch_bytes(int na, int nb, int K, int p, int* sp_per_launch) {
 // hist[((s * nb) + j) * K + k][64] for every s < na, j < nb; every word of it is written.  scratch: cross_scratch_bytes(),
 // its head as launch_cross_range left it for the slabs of the whole call (a_dev may be a round's rows of a larger slab).
 // A blocks of 64 rows take kCross; a last block of at most 32 rows -- the only one when na <= 32 -- takes kCrossHalf.
-void launch_cross_gram(const uint8_t* a_dev, int na, const uint8_t* b_dev, int nb, int K, int p, uint32_t* hist_dev, void* scratch,
+// Returns the number of cross_kernel launches it enqueued.
+int launch_cross_gram(const uint8_t* a_dev, int na, const uint8_t* b_dev, int nb, int K, int p, uint32_t* hist_dev, void* scratch,
                        hipStream_t st) {
     const int nsa = (na + 63) / 64, nsb = (nb + 63) / 64;
     int sp_fit = 1;
@@ -642,6 +656,7 @@ void launch_cross_gram(const uint8_t* a_dev, int na, const uint8_t* b_dev, int n
     const int len = gram_len(nsa * nsb, K, p);
     const int RR = (int)(((size_t)1 << p) / (size_t)len);
     const int nhalf = na - 64 * (nsa - 1) <= 32 ? 1 : 0;     // A blocks in the half-height form: the last one, or none
+    int launches = 0;
     for (int half = 0; half <= 1; ++half) {
         const int first = half ? (nsa - nhalf) * nsb : 0;    // units P * nsb + Q of this form: [first, first + total)
         const int total = (half ? nhalf : nsa - nhalf) * nsb;
@@ -653,10 +668,12 @@ void launch_cross_gram(const uint8_t* a_dev, int na, const uint8_t* b_dev, int n
 #define DD_CROSS_LAUNCH(S) hipLaunchKernelGGL(cross_kernel<S>, dim3((unsigned)units), dim3(256), 0, st, a_dev, na, b_dev, nb, K, p, rng, first + u, nsb, RR, len, slots, units, cnt, part)
             if (half) DD_CROSS_LAUNCH(kCrossHalf); else DD_CROSS_LAUNCH(kCross);
 #undef DD_CROSS_LAUNCH
+            ++launches;
             hipLaunchKernelGGL(cross_finish_kernel, dim3((unsigned)((size_t)cnt * K * (half ? 2 : 4) * 16)), dim3(256), 0, st, part, na, nb, K, p,
                                rng, half, first + u, nsb, RR, slots, hist_dev);
         }
     }
+    return launches;
 }
 
 }  // namespace dd

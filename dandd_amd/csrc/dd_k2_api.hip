@@ -144,11 +144,12 @@ int pairwise(dd_ctx* c, Slab leaf, int n, int K, double* card) {
     const bool gram = dd::gram_usable(n, c->p) && !getenv("DD_PAIRWISE_STREAM");
     if (gram && (rc = c->gram.reserve(dd::gram_scratch_bytes(n, K, c->p, nullptr)))) return rc;
     c->k2_path = gram ? DD_K2_PAIRWISE_GRAM : DD_K2_PAIRWISE_STREAM;
+    c->k2_launches = 0;
     std::vector<double> tmp(njobs);
     rc = hist_step(c, njobs, nullptr, 0, tmp.data(), [&](uint32_t* hist, const int32_t*) {
         if (gram) {
             DD_HIP(hipMemsetAsync(hist, 0, njobs * 64 * sizeof(uint32_t), c->stream));
-            dd::launch_pairwise_gram(leaf_dev, n, K, c->p, hist, c->gram.p, c->stream);
+            c->k2_launches = dd::launch_pairwise_gram(leaf_dev, n, K, c->p, hist, c->gram.p, c->stream);
         } else {
             dd::launch_pairwise(leaf_dev, n, K, c->p, hist, c->stream);
         }
@@ -188,6 +189,7 @@ int cross(dd_ctx* c, Slab a, int na, Slab b, int nb, int K, double* card) {
     // runs and for the equality test
     const bool gram = dd::cross_gram_usable(c->p) && !getenv("DD_CROSS_STREAM");
     c->k2_path = gram ? DD_K2_CROSS_GRAM : DD_K2_CROSS_STREAM;
+    c->k2_launches = 0;
     const char* mb = getenv("DD_CROSS_HIST_MB");
     const size_t budget = (size_t)(mb && atol(mb) > 0 ? atol(mb) : 1024) << 20;
     const size_t per_block = (size_t)64 * nb * K * 64 * sizeof(uint32_t);
@@ -207,7 +209,7 @@ int cross(dd_ctx* c, Slab a, int na, Slab b, int nb, int K, double* card) {
                 return DD_OK;
             }
             if (s0 == 0) dd::launch_cross_range(a_dev, na, b_dev, nb, K, c->p, static_cast<uint32_t*>(c->gram.p), c->stream);
-            dd::launch_cross_gram(a_round, cnt, b_dev, nb, K, c->p, hist, c->gram.p, c->stream);
+            c->k2_launches += dd::launch_cross_gram(a_round, cnt, b_dev, nb, K, c->p, hist, c->gram.p, c->stream);
             return DD_OK;
         });
         if (rc) return rc;

@@ -220,8 +220,8 @@ void launch_pairwise(const uint8_t* leaf_dev, int n, int K, int log2m, uint32_t*
 // the same histograms through int8 Gram matrices on the matrix cores (dd_gram.hip); hist_dev zeroed by the caller
 bool gram_usable(int n, int log2m);
 size_t gram_scratch_bytes(int n, int K, int log2m, int* sp_per_launch);
-void launch_pairwise_gram(const uint8_t* leaf_dev, int n, int K, int log2m, uint32_t* hist_dev, void* scratch,
-                          hipStream_t st);
+int launch_pairwise_gram(const uint8_t* leaf_dev, int n, int K, int log2m, uint32_t* hist_dev, void* scratch,
+                         hipStream_t st);   // (the gram_kernel launches it enqueued)
 void launch_register_range(const uint8_t* leaf_dev, int n, int K, int log2m, uint32_t* rng_dev, hipStream_t st);
 // the rectangle, na rows of slab a against nb rows of slab b: hist[((s*nb)+j)*K + kk][64] for every s < na, j < nb.  The
 // streaming kernel (dd_union.hip) zeroes what it needs; the Gram form (dd_gram.hip, log2m >= 12) writes every word and wants
@@ -230,8 +230,8 @@ void launch_cross_stream(const uint8_t* a_dev, int na, const uint8_t* b_dev, int
 bool cross_gram_usable(int log2m);
 size_t cross_scratch_bytes(int na, int nb, int K, int log2m, int* sp_per_launch);
 void launch_cross_range(const uint8_t* a_dev, int na, const uint8_t* b_dev, int nb, int K, int log2m, uint32_t* rng_dev, hipStream_t st);
-void launch_cross_gram(const uint8_t* a_dev, int na, const uint8_t* b_dev, int nb, int K, int log2m, uint32_t* hist_dev, void* scratch,
-                       hipStream_t st);
+int launch_cross_gram(const uint8_t* a_dev, int na, const uint8_t* b_dev, int nb, int K, int log2m, uint32_t* hist_dev, void* scratch,
+                      hipStream_t st);   // (the cross_kernel launches it enqueued)
 // progressive unions as a bit-plane AND-scan (dd_pscan.hip); the streaming launch_progressive stays as the fallback
 bool pscan_usable(int n, int norder, int log2m);
 size_t pscan_scratch_bytes(int n, int K, int log2m, int norder);

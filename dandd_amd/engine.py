@@ -46,7 +46,7 @@ EXPORTS = [
     "dd_exact_cover", "dd_exact_cover_device",
     "dd_exact_gather", "dd_exact_gather_device",
     "dd_exact_patterns", "dd_exact_patterns_device",
-    "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path",
+    "dd_timing_enable", "dd_timing_read", "dd_timing_reset", "dd_last_sketch_stats", "dd_last_k2_path", "dd_last_k2_launches",
     "dd_synth_size", "dd_synth_fasta_device", "dd_synth_realistic_size", "dd_synth_realistic_device", "dd_plan_sweep",
     "dd_comm_unique_id", "dd_comm_init", "dd_comm_destroy", "dd_comm_info", "dd_allreduce_max_u8", "dd_allgather_u8",
 ]
@@ -216,6 +216,8 @@ def load_library(path=None):
     lib.dd_last_sketch_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     lib.dd_last_k2_path.restype = i32
     lib.dd_last_k2_path.argtypes = [vp]
+    lib.dd_last_k2_launches.restype = i32
+    lib.dd_last_k2_launches.argtypes = [vp]
     lib.dd_synth_size.restype = sz
     lib.dd_synth_size.argtypes = [u64, i32]
     lib.dd_synth_fasta_device.restype = i32
@@ -1265,6 +1267,14 @@ class Engine:
         if rc < 0:
             self._check(rc)
         return self.K2_PATHS[rc]
+
+    def last_k2_launches(self):
+        """How many gram_kernel / cross_kernel launches the last pairwise / cross call enqueued, summed over cross's rounds
+        (0: a streaming form).  DD_GRAM_PART_MB sets what the partial counts of one launch may take."""
+        rc = self._lib.dd_last_k2_launches(self._ctx)
+        if rc < 0:
+            self._check(rc)
+        return rc
 
     def warmup(self):
         """One tiny sketch + cardinality: HIP loads a kernel module at its first launch, this makes the first launches

@@ -624,6 +624,10 @@ int dd_last_sketch_stats(dd_ctx *, uint64_t *tokens, uint64_t *updates, int *swe
 #define DD_K2_CROSS_STREAM 5       /* cross_stream_kernel: one LDS atomic per register per (row of a, row of b) */
 #define DD_K2_CROSS_GRAM 6         /* cross_kernel: the rectangle as int8 Gram blocks (log2m >= 12) */
 int dd_last_k2_path(dd_ctx *);
+/* how many gram_kernel / cross_kernel launches the last dd_pairwise* / dd_cross* call of the context enqueued, summed over
+ * dd_cross's rounds; 0 when it took a streaming form.  The Gram forms cut their units into launches whose partial counts
+ * fit DD_GRAM_PART_MB MiB (1024 when unset or <= 0; read on every call), one unit at the least. */
+int dd_last_k2_launches(dd_ctx *);
 
 /* ---- synthetic FASTA on the device (bench / tests) ----------
  * Byte-identical to oracle/dd_oracle.c:orc_synth_fasta for the same arguments. */

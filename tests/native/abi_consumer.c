@@ -37,6 +37,7 @@ int main(void) {
             return 20;
         if (DD_COMM_ID_BYTES != 128) return 21;
     }
+    if (dd_last_k2_launches(NULL) >= 0) return 22; /* (additive, ABI 4 still) a count on no context is an error code */
     printf("abi_consumer: ok (%ld jobs)\n", n);
     return 0;
 }

@@ -49,12 +49,11 @@ def host():
     deltatree.set_backend_factory(None)
 
 
-@pytest.fixture
-def world(tmp_path, host):
+def make_world(tmp_path, host, registers=REGS):
     """A 5-leaf tree of sketches with a window, and three samples: a copy of leaf g2 under another name, a mutated g0, and
     a sequence of its own"""
     with redirect_stdout(io.StringIO()):
-        data, pk = dd._tree(str(tmp_path), host, registers=REGS, extra=WINDOW)
+        data, pk = dd._tree(str(tmp_path), host, registers=registers, extra=WINDOW)
     rng = np.random.default_rng(3)
     sdir = tmp_path / "samples"
     sdir.mkdir()
@@ -69,6 +68,11 @@ def world(tmp_path, host):
     alone = str(sdir / "alone.fasta")
     open(alone, "wb").write(b">alone\n" + rng.choice(np.frombuffer(b"ACGT", np.uint8), size=6000).tobytes() + b"\n")
     return data, pk, [cousin, twin, alone]
+
+
+@pytest.fixture
+def world(tmp_path, host):
+    return make_world(tmp_path, host)
 
 
 def _neighbors(host, argv, backend=NeighborsBackend):
